@@ -2,6 +2,8 @@
 """Headline benchmark: CSA forward + backward query-points/sec (BASELINE.json metric) on N MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5                      # BASELINE.json configs[2] (the metric's config)
+    python bench.py --full                                              # + launches, roofline, secondary runs, named modes, CPU baseline
+    python bench.py --dump-outputs DIR                                  # + the last timed step's logits / loss / gradients as .npy
     python bench.py --same-work                                         # N = 1 with the per-GPU work of the N > 1 path (K+2 evaluations)
     python bench.py --config 2 | --config 5                             # configs[1] / configs[4] as workloads of their own
     python bench.py --gpus N --steps K --warmup W                      # N > 1 without a launcher: starts its own N ranks
@@ -22,11 +24,20 @@ Workloads (`--config`, numbering of SURVEY.md §8d = BASELINE.json configs[i-1])
   5            8 query shapes x 50000 points x 96 channels (d_k = d_v = 96), K = 4, 100 blocks of 500.
 n_heads = 1 (csa_training.py:37 default), 39 classes (PartNet Chair), train mode (dropout 0.1 live, csa_training.py:192).
 
-Prints ONE JSON line (rank 0).  EVERY launching entry point of the C ABI is bracketed by HIP events on the launch stream in
-every timed step (csn_amd._lib.set_call_hook); `launches` lists them (mean ms per step), `roofline` describes the longest one
-WHATEVER it is — today a fused block-attention launch (forward: S = Q K^T, softmax, P V; backward: dP = dO V^T, dS, dQ = dS K)
-— and `roofline_other` the next attention launch.
-`cpu_baseline` is the oracle's faithful op-for-op port of the reference timed on the host cores over a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps
+(`ms_per_step` = their median, `value` = points/s on it), the outputs if `--dump-outputs DIR` is given, the line.
+
+`--full` adds everything else, as before the option existed: EVERY launching entry point of the C ABI is bracketed by HIP
+events on the launch stream in every step (csn_amd._lib.set_call_hook); `launches` lists them (mean ms per step), `roofline`
+describes the longest one WHATEVER it is — today a fused block-attention launch (forward: S = Q K^T, softmax, P V; backward:
+dP = dO V^T, dS, dQ = dS K) — and `roofline_other` the next attention launch; the secondary runs (the module's default
+path, eval-mode arithmetic, the other arithmetic mode with its cross-mode check), `config.named_modes`, the N > 1 line's
+same-work reference, and `cpu_baseline`, the oracle's faithful op-for-op port of the reference timed on the host cores over
+a bounded sample.  (`--headline-only`, `--no-named-modes` and `--no-cpu-baseline` trim a `--full` run.)
+
+`--dump-outputs DIR` (rank 0) writes what the headline's LAST timed step handed its caller, as float32 .npy files: `logits`
+(B, classes, N, 1) — or, beyond the 64 MB budget, `logits_points_sample` with the seeded point indices beside it —, `loss`, and
+`grad.<parameter>` for every trained parameter.  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import datetime
@@ -75,6 +86,35 @@ def masked_ce(logits, label):
     ignored; class-major logits are consumed in place instead of being transposed and gathered)."""
     from csn_amd.functional import masked_cross_entropy
     return masked_cross_entropy(logits, label, 0)[0]
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together, headers included
+DUMP_HEADER_BYTES = 256               # upper bound on one .npy header
+DUMP_SAMPLE_SEED = 0
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as float32 out_dir/<name>.npy.  The logits (B, classes, N, 1) go whole if they fit the budget
+    beside the rest; otherwise a seeded sample of point indices (every shape and class at those points, axis 2) goes as
+    `logits_points_sample`, the indices as `logits_points_sample_index` (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items() if k != "logits"}
+    used = sum(a.nbytes + DUMP_HEADER_BYTES for a in files.values())
+    logits = np.asarray(arrays["logits"], dtype=np.float32)
+    if used + logits.nbytes + DUMP_HEADER_BYTES <= DUMP_BUDGET_BYTES:
+        files["logits"] = logits
+    else:
+        n_pts = logits.shape[2]
+        per_point = logits.nbytes // n_pts + 8                          # every shape and class at one point, + its index
+        m = min(n_pts, (DUMP_BUDGET_BYTES - used - 2 * DUMP_HEADER_BYTES) // per_point)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pts, size=m, replace=False))
+        files["logits_points_sample"] = np.take(logits, idx, axis=2)
+        files["logits_points_sample_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes + DUMP_HEADER_BYTES for a in files.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget"
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench: wrote {len(files)} arrays ({total / 1e6:.1f} MB) to {out_dir}", file=sys.stderr, flush=True)
 
 
 def cpu_model_name():
@@ -257,11 +297,30 @@ def launch_check():
     dist.destroy_process_group()
 
 
+def _positive(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {n}")
+    return n
+
+
+def _non_negative(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {n}")
+    return n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)       # median of >= 20 timed steps after >= 5 warm-ups
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=_positive, default=20)    # median of >= 20 timed steps after >= 5 warm-ups
+    ap.add_argument("--warmup", type=_non_negative, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-launch HIP events, roofline, the secondary runs, named modes, the "
+                         "N > 1 same-work reference and the CPU baseline (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits, loss and parameter gradients as float32 DIR/<name>.npy (64 MB at most)")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=3,
                     help="workload: 3 = the metric's configuration (default), 2 / 5 = BASELINE configs[1] / configs[4]")
     ap.add_argument("--shapes", type=int, default=None, help="query shapes per GPU (default: the configuration's)")
@@ -269,7 +328,7 @@ def main():
     ap.add_argument("--heads", type=int, default=1,
                     help="n_heads (d_k = d_v = d per head): 1 = csa_training.py:37's default and the metric's configuration; 8 with "
                          "--K 4 = the reference's published checkpoint (get_csa_pred.py:35-36)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--math", choices=sorted(MATH_MODES), default="bf16x3",
                     help="arithmetic of the contractions: exact fp32 matrix cores; three bf16 products per fp32 product "
                          "(default: inside the 1e-4 contract); one bf16 / fp16 product (outside it, reported with its error)")
@@ -278,9 +337,9 @@ def main():
                          "computed once, by its owner; the 32 shapes are their own collection, no exchange) instead of the "
                          "reference's 2K+2 — the like-for-like N = 1 point of the scaling curve")
     ap.add_argument("--no-named-modes", action="store_true",
-                    help="skip config.named_modes (BASELINE configs[1] in bf16 and configs[4] in fp16 after the default headline)")
+                    help="--full: skip config.named_modes (BASELINE configs[1] in bf16 and configs[4] in fp16 after the default headline)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary runs (other math mode, eval-mode arithmetic): what the profiles are taken with")
+                    help="--full: skip the secondary runs (other math mode, eval-mode arithmetic): what the profiles are taken with")
     args = ap.parse_args()
     H = args.heads
 
@@ -336,7 +395,7 @@ NAMED_STEPS, NAMED_WARMUP = 5, 2
 
 
 def named_modes_wanted(args, grouped):
-    return (not grouped and not args.no_named_modes and not args.headline_only and not args.same_work and args.config == 3
+    return (args.full and not grouped and not args.no_named_modes and not args.headline_only and not args.same_work and args.config == 3
             and args.math == "bf16x3" and args.shapes is None and args.K is None and args.heads == 1
             and not any(os.environ.get(k) for k in ("CSN_BENCH_HOST_NB", "CSN_BENCH_SPLIT")))
 
@@ -347,6 +406,7 @@ def named_modes(args, ctx):
     for config, math in NAMED_MODES:
         a = copy.copy(args)
         a.config, a.math, a.steps, a.warmup, a.headline_only, a.no_cpu_baseline = config, math, NAMED_STEPS, NAMED_WARMUP, True, True
+        a.dump_outputs = None                                            # (the headline's outputs only)
         o = run(a, ctx)
         r = o["roofline"]
         res.append({"baseline_config": CONFIGS[config]["name"], "workload": o["config"]["workload"], "math": math, "dtype": o["dtype"],
@@ -382,7 +442,8 @@ def run(args, ctx):
     torch.manual_seed(0)
     model = get_model("csa", N_CLS, H, K, d_model=C, d_k=d, d_v=d, block=T, n_blocks=nb).to(dev)
     model.trust_neighbor_slot0 = True      # the stack built below has the shape itself in slot 0, like CSADatasetK
-    params = [p for n, p in model.named_parameters() if not n.startswith("fc_1")]
+    named_params = [(n, p) for n, p in model.named_parameters() if not n.startswith("fc_1")]
+    params = [p for _, p in named_params]
 
     rng = np.random.default_rng(1234 + (args.config - 1) + 1000 * rank)
     feats = torch.from_numpy(rng.standard_normal(size=(B, C, N)).astype(np.float32)).to(dev)
@@ -473,8 +534,9 @@ def run(args, ctx):
         x_nb_resident[:, 1:, :, :, 0] = feats[local_graph]
     same_work_n1 = not grouped and args.same_work
 
-    def step(record=False, local=False):
-        """local: the same-work step on this rank's own shapes (no exchange, no gradient all-reduce)"""
+    def step(record=False, local=False, keep=False):
+        """local: the same-work step on this rank's own shapes (no exchange, no gradient all-reduce); keep: also return the
+        logits (only the last timed step is asked to, so that no step runs with an earlier step's logits still alive)"""
         for p in params:
             p.grad = None
         if shard is not None and not local:
@@ -501,9 +563,13 @@ def run(args, ctx):
             csn_amd._lib.set_call_hook(None)
         if shard is not None and not local:
             shard.allreduce_grads(params)                                # one 1.6 MB bucket
-        return loss
+        return (loss, logits.detach()) if keep else loss
 
-    def timed(train_mode, local=False):
+    # --full brackets the launches with HIP events (launches / roofline); a plain run times the step without them
+    instrument = args.full
+    dumped = {}                                                          # --dump-outputs: the headline's last step, on the host
+
+    def timed(train_mode, local=False, dump=False):
         """W warm-up + K timed steps, barrier + synchronize on both sides, max over ranks.  Every run starts from the same
         generator state, so the dropout masks (pure functions of seed and position) are the same in every math mode and
         the losses of two modes can be compared.  Returns the bracketed wall time of the K steps (max over ranks) and the
@@ -517,7 +583,7 @@ def run(args, ctx):
         for w in range(args.warmup):
             if w == 1:
                 call_events.clear()                                      # (the first warm-up step pays for allocations)
-            step(record=True, local=local)
+            step(record=instrument, local=local)
         torch.cuda.synchronize()
         n_warm = max(1, args.warmup - 1) if args.warmup else 0
         warm_calls = {k: float(np.sum([a.elapsed_time(b) for a, b in v])) / n_warm for k, v in call_events.items()} if n_warm else {}
@@ -531,7 +597,10 @@ def run(args, ctx):
         t0 = time.perf_counter()
         for i in range(args.steps):
             marks[i].record()
-            loss = step(record=True, local=local)
+            if dump and i == args.steps - 1:
+                loss, logits = step(record=instrument, local=local, keep=True)
+            else:
+                loss = step(record=instrument, local=local)
         marks[args.steps].record()
         torch.cuda.synchronize()
         if group:
@@ -556,18 +625,28 @@ def run(args, ctx):
             if name in per_call:
                 ms[which] = per_call[name] if np.isnan(ms[which]) else ms[which] + per_call[name]
         gnorm = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in params if p.grad is not None)).item())
+        if dump:
+            dumped["logits"] = logits.float().cpu().numpy()
+            dumped["loss"] = loss.detach().float().cpu().numpy()
+            for n, p in named_params:
+                if p.grad is not None:
+                    dumped["grad." + n] = p.grad.float().cpu().numpy()
         return el, float(loss.item()), ms, gnorm, step_ms
 
     # headline first (the training step as the reference runs it), then the secondary runs: eval-mode arithmetic in the
     # headline mode, and the same train-mode step in the other arithmetic mode
     other = "fp32" if args.math != "fp32" else "bf16x3"
     same_work_ms = None
-    if grouped:
+    if grouped and args.full:
         # the like-for-like single-GPU reference of this line: the same K+2 evaluations per shape on this rank's own shapes
         _, _, _, _, sw = timed(True, local=True)
         same_work_ms = float(np.median(sw))
-    elapsed, loss_val, attn_ms, gnorm, step_ms = timed(True)
-    if not args.headline_only:
+    elapsed, loss_val, attn_ms, gnorm, step_ms = timed(True, dump=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dumped)
+        dumped.clear()
+    secondary = args.full and not args.headline_only
+    if secondary:
         if not grouped and x_nb_host is None and not same_work_n1:
             # the module's DEFAULT path beside the headline: without `trust_neighbor_slot0` CrossShapeAt re-assembles the neighbour
             # stack with the query features in slot 0 (csa_models.py:344-356 of this package; 1.3 GB at config 3) — what a caller
@@ -589,7 +668,7 @@ def run(args, ctx):
     if rank == 0:
         launch_flops = n_evals * 4 * N * T * D         # forward: QK^T + PV; backward: dO V^T + dS K — the same count
         traffic_tab = {}
-        if os.path.exists(TRAFFIC_FILE):
+        if instrument and os.path.exists(TRAFFIC_FILE):
             with open(TRAFFIC_FILE) as fh:
                 traffic_tab = json.load(fh)
 
@@ -670,7 +749,6 @@ def run(args, ctx):
             dom, oth = ran[0], (ran[1] if len(ran) > 1 else ran[0])
             return roof(math, dom, ms), roof(math, oth, ms)
 
-        dominant, second = roofs(args.math, attn_ms)
         med_ms = float(np.median(step_ms))
         out = {
             "metric": "CSA fwd+bwd points/sec (10k pts x 256 ch, K=3)" if args.config == 3 else
@@ -696,13 +774,17 @@ def run(args, ctx):
                                        + (", descriptor reuse" if reuse else "")) if grouped else "single GPU",
                        "loss": loss_val, "grad_norm": gnorm,
                        "step_tflops_algorithmic": 3 * algorithmic_flops_fwd(S, K, N, C, D, T) / (med_ms * 1e-3) / 1e12},
-            "roofline": dominant, "roofline_other": second,
-            # every launching entry point of the step, mean ms per step (HIP events around the C-ABI calls; a call may be several
-            # kernels: csn_outproj_ln_bwd_f32 = LayerNorm backward + dCtx + W_fc gradient, csn_block_attn_bwd_dkv_f32 = dV + dK).
-            # launches_live: the entry points bracketed inside the timed steps; the others were bracketed in the warm-up steps
-            "launches": {k: round(v, 4) for k, v in sorted(attn_ms.get("calls", {}).items(), key=lambda kv: -kv[1])},
-            "launches_live": attn_ms.get("calls_live", []),
         }
+        if instrument:
+            dominant, second = roofs(args.math, attn_ms)
+            out.update({
+                "roofline": dominant, "roofline_other": second,
+                # every launching entry point of the step, mean ms per step (HIP events around the C-ABI calls; a call may be several
+                # kernels: csn_outproj_ln_bwd_f32 = LayerNorm backward + dCtx + W_fc gradient, csn_block_attn_bwd_dkv_f32 = dV + dK).
+                # launches_live: the entry points bracketed inside the timed steps; the others were bracketed in the warm-up steps
+                "launches": {k: round(v, 4) for k, v in sorted(attn_ms.get("calls", {}).items(), key=lambda kv: -kv[1])},
+                "launches_live": attn_ms.get("calls_live", []),
+            })
         if grouped:
             sent, recvd = getattr(shard, "payload_bytes", (None, None))
             out["config"]["exchange"] = {"mode": exchange_mode, "payload_dtype": str(payload_dtype or torch.float32).replace("torch.", ""),
@@ -713,14 +795,14 @@ def run(args, ctx):
             out["config"]["scaling_note"] = (
                 f"this line runs K+2 = {K + 2} evaluations per shape (descriptor reuse: a neighbour's pooled SSA descriptor is its "
                 f"owner's), the default N = 1 line runs the reference's 2K+2 = {2 * K + 2}: compare N > 1 lines with "
-                "`bench.py --same-work` at N = 1, or with n1_same_work_ms_per_step — that step (same evaluations, own shapes as "
-                "the collection, no exchange, no gradient all-reduce) timed on rank 0 of THIS run before the group steps"
+                "`bench.py --same-work` at N = 1, or with n1_same_work_ms_per_step (--full) — that step (same evaluations, own "
+                "shapes as the collection, no exchange, no gradient all-reduce) timed on rank 0 of THIS run before the group steps"
                 if reuse else "same evaluations per shape as the N = 1 line (descriptor reuse off)")
         if same_work_n1:
             out["config"]["scaling_note"] = ("--same-work: the per-GPU work of the N > 1 path (K+2 evaluations per shape, own shapes "
                                              "as the collection, no exchange) — the like-for-like N = 1 point of the scaling curve; "
                                              "NOT the metric's headline (that is the default run: the reference's 2K+2)")
-        if not args.headline_only:
+        if secondary:
             if step_ms_default is not None:
                 out["config"]["default_path"] = {"ms_per_step": float(np.median(step_ms_default)),
                                                  "points_per_s": S * N / (float(np.median(step_ms_default)) * 1e-3), "loss": loss_default,
@@ -744,7 +826,7 @@ def run(args, ctx):
             if not ok:
                 print(f"bench: WARNING the {args.math} step disagrees with the {other} step beyond {tol}: "
                       f"loss {loss_val} vs {loss_other}, |grad| {gnorm} vs {gnorm_other}", file=sys.stderr, flush=True)
-        if not grouped and not args.no_cpu_baseline:
+        if args.full and not grouped and not args.no_cpu_baseline:
             cores = min(len(os.sched_getaffinity(0)), 16)          # the GPU box gives one GPU a 16-core share
             sample = 1 if H > 1 else (4 if args.config == 3 else (2 if args.config == 2 else 1))
             out["cpu_baseline"] = cpu_baseline(cfg, min(sample, B), cores, H=H)
