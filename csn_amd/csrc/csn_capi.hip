@@ -880,4 +880,96 @@ int csn_compat_bwd_f32(const float* dcomp, const float* comp, const double* save
                                k1, channels, reference_layout, (hipStream_t)stream);
 }
 
+// ---- (11) ragged MinkowskiNet head ----
+// offsets [n + 1]: offsets[0] == 0, strictly increasing (every shape >= 1 point); returns the longest shape, or -1
+static long long ragged_offsets_max(const int* off, int n) {
+  if (!off || n <= 0 || off[0] != 0) return -1;
+  long long mx = 0;
+  for (int i = 0; i < n; ++i) {
+    if (off[i + 1] <= off[i]) return -1;
+    mx = off[i + 1] - off[i] > mx ? off[i + 1] - off[i] : mx;
+  }
+  return mx;
+}
+
+static bool ragged_maps_ok(long long eval_stride, int ld, int channels) {
+  return ld > 0 && channels > 0 && eval_stride >= (long long)channels * ld;
+}
+
+int csn_ragged_pool_f32(const float* xhat, long long eval_stride, int ld, const int* counts_host, const int* counts,
+                        int n_evals, int channels, const float* gamma, const float* beta, float* pooled, float* mean, void* stream) {
+  if (!xhat || !counts_host || !counts || !gamma || !beta || !pooled || n_evals <= 0) return CSN_E_ARG;
+  if (!ragged_maps_ok(eval_stride, ld, channels)) return CSN_E_ARG;
+  for (int e = 0; e < n_evals; ++e)
+    if (counts_host[e] < 1 || counts_host[e] > ld) return CSN_E_ARG;
+  if ((ld & 3) || (eval_stride & 3)) return CSN_E_ALIGN;
+  if (mis16(xhat)) return CSN_E_PTR;
+  return csn_launch_ragged_pool_f32(xhat, eval_stride, ld, counts, n_evals, channels, gamma, beta, pooled, mean, (hipStream_t)stream);
+}
+
+int csn_ragged_pool_bwd_f32(const float* dpooled, const float* gamma, const int* counts_host, const int* counts, int n_evals,
+                            int channels, float* dxhat, long long eval_stride, int ld, int accumulate, void* stream) {
+  if (!dpooled || !gamma || !counts_host || !counts || !dxhat || n_evals <= 0 || accumulate < 0 || accumulate > 1) return CSN_E_ARG;
+  if (!ragged_maps_ok(eval_stride, ld, channels)) return CSN_E_ARG;
+  for (int e = 0; e < n_evals; ++e)
+    if (counts_host[e] < 1 || counts_host[e] > ld) return CSN_E_ARG;
+  if ((ld & 3) || (eval_stride & 3)) return CSN_E_ALIGN;
+  if (mis16(dxhat)) return CSN_E_PTR;
+  return csn_launch_ragged_pool_bwd_f32(dpooled, gamma, counts, n_evals, channels, dxhat, eval_stride, ld, accumulate,
+                                        (hipStream_t)stream);
+}
+
+// the mixed evaluations ev(b, j) lie inside [0, n_evals) and the cross ones after the shapes' own
+static bool ragged_mix_evals_ok(int n_evals, int cross_first, int n_shapes, int k1) {
+  if (n_shapes > n_evals) return false;
+  if (k1 == 1) return true;
+  return cross_first >= n_shapes && (long long)cross_first + (long long)(k1 - 1) * n_shapes <= n_evals;
+}
+
+int csn_ragged_mix_fwd_f32(const float* xhat, long long eval_stride, int ld, int n_evals, int cross_first,
+                           const int* offsets_host, const int* offsets, int n_shapes, int k1, int channels, const float* comp,
+                           const float* gamma, const float* beta, float* out, long long ld_out, void* stream) {
+  if (!xhat || !offsets || !comp || !gamma || !beta || !out || n_shapes <= 0 || k1 <= 0 || k1 > 8) return CSN_E_ARG;
+  if (!ragged_maps_ok(eval_stride, ld, channels) || ld_out < channels) return CSN_E_ARG;
+  if (!ragged_mix_evals_ok(n_evals, cross_first, n_shapes, k1)) return CSN_E_ARG;
+  const long long mx = ragged_offsets_max(offsets_host, n_shapes);
+  if (mx < 1 || mx > ld) return CSN_E_ARG;
+  if ((ld & 3) || (eval_stride & 3) || (ld_out & 3) || (channels & 3)) return CSN_E_ALIGN;
+  if (mis16(xhat) || mis16(out)) return CSN_E_PTR;
+  return csn_launch_ragged_mix_fwd_f32(xhat, eval_stride, ld, cross_first, offsets, n_shapes, k1, channels, (int)mx, comp, gamma, beta,
+                                       out, ld_out, (hipStream_t)stream);
+}
+
+int csn_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const float* xhat, long long eval_stride, int ld, int n_evals,
+                           int cross_first, const int* offsets_host, const int* offsets, int n_shapes, int k1, int channels,
+                           const float* comp, const float* gamma, float* dxhat, double* rowdot, double* rowsum, double* ws,
+                           long long ws_doubles, void* stream) {
+  if (!dout || !xhat || !offsets || !comp || !gamma || !dxhat || !rowdot || !rowsum || !ws) return CSN_E_ARG;
+  if (n_shapes <= 0 || k1 <= 0 || k1 > 8) return CSN_E_ARG;
+  if (!ragged_maps_ok(eval_stride, ld, channels) || ld_dout < channels) return CSN_E_ARG;
+  if (!ragged_mix_evals_ok(n_evals, cross_first, n_shapes, k1)) return CSN_E_ARG;
+  const long long mx = ragged_offsets_max(offsets_host, n_shapes);
+  if (mx < 1 || mx > ld) return CSN_E_ARG;
+  if ((ld & 3) || (eval_stride & 3) || (ld_dout & 3) || (channels & 3)) return CSN_E_ALIGN;
+  if (mis16(dout) || mis16(xhat) || mis16(dxhat)) return CSN_E_PTR;
+  if (ws_doubles < (long long)n_shapes * (k1 + 1) * csn_ragged_mix_tiles(ld) * channels) return CSN_E_WORKSPACE;
+  return csn_launch_ragged_mix_bwd_f32(dout, ld_dout, xhat, eval_stride, ld, cross_first, offsets, n_shapes, k1, channels, comp, gamma,
+                                       dxhat, rowdot, rowsum, ws, (hipStream_t)stream);
+}
+
+int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                             const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
+                             long long ws_floats, void* stream) {
+  if (!f1 || !f2 || !offsets1 || !offsets2 || !out || !ws || s1 <= 0 || s2 <= 0 || channels <= 0) return CSN_E_ARG;
+  const long long mx1 = ragged_offsets_max(offsets1_host, s1), mx2 = ragged_offsets_max(offsets2_host, s2);
+  if (mx1 < 1 || mx2 < 1) return CSN_E_ARG;
+  if ((long long)s1 * s2 > 0x7fffffffLL) return CSN_E_ARG;
+  if (channels & 3) return CSN_E_ALIGN;
+  if (mis16(f1) || mis16(f2) || mis16(ws)) return CSN_E_PTR;
+  const long long N1 = offsets1_host[s1], N2 = offsets2_host[s2];
+  const long long need = N1 + N2 + (long long)s1 * s2 * ((mx1 + 127) / 128);
+  if (ws_floats < need) return CSN_E_WORKSPACE;
+  return csn_launch_ragged_retrieval_f32(f1, offsets1, s1, N1, f2, offsets2, s2, N2, (int)mx1, channels, out, ws, (hipStream_t)stream);
+}
+
 }  // extern "C"

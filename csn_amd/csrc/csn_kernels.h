@@ -225,6 +225,21 @@ int csn_launch_mix_bwd_f32(const float* dfeats, const float* xhat, const float* 
 int csn_launch_retrieval_f32(const float* f1, const float* f2, float* out, int s1, int n1, int s2, int n2, int C,
                              float* ws, hipStream_t st);
 
+// ---- ragged MinkowskiNet head (minkowski_csn.hip) and ragged retrieval (retrieval.hip) --------------
+int csn_ragged_mix_tiles(int max_points);
+int csn_launch_ragged_pool_f32(const float* xhat, long long eval_stride, int ld, const int* counts, int E, int C, const float* gamma,
+                               const float* beta, float* pooled, float* mean, hipStream_t st);
+int csn_launch_ragged_pool_bwd_f32(const float* dpooled, const float* gamma, const int* counts, int E, int C, float* dxhat,
+                                   long long eval_stride, int ld, int accumulate, hipStream_t st);
+int csn_launch_ragged_mix_fwd_f32(const float* xhat, long long eval_stride, int ld, int cross_first, const int* offsets, int B,
+                                  int K1, int C, int max_points, const float* comp, const float* gamma, const float* beta, float* out,
+                                  long long ld_out, hipStream_t st);
+int csn_launch_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const float* xhat, long long eval_stride, int ld,
+                                  int cross_first, const int* offsets, int B, int K1, int C, const float* comp, const float* gamma,
+                                  float* dxhat, double* rowdot, double* rowsum, double* ws, hipStream_t st);
+int csn_launch_ragged_retrieval_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2, int s2,
+                                    long long N2, int max_n1, int C, float* out, float* ws, hipStream_t st);
+
 // ---- compatibility head (compat.hip): normalize(W_q y_0 + b), normalize(W_k y_k + b), dot, softmax over the K+1 keys ----
 int csn_launch_compat_fwd(const float* pooled, const float* wq_t, const float* bq, const float* wk_t, const float* bk, float* comp,
                           double* save_u, double* save_n, int B, int K1, int C, int reference_layout, hipStream_t st);

@@ -437,6 +437,49 @@ CSN_API int csn_masked_ce_bwd_f32(const float* logits, long long shape_stride, i
                           int n_shapes, int n_classes, int n_points, int mask, const float* lse, const float* stats,
                           const float* grad_out, float* dlogits, long long dshape_stride, int dld, void* stream);
 
+/* ---- (11) the MinkowskiNet cross-shape head on ragged shape batches (MinkowskiNet/models/hrnet.py:359-423, 472-490) -------
+ * A MinkowskiNet batch packs the points of its shapes row after row; shape b owns the rows offsets[b] .. offsets[b+1] - 1
+ * (the cu_seqlens of rows sorted by shape, every shape >= 1 point).  Every offsets / counts array is passed TWICE, with the
+ * same numbers: *_host (host memory: validated and used to size the grid before anything is enqueued) and the device copy
+ * the kernels read.  Maps xhat / dxhat are the varlen attention's channel-major, pre-affine LayerNorm outputs
+ * [n_evals][channels][ld] at eval_stride floats per evaluation (ld, eval_stride % 4, 16-byte aligned); evaluation e has
+ * counts[e] real points — the points [counts[e], ld) enter no sum and are written as zero in every gradient map (the varlen
+ * attention runs round-up-4(counts[e]) queries: the points up to that bound hold real, non-zero values).
+ * Evaluation order of the mix: ev(b, 0) = b (SSA of query shape b), ev(b, j >= 1) = cross_first + (j-1) n_shapes + b
+ * (MHA(q_b, k_{j,b}, k_{j,b})); k1 = K + 1 <= 8.  All sums accumulate in fp64 in a fixed order (bitwise reproducible).
+ * csn_ragged_pool_f32      pooled[e][c] = gamma[c] mean_{n < counts[e]} xhat[e][c][n] + beta[c]  (hrnet.py:380-381, 388-389:
+ *                          torch.mean of the affine SSA rows); mean (optional) [e][c] = the mean before the affine.
+ * csn_ragged_pool_bwd_f32  dxhat[e][c][n] = (accumulate ? dxhat[e][c][n] : 0) + (n < counts[e] ? gamma[c] dpooled[e][c] / counts[e]
+ *                          : 0) for n < ld.
+ * csn_ragged_mix_fwd_f32   out[offsets[b] + n][c] = sum_j comp[b][j] (gamma[c] xhat[ev(b,j)][c][n] + beta[c]), n < the shape's
+ *                          points, POINT-MAJOR at ld_out floats per row (hrnet.py:397-411; with out = the second half of the output
+ *                          layer's (rows, 2 channels) input the concatenation of :423 costs nothing).  k1 = 1, comp = 1: the SSA
+ *                          rows themselves (:366-368, K = 0).  Needs the longest shape <= ld.
+ * csn_ragged_mix_bwd_f32   dxhat[ev(b,j)][c][n] = comp[b][j] gamma[c] dout[offsets[b] + n][c] (0 from the shape's points to ld);
+ *                          rowdot[b][j][c] = sum_n dout[..][c] xhat[ev(b,j)][c][n], rowsum[b][c] = sum_n dout[..][c] (DOUBLES),
+ *                          from which d comp, d gamma and d beta follow with O(n_shapes k1 channels) math.
+ *                          ws >= n_shapes (k1 + 1) ceil(ld / 64) channels doubles (per-64-point-tile partial sums).
+ * csn_ragged_retrieval_f32 out[i][j] = mean_{n < n1_i} max_{m < n2_j} cos(f1[offsets1[i] + n], f2[offsets2[j] + m])  (hrnet.py:472-490
+ *                          for every (query, key) pair at once; point-major rows, channels % 4, the fp32 matrix-core arithmetic of
+ *                          (7); the rows are normalised with max(|x|, 1e-12), where the reference divides by the raw norm: they
+ *                          differ only for an all-zero row).  No n x m matrix and no padding: a work-group of 128 query points
+ *                          exits at once past its shape, the candidate sweep stops at the candidate's points.
+ *                          ws >= N1 + N2 + s1 s2 ceil(max n1_i / 128) floats (inverse row norms + per-tile partial sums). */
+CSN_API int csn_ragged_pool_f32(const float* xhat, long long eval_stride, int ld, const int* counts_host, const int* counts,
+                        int n_evals, int channels, const float* gamma, const float* beta, float* pooled, float* mean, void* stream);
+CSN_API int csn_ragged_pool_bwd_f32(const float* dpooled, const float* gamma, const int* counts_host, const int* counts, int n_evals,
+                            int channels, float* dxhat, long long eval_stride, int ld, int accumulate, void* stream);
+CSN_API int csn_ragged_mix_fwd_f32(const float* xhat, long long eval_stride, int ld, int n_evals, int cross_first,
+                           const int* offsets_host, const int* offsets, int n_shapes, int k1, int channels, const float* comp,
+                           const float* gamma, const float* beta, float* out, long long ld_out, void* stream);
+CSN_API int csn_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const float* xhat, long long eval_stride, int ld, int n_evals,
+                           int cross_first, const int* offsets_host, const int* offsets, int n_shapes, int k1, int channels,
+                           const float* comp, const float* gamma, float* dxhat, double* rowdot, double* rowsum, double* ws,
+                           long long ws_doubles, void* stream);
+CSN_API int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                             const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
+                             long long ws_floats, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

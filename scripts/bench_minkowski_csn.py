@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Throughput of the MinkowskiNet cross-shape head on ragged shape batches (csn_amd/minkowski_csn.py, hrnet.py:359-423) and of
+the ragged retrieval measure (hrnet.py:472-490).  Development aid, not the headline bench.
+
+  head       B query shapes of 3000..5000 points (seeded), K neighbour batches, d_model 256, n_head 4, train mode, forward +
+             backward with gradients to queries, keys and every parameter: SimCSNHead (one varlen launch chain) against the
+             reference's structure — a Python loop of per-shape / per-pair MultiHeadAttention calls plus eager head math.
+  retrieval  16 x 16 shapes of 4096 points against csn_retrieval_measure_f32 on the same data, and a ragged 16 x 16 case of
+             1000..5000 points in TFLOP/s counting only real point pairs (2 C n m per pair)."""
+import argparse, os, sys, time
+import numpy as np, torch
+import torch.nn.functional as F
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from csn_amd import _lib
+from csn_amd import functional as CF
+from csn_amd.minkowski_csn import SimCSNHead, retrieval_measure_ragged
+
+
+def timed(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def loop_step(head, qs, keys):
+    """hrnet.py:359-423 as the reference runs it: get_SSA per shape, 2K+1 MHA calls per query shape, eager head math."""
+    mha = head.MHA
+    ssa = [mha(q[None], q[None], q[None])[0][0] for q in qs]
+    K = len(keys)
+    key_ssa = [[mha(k[None], k[None], k[None])[0][0] for k in ks] for ks in keys]
+    csa = []
+    for b, q in enumerate(qs):
+        u = F.normalize(head.linear_q(ssa[b].mean(0)), dim=-1)
+        sims = [head.sim(u[None], F.normalize(head.linear_k(t.mean(0)), dim=-1)[None]).squeeze()
+                for t in [ssa[b]] + [key_ssa[i][b] for i in range(K)]]
+        comp = F.softmax(torch.stack(sims), dim=0)
+        c = comp[0] * ssa[b]
+        for i in range(K):
+            c = c + comp[i + 1] * mha(q[None], keys[i][b][None], keys[i][b][None])[0][0]
+        csa.append(c)
+    return head.output(torch.cat([torch.cat(qs), torch.cat(csa)], 1))
+
+
+def bench_head(a, mode, K):
+    _lib.check(_lib.lib().csn_set_math_mode(mode))
+    rng = np.random.default_rng(0)
+    H, C = 4, 256
+    torch.manual_seed(0)
+    head = SimCSNHead(C, H, 20, K).cuda().train()
+    lens = lambda: rng.integers(3000, 5001, a.shapes).tolist()
+    qs = [torch.randn((n, C), device="cuda", requires_grad=True) for n in lens()]
+    keys = [[torch.randn((n, C), device="cuda", requires_grad=True) for n in lens()] for _ in range(K)]
+    q = torch.cat([t.detach() for t in qs]).requires_grad_(True)
+    qo = np.concatenate([[0], np.cumsum([t.shape[0] for t in qs])]).tolist()
+    kb = []
+    for ks in keys:
+        kb.append((torch.cat([t.detach() for t in ks]).requires_grad_(True),
+                   np.concatenate([[0], np.cumsum([t.shape[0] for t in ks])]).tolist()))
+
+    def fused():
+        head.zero_grad(set_to_none=True)
+        head(q, qo, kb).square().mean().backward()
+
+    def loop():
+        head.zero_grad(set_to_none=True)
+        loop_step(head, qs, keys).square().mean().backward()
+
+    ms = timed(fused, a.warmup, a.steps)
+    ms_loop = timed(loop, a.warmup, a.steps) if not a.no_loop else float("nan")
+    print(f"head mode {'bf16x3' if mode else 'fp32'}: B={a.shapes} shapes of 3000..5000 points, K={K}, d_model={C}, n_head={H}, "
+          f"train fwd+bwd: SimCSNHead {ms:8.2f} ms/step, per-pair loop {ms_loop:8.2f} ms/step ({ms_loop / ms:4.2f}x)", flush=True)
+
+
+def bench_retrieval(a):
+    C = 256
+    g = torch.Generator(device="cuda").manual_seed(1)
+    S, N = 16, 4096
+    f1 = torch.randn((S, N, C), device="cuda", generator=g)
+    f2 = torch.randn((S, N, C), device="cuda", generator=g)
+    off = [i * N for i in range(S + 1)]
+    ms_fixed = timed(lambda: CF.retrieval_measure(f1, f2), a.warmup, a.steps)
+    ms_rag = timed(lambda: retrieval_measure_ragged(f1.view(-1, C), off, f2.view(-1, C), off), a.warmup, a.steps)
+    flop = 2.0 * C * S * S * N * N
+    print(f"retrieval 16 x 16 shapes of {N} points: fixed-length {ms_fixed:7.3f} ms ({flop / ms_fixed / 1e9:6.1f} TFLOP/s), "
+          f"ragged {ms_rag:7.3f} ms ({flop / ms_rag / 1e9:6.1f} TFLOP/s) = {ms_rag / ms_fixed:4.2f}x the fixed-length time", flush=True)
+    rng = np.random.default_rng(2)
+    n1, n2 = rng.integers(1000, 5001, S).tolist(), rng.integers(1000, 5001, S).tolist()
+    r1 = torch.randn((sum(n1), C), device="cuda", generator=g)
+    r2 = torch.randn((sum(n2), C), device="cuda", generator=g)
+    o1 = np.concatenate([[0], np.cumsum(n1)]).tolist()
+    o2 = np.concatenate([[0], np.cumsum(n2)]).tolist()
+    ms = timed(lambda: retrieval_measure_ragged(r1, o1, r2, o2), a.warmup, a.steps)
+    flop = 2.0 * C * sum(n1) * sum(n2)
+    print(f"retrieval ragged 16 x 16 shapes of 1000..5000 points: {ms:7.3f} ms, {flop / ms / 1e9:6.1f} TFLOP/s over real point "
+          f"pairs = {flop / ms / 1e9 / 157.3:.3f} of the fp32 matrix peak", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", type=int, default=8)
+    ap.add_argument("--ks", default="1,3")
+    ap.add_argument("--modes", default="1,0")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--no-loop", action="store_true", help="time only SimCSNHead (e.g. under a profiler)")
+    ap.add_argument("--no-retrieval", action="store_true")
+    a = ap.parse_args()
+    for mode in (int(m) for m in a.modes.split(",")):
+        for K in (int(k) for k in a.ks.split(",")):
+            bench_head(a, mode, K)
+    if not a.no_retrieval:
+        bench_retrieval(a)
+    _lib.lib().csn_set_math_mode(1)
+
+
+if __name__ == "__main__":
+    main()
