@@ -26,24 +26,6 @@
 #include "csn_common.h"
 #include "csn_kernels.h"
 
-#ifdef CSN_STAMPS
-__device__ unsigned long long csn_dbg[2048 * 8 * 4 * 8];
-extern "C" __attribute__((visibility("default"))) int csn_debug_read(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_dbg), bytes); }
-// whole-kernel stamps per wave: entry, tile loop start, tile loop end, exit
-__device__ unsigned long long csn_dbg_wg[2048 * 8 * 4];
-__device__ unsigned long long csn_dbg_rt[2048 * 8 * 2];     // s_memrealtime (100 MHz) at entry and exit: in-kernel clock
-extern "C" __attribute__((visibility("default"))) int csn_debug_read_wg(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_dbg_wg), bytes); }
-extern "C" __attribute__((visibility("default"))) int csn_debug_read_rt(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_dbg_rt), bytes); }
-#define WGSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if ((BWD == (CSN_STAMPS != 0)) && DT == 8 && blockIdx.x >= 4096 && blockIdx.x < 6144 && (threadIdx.x & 63) == 0) { csn_dbg_wg[((blockIdx.x - 4096) * 8 + (threadIdx.x >> 6)) * 4 + i] = __builtin_amdgcn_s_memtime(); if (i == 0 || i == 3) csn_dbg_rt[((blockIdx.x - 4096) * 8 + (threadIdx.x >> 6)) * 2 + (i == 3)] = __builtin_amdgcn_s_memrealtime(); } __builtin_amdgcn_sched_barrier(0); } while (0)
-// prologue stamps of the same work-groups: entry, operand block requested, landed (barrier), picked, tiles fetched and committed
-__device__ unsigned long long csn_dbg_pro[2048 * 8 * 8];
-extern "C" __attribute__((visibility("default"))) int csn_debug_read_pro(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_dbg_pro), bytes); }
-#define PSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if ((BWD == (CSN_STAMPS != 0)) && DT == 8 && blockIdx.x >= 4096 && blockIdx.x < 6144 && (threadIdx.x & 63) == 0) csn_dbg_pro[((blockIdx.x - 4096) * 8 + (threadIdx.x >> 6)) * 8 + i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WGSTAMP(i)
-#define PSTAMP(i)
-#endif
-
 namespace {
 
 constexpr int KT = 32;               // keys per streamed tile
@@ -86,18 +68,12 @@ CSN_DEVINL f32x4v mma16(s16x8 ah, s16x8 al, s16x8 bh, s16x8 bl, f32x4v c) {
 // images leave room for a second work-group on the CU: one plane up to d = 96, two planes up to d = 64.  There the bound is
 // four (128 registers), which costs the recomputing dQ instances 13-18 spilled registers and still pays: a second work-group
 // hides what a latency-bound loop cannot (config-5 geometry, bf16: dQ 3.53 -> 2.69 ms; bf16x3 at d = 64: 2.43 -> 1.75 ms).
-// Measured and NOT taken (scripts/dev/ab_attn.sh): one plane at d = 128 (+-0), two planes at d = 96 / 128 with the default
-// ring depth (38-82 spilled registers inside the loop: forward 3.8 -> 6.6 ms; the d = 96 forward with a ring of two: below).
-#ifndef CSN_LB_NARROW
-#define CSN_LB_NARROW 4
-#endif
-#ifndef CSN_LB_X3FWD96
-#define CSN_LB_X3FWD96 1
-#endif
+// Measured and NOT taken in round 3 (profiles/HISTORY.md, 4b): one plane at d = 128 (+-0), two planes at d = 96 / 128 with the
+// default ring depth (38-82 spilled registers inside the loop: forward 3.8 -> 6.6 ms; the d = 96 forward with a ring of two: below).
 // (two planes, d = 96, FORWARD: with a fragment ring two deep instead of four it fits 128 registers with 4 spills)
-constexpr bool csn_attn_x3fwd96(int npl, int dt, bool bwd) { return CSN_LB_X3FWD96 && npl == 2 && dt == 3 && !bwd; }
+constexpr bool csn_attn_x3fwd96(int npl, int dt, bool bwd) { return npl == 2 && dt == 3 && !bwd; }
 constexpr int csn_attn_waves(int npl, int dt, bool bwd) {
-  return ((npl == 1 ? dt <= 3 : dt <= 2) || csn_attn_x3fwd96(npl, dt, bwd)) ? CSN_LB_NARROW : 2;
+  return ((npl == 1 ? dt <= 3 : dt <= 2) || csn_attn_x3fwd96(npl, dt, bwd)) ? 4 : 2;
 }
 template <typename PR, int DT, bool BWD, bool KVP, bool RC = false>
 __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
@@ -112,48 +88,33 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
   // plane pitch: 64 bytes of phase between hi and lo.  LDS STORES bank on 32 dwords (128 bytes): a staging instruction of the
   // tile-plane path writes the hi and the lo unit of a row together (lanes u and u + 4), and with the planes a multiple of
   // 128 bytes apart the two would land on the same banks (measured: SQ_LDS_BANK_CONFLICT = 15 % of the LDS cycles of both
-  // attention kernels, all of it these stores).  CSN_LDS_V=0 rebuilds the old image (128 bytes of phase) for A/B timing.
-#ifndef CSN_LDS_V
-#define CSN_LDS_V 1
-#endif
-// (1: the forward asks for the first K / V tile before it stages its operand block, 2: the backward too.  Measured: forward
-//  5.17 / 5.16 ms against 5.17 / 5.14 without, backward 7.41 / 7.33 against 7.14 / 7.06 — 53 spilled registers instead of 19;
-//  profiles/r4u_attention_prologue_and_priority.txt.  Off.)
-#ifndef CSN_PREFETCH_TILE0
-#define CSN_PREFETCH_TILE0 0
-#endif
-  constexpr int PLANE = D * KT + (CSN_LDS_V ? 32 : 64);
+  // attention kernels, all of it these stores).  The old image (128 bytes of phase) was measured in round 2 (+-0, 5.30 -> 5.28
+  // ms; profiles/HISTORY.md); removed with its switch.
+  // (Asking for the first K / V tile before the operand block is staged was measured in round 4: forward 5.17 / 5.16 ms against
+  //  5.17 / 5.14 without, backward 7.41 / 7.33 against 7.14 / 7.06 — 53 spilled registers instead of 19;
+  //  profiles/r4u_attention_prologue_and_priority.txt.  Removed with its switch.)
+  constexpr int PLANE = D * KT + 32;
   // [A | B][stage][plane hi/lo][row][32 keys] — one array, so that the prologue / epilogue can use all of it as a
   // [D rows][128 queries] fp32 staging block for 16-byte global accesses (which sets the size in the one-plane modes)
   // EARLY: the narrow instances (and every one-plane instance) request the tiles a whole segment earlier, into a second
   // register set — their matrix phases are too short to cover the HBM latency of a request made one phase before its use
-#ifndef CSN_EARLY
-#define CSN_EARLY 1
-#endif
-#ifndef CSN_EARLY_ALL
-#define CSN_EARLY_ALL 0
-#endif
   // Round 5: the two-plane d = 256 FORWARD too — its second register set costs no spills there (255 registers) — forward alone
   // 5.29 -> 5.22 ms, config-3 step 25.94 -> 25.76 ms over four alternations (profiles/r5q_forward_early_requests.txt); the
-  // backward at this width does not gain (-DCSN_EARLY_ALL=1: 7.00 -> 7.10 ms)
-#ifndef CSN_EARLY_FWD8
-#define CSN_EARLY_FWD8 1
-#endif
-  constexpr bool EARLY = CSN_EARLY && (NPL == 1 || DT <= 4 || CSN_EARLY_ALL || (CSN_EARLY_FWD8 && !BWD && !RC));
-  // LDS images: A x 2 stages, B x 2 (RC && EARLY: x 3 — the key-contiguous K image is then committed in segment 1 too, which
-  // needs a third stage), RC: + C x 2 (the K tile in tileA's form)
-  constexpr int NB_ST = (RC && EARLY) ? 3 : 2;
-  constexpr bool C_ALIASED = CSN_RC_ALIAS && RC && NPL == 2 && DT > 4;        // timing experiment: image C laid over image B
-  constexpr int TILE_EL = (2 + NB_ST + (RC && !C_ALIASED ? 2 : 0)) * NPL * PLANE, STAGE_EL = D * 128 * 2;
+  // backward at this width does not gain (7.00 -> 7.10 ms, measured in round 5; removed with its switch)
+  constexpr bool EARLY = NPL == 1 || DT <= 4 || (!BWD && !RC);
+  static_assert(!RC || EARLY, "score recomputation: early requests (where three LDS images per stage fit)");
+  // LDS images: A x 2 stages, B x 2 (RC: x 3 — the key-contiguous K image is then committed in segment 1 too, which needs a
+  // third stage), RC: + C x 2 (the K tile in tileA's form)
+  constexpr int NB_ST = RC ? 3 : 2;
+  constexpr int TILE_EL = (2 + NB_ST + (RC ? 2 : 0)) * NPL * PLANE, STAGE_EL = D * 128 * 2;
   static_assert(2 * (TILE_EL > STAGE_EL ? TILE_EL : STAGE_EL) <= 160 * 1024, "LDS budget of one CU");
   __shared__ __attribute__((aligned(16))) short tiles[TILE_EL > STAGE_EL ? TILE_EL : STAGE_EL];
   auto tileA = [&](int st, int pl) -> short* { return tiles + (st * NPL + pl) * PLANE; };
   auto tileB = [&](int st, int pl) -> short* { return tiles + ((2 + st) * NPL + pl) * PLANE; };
-  auto tileC = [&](int st, int pl) -> short* { return tiles + ((2 + (C_ALIASED ? 0 : NB_ST) + st) * NPL + pl) * PLANE; };
+  auto tileC = [&](int st, int pl) -> short* { return tiles + ((2 + NB_ST + st) * NPL + pl) * PLANE; };
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lq = lane & 15, kq = lane >> 4;
-  WGSTAMP(0);
   // XCD-aware work-group order.  A unit = one (evaluation, head, block); its QT query tiles all stream the same K/V
   // block, so they should share one XCD's L2.  Work-groups are dealt round-robin over the 8 XCDs, hence the QT tiles of
   // unit u get ids 8 * (QT * (u / 8) + qt) + (u % 8): same residue mod 8 (same XCD), adjacent in dispatch order.
@@ -289,7 +250,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
   constexpr int SWB = (KVP && NPL == 1) ? 1 : 0;        // one plane: a 16-lane store group covers rows r .. r + 3 — swap on bit 1
   // tileA chunk swap: rows r and r + 8 are read together by the transposing read, and the 8-byte stores of a 16-lane group
   // cover rows r, r + 1 of both planes — so the swap bit is (r >> 3) ^ r: both pairs then sit on complementary banks
-  const int t_sw = (CSN_LDS_V ? ((t_row >> 3) ^ (t_row >> SWB)) : (t_row >> 3)) & 1, t_swz = (-((t_row >> 2) & 3)) & 3;
+  const int t_sw = ((t_row >> 3) ^ (t_row >> SWB)) & 1, t_swz = (-((t_row >> 2) & 3)) & 3;
   const unsigned t_off = KVP ? (unsigned)(t_row * kld * 2 + t_c * 16) : (unsigned)(t_row * ldk + 4 * t_c) * 4u;
   // only the last piece can fall beyond the tile — and not even that one when the pieces fill the passes (compile-time: the
   // guards around the last piece's stores fold away)
@@ -317,13 +278,6 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
         g[i] = csn_bload4(rs, (i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off, (unsigned)(k0 + 64 * i * ldk) * 4u);
     }
   };
-  // The first tile's pieces are asked for BEFORE the operand block is staged (the stamps of the d = 256 forward: 21 k of a
-  // work-group's 135 k cycles were this prologue, most of it three memory round trips in a row — operand block, K tile, V
-  // tile — with nothing else in flight; profiles/r4u_attention_forward_stamps.txt): they travel beside the operand block and
-  // wait in registers until the staging block has been read
-  constexpr bool PRE0 = CSN_PREFETCH_TILE0 && !RC && !EARLY && (!BWD || CSN_PREFETCH_TILE0 > 1);      // (backward: 19 -> 53 spilled registers)
-  f32x4 gp[PRE0 ? NP_T : 1];
-  if constexpr (PRE0) { fetch_to(Ar, 0, g); fetch_to(Br, 0, gp); }
 
   // ---- register-resident operand R[d][q]: lane (q, kq) keeps rows d = 32 s + 8 kq + j as bf16 hi / lo ------
   // A wave-level memory instruction costs ~100 cycles of issue whatever its width, and the register layout would need
@@ -351,13 +305,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     }
   };
   auto pick = [&](int row) { return xbuf[row * 128 + ((((col >> 2) ^ (4 * ((row >> 3) & 1))) << 2) | (col & 3))]; };
-  PSTAMP(0);
   float rv[D / 4];
   if (BWD || it == it0) {                                          // (forward group: the operand of the first item serves them all)
     stage_in(Rr, p.r_fmt);
-    PSTAMP(1);
     __syncthreads();
-    PSTAMP(2);
 #pragma unroll
     for (int s = 0; s < D / 32; ++s)
 #pragma unroll
@@ -375,7 +326,6 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     for (int c = 0; c < D / 16; ++c) O[c] = f32x4v{0.f, 0.f, 0.f, 0.f};
     m_run = -INFINITY; m2_run = -INFINITY; l_run = 0.f;
   }
-  PSTAMP(3);
   float delta_q = 0.f;
   if (BWD) {
     const csn_rsrc_t Xr = map_rsrc(p.ctx, qs * p.q_shape_stride + head_off, p.ctx_fmt);
@@ -491,7 +441,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
   // row 8 kq + q' and the 4-key chunk that feeds score rows 4 p .. 4 p + 3: keys 8 p .. 8 p + 3 for S0, 8 p + 4 .. for S1
   // (chunks swapped inside their 16-byte unit when (row >> 3) & 1 = kq & 1 is set)
   const int tr_row = 8 * kq + (lq >> 2);
-  const int tr_sw = (CSN_LDS_V ? (kq ^ (lq >> (2 + SWB))) : kq) & 1;      // = the store side's swap bit of row tr_row (and of tr_row + 4)
+  const int tr_sw = (kq ^ (lq >> (2 + SWB))) & 1;      // = the store side's swap bit of row tr_row (and of tr_row + 4)
   const int a_pos0 = tr_row * KT + 8 * (lq & 3) + 4 * tr_sw, a_pos1 = tr_row * KT + 8 * (lq & 3) + 4 * (tr_sw ^ 1);
   // tileB: row lq of the 16-channel tile, 16-byte unit kq ^ ((-(lq >> 2)) & 3): keys 8 kq .. 8 kq + 7
   const int b_pos = lq * KT + 8 * (kq ^ ((-((lq >> 2) & 3)) & 3));
@@ -522,12 +472,9 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     }
   };
   // phase 1: T1[key][q] = sum_d tileA[d][key] R[d][q]
-#ifndef CSN_PD
-#define CSN_PD 4
-#endif
-  // LDS fragment reads run CSN_PD steps ahead of the matrix instructions that consume them (explicit register ring):
+  // LDS fragment reads run PD = 4 steps ahead of the matrix instructions that consume them (explicit register ring):
   // with two waves per SIMD nothing else hides the ~150-cycle LDS latency, and a step is only 48 matrix-pipe cycles.
-  constexpr int PD = csn_attn_x3fwd96(NPL, DT, BWD) ? 2 : CSN_PD;
+  constexpr int PD = csn_attn_x3fwd96(NPL, DT, BWD) ? 2 : 4;
   f32x4v Z0, Z1;                                        // RC: the recomputed scores of this lane's 8 keys (S0 / S1 hold dP)
   auto phase1_on = [&](const short* __restrict__ tAh, const short* __restrict__ tAl, const s16x8* Rh, const s16x8* Rl,
                        f32x4v& S0, f32x4v& S1) {
@@ -710,9 +657,8 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
   if constexpr (RC) {
     // three images: V (k-major, tileA), K (k-major, tileC) and K (key-contiguous, tileB).  Both k-major images are read in
     // segment 1, so both are committed in segment 1 of the tile before (see the hazard note below); the K pieces stay in
-    // registers (g2) until the key-contiguous image has taken them in segment 2 — or, EARLY, go into the third stage of that
-    // image in segment 1 as well (stage (kt + 1) % 3 was last read two tiles ago), which frees both register sets for the
-    // request of tile kt + 2 a whole segment earlier.
+    // go into the third stage of the key-contiguous image in segment 1 as well (stage (kt + 1) % 3 was last read two tiles
+    // ago), which frees both register sets for the request of tile kt + 2 a whole segment earlier.
     fetch_to(Ar, 0, g); commitA_to(tileA(0, 0), tileA(0, NPL - 1), g);
     fetch_to(Br, 0, g2); commitA_to(tileC(0, 0), tileC(0, NPL - 1), g2); commitB_from(0, g2, false);
     if (nkt > 1) { fetch_to(Ar, 1, g); fetch_to(Br, 1, g2); }
@@ -721,27 +667,12 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     fetch_to(Br, 0, g2); commitB_from(0, g2);
     if (nkt > 1) fetch_to(Ar, 1, g);
   } else {
-    PSTAMP(4);
-    if constexpr (PRE0) {
-      commitA(0); commitB_from(0, gp);
-    } else {
-      fetch(Ar, 0); commitA(0);
-      PSTAMP(5);
-      fetch(Br, 0); commitB(0);
-    }
-    PSTAMP(6);
+    fetch(Ar, 0); commitA(0);
+    fetch(Br, 0); commitB(0);
     if (nkt > 1) fetch(Ar, 1);
   }
   __syncthreads();
-  PSTAMP(7);
 
-  // -DCSN_STAMPS: development build that records s_memtime at the phase boundaries of tiles 4..7 (scripts/attn_stamps.py)
-#ifdef CSN_STAMPS
-#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (dbg_on) stamps[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-  unsigned long long stamps[8];
-#else
-#define STAMP(i)
-#endif
   // Staggered schedule.  A tile is two barrier-delimited segments,
   //   seg 1: phase 1 (matrix)              + commit K tile kt+1, request V tile kt+1
   //   seg 2: pointwise (vector) + phase 2  + commit V tile kt+1, request K tile kt+2
@@ -750,41 +681,27 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
   // starts with its vector work, instead of two waves fighting over the same pipe.  With the commits placed as above the
   // shift is hazard-free: a K stage is rewritten in segments 2kt / 2kt+1 (early / late half), last read in 2kt-1 and
   // next read in 2kt+2; a V stage is rewritten in 2kt+1 / 2kt+2, last read in 2kt and next read in 2kt+3.
-  WGSTAMP(1);
   // Static priority for the late half.  The stamps of the d = 256 forward (profiles/r4u_attention_forward_stamps.txt): waves 4..7
   // — dispatched second, the losers of the SIMD's age-ordered issue arbitration — spend 5.65 k cycles of a tile working and
   // 0.5 k at barriers, waves 0..3 4.4 k and 2.1 k: the older half waits for the younger at both barriers of every tile.
   // Measured with s_setprio 1 on the late half: forward 5.26 / 5.20 ms against 5.25 / 5.17, backward 7.32 / 7.16 against 7.05 /
-  // 7.32 — nothing (profiles/r4u_attention_prologue_and_priority.txt).  Off.
-#ifndef CSN_LATE_PRIO
-#define CSN_LATE_PRIO 0
-#endif
-  if (late) {
-    if (CSN_LATE_PRIO) __builtin_amdgcn_s_setprio(CSN_LATE_PRIO);
-    __syncthreads();
-  }
+  // 7.32 — nothing (profiles/r4u_attention_prologue_and_priority.txt); removed with its switch.
+  if (late) __syncthreads();
   // (a two-tiles-per-trip form of this loop, with the LDS stage a compile-time constant, was built and dropped: at d = 256 it
   //  spilled 28 registers in the forward and 82 in the backward kernel)
   for (int kt = 0; kt < nkt; ++kt) {
     const int cur = kt & 1, nxt = cur ^ 1;
-    const int b_cur = (RC && EARLY) ? kt % 3 : cur, b_nxt = (RC && EARLY) ? (kt + 1) % 3 : nxt;     // stage of the key-contiguous image
+    const int b_cur = RC ? kt % 3 : cur, b_nxt = RC ? (kt + 1) % 3 : nxt;     // stage of the key-contiguous image
     const bool more = kt + 1 < nkt;
-#ifdef CSN_STAMPS
-    const bool dbg_on = (BWD == (CSN_STAMPS != 0)) && DT == 8 && blockIdx.x < 2048 && kt >= 4 && kt < 8;   // -DCSN_STAMPS=0: forward, =1: backward
-#endif
-    STAMP(0);
     // (requesting the NEXT tile's saved scores right after this tile's pointwise — a phase earlier — was measured in the
     //  backward: 16 more spilled registers inside the loop, 6.8 -> 9.4 ms; the request stays at the top of its own trip)
     load_sv(kt);
     phase1(cur);
-    STAMP(1);
     if constexpr (RC) {
       if (more) {
         commitA_to(tileA(nxt, 0), tileA(nxt, NPL - 1), g); commitA_to(tileC(nxt, 0), tileC(nxt, NPL - 1), g2);
-        if constexpr (EARLY) {
-          commitB_from(b_nxt, g2, false);
-          if (kt + 2 < nkt) { fetch_to(Ar, kt + 2, g); fetch_to(Br, kt + 2, g2); }
-        }
+        commitB_from(b_nxt, g2, false);
+        if (kt + 2 < nkt) { fetch_to(Ar, kt + 2, g); fetch_to(Br, kt + 2, g2); }
       }
     } else if constexpr (EARLY) {
       if (more) {
@@ -795,40 +712,24 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     } else {
       if (more) { commitA(nxt); fetch(Br, kt + 1); }
     }
-    STAMP(2);
     __syncthreads();
-    STAMP(3);
     pointwise(kt);
-    STAMP(4);
     phase2(b_cur);
-    STAMP(5);
     if constexpr (RC) {
-      if constexpr (!EARLY) {
-        if (more) { commitB_from(nxt, g2, false); if (kt + 2 < nkt) { fetch_to(Ar, kt + 2, g); fetch_to(Br, kt + 2, g2); } }
-      }
+      // (the key-contiguous K image of tile kt + 1 was committed in segment 1)
     } else if constexpr (EARLY) {
       if (more) commitB_from(nxt, g2);
     } else {
       if (more) { commitB(nxt); if (kt + 2 < nkt) fetch(Ar, kt + 2); }
     }
-    STAMP(6);
     __syncthreads();
-    STAMP(7);
-#ifdef CSN_STAMPS
-    if (dbg_on && lane == 0) {
-      for (int i = 0; i < 8; ++i) csn_dbg[((blockIdx.x * 8 + wave) * 4 + (kt - 4)) * 8 + i] = stamps[i];
-    }
-#endif
   }
 
   if (!late) __syncthreads();                           // pairs with the last barrier of the late half: tiles are idle now
-  else if (CSN_LATE_PRIO) __builtin_amdgcn_s_setprio(0);
   if constexpr (!BWD) write_out();                      // (the barrier that ends the next item's prologue separates its tile commits from this)
   }                                                     // next item of the group (its prologue reuses the tiles as staging)
 
-  WGSTAMP(2);
   if constexpr (BWD) write_out();
-  WGSTAMP(3);
 }
 
 template <typename PR, int DT>

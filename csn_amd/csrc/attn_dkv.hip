@@ -20,20 +20,10 @@
 #include "csn_common.h"
 #include "csn_kernels.h"
 
-#ifdef CSN_DKV_STAMPS
-// -DCSN_DKV_STAMPS: development build that records s_memtime at the phase boundaries of tiles 4..7 of 1024 work-groups of the
-// d = 96 one-plane instances (scripts/dkv_stamps.py)
-__device__ unsigned long long csn_dkv_dbg[1024 * 8 * 4 * 8];
-extern "C" __attribute__((visibility("default"))) int csn_dkv_debug_read(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_dkv_dbg), bytes); }
-#define DSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (dbg_on) dstamps[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DSTAMP(i)
-#endif
-
 namespace {
 
 constexpr int QT = 32;               // queries per streamed tile
-// keys per work-group = 16 per wave: 128 (8 waves), or 64 (4 waves) where three such work-groups fit a CU (csn_dkv_waves)
+// keys per work-group = 16 per wave and key group: 128 (8 waves; 256 with two key groups per wave)
 constexpr float LOG2E = 1.4426950408889634f;
 
 using namespace csn_mode;
@@ -72,23 +62,13 @@ CSN_DEVINL f32x4v mma16(s16x8 ah, s16x8 al, s16x8 bh, s16x8 bl, f32x4v c) {
 // converted to bf16 at the commit) and dO in bf16 — a compile-time property: a format branch inside the tile loop costs the
 // kernel its schedule (measured: 3.7 -> 5.2 ms at config-5 geometry)
 // Occupancy.  At d = 96 one plane the kernel needs ~175 registers: two waves per SIMD, ONE work-group of 8 waves per CU.  Both
-// ways to more resident waves were built and measured at config-5 geometry (scripts/dev/ab_attn.sh, ab_step.sh) and lose:
+// ways to more resident waves were built and measured at config-5 geometry (profiles/HISTORY.md, 4b) and lose:
 // the register bound of four waves per SIMD spills 96 registers (4.2 -> 15.5 ms); work-groups of four waves / 64 keys
-// (-DCSN_DKV_NW=4: three per CU under a bound of 168 registers) stage every tile for half as many keys and still spill 32
-// registers (3.7 -> 6.0 ms).  The default stays 8 waves, two per SIMD.  NARROW (one plane, d <= 64): there the kernel does fit
-// 128 registers without spills once the fragment rings are one deep and the phase-2 reads follow the pointwise segment, so
-// these instances run under the four-wave bound: two work-groups per CU.
-#ifndef CSN_DKV_NW
-#define CSN_DKV_NW 8
-#endif
-#ifndef CSN_DKV_NARROW
-#define CSN_DKV_NARROW 1
-#endif
-constexpr int csn_dkv_waves(int npl, int dt) { return (npl == 1 && dt <= 3) ? CSN_DKV_NW : 8; }
-#ifndef CSN_DKV_NARROW_MAXDT
-#define CSN_DKV_NARROW_MAXDT 2
-#endif
-constexpr bool csn_dkv_narrow(int npl, int dt) { return CSN_DKV_NARROW && npl == 1 && dt <= CSN_DKV_NARROW_MAXDT; }
+// (three per CU under a bound of 168 registers) stage every tile for half as many keys and still spill 32 registers
+// (3.7 -> 6.0 ms); removed with its switch.  The kernel runs 8 waves, two per SIMD.  NARROW (one plane, d <= 64): there the
+// kernel does fit 128 registers without spills once the fragment rings are one deep and the phase-2 reads follow the pointwise
+// segment, so these instances run under the four-wave bound: two work-groups per CU.
+constexpr bool csn_dkv_narrow(int npl, int dt) { return npl == 1 && dt <= 2; }
 // DR: dropout live (a compile-time property since round 6: as a run-time flag every element of the pointwise segment carried its
 // own wave-uniform branch around the keep decision — sixteen branch instructions per tile in a loop that is bound by the
 // number of instructions a wave issues)
@@ -98,10 +78,10 @@ constexpr bool csn_dkv_narrow(int npl, int dt) { return CSN_DKV_NARROW && npl ==
 // work-group stages each tile for twice the keys: per key half the LDS reads, commits, requests, barriers and scalar work.
 // Costs 88 registers (operands, accumulators, S / dP of the second group): the one-plane d = 96 instance has them.
 template <typename PR, int DT, int QF = 0, int NW = 8, bool DR = true, int G = 1>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT) ? 4 : 2)) void csn_attn_dkv_kernel(CsnAttnDkvArgs p) {
+__global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void csn_attn_dkv_kernel(CsnAttnDkvArgs p) {
   constexpr bool NARROW = csn_dkv_narrow(PR::NPL, DT);
   static_assert(QF == 0 || PR::NPL == 1, "16-bit activation maps: the one-plane mode");
-  static_assert(NW == 8 || NW == 4, "work-groups of 8 or 4 waves");
+  static_assert(NW == 8, "work-groups of 8 waves");
   constexpr int NT = 64 * NW;                           // threads
   constexpr int KW = 16 * NW * G;                       // keys per work-group
   constexpr int NPL = PR::NPL;
@@ -136,14 +116,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
   const long long kslot = p.kv_index ? p.kv_index[e_first] : e_first;
   const int nqt = (T + QT - 1) / QT;
   const int n_steps = (it1 - it0) * nqt;
-#ifndef CSN_DKV_LOCKSTEP
-#define CSN_DKV_LOCKSTEP 0
-#endif
-#ifndef CSN_DKV_ABL        // timing-only ablations (WRONG results): 1 no tile loads, 2 no pointwise, 4 no phase 2, 8 no phase 1
-#define CSN_DKV_ABL 0
-#endif
-  // (-DCSN_DKV_LOCKSTEP=1, measured: all waves in step, ONE barrier per tile instead of two and no stagger)
-  const bool late = !CSN_DKV_LOCKSTEP && __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
+  // (all waves in step, ONE barrier per tile instead of two and no stagger, was measured in round 6
+  //  (profiles/r6_dkv_kernel.txt); removed with its switch)
+  const bool late = __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
   const int col0 = 16 * G * wave + lq;                              // this lane's (first) key inside the chunk; group g: + 16 g
   const int key0 = kc * KW + col0;                                  // ... inside the block
 
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
     const unsigned off = (q_first + 4 * t_c) < T ? t_off : CSN_OOB;                   // T % 4 == 0: a piece is all in or all out
 #pragma unroll
     for (int i = 0; i < NP_T; ++i) {
-      const unsigned o = ((CSN_DKV_ABL & 1) || (i == NP_T - 1 && !t_last_ok)) ? CSN_OOB : off;
+      const unsigned o = (i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off;
       if constexpr (q_fmt != 0) hQ[i] = csn_bload2(Qr_it, o == CSN_OOB ? o : o * 2u, (unsigned)(q_first + RPT * i * ld) * 2u);
       else gQ[i] = csn_bload4(Qr_it, o == CSN_OOB ? o : o * 4u, (unsigned)(q_first + RPT * i * ld) * 4u);
       if constexpr (o_fmt != 0) hO[i] = csn_bload2(Or_it, o == CSN_OOB ? o : o * 2u, (unsigned)(q_first + RPT * i * ld) * 2u);
@@ -342,18 +317,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
   // fragment reads of the two images run PD1 / PD2 steps ahead of the matrix instructions in one register ring each, and a phase
   // pays the LDS latency once.  At the narrow head widths a phase is only 2 x D/16 matrix instructions, so what a tile costs
   // is the number of such exposed latencies, not the matrix work.
-  // Ring depths.  Round 6 measured deeper rings on the one-plane instances (-DCSN_DKV_PD1=4 -DCSN_DKV_PD2=6: ALL of phase 2's
-  // fragments requested before the pointwise segment, 203 registers at d = 96): phase 2 655 -> 584 cycles by the stamps, the
-  // pointwise segment behind the twelve reads 436 -> 655, the config-5 step +-0 (profiles/r6_dkv_kernel.txt) — the phases are
-  // not waiting for LDS, the SIMD's two waves are waiting for each other's vector and matrix issue.  Two deep stays.
-#ifndef CSN_DKV_PD1
-#define CSN_DKV_PD1 2
-#endif
-#ifndef CSN_DKV_PD2
-#define CSN_DKV_PD2 2
-#endif
-  constexpr int PD1 = NARROW ? 1 : (NPL == 1 ? CSN_DKV_PD1 : 2);
-  constexpr int PD2 = NARROW ? 1 : (NPL == 1 ? CSN_DKV_PD2 : 2);
+  // Ring depths.  Round 6 measured deeper rings on the one-plane instances (4 and 6: ALL of phase 2's fragments requested
+  // before the pointwise segment, 203 registers at d = 96): phase 2 655 -> 584 cycles by the stamps, the pointwise segment
+  // behind the twelve reads 436 -> 655, the config-5 step +-0 (profiles/r6_dkv_kernel.txt) — the phases are not waiting for
+  // LDS, the SIMD's two waves are waiting for each other's vector and matrix issue.  Two deep stays; removed with its switch.
+  constexpr int PD1 = NARROW ? 1 : 2;
+  constexpr int PD2 = NARROW ? 1 : 2;
   // phase 1: S[q][key] = sum_d Qs^T[d][q] K^T[d][key]  and  dP[q][key] = sum_d dO^T[d][q] V^T[d][key]   (images 0 and 1)
   f32x4v S0[G], S1[G], P0[G], P1[G];                                // phase 1's accumulators: S and dP of the tile, per key group
   auto phase1 = [&](int st) {
@@ -451,7 +420,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
     // here: the even lane hashes queries 0..3, the odd lane 4..7, and a quad swap hands each the other's four — half the
     // quarter-rate multiplies of the pointwise segment for four full-rate moves.
     unsigned hsh[8];
-    if (drop && !(CSN_DKV_ABL & 2)) {
+    if (drop) {
       unsigned mine[4], theirs[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) mine[j] = csn_pair_hash(pw_key + (unsigned)(8 * g * mp) + (unsigned)(q0 + (key_odd ? 4 : 0) + j), salt);
@@ -462,7 +431,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-      if (CSN_DKV_ABL & 2) { pd[r] = sv[r]; ds[r] = dp[r]; continue; }
       const float pv = __builtin_amdgcn_exp2f(fmaf(sv[r], LOG2E, -lse2[r]));  // softmax probability (csa_models.py:141)
       bool keep = true;
       if (drop) keep = (key_odd ? (hsh[r] >> 16) : (hsh[r] & 0xffffu)) >= thr16;
@@ -503,38 +471,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
       const int e = p.eval_ids ? p.eval_ids[c_it] : c_it;
       salt = csn_block_salt((unsigned long long)(((long long)e * p.H + hd) * p.n_blocks + blk), p.seed);
     }
-#ifdef CSN_DKV_STAMPS
-    unsigned long long dstamps[8];
-    const bool dbg_on = DT == 3 && PR::NPL == 1 && blockIdx.x >= 2048 && blockIdx.x < 3072 && step >= 4 && step < 8;
-#endif
-    DSTAMP(0);
-    if (!(CSN_DKV_ABL & 8)) phase1(cur);                                    // S = Qs K^T (the forward's product, roles transposed), dP = dO V^T
-    DSTAMP(1);
+    phase1(cur);                                                    // S = Qs K^T (the forward's product, roles transposed), dP = dO V^T
     if (more) {
       commit_kmajor(nxt);                                           // (splits the pieces: the fp32 registers are free again)
       commit_rowc(rc_nxt);
       if (step + 2 < n_steps) fetch();                              // a whole tile ahead of its first use
     }
-    DSTAMP(2);
-    if (!CSN_DKV_LOCKSTEP) __syncthreads();
-    DSTAMP(3);
+    __syncthreads();
     if constexpr (!NARROW) phase2_ahead(cur);
     pointwise(c_qt, salt, rc_cur);
-    DSTAMP(4);
     if constexpr (NARROW) phase2_ahead(cur);                         // (register diet: nothing of phase 2 lives across the pointwise segment)
-    if (!(CSN_DKV_ABL & 4)) phase2();                                                       // dV^T += dO^T P_drop,  dK^T += Qs^T dS
-    else { dV[0][0][0] += from16<PR::HALF>(ph[0][0]) + from16<PR::HALF>(ph[0][7]); dK[0][0][0] += from16<PR::HALF>(dh[0][0]) + from16<PR::HALF>(dh[0][7]); }
-    DSTAMP(5);
+    phase2();                                                       // dV^T += dO^T P_drop,  dK^T += Qs^T dS
     if (more) commit_contig(nxt);
     if (++c_qt == nqt) { c_qt = 0; ++c_it; }
     rc_cur = rc_nxt;
-    DSTAMP(6);
     __syncthreads();
-    DSTAMP(7);
-#ifdef CSN_DKV_STAMPS
-    if (dbg_on && lane == 0)
-      for (int i = 0; i < 8; ++i) csn_dkv_dbg[(((blockIdx.x - 2048) * 8 + wave) * 4 + (step - 4)) * 8 + i] = dstamps[i];
-#endif
   }
   if (!late) __syncthreads();                                       // pairs with the last barrier of the late half
 
@@ -590,17 +541,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (csn_dkv_narrow(PR::NPL, DT)
   store_out(dV, p.dv, ovslot);
 }
 
-#ifndef CSN_DKV_G2
-#define CSN_DKV_G2 1
-#endif
 // two 16-key groups per wave where the registers allow: one plane, d = 96 (the instances below it run two work-groups per CU
 // under the four-wave bound instead, the ones above it and the two-plane ones have no room)
-constexpr int csn_dkv_groups(int npl, int dt, int nw) { return (CSN_DKV_G2 && npl == 1 && dt == 3 && nw == 8) ? 2 : 1; }
+constexpr int csn_dkv_groups(int npl, int dt) { return (npl == 1 && dt == 3) ? 2 : 1; }
 
 template <typename PR, int DT, bool DR>
 int launch_dt(const CsnAttnDkvArgs& a, hipStream_t st) {
-  constexpr int NW = csn_dkv_waves(PR::NPL, DT);
-  constexpr int G = csn_dkv_groups(PR::NPL, DT, NW);
+  constexpr int NW = 8;
+  constexpr int G = csn_dkv_groups(PR::NPL, DT);
   const long long units = (long long)a.n_blocks * a.H * a.n_groups;
   const int KC = (a.T + 16 * NW * G - 1) / (16 * NW * G);
   dim3 grid((unsigned)(((units + 7) / 8) * 8 * KC));

@@ -132,7 +132,10 @@ int csn_dev_set(int key, int value) {
     case CSN_DEV_BIG_TILES: csn_gemm_big_tiles = value; break;
     case CSN_DEV_WIDE_GEMM: csn_gemm_wide = value; break;
     case CSN_DEV_WIDE_FORMS: csn_gemm_wide_set = value; break;
-    case CSN_DEV_WX: csn_dev_wx = value; break;
+    case CSN_DEV_WX:
+      if (value & ~(1 | 4 | 8)) return CSN_E_ARG;                   // only the bits of csn_hip.h: the setting stays as it was
+      csn_dev_wx = value;
+      break;
     case CSN_DEV_LNB_GROUP: csn_dev_lnb_group = value < 0 ? 0 : value; break;
     default: return CSN_E_ARG;
   }

@@ -63,17 +63,14 @@ CSN_DEVINL void csn_bstore4(f32x4 v, csn_rsrc_t r, unsigned voff, unsigned soff 
   if (!__builtin_constant_p(soff)) csn_store_guard(v);
 }
 // streaming forms for bytes that are written once and read once much later (the saved scores, the P / dS planes).
-// -DCSN_NT=1 gives them the nt cache policy (aux bit 1) so that they do not push the K / V tiles out of the XCD's L2:
-// measured over the whole step it changes nothing in time (28.93 vs 28.94 ms, same box) and WRITES 9 % MORE to HBM
-// (the two 16-byte stores a lane makes into one 32-byte sector are no longer merged in L2) — off by default.
-#ifndef CSN_NT
-#define CSN_NT 0
-#endif
+// The nt cache policy (aux bit 1), so that they do not push the K / V tiles out of the XCD's L2, was measured in round 2
+// (profiles/HISTORY.md): over the whole step it changes nothing in time (28.93 vs 28.94 ms, same box) and WRITES 9 % MORE to
+// HBM (the two 16-byte stores a lane makes into one 32-byte sector are no longer merged in L2); removed with its switch.
 CSN_DEVINL f32x4 csn_bload4_stream(csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CSN_NT ? 2 : 0));
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 CSN_DEVINL void csn_bstore4_stream(f32x4 v, csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, CSN_NT ? 2 : 0);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
   if (!__builtin_constant_p(soff)) csn_store_guard(v);
 }
 // 8-byte (4 x bf16) and 2-byte (1 x bf16) accesses for split-bf16 planes

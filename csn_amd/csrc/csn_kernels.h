@@ -43,8 +43,6 @@ struct CsnWxArgs {
   int n_items, n_points, n_sets;
   int div_rows;  float div_val;  float div_rcp;  int div_exact;   // rows < div_rows are divided by div_val (exact as * div_rcp when it is a power of two)
   int tb;                                                 // tile planes: points per attention block
-  int stagger = 0;                                        // waves 4..7 half an iteration behind waves 0..3 (development; filled in by the launcher)
-  int ablate = 0;                                         // development: timing-only ablations (bits 4..7 of CSN_DEV_WX)
   // out_mode 3 — out-projection + fc dropout + residual + LayerNorm (csa_models.py:115-118): x = Ctx^T, w = W_fc, out = xhat
   const float* res = nullptr;  long long res_shape_stride = 0;  const int* res_index = nullptr;   // residual x[shape][256][ldo]
   float* rstd = nullptr;                                  // [item][n_points]
@@ -111,12 +109,9 @@ struct CsnAttnArgs {
   int sc_layout = 0;
 };
 // score recomputation needs three LDS tile images per stage: one plane at every width, two planes up to d = 128
-// (-DCSN_RC_ALIAS=1, TIMING EXPERIMENT ONLY — results are wrong: the two-plane d = 256 instance is built with its third image
-//  laid over the second, to price a one-K-image recomputing kernel before writing it; profiles/r4r_recompute_d256_experiment.txt)
-#ifndef CSN_RC_ALIAS
-#define CSN_RC_ALIAS 0
-#endif
-constexpr bool csn_attn_recompute_fits(int planes, int dt) { return planes == 1 || dt <= 4 || CSN_RC_ALIAS; }
+// (a two-plane d = 256 instance with its third image laid over the second — a timing build with wrong results — was measured
+//  in round 4: 167 spilled registers, 7.2 -> 24.7 ms; profiles/r4r_recompute_d256_experiment.txt; removed with its switch)
+constexpr bool csn_attn_recompute_fits(int planes, int dt) { return planes == 1 || dt <= 4; }
 // ---- key-stationary dK / dV with recomputed scores (attn_dkv.hip; 16-bit modes, block mode, d <= 128) ----------------
 struct CsnAttnDkvArgs {
   const float* q;     long long q_shape_stride;  const int* q_index;     // pre-scaled queries Qs^T [slot][H*d][ld], evaluation -> slot
@@ -205,7 +200,6 @@ struct CsnWxLnbArgs {
   float* dctx; long long dctx_eval_stride;                     // [e][256][ld]
   int n_items, n_points, e_base;                               // evaluations e_base .. e_base + n_items - 1
   float dropout_p; unsigned long long seed;
-  int ablate = 0;
 };
 bool csn_wx_lnb_takes(const CsnLnBwdArgs& a, int d_inner);
 int csn_launch_wx_lnb(const CsnWxLnbArgs& a, hipStream_t st);

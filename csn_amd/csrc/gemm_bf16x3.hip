@@ -27,19 +27,6 @@
 #include "csn_kernels.h"
 #include "csn_window.h"
 
-// -DCSN_STAMPS: development build that records s_memtime after the prologue, the main loop and the epilogue of every
-// work-group (scripts/gemm_stamps.py)
-#ifdef CSN_STAMPS
-__device__ unsigned long long csn_gdbg[65536 * 8];
-extern "C" __attribute__((visibility("default"))) int csn_gemm_debug_read(void* dst, long long bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csn_gdbg), bytes); }
-#define GSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); gst[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-// 256 x 256 kernel: entry, tile loop start, tile loop end, [LN: after the residual pass, after the variance pass], exit
-#define BSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && blockIdx.x < 8192) csn_gdbg[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define GSTAMP(i)
-#define BSTAMP(i)
-#endif
-
 namespace {
 
 using namespace csn_mode;
@@ -81,10 +68,6 @@ __global__ __launch_bounds__(256, 2) void csn_gemm_bf16x3_kernel(CsnGemmArgs p) 
   __shared__ __attribute__((aligned(16))) short Bs[2][NPL][B_EL];   // NK: [stage][plane][col][k]   KN: [stage][plane][k][col]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef CSN_STAMPS
-  unsigned long long gst[4], gin[4] = {0, 0, 0, 0}, gt0 = 0, gt1 = 0;
-#endif
-  GSTAMP(0);
   const int l31 = lane & 31, h = lane >> 5;
   const int wm0 = (wave >> 1) * (BM / 2), wn0 = (wave & 1) * (BN / 2);
 
@@ -242,17 +225,8 @@ __global__ __launch_bounds__(256, 2) void csn_gemm_bf16x3_kernel(CsnGemmArgs p) 
   if (nk > 0) { load_slab(0); store_slab(0, 0); }
   if (nk > 1) load_slab(BK);
   __syncthreads();
-  GSTAMP(1);
-#ifdef CSN_STAMPS
-#define GIN(i, a, b) do { __builtin_amdgcn_sched_barrier(0); a = __builtin_amdgcn_s_memtime(); gin[i] += a - b; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define GIN(i, a, b)
-#endif
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-#ifdef CSN_STAMPS
-    __builtin_amdgcn_sched_barrier(0); gt0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       s16x8 ah[MT], al[MT], bh[NT], bl[NT];
@@ -286,18 +260,13 @@ __global__ __launch_bounds__(256, 2) void csn_gemm_bf16x3_kernel(CsnGemmArgs p) 
     }
     // slab kt + 1 (loaded one iteration ago) is split and written into the other stage while the matrix pipe drains;
     // slab kt + 2 starts its trip from HBM
-    GIN(0, gt1, gt0);
     if (kt + 1 < nk) {
       store_slab(cur ^ 1, (kt + 1) * BK);
-      GIN(1, gt0, gt1);
       if (kt + 2 < nk) load_slab((kt + 2) * BK);
     }
-    GIN(3, gt1, gt0);
     __syncthreads();
-    GIN(2, gt0, gt1);
   }
 
-  GSTAMP(2);
   const float alpha = p.alpha;
   // output positions: the lane's part (its column, its half's 4-row shift; columns beyond N switched off) in cv[j], the row of
   // accumulator (i, r) as a scalar offset c_so(i, r), rows beyond M cut off by the window Cw — no per-element offset registers
@@ -381,11 +350,6 @@ __global__ __launch_bounds__(256, 2) void csn_gemm_bf16x3_kernel(CsnGemmArgs p) 
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) csn_bstore(acc[i][j][r], Cw, cv[j], c_so(i, r));
-#ifdef CSN_STAMPS
-  __builtin_amdgcn_s_waitcnt(0);
-  GSTAMP(3);
-  if (tid == 0 && blockIdx.x < 65536) for (int i = 0; i < 4; ++i) { csn_gdbg[blockIdx.x * 8 + i] = gst[i]; csn_gdbg[blockIdx.x * 8 + 4 + i] = gin[i]; }
-#endif
 }
 
 // ---- 256 x 256 x 32 tiles, 8 waves -----------------------------------------------------------------------------------
@@ -423,7 +387,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
-  BSTAMP(0);
   const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 128;
 
   const int tiles_n = (p.N + BN - 1) / BN, tiles = tiles_n * ((p.M + BM - 1) / BM);
@@ -585,7 +548,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
   const int tr_base = (8 * (grp >> 1) + gq) * PN + 16 * (grp & 1) + 4 * gp;
 
   const int nk = (K + BK - 1) / BK;
-  BSTAMP(1);
   for (int it = it0; it < it1; ++it) {
   if (it > it0) {
     __syncthreads();                                    // the previous item's last slab has been read by every wave
@@ -634,7 +596,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
   }
   }
 
-  BSTAMP(2);
   // per-wave 16 KB of LDS for the epilogues (the tile loop is over; waves 0..3 take As, 4..7 Bs): 32 rows x 128 columns fp32
   float* wbuf = reinterpret_cast<float*>(wave < 4 ? reinterpret_cast<char*>(As_raw) : reinterpret_cast<char*>(Bs_raw))
                 + (wave & 3) * 4096;
@@ -681,7 +642,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
       if (h == 0) red[wmi * 256 + nl] = s1;
     }
     __syncthreads();
-    BSTAMP(3);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int nl = wn0 + 32 * j + l31;
@@ -698,7 +658,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
       if (h == 0) red[1024 + wmi * 256 + nl] = s2;
     }
     __syncthreads();
-    BSTAMP(4);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int nl = wn0 + 32 * j + l31;
@@ -736,7 +695,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
       s += __shfl_xor(s, 1, 64);
       if ((tid & 1) == 0) q.sum_ws[((long long)z2 * tiles_n + tile_n) * 256 + (tid >> 1)] = s;
     }
-    BSTAMP(5);
     return;
   }
 
@@ -810,7 +768,6 @@ __global__ __launch_bounds__(512, 2) void csn_gemm_bf16x3_big_kernel(CsnGemmArgs
       for (int t = 0; t < 16; ++t) csn_bstore4(vals[t], Cr, off[t]);
     }
   }
-  BSTAMP(5);
 }
 
 // ---- 256 x 256 x 32 tiles on SIXTEEN waves ---------------------------------------------------------------------------

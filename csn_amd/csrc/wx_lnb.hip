@@ -92,7 +92,7 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
   auto locate = [&](const Cursor& c, int& col0, int& valid, unsigned& item) {
     const bool exists = c.q < q_end;
     col0 = exists ? (int)(c.tile * WX_CH) : 0;
-    valid = exists && !(p.ablate & 4) ? min(WX_CH, p.n_points - col0) : 0;
+    valid = exists ? min(WX_CH, p.n_points - col0) : 0;
     item = __builtin_amdgcn_readfirstlane(exists ? c.item : 0u);
   };
   // a chunk of xhat (4 pieces) and its 4 rstd values into a register set of 5
@@ -138,10 +138,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
       fl = join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a + WX_PLANE)),
                  __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a + WX_PLANE + 4 * WX_CH)));
     };
-    if (p.ablate & 1) {
-      acc[0] = __builtin_bit_cast(float, (int)xh[0]);
-      return acc;
-    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < WX_PD; ++s) rd(s, bh[s], bl[s]);
@@ -162,7 +158,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
   auto epilogue = [&](const Cursor& cu, const f32x16& acc) {
     int col0, valid; unsigned item;
     locate(cu, col0, valid, item);
-    if (p.ablate & 2) valid = 0;
     const bool n_ok = 4 * c8 < valid;
     const u32x4 Or = wx_rsrc(p.dctx + (long long)(p.e_base + item) * p.dctx_eval_stride, (long long)256 * ld * 4);
 #pragma unroll
@@ -185,7 +180,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
   auto commit = [&](auto wait_c, int stage, f32x4* R, const Cursor& cu, const Cursor& cg) __attribute__((always_inline)) {
     int col0, valid; unsigned item;
     locate(cu, col0, valid, item);
-    if (p.ablate & 2) valid = 0;
     const unsigned e = (unsigned)p.e_base + item;
     const bool dense = (int)e < p.n_dense;
     if (item != cst_item) {                                  // (work-group uniform; once per item and stream: every wave is past the
@@ -317,12 +311,10 @@ bool csn_wx_lnb_takes(const CsnLnBwdArgs& a, int d_inner) {
 int csn_launch_wx_lnb(const CsnWxLnbArgs& a, hipStream_t st) {
   if (a.n_items <= 0 || a.n_points <= 0) return 0;
   if ((long long)a.n_items * ((a.n_points + WX_CH - 1) / WX_CH + 16) * 2 >= (1ll << 31)) return CSN_NOT_TAKEN;
-  CsnWxLnbArgs b = a;
-  b.ablate = (csn_dev_wx >> 4) & 15;
   const int grid = wx_grid();
   // (always the instance with the mask code: at p = 0 the threshold is 0 and the scale 1 — every element kept, times 1.0.  The
   //  instances without it compile to 90 spilled registers: the scheduler then hoists the whole commit's loads)
-  if (a.dz_res) hipLaunchKernelGGL((csn_wx_lnb_kernel<true, true>), dim3(grid), dim3(512), 0, st, b);
-  else hipLaunchKernelGGL((csn_wx_lnb_kernel<true, false>), dim3(grid), dim3(512), 0, st, b);
+  if (a.dz_res) hipLaunchKernelGGL((csn_wx_lnb_kernel<true, true>), dim3(grid), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((csn_wx_lnb_kernel<true, false>), dim3(grid), dim3(512), 0, st, a);
   return (int)hipGetLastError();
 }

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
     const bool exists = cu.q < q_end;
     int col0, valid;
     locate(cu, col0, valid);
-    if (valid < 0 || !exists || (p.ablate & 4)) valid = 0;
+    if (valid < 0 || !exists) valid = 0;
     const unsigned item = exists ? cu.item : 0u;
     if (!exists) col0 = 0;
     const u32x4 Xr = wx_rsrc(p.x + (long long)item * p.x_item_stride + col0, ((long long)(WX_K - 1) * p.ldx + valid) * 4);
@@ -161,10 +161,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
       fl = join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a + WX_PLANE)),
                  __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a + WX_PLANE + 4 * WX_CH)));
     };
-    if (p.ablate & 1) {
-      acc[0] = __builtin_bit_cast(float, (int)xh[0]);
-      return acc;
-    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < WX_PD; ++s) rd(s, bh[s], bl[s]);
@@ -188,7 +184,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
     int col0, valid;
     locate(cu, col0, valid);
     const int n = col0 + 4 * c8;
-    if (p.ablate & 2) valid = 0;
     const bool n_ok = 4 * c8 < valid;                                  // (a tile beyond a short last block: no lane stores)
     if (true_div) {
 #pragma unroll
@@ -214,45 +209,23 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
       // the tile's 32 keys leave whole, 8 keys = 16 bytes per lane and plane (lane -> row lane / 4 + 16 t, keys 8 (lane % 4) ..):
       // points beyond the block's (or the row's) end were never loaded, their sums are zeros — exactly the padding the
       // attention kernels expect behind a block's last key
-// (-DCSN_WX_PLANE_LINES=1: every store instruction writes 8 whole 128-byte lines instead of 16 half lines, at twice the
-//  conversion work — measured 1.10 ms against 1.06 for the K / V projection, same bits; off)
-#ifndef CSN_WX_PLANE_LINES
-#define CSN_WX_PLANE_LINES 0
-#endif
+      // (whole 128-byte lines per store instruction — 8 whole lines instead of 16 half lines, at twice the conversion work — were
+      //  measured in round 4: 1.10 ms against 1.06 for the K / V projection, same bits; removed with its switch)
       const csn_rsrc_t Or = csn_make_rsrc(reinterpret_cast<short*>(p.out) + (long long)item * p.out_item_stride + (long long)(256 * pset) * p.ldo,
                                           (long long)256 * p.ldo * 2);
-      if constexpr (CSN_WX_PLANE_LINES != 0) {
-        // whole 128-byte lines per store instruction: lane -> row lane / 8 + 8 t, 16-byte unit lane % 8 of the row's [hi 32 | lo 32]
-        // (units 0..3: keys 8 u .. + 7 of the hi plane, 4..7: of the lo plane).  A lane splits its 8 keys and keeps one plane —
-        // twice the conversion work of the form below, where a store instruction wrote 16 half lines (rows 40 KB apart)
-        const int prow = lane >> 3, u = lane & 7, ku = u & 3;
-        const unsigned tcol = blk * 1024u + tile * 64u + 8u * (unsigned)u;
-        const unsigned off = valid > 0 ? ((unsigned)((32 * wave + prow) * p.ldo) + tcol) * 2u : CSN_OOB;
+      const int prow = lane >> 2, c4k = lane & 3;
+      const unsigned tcol = blk * 1024u + tile * 64u + 8u * (unsigned)c4k;
+      const unsigned off = valid > 0 ? ((unsigned)((32 * wave + prow) * p.ldo) + tcol) * 2u : CSN_OOB;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const f32x4 v0 = *reinterpret_cast<const f32x4*>(&eb[(prow + 8 * t) * 32 + 8 * ku]);
-          const f32x4 v1 = *reinterpret_cast<const f32x4*>(&eb[(prow + 8 * t) * 32 + 8 * ku + 4]);
-          s16x4 h0, l0, h1, l1;
-          split4<Bf16x3>(v0, h0, l0);
-          split4<Bf16x3>(v1, h1, l1);
-          const s16x8 keep = u < 4 ? join8(h0, h1) : join8(l0, l1);
-          csn_bstore4(__builtin_bit_cast(f32x4, keep), Or, off, (unsigned)(8 * t * p.ldo) * 2u);
-        }
-      } else {
-        const int prow = lane >> 2, c4k = lane & 3;
-        const unsigned tcol = blk * 1024u + tile * 64u + 8u * (unsigned)c4k;
-        const unsigned off = valid > 0 ? ((unsigned)((32 * wave + prow) * p.ldo) + tcol) * 2u : CSN_OOB;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const f32x4 v0 = *reinterpret_cast<const f32x4*>(&eb[(prow + 16 * t) * 32 + 8 * c4k]);
-          const f32x4 v1 = *reinterpret_cast<const f32x4*>(&eb[(prow + 16 * t) * 32 + 8 * c4k + 4]);
-          s16x4 h0, l0, h1, l1;
-          split4<Bf16x3>(v0, h0, l0);
-          split4<Bf16x3>(v1, h1, l1);
-          const unsigned so = (unsigned)(16 * t * p.ldo) * 2u;
-          csn_bstore4(__builtin_bit_cast(f32x4, join8(h0, h1)), Or, off, so);
-          csn_bstore4(__builtin_bit_cast(f32x4, join8(l0, l1)), Or, off, so + 64u);
-        }
+      for (int t = 0; t < 2; ++t) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(&eb[(prow + 16 * t) * 32 + 8 * c4k]);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(&eb[(prow + 16 * t) * 32 + 8 * c4k + 4]);
+        s16x4 h0, l0, h1, l1;
+        split4<Bf16x3>(v0, h0, l0);
+        split4<Bf16x3>(v1, h1, l1);
+        const unsigned so = (unsigned)(16 * t * p.ldo) * 2u;
+        csn_bstore4(__builtin_bit_cast(f32x4, join8(h0, h1)), Or, off, so);
+        csn_bstore4(__builtin_bit_cast(f32x4, join8(l0, l1)), Or, off, so + 64u);
       }
     }
   };
@@ -266,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
     const bool exists = cu.q < q_end;
     int col0, valid;
     locate(cu, col0, valid);
-    if (valid < 0 || !exists || (p.ablate & 4)) valid = 0;
+    if (valid < 0 || !exists) valid = 0;
     const unsigned item = __builtin_amdgcn_readfirstlane(exists ? cu.item : 0u);
     if (!exists) col0 = 0;
     const long long rs = p.res_index ? (long long)wx_sload(p.res_index + item) : (long long)item;
@@ -302,7 +275,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
   auto epilogue_ln = [&](const Cursor& cu, f32x16 acc) __attribute__((always_inline)) {
     int col0, valid;
     locate(cu, col0, valid);
-    if (p.ablate & 2) valid = 0;
     const bool pt_ok = l31 < valid;
     if (cu.item != sum_item) {                          // (work-group uniform)
       flush_sums();
@@ -382,23 +354,16 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
     }
   };
 
-  // Chunk i of this stream is stream + n_streams * i.  Iteration c: request chunk c + 3 (register set (c + 1) & 1),
-  // contract chunk c (stage c % 3) | store it, commit chunk c + 2 (requested in iteration c - 1) to stage (c + 2) % 3.
-  // Staggered halves (p.stagger; measured: no gain — the CU's memory pipe, not the overlap of the parts, sets the pace — and
-  // off by default): a barrier between the two parts, and waves 4..7 — the SIMD partners of waves 0..3 — run one
-  // part behind (one extra barrier in front of their loop, one behind the loop of the others): a SIMD then always has one wave
-  // in its matrix part beside one in its memory part, instead of eight waves in lock step leaving each pipe idle in turn.
-  // Hazards (barrier intervals; waves 0..3 contract chunk c in 2c and commit in 2c + 1, waves 4..7 in 2c + 1 and 2c + 2):
-  // chunk c lands in stage c % 3 in intervals 2c - 3 / 2c - 2 and is first read in 2c; the stage's previous chunk c - 3 was
-  // last read in 2c - 5.  Without the stagger: one barrier per iteration, written in c - 2, read in c, previous read in c - 3.
-  // (p.ablate, development timing only: 1 no matrix instructions, 2 every store lane off, 4 every request lane off)
+  // Chunk i of this stream is stream + n_streams * i (LN: q0 + i).  One barrier per iteration.  Hazards: chunk c lands in
+  // stage c % 3 in iteration c - 2 and is read in iteration c; the stage's previous chunk c - 3 was last read in iteration c - 3.
+  // (Staggered wave halves — a barrier between the two parts, waves 4..7 one part behind waves 0..3 — were measured in round 4:
+  //  no gain, the CU's memory pipe, not the overlap of the parts, sets the pace; removed with their switch.)
   // THREE chunks in flight: chunk k travels in register set k % 3 and lands in LDS stage k % 3.  Iteration c requests chunk
   // c + 4, contracts and stores chunk c, then commits chunk c + 2 — requested at the top of iteration c - 2, so a request has
   // two whole iterations (and a store three) to complete: 96 KB of loads and 96 KB of stores per CU in flight.  (With two
   // sets — 64 KB — loads-only and stores-only timings added up to the kernel's time: each was bound by its own queue depth
   // times the memory latency, ~3 us under load.)
   f32x4 R0[4], R1[4], R2[4];
-  const bool stag = p.stagger != 0, late = stag && wave >= 4;
   // issued behind a request when its commit waits for it: three epilogues' stores, two requests (LN: three residual requests)
   constexpr int BEHIND = 3 * NST + 8 + (LN ? 12 : 0);
   Cursor ci = cursor_at(q0), ce = ci;              // request cursor (runs four chunks ahead), contraction / store cursor
@@ -428,13 +393,11 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
   }
   standin(std::integral_constant<int, NST>{});
   __syncthreads();
-  if (late) __syncthreads();
   // one iteration: ST = c % 3 (compile time: the loop is unrolled by three), RQ the set chunk c + 4 goes to, RC the set of chunk c + 2
   auto iteration = [&](auto st_c, f32x4* RQ, f32x4* RC) {
     constexpr int ST = decltype(st_c)::value;
     issue(ci, RQ); advance(ci);
     const f32x16 acc = compute(ST);
-    if (stag) __syncthreads();
     if constexpr (LN) epilogue_ln(ce, acc);
     else epilogue(ce, acc);
     advance(ce);
@@ -451,7 +414,6 @@ __global__ __launch_bounds__(512, 2) void csn_wx_kernel(CsnWxArgs p) {
     iteration(std::integral_constant<int, 2>{}, R0, R1);
   }
   if constexpr (LN) flush_sums();
-  if (stag && !late) __syncthreads();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (requests beyond the last chunk: every lane off, nothing fetched)
 }
 
@@ -481,9 +443,9 @@ void wx_ln_geometry(int n_items, int n_points, int& cpi, int& run, int& slots) {
 // 32 -0.08, 64 -0.10..-0.18, 128 -0.14 — not cache residency (a group of 128 is 1.3 GB of dz); with the fused kernel
 // (wx_lnb.hip) one launch is best (25.96 against 26.04 in groups of 128).  The same bits either way.
 int csn_dev_lnb_group = 0;
-// development switch (csn_dev_set): bit 0 these products on the streaming kernel (0: on the tiled kernels of gemm_bf16x3.hip), bit 1
-// staggered wave halves, bit 2 out-projection + LayerNorm back on the tiled kernel, bit 3 LayerNorm backward fused into the dCtx
-// stream (wx_lnb.hip), bits 4..7 timing-only ablations
+// development switch (csn_dev_set): bit 0 these products on the streaming kernel (0: on the tiled kernels of gemm_bf16x3.hip),
+// bit 2 out-projection + LayerNorm back on the tiled kernel, bit 3 LayerNorm backward fused into the dCtx stream (wx_lnb.hip);
+// csn_dev_set refuses every other bit
 int csn_dev_wx = 9;
 
 bool csn_wx_takes(int rows, int k) { return (csn_dev_wx & 1) != 0 && k == WX_K && rows > 0 && rows % 256 == 0 && rows / 256 <= 32; }
@@ -515,18 +477,14 @@ int csn_launch_wx(const CsnWxArgs& a, int out_mode, hipStream_t st) {
   if (out_mode == 4 && (a.n_f32 <= 0 || a.n_f32 >= a.n_sets || !a.out_f32 || (a.ldo_f32 & 3))) return -2;
   if ((a.div_rows & 31) || !csn_wx_geometry_takes(a.n_items, a.n_points, a.n_sets)) return CSN_NOT_TAKEN;
   const int grid = wx_grid();
-  CsnWxArgs b = a;
-  b.stagger = (csn_dev_wx & 2) ? 1 : 0;
-  b.ablate = (csn_dev_wx >> 4) & 15;
   if (out_mode == 3) {
     if (a.n_sets != 1 || !a.res || !a.rstd || a.div_rows) return -2;
-    b.stagger = 0;
     if (a.sum_ws && a.sum_slots != csn_wx_ln_sum_slots(a.n_items, a.n_points)) return -2;
-    if (a.dropout_p > 0.f) hipLaunchKernelGGL((csn_wx_kernel<3, true>), dim3(grid), dim3(512), 0, st, b);
-    else hipLaunchKernelGGL((csn_wx_kernel<3, false>), dim3(grid), dim3(512), 0, st, b);
-  } else if (out_mode == 0) hipLaunchKernelGGL((csn_wx_kernel<0>), dim3(grid), dim3(512), 0, st, b);
-  else if (out_mode == 2) hipLaunchKernelGGL((csn_wx_kernel<2>), dim3(grid), dim3(512), 0, st, b);
-  else if (out_mode == 4) hipLaunchKernelGGL((csn_wx_kernel<4>), dim3(grid), dim3(512), 0, st, b);
+    if (a.dropout_p > 0.f) hipLaunchKernelGGL((csn_wx_kernel<3, true>), dim3(grid), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((csn_wx_kernel<3, false>), dim3(grid), dim3(512), 0, st, a);
+  } else if (out_mode == 0) hipLaunchKernelGGL((csn_wx_kernel<0>), dim3(grid), dim3(512), 0, st, a);
+  else if (out_mode == 2) hipLaunchKernelGGL((csn_wx_kernel<2>), dim3(grid), dim3(512), 0, st, a);
+  else if (out_mode == 4) hipLaunchKernelGGL((csn_wx_kernel<4>), dim3(grid), dim3(512), 0, st, a);
   else return CSN_NOT_TAKEN;
   return (int)hipGetLastError();
 }

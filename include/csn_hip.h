@@ -484,14 +484,15 @@ CSN_API int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, 
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
- * build leaves every key at its default.  csn_dev_set returns the previous value (CSN_E_ARG for an unknown key).
+ * build leaves every key at its default.  csn_dev_set returns the previous value (CSN_E_ARG for an unknown key or a value
+ * that the key does not take; the setting is then unchanged).
  *   CSN_DEV_BIG_TILES   1   256 x 256 GEMM tiles where the output fills them (0: 128 x 128 tiles everywhere)
  *   CSN_DEV_WIDE_GEMM   1   sixteen-wave form of the 256 x 256 tiles in the bf16x3 mode (0 off, 2: the one-plane modes too)
  *   CSN_DEV_WIDE_FORMS  7   bit set of the product forms that take it: 1 plain, 2 tile-plane B (dV / dK), 4 weight gradients
  *   CSN_DEV_WX          9   bit set for the K = 256 weight products of the bf16x3 mode: 1 projections, dCtx and out-projection +
- *                           LayerNorm on the weight-stationary streaming kernel (0: the tiled GEMM kernels); 2 its wave halves
- *                           staggered; 4 out-projection + LayerNorm back on the tiled kernel; 8 LayerNorm backward fused into
- *                           the dCtx stream; bits 4..7: timing-only ablations, results wrong */
+ *                           LayerNorm on the weight-stationary streaming kernel (0: the tiled GEMM kernels); 4 out-projection +
+ *                           LayerNorm back on the tiled kernel; 8 LayerNorm backward fused into the dCtx stream.  Any other bit:
+ *                           CSN_E_ARG (2 and 16..128 were the staggered wave halves and timing-only ablations of round 4; removed) */
 #define CSN_DEV_BIG_TILES 0
 #define CSN_DEV_WIDE_GEMM 1
 #define CSN_DEV_WIDE_FORMS 2

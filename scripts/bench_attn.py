@@ -4,7 +4,7 @@
     python scripts/bench_attn.py [--evals 128] [--mode 1] [--drop 0.1] [--check]
 """
 import argparse, os, sys
-import numpy as np, torch
+import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from csn_amd import _lib, functional as CF
 
@@ -154,18 +154,6 @@ def main():
         print("digest dq: dq", dig(dqkv[:, :D]), "delta", dig(delta), "P", dig(scores), "dS", dig(dscores), flush=True)
         dkv(); torch.cuda.synchronize()
         print("digest dkv: dk", dig(dqkv[:, D:2 * D]), "dv", dig(dqkv[:, 2 * D:]), flush=True)
-    if hasattr(L, "csn_gemm_debug_read") or os.environ.get("CSN_GEMM_STAMPS"):
-        import ctypes
-        L.csn_gemm_debug_read.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
-        buf = np.zeros(65536 * 8, dtype=np.uint64)
-        L.csn_gemm_debug_read(buf.ctypes.data, buf.nbytes)
-        full = buf.reshape(65536, 8).astype(np.int64)
-        st, inner = full[:, :4], full[:, 4:]
-        d_ = np.diff(st, axis=1)
-        nslab = 16
-        print(f"GEMM stamps (last launch, first 65536 work-groups): prologue={d_[:,0].mean():7.0f} loop={d_[:,1].mean():7.0f} epilogue={d_[:,2].mean():7.0f}"
-              f" | per slab: reads+mfma={inner[:,0].mean()/nslab:6.0f} split+lds-write={inner[:,1].mean()/nslab:6.0f} "
-              f"issue loads={inner[:,3].mean()/nslab:6.0f} barrier={inner[:,2].mean()/nslab:6.0f}")
     L.csn_set_math_mode(0)
 
 

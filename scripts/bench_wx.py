@@ -79,28 +79,10 @@ if a.ln:
         print(f"out-projection + LayerNorm + sums ({E} evaluations, fc dropout {p_fc}): tiled {t0:.3f} ms ({nbytes / t0 / 1e9:.2f} TB/s of its own bytes)   "
               f"streaming {t1:.3f} ms ({nbytes / t1 / 1e9:.2f} TB/s)   min {min(times[5]):.3f} / {min(times[1]):.3f}", flush=True)
     sys.exit(0)
-ap2 = os.environ.get("WX_ABLATE")
-if ap2:
-    # timing-only ablations of the streaming kernel (outputs are wrong): CSN_DEV_WX value = 1 | 2 (lock step) | bits << 4
-    for name, fn, nbytes in cases:
-        row = []
-        for label, v in (("full", 1), ("full staggered", 3), ("no mfma", 1 | 16), ("no stores", 1 | 32), ("no loads", 1 | 64), ("no mfma no stores", 1 | 48),
-                         ("no mfma no loads", 1 | 80), ("skeleton", 1 | 112)):
-            L.csn_dev_set(_lib.DEV_WX, v)
-            ts = []
-            for rep in range(7):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-                if rep >= 2:
-                    ts.append(e0.elapsed_time(e1))
-            row.append(f"{label} {float(np.median(ts)):.3f}")
-        L.csn_dev_set(_lib.DEV_WX, 1)
-        print(name + ":  " + "   ".join(row), flush=True)
-    sys.exit(0)
 for name, fn, nbytes in cases:
-    times = {0: [], 1: [], 3: []}
+    times = {0: [], 1: []}
     for rep in range(a.reps + 2):
-        for wx in (0, 3, 1):
+        for wx in (0, 1):
             L.csn_dev_set(_lib.DEV_WX, wx)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -110,6 +92,6 @@ for name, fn, nbytes in cases:
             if rep >= 2:
                 times[wx].append(e0.elapsed_time(e1))
     L.csn_dev_set(_lib.DEV_WX, 1)
-    t0, t1, t3 = float(np.median(times[0])), float(np.median(times[1])), float(np.median(times[3]))
-    print(f"{name}: tiled {t0:.3f} ms ({nbytes / t0 / 1e9:.2f} TB/s of its own bytes)   streaming, staggered {t3:.3f} ms ({nbytes / t3 / 1e9:.2f} TB/s)   "
-          f"streaming {t1:.3f} ms ({nbytes / t1 / 1e9:.2f} TB/s)   min {min(times[0]):.3f} / {min(times[3]):.3f} / {min(times[1]):.3f}", flush=True)
+    t0, t1 = float(np.median(times[0])), float(np.median(times[1]))
+    print(f"{name}: tiled {t0:.3f} ms ({nbytes / t0 / 1e9:.2f} TB/s of its own bytes)   "
+          f"streaming {t1:.3f} ms ({nbytes / t1 / 1e9:.2f} TB/s)   min {min(times[0]):.3f} / {min(times[1]):.3f}", flush=True)

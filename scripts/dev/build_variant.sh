@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build csn_amd/libcsn_<name>.so from the same sources with extra compiler flags (timing experiments; load it with
-# CSN_LIB_PATH=csn_amd/libcsn_<name>.so).   scripts/dev/build_variant.sh rcx -DCSN_RC_ALIAS=1
+# CSN_LIB_PATH=csn_amd/libcsn_<name>.so).   scripts/dev/build_variant.sh <name> -D<MACRO>=<value>
 set -e
 cd "$(dirname "$0")/../.."
 name=$1; shift

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build csn_amd/libcsn_<name>.so = the production objects (csn_amd/_obj, built by csn_amd.build()) with ONE source recompiled
 # under extra compiler flags (timing experiments; load it with CSN_LIB_PATH=csn_amd/libcsn_<name>.so):
-#   scripts/dev/build_variant_one.sh abl2 attn_dkv.hip -DCSN_DKV_ABL=2
+#   scripts/dev/build_variant_one.sh <name> attn_dkv.hip -D<MACRO>=<value>
 set -e
 cd "$(dirname "$0")/../.."
 name=$1; src=$2; shift; shift

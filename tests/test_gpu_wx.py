@@ -61,6 +61,10 @@ def test_projection_against_float64_and_the_tiled_kernel(L, S, N, ld, R, div_row
             outs.append(out.cpu())
         finally:
             lib.csn_dev_set(L.DEV_WX, L.DEV_WX_DEFAULT)
+    # bit 1 (staggered wave halves) and bits 4..7 (timing-only ablations) are gone: refused, the setting left as it was
+    for bad in (L.DEV_WX_DEFAULT | 2, L.DEV_WX_DEFAULT | 16):
+        assert lib.csn_dev_set(L.DEV_WX, bad) == -1                   # CSN_E_ARG
+        assert lib.csn_dev_get(L.DEV_WX) == L.DEV_WX_DEFAULT
     for out in outs:
         assert _rel(out[:, :, :N], ref) < 2e-5
         assert torch.isnan(out[:, :, N:]).all()                       # nothing beyond the points of a row is written
