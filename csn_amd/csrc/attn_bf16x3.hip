@@ -271,7 +271,9 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
         g[i] = csn_bload4(rs, (i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off, (unsigned)(kt * (64 * NPL) + RPP * i * kld * 2));
     } else {
       const int k0 = kt * KT;
-      // T % 4 == 0: a 16-byte piece is all in or all out; pieces past the block end are switched off
+      // pieces that start past the block end are switched off.  Block mode has T % 4 == 0 (a 16-byte piece is all in or all
+      // out); on the cross-length path T is arbitrary and the last piece is fetched whole: its keys past T must be finite
+      // and are masked in the pointwise phase (-inf scores in the forward, P = dS = 0 in the backward)
       const unsigned off = (k0 + 4 * t_c) < T ? t_off : CSN_OOB;
 #pragma unroll
       for (int i = 0; i < NP_T; ++i)
@@ -377,7 +379,8 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_att
     if (q_ok && kq == 0 && p.delta) p.delta[stat_off + qrow] = delta_q;
   }
   // score positions of this lane: the scores of a block are stored [query][key] (pitch Tp), so the 8 consecutive keys
-  // kt*32 + 8 kq .. + 7 of this lane's query are two 16-byte runs (half j = keys + 4 j .. + 3: all in or all out, T % 4 == 0)
+  // kt*32 + 8 kq .. + 7 of this lane's query are two 16-byte runs (half j = keys + 4 j .. + 3: all in or all out in block mode, T % 4 == 0;
+  // cross-length path: a run that starts below T is stored whole — -inf / zeros in its columns T .. round-up-4(T))
   // (tile-major storage: tile kt of the block is [query][32 keys], Tq * 128 bytes per tile)
   const bool tile_major = p.sc_layout != 0;
   const unsigned s_base = tile_major ? (unsigned)(qrow * KT + 8 * kq) * 4u : (unsigned)(qrow * Tp + 8 * kq) * 4u;

@@ -271,10 +271,19 @@ CSN_API int csn_block_attn_bwd_dkv_flash_f32(const float* dctx, long long ctx_ev
  * MinkowskiNet/models/hrnet.py:378-410, 456-470): softmax(Qs K^T) V over ALL keys of the other shape, gradients flowing
  * to queries, keys and values.  Same kernels as (2)/(3) with n_blocks = 1 and separate query / key counts:
  *   q, ctx, dctx, dq : [n_evals][n_heads*d_head][ld_q]   (n_queries <= ld_q)
- *   k, v, dk, dv     : [n_evals][n_heads*d_head][ld_kv]  (round-up-4(n_keys) <= ld_kv; the padding columns of dk / dv
- *                                                          are written as zeros)
- *   scores, dscores  : [n_evals][n_heads][n_queries][score_pitch], score_pitch >= round-up-4(n_keys) (32 in math mode 1)
+ *   k, v, dk, dv     : [n_evals][n_heads*d_head][ld_kv]  (round-up-4(n_keys) <= ld_kv; the columns n_keys ..
+ *                                                          round-up-4(n_keys) of dk / dv are written as zeros, of
+ *                                                          either sign; from there to ld_kv nothing is written)
+ *   scores, dscores  : [n_evals][n_heads][n_queries][score_pitch], score_pitch % 4 == 0, >= round-up-4(n_keys)
  *   lse, delta       : [n_evals][n_heads][n_queries]
+ * The columns n_keys .. ld_kv of k / v must be FINITE (the last 16-byte piece of a key row is read whole and its keys beyond
+ * n_keys are masked afterwards); they are never read as data.  Score rows are stored in 16-byte runs: the columns n_keys ..
+ * round-up-4(n_keys) of a row may be written (-inf by the forward, 0 by the backward).
+ * In math mode 1 score_pitch selects the backward's data flow: from round-up-32(n_keys) on, P_drop and dS leave the first
+ * kernel as bf16 TILE PLANES (per query row tiles of [hi: 32 keys | lo: 32 keys], the bytes of the fp32 row; every tile that
+ * holds a key is written, its padding keys as zeros) and the dK / dV products stage them with plain copies — what csn_amd
+ * passes; below it they leave as fp32 rows (as in mode 0) and the products split them while staging.  Same results to the
+ * mode's rounding; the mask pitch of the dropout is max(n_queries, score_pitch) in either flow.
  * n_keys is arbitrary; n_queries must be a multiple of 4 (pad with zero points: their rows cost little and contribute
  * nothing to any gradient).  Evaluation e reads maps e (no slot indices, no accumulation). */
 CSN_API int csn_cross_attn_fwd_f32(const float* q, const float* k, const float* v, long long q_shape_stride,
@@ -298,8 +307,11 @@ CSN_API int csn_cross_attn_bwd_f32(const float* dctx, const float* ctx, long lon
  * n_queries[e] % 4 == 0 (round a shape's point count up: its zero points cost little and contribute nothing); n_keys[e] is
  * arbitrary (>= 1).  Work-groups of query tiles beyond n_queries[e] exit at once and key tiles beyond n_keys[e] are never
  * visited, so a short evaluation costs its own size.  Rows / columns beyond an evaluation's own counts are neither read as
- * data nor written: the caller zero-fills ctx, dq, dk, dv where it goes on to use the padding (csn_amd does), and the padding
- * points of the input maps must be finite (zeros).  Dropout masks are indexed with the launch's max_queries / score_pitch. */
+ * data nor written — with the exception (3b) has too: the dK / dV products and the score rows store 16-byte runs, so the columns
+ * n_keys[e] .. round-up-4(n_keys[e]) of dk / dv are written as zeros (and those of a score row may be written).  The caller
+ * zero-fills ctx, dq, dk, dv where it goes on to use the padding (csn_amd does), and the padding points of the input maps must
+ * be finite (zeros).  Dropout masks are indexed with the launch's max_queries / score_pitch; the mode-1 data flow of the
+ * backward is chosen by score_pitch against round-up-32(max_keys). */
 CSN_API int csn_varlen_attn_fwd_f32(const float* q, const float* k, const float* v, long long q_shape_stride,
                             long long kv_shape_stride, int ld_q, int ld_kv, float* ctx, long long ctx_eval_stride,
                             float* scores, float* lse, int n_evals, int n_heads, int d_head, int max_queries, int max_keys,

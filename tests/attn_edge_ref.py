@@ -4,9 +4,12 @@ torch / numpy, like tests/dropout_ref.py.
 - pack_tile_planes: the K / V tile planes of include/csn_hip.h (TILE PLANES), written from the contract: per row and block
   16 tiles of [hi 32 | lo 32] bf16 (math mode 1) or of [32] bf16 / fp16 (modes 2 / 3); the padding keys of a block's last
   32-key tile are zero and every tile past it — "never read" — is filled with NaN.
-- block_attention_ref: float64 autograd of softmax(Qs K^T) -> dropout -> @ V per (evaluation, head, block), short last block
-  and keep mask included; returns ctx, lse, S, P_drop, dS, dQ, dK, dV.
+- attention_core: float64 autograd of softmax(Qs K^T) -> dropout -> @ V of one rectangular problem — the one implementation of
+  the arithmetic, shared with the cross-length sweep (tests/cross_attn_ref.py).
+- block_attention_ref: the same per (evaluation, head, block), short last block and keep mask included; returns ctx, lse, S,
+  P_drop, dS, dQ, dK, dV.
 - probe_inputs: queries / keys / values whose probe rows turn a one-key error of a kernel into an O(1) error.
+- Canary: an output buffer of the GPU sweeps, filled with a NaN pattern and guarded on both sides.
 - The row table of the sweep and the csn_attn_bwd_grouping rules restated as data.
 """
 import math
@@ -34,6 +37,42 @@ def block_lengths(T, nb, T_last=None):
 
 def n_points(T, nb, T_last=None):
     return sum(block_lengths(T, nb, T_last))
+
+
+# ---- output buffers ------------------------------------------------------------------------------------------------------
+GUARD = 64                     # int32 guard elements before and after every output
+
+
+class Canary:
+    """n fp32 elements inside a buffer of the NaN pattern with guards on both sides; compared as integers"""
+
+    def __init__(self, n):
+        self.n = n
+        self.buf = torch.full((GUARD + n + GUARD,), CANARY32, dtype=torch.int32, device="cuda")
+
+    @property
+    def body(self):
+        return self.buf[GUARD:GUARD + self.n]
+
+    @property
+    def ptr(self):
+        return self.body.data_ptr()
+
+    def f32(self):
+        return self.body.view(torch.float32)
+
+    def clone(self):
+        c = Canary(self.n)
+        c.buf.copy_(self.buf)
+        return c
+
+    def check(self, written, what):
+        """guards intact; every element outside `written` (bool, n elements) still holds the pattern"""
+        g = torch.cat((self.buf[:GUARD], self.buf[GUARD + self.n:]))
+        assert bool((g == CANARY32).all()), f"{what}: a guard was written"
+        untouched = self.body[~written.reshape(-1)]
+        bad = int((untouched != CANARY32).sum())
+        assert bad == 0, f"{what}: {bad} elements outside the contract's region were written"
 
 
 # ---- tile planes ---------------------------------------------------------------------------------------------------------
@@ -93,6 +132,37 @@ def block_keep(E, H, T, nb, Tp, seed, p, extra_keys=0):
 
 
 # ---- float64 reference ----------------------------------------------------------------------------------------------------
+def attention_core(q, k, v, dO, keep=None, scale=1.0, extra_k=None, extra_v=None, grads=True, dtype=torch.float64):
+    """The arithmetic of every reference of the sweeps, once: autograd of softmax(Qs K^T) -> dropout -> @ V for a batch of
+    rectangular problems.  q, dO: (..., d, nq); k, v: (..., d, nk); keep: (..., nq, nk) bool or None, scale = 1 / (1 - p);
+    extra_k / extra_v: (..., d, n) keys let in after the real ones, always kept (the padding control).  Returns in `dtype`
+    ctx, dq (..., d, nq); dk, dv (..., d, nk) — the real keys only; lse, delta (..., nq); S, P (after dropout), dS
+    (..., nq, nk + n) [query][key].  grads = False: the forward quantities alone."""
+    dev = q.device
+    qb = q.to(dtype).detach().requires_grad_(grads)
+    kb = k.to(dtype).detach().requires_grad_(grads)
+    vb = v.to(dtype).detach().requires_grad_(grads)
+    kk, vv = kb, vb
+    n_extra = 0
+    if extra_k is not None:
+        n_extra = extra_k.shape[-1]
+        kk, vv = torch.cat((kb, extra_k.to(dtype)), -1), torch.cat((vb, extra_v.to(dtype)), -1)
+    s = qb.transpose(-1, -2) @ kk                                       # [query][key]
+    pr = torch.softmax(s, dim=-1)
+    if keep is not None:
+        m = keep.to(dev).to(dtype)
+        if n_extra:
+            m = torch.cat((m, torch.ones(m.shape[:-1] + (n_extra,), dtype=dtype, device=dev)), -1)
+        pr = pr * m * scale
+    ctx = (pr @ vv.transpose(-1, -2)).transpose(-1, -2)                 # (..., d, nq)
+    out = {"ctx": ctx.detach(), "lse": torch.logsumexp(s.detach(), dim=-1), "S": s.detach(), "P": pr.detach()}
+    if grads:
+        s.retain_grad()
+        ctx.backward(dO.to(dtype))
+        out.update(dq=qb.grad, dk=kb.grad, dv=vb.grad, dS=s.grad, delta=(dO.to(dtype) * ctx.detach()).sum(-2))
+    return out
+
+
 def block_attention_ref(q, k, v, dctx, T, nb, T_last=None, keep=None, p=0.0, drop_last_key=False, pad_keys=0):
     """float64 autograd of block attention.  q, k, v, dctx: (E, H, d, >= n_points) per EVALUATION (slots already gathered).
     keep: [E][H][nb][T][>= T] bool ([query][key]) or None.  Negative controls: drop_last_key removes key T_b - 1 of every
@@ -110,32 +180,17 @@ def block_attention_ref(q, k, v, dctx, T, nb, T_last=None, keep=None, p=0.0, dro
     for b, Tb in enumerate(block_lengths(T, nb, T_last)):
         c0 = b * T
         nk = Tb - 1 if drop_last_key else Tb
-        qb = q[..., c0:c0 + Tb].double().detach().requires_grad_(True)
-        kb = k[..., c0:c0 + nk].double().detach().requires_grad_(True)
-        vb = v[..., c0:c0 + nk].double().detach().requires_grad_(True)
-        kk, vv = kb, vb
-        if pad_keys:
-            z = torch.zeros((E, H, d, pad_keys), dtype=torch.float64, device=dev)
-            kk, vv = torch.cat((kb, z), -1), torch.cat((vb, z), -1)
-        s = qb.transpose(-1, -2) @ kk                                   # [query][key]
-        s.retain_grad()
-        pr = torch.softmax(s, dim=-1)
-        if keep is not None:
-            m = keep[:, :, b, :Tb, :nk].to(dev).double()
-            if pad_keys:
-                m = torch.cat((m, torch.ones((E, H, Tb, pad_keys), dtype=torch.float64, device=dev)), -1)
-            pr = pr * m * scale
-        pr.retain_grad()
-        ctx = (pr @ vv.transpose(-1, -2)).transpose(-1, -2)             # (E, H, d, Tb)
-        ctx.backward(dctx[..., c0:c0 + Tb].double())
-        out["ctx"][..., c0:c0 + Tb] = ctx.detach()
-        out["dq"][..., c0:c0 + Tb] = qb.grad
-        out["dk"][..., c0:c0 + nk] = kb.grad
-        out["dv"][..., c0:c0 + nk] = vb.grad
-        out["lse"][..., c0:c0 + Tb] = torch.logsumexp(s.detach(), dim=-1)
-        out["S"][:, :, b, :Tb, :nk] = s.detach()[..., :nk]
-        out["P"][:, :, b, :Tb, :nk] = pr.detach()[..., :nk]
-        out["dS"][:, :, b, :Tb, :nk] = s.grad[..., :nk]
+        z = torch.zeros((E, H, d, pad_keys), dtype=torch.float64, device=dev) if pad_keys else None
+        r = attention_core(q[..., c0:c0 + Tb], k[..., c0:c0 + nk], v[..., c0:c0 + nk], dctx[..., c0:c0 + Tb],
+                           keep[:, :, b, :Tb, :nk] if keep is not None else None, scale, z, z)
+        out["ctx"][..., c0:c0 + Tb] = r["ctx"]
+        out["dq"][..., c0:c0 + Tb] = r["dq"]
+        out["dk"][..., c0:c0 + nk] = r["dk"]
+        out["dv"][..., c0:c0 + nk] = r["dv"]
+        out["lse"][..., c0:c0 + Tb] = r["lse"]
+        out["S"][:, :, b, :Tb, :nk] = r["S"][..., :nk]
+        out["P"][:, :, b, :Tb, :nk] = r["P"][..., :nk]
+        out["dS"][:, :, b, :Tb, :nk] = r["dS"][..., :nk]
     return out
 
 

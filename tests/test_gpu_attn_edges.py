@@ -14,7 +14,7 @@ from tests import attn_edge_ref as ar
 pytestmark = pytest.mark.gpu
 
 ROWS = ar.rows()
-GUARD = 64                     # int32 guard elements before and after every output
+Canary = ar.Canary
 
 
 @pytest.fixture(scope="module")
@@ -33,38 +33,6 @@ def _restore(L):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-class Canary:
-    """n fp32 elements inside a buffer of the NaN pattern with guards on both sides; compared as integers"""
-
-    def __init__(self, n):
-        self.n = n
-        self.buf = torch.full((GUARD + n + GUARD,), ar.CANARY32, dtype=torch.int32, device="cuda")
-
-    @property
-    def body(self):
-        return self.buf[GUARD:GUARD + self.n]
-
-    @property
-    def ptr(self):
-        return self.body.data_ptr()
-
-    def f32(self):
-        return self.body.view(torch.float32)
-
-    def clone(self):
-        c = Canary(self.n)
-        c.buf.copy_(self.buf)
-        return c
-
-    def check(self, written, what):
-        """guards intact; every element outside `written` (bool, n elements) still holds the pattern"""
-        g = torch.cat((self.buf[:GUARD], self.buf[GUARD + self.n:]))
-        assert bool((g == ar.CANARY32).all()), f"{what}: a guard was written"
-        untouched = self.body[~written.reshape(-1)]
-        bad = int((untouched != ar.CANARY32).sum())
-        assert bad == 0, f"{what}: {bad} elements outside the contract's region were written"
 
 
 def _map_written(n_slots, slots, stride, D, ld, N):
