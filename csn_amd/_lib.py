@@ -167,6 +167,15 @@ _SIGNATURES = {
                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_longlong, c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                         c_float, c_ulonglong, c_void_p]),
+    "csn_cross_attn_flash_available": (c_int, [c_int]),
+    "csn_cross_attn_bwd_flash_f32": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong,
+                                             c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong,
+                                             c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong,
+                                             c_void_p]),
+    "csn_varlen_attn_bwd_flash_f32": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong,
+                                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong,
+                                              c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float,
+                                              c_ulonglong, c_void_p]),
     "csn_project_qkv_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_void_p,
                                     c_longlong, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "csn_outproj_ln_workspace_floats": (c_longlong, [c_int, c_int, c_int, c_int]),

@@ -60,10 +60,14 @@ CSN_DEVINL f32x4v mma16(s16x8 ah, s16x8 al, s16x8 bh, s16x8 bl, f32x4v c) {
 // PR = csn_mode::Bf16x3 (math mode 1: hi / lo planes, three products), Bf16 / F16 (modes 2 / 3: one plane, one product;
 // tile-plane K/V only, F16 forward only).  The single-product modes drop every "lo" object of this file: the LDS planes, the
 // fragment reads, the conversions, two of the three matrix instructions, and half of the bytes of every tile plane.
-// RC (backward, tile-plane K / V only): the scores are RECOMPUTED — S = Qs K^T from a second register operand (Qs^T of the
+// RC (backward): the scores are RECOMPUTED — S = Qs K^T from a second register operand (Qs^T of the
 // query slot) and a third LDS image (the K tile in the k-major form of tileA) — instead of being read back from the forward's
 // saved copy: no score loads, and with sc_tiles == 0 no P / dS stores either (the key-stationary dK / dV kernel of
 // attn_dkv.hip recomputes them for itself).  One more matrix product per tile; LDS holds three images per stage.
+// RC on fp32 K / V maps (KVP = false, two planes): the score-free backward of the cross-length / ragged entry points — one
+// unchunked block of ANY key count per evaluation.  The K pieces are split while they are staged, into both K images; the keys
+// of the last 4-group and of the last tile are masked one by one in P (hence in dS), as in the kept-scores kernel, so a padding
+// key of the recomputed S never enters a row.  These instances run under the two-wave bound: no spilled registers.
 // Waves per SIMD (the second launch bound).  Two everywhere — 256 registers a wave — except the narrow instances, whose tile
 // images leave room for a second work-group on the CU: one plane up to d = 96, two planes up to d = 64.  There the bound is
 // four (128 registers), which costs the recomputing dQ instances 13-18 spilled registers and still pays: a second work-group
@@ -72,13 +76,13 @@ CSN_DEVINL f32x4v mma16(s16x8 ah, s16x8 al, s16x8 bh, s16x8 bl, f32x4v c) {
 // default ring depth (38-82 spilled registers inside the loop: forward 3.8 -> 6.6 ms; the d = 96 forward with a ring of two: below).
 // (two planes, d = 96, FORWARD: with a fragment ring two deep instead of four it fits 128 registers with 4 spills)
 constexpr bool csn_attn_x3fwd96(int npl, int dt, bool bwd) { return npl == 2 && dt == 3 && !bwd; }
-constexpr int csn_attn_waves(int npl, int dt, bool bwd) {
-  return ((npl == 1 ? dt <= 3 : dt <= 2) || csn_attn_x3fwd96(npl, dt, bwd)) ? 4 : 2;
+constexpr int csn_attn_waves(int npl, int dt, bool bwd, bool rc_f32 = false) {
+  return (!rc_f32 && ((npl == 1 ? dt <= 3 : dt <= 2) || csn_attn_x3fwd96(npl, dt, bwd))) ? 4 : 2;
 }
 template <typename PR, int DT, bool BWD, bool KVP, bool RC = false>
-__global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
+__global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
   static_assert(PR::NT == 3 || KVP, "single-product modes take K / V as tile planes");
-  static_assert(!RC || (BWD && KVP), "score recomputation: backward kernel on tile-plane K / V");
+  static_assert(!RC || BWD, "score recomputation: backward kernel");
   constexpr int NPL = PR::NPL;                          // planes: hi (+ lo)
   constexpr int D = 32 * DT;
   constexpr int UPR = KVP ? 4 * NPL : 8;                // 16-byte pieces per tile row (tile planes: 4 per plane; fp32: 8)
@@ -751,7 +755,11 @@ int launch_dt(const CsnAttnArgs& a, bool bwd, hipStream_t st) {
     } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, false, true>), grid, dim3(512), 0, st, a);
   } else {
     if constexpr (PR::NT == 3) {
-      if (bwd) hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, false>), grid, dim3(512), 0, st, a);
+      if (bwd && a.q2) {                                            // score recomputation from fp32 K / V maps (cross-length path)
+        if constexpr (csn_attn_recompute_fits(PR::NPL, DT))
+          hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, false, true>), grid, dim3(512), 0, st, a);
+        else return -1;
+      } else if (bwd) hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, false>), grid, dim3(512), 0, st, a);
       else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, false, false>), grid, dim3(512), 0, st, a);
     } else return -1;                                               // single-product modes: tile-plane K / V only
   }
@@ -767,7 +775,8 @@ int launch_any(const CsnAttnArgs& a, int d, bool bwd, hipStream_t st) {
   if (a.sc_tiles && a.Tp < (a.T + 31) / 32 * 32) return -2;
   if (a.sc_layout && (PR::NPL != 2 || !a.kv_planes || a.Tq > 0 || a.tq_arr || a.t_arr || a.Tp < (a.T + 31) / 32 * 32 || (bwd && !a.sc_tiles)))
     return -1;                                                      // tile-major scores: block mode, two planes, tile-plane K / V
-  if (a.q2 && (!bwd || !a.kv_planes || (a.q2_shape_stride & 3))) return -1;
+  if (a.q2 && (!bwd || (a.q2_shape_stride & 3))) return -1;
+  if (a.q2 && !a.kv_planes && (a.sc_tiles || a.grp_off)) return -1;     // fp32 K / V maps: nothing score-sized leaves, one evaluation per launch unit
   if ((a.r_fmt || a.ctx_fmt || a.q2_fmt || a.out_fmt) && (PR::NPL != 1 || !a.kv_planes)) return -1;   // 16-bit maps: single-product modes
   if (a.out_fmt && a.accumulate) return -1;
   if (a.kv_planes && (a.T > 512 || (a.kv_ld & 7) || (a.kv_shape_stride & 7))) return -2;    // 16 tiles of 32 keys per block

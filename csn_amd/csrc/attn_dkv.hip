@@ -16,6 +16,13 @@
 // LDS: per stage four images — Qs and dO tiles each in the k-major form (phase 1, transposing reads) and the query-contiguous
 // form (phase 2, 16-byte reads) — of bf16 hi / lo planes (one plane in the single-product mode), two stages; the 32 lse2 /
 // delta values of a tile beside them.  fp32 sources are split while they are staged (once per tile and work-group).
+// XL (two planes, fp32 Qs / dO): the cross-length / ragged geometry — one unchunked block per evaluation with its own query
+// count (the streamed tiles run to n_queries[e], a multiple of 4) and key count (ANY number: the key chunks run to n_keys[e], a
+// work-group beyond them exits at once), K and V as fp32 [d][ld_kv] maps that are split into hi / lo once, in the prologue.
+// The query tail needs no masks: pieces and row constants beyond n_queries[e] are switched off in the requests (zeros in the
+// images, as in block mode), whatever the padding of the maps holds.  The key tail needs none either: a key is a COLUMN of both
+// matrix products, so a padding key of the last 4-group only fills its own columns of dK^T / dV^T, and the epilogue stores
+// exact zeros there (nothing beyond round-up-4(n_keys[e])).
 // Schedule: the two barrier segments per tile and the one-segment stagger between waves 0..3 and 4..7 of attn_bf16x3.hip.
 #include "csn_common.h"
 #include "csn_kernels.h"
@@ -49,6 +56,16 @@ CSN_DEVINL u32x2 moved(u32x2 v) {
   return r;
 }
 
+// A register operand that is COMPLETE here.  The compiler may sink plain LDS reads below a barrier towards their first use
+// (the C++ memory model lets a read move down past the fence of __syncthreads()); for the fp32 prologue it did — the picks of
+// V landed behind the barrier that hands the staging block to the tile images, where the other waves were already committing
+// tiles over it.  The operand passes through an opaque instruction before the barrier, so its reads have returned by then.
+CSN_DEVINL void landed(s16x8& v) {
+  u32x4 w = __builtin_bit_cast(u32x4, v);
+  asm volatile("" : "+v"(w));
+  v = __builtin_bit_cast(s16x8, w);
+}
+
 template <typename PR>
 CSN_DEVINL f32x4v mma16(s16x8 ah, s16x8 al, s16x8 bh, s16x8 bl, f32x4v c) {
   if constexpr (PR::NT == 3) {
@@ -77,11 +94,12 @@ constexpr bool csn_dkv_narrow(int npl, int dt) { return npl == 1 && dt <= 2; }
 // with the keys.  A wave that owns TWO groups (32 keys; the work-group 256) reuses every fragment it reads for both, and the
 // work-group stages each tile for twice the keys: per key half the LDS reads, commits, requests, barriers and scalar work.
 // Costs 88 registers (operands, accumulators, S / dP of the second group): the one-plane d = 96 instance has them.
-template <typename PR, int DT, int QF = 0, int NW = 8, bool DR = true, int G = 1>
+template <typename PR, int DT, int QF = 0, int NW = 8, bool DR = true, int G = 1, bool XL = false>
 __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void csn_attn_dkv_kernel(CsnAttnDkvArgs p) {
   constexpr bool NARROW = csn_dkv_narrow(PR::NPL, DT);
   static_assert(QF == 0 || PR::NPL == 1, "16-bit activation maps: the one-plane mode");
   static_assert(NW == 8, "work-groups of 8 waves");
+  static_assert(!XL || (PR::NT == 3 && QF == 0 && G == 1), "cross-length geometry: bf16x3 on fp32 maps");
   constexpr int NT = 64 * NW;                           // threads
   constexpr int KW = 16 * NW * G;                       // keys per work-group
   constexpr int NPL = PR::NPL;
@@ -109,12 +127,16 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
   const int grp = u / Y, hd = (u % Y) % p.H, blk = (u % Y) / p.H;
   const int it0 = p.grp_off ? p.grp_off[grp] : grp, it1 = p.grp_off ? p.grp_off[grp + 1] : grp + 1;
   const bool short_blk = p.T_last > 0 && blk == p.n_blocks - 1;
-  const int T = short_blk ? p.T_last : p.T;                         // queries = keys of this block
-  if (kc * KW >= T) return;
-  const int ld = p.ld, Tp = p.Tp;
   const int e_first = p.eval_ids ? p.eval_ids[it0] : it0;
+  // block mode: queries = keys of this block.  XL: this evaluation's own key count T and query count TQ; QL = the queries per
+  // block that lay out the maps and the statistics (the launch's maximum)
+  const int T = XL ? (p.t_arr ? p.t_arr[e_first] : p.T) : (short_blk ? p.T_last : p.T);
+  if (kc * KW >= T) return;
+  const int TQ = XL ? (p.tq_arr ? p.tq_arr[e_first] : p.Tq) : T;
+  const int QL = XL ? p.Tq : p.T;
+  const int ld = p.ld, Tp = p.Tp, ldk = XL ? p.ld_kv : p.ld;
   const long long kslot = p.kv_index ? p.kv_index[e_first] : e_first;
-  const int nqt = (T + QT - 1) / QT;
+  const int nqt = (TQ + QT - 1) / QT;
   const int n_steps = (it1 - it0) * nqt;
   // (all waves in step, ONE barrier per tile instead of two and no stagger, was measured in round 6
   //  (profiles/r6_dkv_kernel.txt); removed with its switch)
@@ -128,7 +150,55 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
   constexpr int RPC = (KW / 8) * NPL;                               // 16-byte pieces per row of the block
   constexpr int CH_K = (D * RPC + NT - 1) / NT;
   s16x8 Kh[G][DT], Kl[G][DT], Vh[G][DT], Vl[G][DT];
-  {
+  if constexpr (XL) {
+    // fp32 [D][ld_kv] maps: the [D][KW keys] block of this chunk travels as 16-byte rows through LDS (the prologue of
+    // attn_bf16x3.hip) and every lane splits its values.  4-key pieces that start beyond the evaluation's keys are switched
+    // off; the last piece is read whole (its padding keys are finite and end in columns that are stored as zeros).
+    constexpr int CH_F = D / 16;                                    // 16-byte pieces per thread: D rows x KW / 4 pieces / NT
+    const int cc = tid & 31, crow = tid >> 5;
+    const int nk = T - kc * KW;
+    const long long off = kslot * p.kv_shape_stride + (long long)hd * D * ldk + (long long)kc * KW;
+    const long long win = ((long long)(D - 1) * ldk + (nk < KW ? (nk + 3) / 4 * 4 : KW)) * 4;
+    const unsigned c_off = (4 * cc) < nk ? (unsigned)(crow * ldk + 4 * cc) * 4u : CSN_OOB;
+    auto stage_f32 = [&](const float* base) {
+      const csn_rsrc_t rs = csn_make_rsrc(base + off, win);
+      f32x4 ch[CH_F];
+#pragma unroll
+      for (int t = 0; t < CH_F; ++t) ch[t] = csn_bload4(rs, c_off, (unsigned)(16 * t * ldk) * 4u);
+#pragma unroll
+      for (int t = 0; t < CH_F; ++t) {
+        const int row = crow + 16 * t;
+        *reinterpret_cast<f32x4*>(&xbuf[row * KW + ((cc ^ (4 * ((row >> 3) & 1))) << 2)]) = ch[t];
+      }
+    };
+    auto pick = [&](int row) { return xbuf[row * KW + ((((col0 >> 2) ^ (4 * ((row >> 3) & 1))) << 2) | (col0 & 3))]; };
+    stage_f32(p.k);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < DT; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x = pick(32 * s + 8 * kq + j);
+        Kh[0][s][j] = to16<PR::HALF>(x);
+        Kl[0][s][j] = to16<PR::HALF>(x - from16<PR::HALF>(Kh[0][s][j]));
+      }
+#pragma unroll
+    for (int s = 0; s < DT; ++s) { landed(Kh[0][s]); landed(Kl[0][s]); }
+    __syncthreads();
+    stage_f32(p.v);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < DT; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x = pick(32 * s + 8 * kq + j);
+        Vh[0][s][j] = to16<PR::HALF>(x);
+        Vl[0][s][j] = to16<PR::HALF>(x - from16<PR::HALF>(Vh[0][s][j]));
+      }
+#pragma unroll
+    for (int s = 0; s < DT; ++s) { landed(Vh[0][s]); landed(Vl[0][s]); }
+    __syncthreads();                                                // the staging block becomes the tile images
+  } else {
     const int kld = p.kv_ld;
     const int cc = tid % RPC, crow = tid / RPC;                     // piece column, first row (rows + NT / RPC per pass)
     constexpr int RPS = NT / RPC;
@@ -203,7 +273,7 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
   constexpr bool drop = DR;
   const unsigned thr16 = csn_drop_threshold16(p.dropout_p);
   const float keep_scale = drop ? 1.f / (1.f - p.dropout_p) : 1.f;
-  const int mp = p.T > Tp ? p.T : Tp;                               // mask pitch of the forward (queries per block vs score pitch)
+  const int mp = QL > Tp ? QL : Tp;                                 // mask pitch of the forward (queries per block vs score pitch)
   const unsigned pw_key = (unsigned)((key0 >> 1) * mp);             // pair index of this lane's key: (key / 2) * mp + query (group g: + 8 g mp)
   const bool key_odd = key0 & 1;                                    // (the same in every group: groups are 16 keys apart)
 
@@ -239,19 +309,19 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
   auto fetch_item = [&]() {
     const int e = p.eval_ids ? p.eval_ids[f_it] : f_it;
     const long long qs = p.q_index ? p.q_index[e] : e;
-    const long long head_off = (long long)hd * D * ld + (long long)blk * p.T;
-    const long long stat = ((long long)e * p.H + hd) * ((long long)p.n_blocks * p.T) + (long long)blk * p.T;
-    const long long win = (long long)(D - 1) * ld + T;                                // elements of a [D][T] window of pitch ld
+    const long long head_off = (long long)hd * D * ld + (long long)blk * QL;
+    const long long stat = ((long long)e * p.H + hd) * ((long long)p.n_blocks * QL) + (long long)blk * QL;
+    const long long win = (long long)(D - 1) * ld + TQ;                               // elements of a [D][TQ] window of pitch ld
     Qr_it = csn_make_rsrc(reinterpret_cast<const char*>(p.q) + (qs * p.q_shape_stride + head_off) * q_es, win * q_es);
     Or_it = csn_make_rsrc(reinterpret_cast<const char*>(p.dctx) + ((long long)e * p.ctx_eval_stride + head_off) * o_es, win * o_es);
-    Lr_it = csn_make_rsrc(p.lse + stat, (long long)T * 4);
-    Dr_it = csn_make_rsrc(p.delta + stat, (long long)T * 4);
+    Lr_it = csn_make_rsrc(p.lse + stat, (long long)TQ * 4);
+    Dr_it = csn_make_rsrc(p.delta + stat, (long long)TQ * 4);
   };
   fetch_item();
   const unsigned t_off = (unsigned)(t_row * ld + 4 * t_c);                             // (elements) this thread's piece inside a tile
   auto fetch = [&]() {
     const int q_first = f_qt * QT;                                                     // first query of the tile inside the block
-    const unsigned off = (q_first + 4 * t_c) < T ? t_off : CSN_OOB;                   // T % 4 == 0: a piece is all in or all out
+    const unsigned off = (q_first + 4 * t_c) < TQ ? t_off : CSN_OOB;                  // TQ % 4 == 0: a piece is all in or all out
 #pragma unroll
     for (int i = 0; i < NP_T; ++i) {
       const unsigned o = (i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off;
@@ -478,9 +548,12 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
       if (step + 2 < n_steps) fetch();                              // a whole tile ahead of its first use
     }
     __syncthreads();
-    if constexpr (!NARROW) phase2_ahead(cur);
+    // (XL at d = 128: the per-evaluation counts cost registers the block-mode instance does not have to spare — its phase-2
+    //  reads follow the pointwise segment too, and the instance keeps every value in registers: no scratch)
+    constexpr bool P2_LATE = NARROW || (XL && DT == 4);
+    if constexpr (!P2_LATE) phase2_ahead(cur);
     pointwise(c_qt, salt, rc_cur);
-    if constexpr (NARROW) phase2_ahead(cur);                         // (register diet: nothing of phase 2 lives across the pointwise segment)
+    if constexpr (P2_LATE) phase2_ahead(cur);                        // (register diet: nothing of phase 2 lives across the pointwise segment)
     phase2();                                                       // dV^T += dO^T P_drop,  dK^T += Qs^T dS
     if (more) commit_contig(nxt);
     if (++c_qt == nqt) { c_qt = 0; ++c_it; }
@@ -494,10 +567,11 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
   const int cc = tid & (KW / 4 - 1), crow = tid / (KW / 4);       // 4-key chunk of the row, first row (+ RPE t)
   constexpr int CH_T = D / RPE;
   const long long okslot = p.dk_index ? p.dk_index[e_first] : e_first, ovslot = p.dv_index ? p.dv_index[e_first] : e_first;
-  const long long out_off = (long long)hd * D * ld + (long long)blk * p.T + kc * KW;
-  const int nk = T - kc * KW;                                       // keys of this chunk that exist
-  const long long owin = ((long long)(D - 1) * ld + (nk < KW ? nk : KW)) * 4;
-  const unsigned c_off = (4 * cc) < nk ? (unsigned)(crow * ld + 4 * cc) * 4u : CSN_OOB;
+  const int ldo = ldk;                                              // pitch of the gradient maps (XL: the K / V maps' own)
+  const long long out_off = (long long)hd * D * ldo + (long long)blk * p.T + kc * KW;
+  const int nk = T - kc * KW;                                       // keys of this chunk that exist (XL: any number — the last 4-group is stored whole)
+  const long long owin = ((long long)(D - 1) * ldo + (nk < KW ? (XL ? (nk + 3) / 4 * 4 : nk) : KW)) * 4;
+  const unsigned c_off = (4 * cc) < nk ? (unsigned)(crow * ldo + 4 * cc) * 4u : CSN_OOB;
   auto store_out = [&](const f32x4v (*OUT)[D / 16], float* base, long long slot) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -516,25 +590,29 @@ __global__ __launch_bounds__(64 * NW, csn_dkv_narrow(PR::NPL, DT) ? 4 : 2) void 
     for (int t = 0; t < CH_T; ++t) {
       const int row = crow + RPE * t;
       ch[t] = *reinterpret_cast<const f32x4*>(&xbuf[row * KW + ((cc ^ (4 * ((row >> 2) & 1))) << 2)]);
+      if constexpr (XL) {                                           // the columns n_keys .. round-up-4(n_keys): exact zeros
+#pragma unroll
+        for (int j = 1; j < 4; ++j) ch[t][j] = (4 * cc + j) < nk ? ch[t][j] : 0.f;
+      }
     }
     if (NPL == 1 && p.out_fmt) {                                    // bf16 gradient maps (16-bit activation maps; written once)
       const csn_rsrc_t r16 = csn_make_rsrc(reinterpret_cast<short*>(base) + slot * p.dkv_slot_stride + out_off, owin / 2);
 #pragma unroll
       for (int t = 0; t < CH_T; ++t)
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, to16x4<false>(ch[t])), r16, c_off == CSN_OOB ? CSN_OOB : c_off >> 1,
-                                              (unsigned)(RPE * t * ld) * 2u, 0);
+                                              (unsigned)(RPE * t * ldo) * 2u, 0);
       return;
     }
     const csn_rsrc_t rs = csn_make_rsrc(base + slot * p.dkv_slot_stride + out_off, owin);
     if (p.accumulate) {
       f32x4 prev[CH_T];
 #pragma unroll
-      for (int t = 0; t < CH_T; ++t) prev[t] = csn_bload4(rs, c_off, (unsigned)(RPE * t * ld) * 4u);
+      for (int t = 0; t < CH_T; ++t) prev[t] = csn_bload4(rs, c_off, (unsigned)(RPE * t * ldo) * 4u);
 #pragma unroll
       for (int t = 0; t < CH_T; ++t) ch[t] += prev[t];
     }
 #pragma unroll
-    for (int t = 0; t < CH_T; ++t) csn_bstore4(ch[t], rs, c_off, (unsigned)(RPE * t * ld) * 4u);
+    for (int t = 0; t < CH_T; ++t) csn_bstore4(ch[t], rs, c_off, (unsigned)(RPE * t * ldo) * 4u);
   };
   store_out(dK, p.dk, okslot);
   __syncthreads();
@@ -548,6 +626,14 @@ constexpr int csn_dkv_groups(int npl, int dt) { return (npl == 1 && dt == 3) ? 2
 template <typename PR, int DT, bool DR>
 int launch_dt(const CsnAttnDkvArgs& a, hipStream_t st) {
   constexpr int NW = 8;
+  if (a.Tq > 0) {                                                   // cross-length geometry: fp32 K / V maps, bf16x3
+    if constexpr (PR::NT == 3) {
+      const long long units = (long long)a.H * a.n_groups;
+      dim3 grid((unsigned)(((units + 7) / 8) * 8 * ((a.T + 16 * NW - 1) / (16 * NW))));
+      hipLaunchKernelGGL((csn_attn_dkv_kernel<PR, DT, 0, NW, DR, 1, true>), grid, dim3(64 * NW), 0, st, a);
+      return (int)hipGetLastError();
+    } else return -1;
+  }
   constexpr int G = csn_dkv_groups(PR::NPL, DT);
   const long long units = (long long)a.n_blocks * a.H * a.n_groups;
   const int KC = (a.T + 16 * NW * G - 1) / (16 * NW * G);
@@ -583,6 +669,14 @@ int launch_any(const CsnAttnDkvArgs& a, int d, hipStream_t st) {
 
 int csn_launch_attn_dkv_flash(const CsnAttnDkvArgs& a, int d, int mode, hipStream_t st) {
   if (a.n_groups <= 0 || a.n_blocks <= 0) return 0;
+  if (a.Tq > 0) {                                                   // one unchunked block per evaluation, any key count
+    if (mode != 1 || a.n_blocks != 1 || a.grp_off || a.eval_ids || a.kv_index || a.T_last || a.accumulate || a.q_fmt || a.dctx_fmt ||
+        a.out_fmt || a.kv_f16)
+      return -1;
+    if ((a.ld & 3) || (a.ld_kv & 3) || (a.Tq & 3) || a.ld_kv < (a.T + 3) / 4 * 4 || a.ld < a.Tq) return -2;
+    if ((a.q_shape_stride & 3) || (a.ctx_eval_stride & 3) || (a.dkv_slot_stride & 3) || (a.kv_shape_stride & 3)) return -4;
+    return launch_any<Bf16x3>(a, d, st);
+  }
   if ((a.ld & 3) || (a.T & 3) || (a.T_last & 3) || a.T > 512 || (a.kv_ld & 7) || (a.kv_shape_stride & 7)) return -2;
   if ((a.q_shape_stride & 3) || (a.ctx_eval_stride & 3) || (a.dkv_slot_stride & 3)) return -4;
   if ((a.q_fmt || a.dctx_fmt) && mode != 2) return -1;              // 16-bit activation maps: the one-plane mode

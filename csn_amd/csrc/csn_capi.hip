@@ -660,6 +660,85 @@ int csn_varlen_attn_bwd_f32(const float* dctx, const float* ctx, long long ctx_e
                            max_queries, ld_kv, nullptr, 0, stream, n_queries, n_keys);
 }
 
+/* the score-free backward of (3b) / (3c): the dQ kernel rebuilds S = Qs K^T from the fp32 K / V maps tile by tile and writes
+ * delta and dQ, the key-stationary kernel rebuilds P and dS from lse and delta and writes dK and dV; both draw the forward's
+ * dropout mask with the pitch max(n_queries, score_pitch).  Math mode 1 (modes 2 / 3 run as mode 1), d_head <= 128. */
+static bool cross_flash_fits(int m, int d_head) {
+  return m == 1 && dim_ok(d_head) && csn_attn_recompute_fits(2, d_head / 32) && csn_attn_dkv_flash_fits(d_head / 32);
+}
+
+int csn_cross_attn_flash_available(int d_head) { return cross_flash_fits(mode() >= 2 ? 1 : mode(), d_head) ? 1 : 0; }
+
+static int cross_bwd_flash_impl(const float* dctx, const float* ctx, long long ctx_eval_stride, const float* q, const float* k,
+                                const float* v, long long q_shape_stride, long long kv_shape_stride, int ld_q, int ld_kv,
+                                const float* lse, float* delta, float* dq, float* dk, float* dv, long long dq_eval_stride,
+                                long long dkv_eval_stride, int n_evals, int n_heads, int d_head, int n_queries, int n_keys,
+                                const int* tq_arr, const int* t_arr, int score_pitch, float dropout_p, unsigned long long seed,
+                                void* stream) {
+  if (!dctx || !ctx || !q || !k || !v || !lse || !delta || !dq || !dk || !dv) return CSN_E_ARG;
+  if (n_evals <= 0 || n_heads <= 0 || ld_q <= 0 || ld_kv <= 0) return CSN_E_ARG;
+  if (dropout_p < 0.f || dropout_p >= 1.f) return CSN_E_ARG;
+  if (!dim_ok(d_head)) return CSN_E_DIM;
+  if (!cross_flash_fits(mode(), d_head)) return CSN_E_ARG;          // exact fp32, or a width no recomputing kernel has room for
+  const int nk4 = (n_keys + 3) / 4 * 4;
+  if (n_queries > ld_q || nk4 > ld_kv) return CSN_E_ARG;            // queries and keys fit their rows
+  if ((ld_q & 3) || (ld_kv & 3) || (score_pitch & 3) || score_pitch < nk4) return CSN_E_ALIGN;
+  if (mis16(dctx) || mis16(ctx) || mis16(q) || mis16(k) || mis16(v) || mis16(dq) || mis16(dk) || mis16(dv)) return CSN_E_PTR;
+  if ((q_shape_stride & 3) || (kv_shape_stride & 3) || (ctx_eval_stride & 3) || (dq_eval_stride & 3) || (dkv_eval_stride & 3))
+    return CSN_E_STRIDE;
+  hipStream_t st = (hipStream_t)stream;
+  CsnAttnArgs a{};
+  a.q = dctx; a.k = k; a.v = v; a.ctx = ctx;
+  a.q_shape_stride = ctx_eval_stride; a.kv_shape_stride = kv_shape_stride;
+  a.ld = ld_q; a.ld_kv = ld_kv;
+  a.out = dq; a.out_eval_stride = dq_eval_stride;
+  a.lse = const_cast<float*>(lse); a.delta = delta;
+  a.E = n_evals; a.H = n_heads; a.T = n_keys; a.Tq = n_queries; a.Tp = score_pitch; a.n_blocks = 1;
+  a.dropout_p = dropout_p; a.seed = seed;
+  a.tq_arr = tq_arr; a.t_arr = t_arr;
+  a.q2 = q; a.q2_shape_stride = q_shape_stride;                      // (scores, dscores: NULL — nothing score-sized is read or written)
+  int rc = csn_launch_attn_bwd_bf16x3(a, d_head, 1, st);
+  if (rc) return rc;
+  CsnAttnDkvArgs b{};
+  b.q = q; b.q_shape_stride = q_shape_stride;
+  b.dctx = dctx; b.ctx_eval_stride = ctx_eval_stride;
+  b.k = k; b.v = v; b.kv_shape_stride = kv_shape_stride;
+  b.lse = lse; b.delta = delta;
+  b.dk = dk; b.dv = dv; b.dkv_slot_stride = dkv_eval_stride;
+  b.n_groups = n_evals;
+  b.ld = ld_q; b.ld_kv = ld_kv; b.H = n_heads; b.T = n_keys; b.Tq = n_queries; b.Tp = score_pitch; b.n_blocks = 1;
+  b.dropout_p = dropout_p; b.seed = seed;
+  b.tq_arr = tq_arr; b.t_arr = t_arr;
+  return csn_launch_attn_dkv_flash(b, d_head, 1, st);
+}
+
+int csn_cross_attn_bwd_flash_f32(const float* dctx, const float* ctx, long long ctx_eval_stride, const float* q, const float* k,
+                                 const float* v, long long q_shape_stride, long long kv_shape_stride, int ld_q, int ld_kv,
+                                 const float* lse, float* delta, float* dq, float* dk, float* dv, long long dq_eval_stride,
+                                 long long dkv_eval_stride, int n_evals, int n_heads, int d_head, int n_queries, int n_keys,
+                                 int score_pitch, float dropout_p, unsigned long long seed, void* stream) {
+  if (n_queries <= 0 || n_keys <= 0) return CSN_E_ARG;
+  if (n_queries & 3) return CSN_E_ALIGN;
+  ModeGuard guard(mode() >= 2 ? 1 : mode());
+  return cross_bwd_flash_impl(dctx, ctx, ctx_eval_stride, q, k, v, q_shape_stride, kv_shape_stride, ld_q, ld_kv, lse, delta, dq,
+                              dk, dv, dq_eval_stride, dkv_eval_stride, n_evals, n_heads, d_head, n_queries, n_keys, nullptr,
+                              nullptr, score_pitch, dropout_p, seed, stream);
+}
+
+int csn_varlen_attn_bwd_flash_f32(const float* dctx, const float* ctx, long long ctx_eval_stride, const float* q, const float* k,
+                                  const float* v, long long q_shape_stride, long long kv_shape_stride, int ld_q, int ld_kv,
+                                  const float* lse, float* delta, float* dq, float* dk, float* dv, long long dq_eval_stride,
+                                  long long dkv_eval_stride, int n_evals, int n_heads, int d_head, int max_queries, int max_keys,
+                                  const int* n_queries, const int* n_keys, int score_pitch, float dropout_p,
+                                  unsigned long long seed, void* stream) {
+  if (max_queries <= 0 || max_keys <= 0 || !n_queries || !n_keys) return CSN_E_ARG;
+  if (max_queries & 3) return CSN_E_ALIGN;
+  ModeGuard guard(mode() >= 2 ? 1 : mode());
+  return cross_bwd_flash_impl(dctx, ctx, ctx_eval_stride, q, k, v, q_shape_stride, kv_shape_stride, ld_q, ld_kv, lse, delta, dq,
+                              dk, dv, dq_eval_stride, dkv_eval_stride, n_evals, n_heads, d_head, max_queries, max_keys, n_queries,
+                              n_keys, score_pitch, dropout_p, seed, stream);
+}
+
 long long csn_masked_ce_workspace_bytes(int n_shapes, int n_points) {
   if (n_shapes <= 0 || n_points <= 0) return 0;
   return csn_masked_ce_blocks(n_shapes, n_points) * 3 * (long long)sizeof(double);

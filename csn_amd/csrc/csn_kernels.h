@@ -128,6 +128,11 @@ struct CsnAttnDkvArgs {
   int kv_f16 = 0;                                                         // one-plane mode: k / v hold fp16 (forward of math mode 3)
   int q_fmt = 0, dctx_fmt = 0;                                            // 16-bit activation maps: 0 fp32, 1 bf16, 2 fp16 (q of a mode-3 forward)
   int out_fmt = 0;                                                        // 1: dk / dv leave as bf16 maps (written once: no accumulate)
+  // cross-length / ragged geometry (math mode 1, n_blocks = 1; Tq > 0 selects it): Tq queries per evaluation (% 4) against T
+  // keys (any number), k / v fp32 maps [evaluation][H*d][ld_kv] (kv_shape_stride in floats), dk / dv of the same pitch;
+  // tq_arr / t_arr: per-evaluation counts of a ragged batch (device arrays; Tq, T are then the maxima that size grid and buffers)
+  int Tq = 0, ld_kv = 0;
+  const int* tq_arr = nullptr;  const int* t_arr = nullptr;
 };
 int csn_launch_attn_dkv_flash(const CsnAttnDkvArgs& a, int d, int mode, hipStream_t st);
 constexpr bool csn_attn_dkv_flash_fits(int dt) { return dt <= 4; }         // K^T, V^T, dK^T, dV^T of 16 keys in one wave's registers

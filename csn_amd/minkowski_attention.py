@@ -9,7 +9,9 @@ Reference (all under /root/reference):
 
 Same class names, constructor arguments, parameter names and ``forward(q, k, v) -> (out, attn)`` as the reference.  The
 arithmetic runs in libcsn_hip.so (``csn_cross_attn_fwd_f32`` / ``csn_cross_attn_bwd_f32`` + the projection / out-projection
-kernels of the MID-FC path); there is no eager fallback.  SURVEY.md §8(f) rank 2.  The sparse-tensor branches of the
+kernels of the MID-FC path); there is no eager fallback.  The backward has two data flows: the kept scores (default) and the
+score-free one (``csn_cross_attn_bwd_flash_f32`` / ``csn_varlen_attn_bwd_flash_f32``: only ``lse`` is kept, nothing
+score-sized is saved or allocated), selected by ``csn_amd.tuning.cross_score_free`` / ``cross_score_budget``.  SURVEY.md §8(f) rank 2.  The sparse-tensor branches of the
 reference (MinkowskiEngine, absent here) are out of scope: callers pass the dense feature matrices (``features_at``).
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import functional as CF
+from . import tuning
 
 
 def _up(n: int, m: int) -> int:
@@ -31,6 +34,25 @@ def _to_cm(x: torch.Tensor, n_pad: int) -> torch.Tensor:
     out = torch.zeros((b, c, n_pad), device=x.device, dtype=torch.float32)
     out[:, :, :n] = x.transpose(1, 2)
     return out
+
+
+def _score_free(L, b: int, H: int, d: int, lq4: int, Tp: int) -> bool:
+    """The data flow of one call's backward (tuning.cross_score_free): True = keep only lse, rebuild the scores in the backward."""
+    want = tuning.current().cross_score_free
+    if want is False:
+        return False
+    available = L.csn_cross_attn_flash_available(d) == 1
+    if want:
+        if not available:
+            raise _lib.CsnError(f"cross_score_free=True: no score-free attention backward in math mode {L.csn_get_math_mode()} "
+                                f"at head width {d} (math modes 1-3, d_head 32 / 64 / 96 / 128)")
+        return True
+    if not available:
+        return False
+    budget = tuning.current().cross_score_budget
+    if budget is None:
+        budget = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+    return tuning.cross_takes_score_free(3 * b * H * lq4 * Tp * 4, budget, available)
 
 
 class _CrossMHA(torch.autograd.Function):
@@ -66,7 +88,9 @@ class _CrossMHA(torch.autograd.Function):
         # a zero row is a finite zero row, and nothing flows back from it)
         att = (torch.zeros if varlen else torch.empty)((b, D, lq4), device=dev, dtype=torch.float32)
         lse = torch.empty((b, H, lq4), device=dev, dtype=torch.float32)
-        scores = torch.empty((b, H, lq4, Tp), device=dev, dtype=torch.float32) if (keep or want_attn) else None
+        # the backward's data flow is decided here and travels in the context (the backward runs on autograd's threads)
+        flash = keep and _score_free(L, b, H, d, lq4, Tp)
+        scores = torch.empty((b, H, lq4, Tp), device=dev, dtype=torch.float32) if ((keep and not flash) or want_attn) else None
         if varlen:
             _lib.check(L.csn_varlen_attn_fwd_f32(CF._ptr(q), CF._ptr(k), CF._ptr(v), D * lq4, D * lk4, lq4, lk4, CF._ptr(att),
                                                  D * lq4, CF._ptr(scores), CF._ptr(lse), b, H, d, lq4, lk, CF._ptr(q_lens),
@@ -87,7 +111,9 @@ class _CrossMHA(torch.autograd.Function):
                                             C * lq4, CF._ptr(rstd), b, C, D, lq4, lq4, CF.LN_EPS, p_fc, seed_fc, None, None, 0, CF._stream()),
                    "csn_outproj_ln_fwd_f32")
         if keep:
-            ctx.save_for_backward(xq_cm, xk_cm, xv_cm, w_qs, w_ks, w_vs, w_fc, q, k, v, att, lse, scores, xhat, rstd)
+            ctx.flash = flash
+            # score-free: only lse is kept (scores exist then only for the returned attn, and are not saved)
+            ctx.save_for_backward(xq_cm, xk_cm, xv_cm, w_qs, w_ks, w_vs, w_fc, q, k, v, att, lse, None if flash else scores, xhat, rstd)
             ctx.dims = (b, lq, lk, C, H, d, Tp)
             ctx.drop = (p_attn, seed_attn, p_fc, seed_fc)
             ctx.lens = (q_lens, k_lens)
@@ -123,7 +149,6 @@ class _CrossMHA(torch.autograd.Function):
                                             CF._ptr(dw_fc), CF._ptr(ws), ws_n, b, C, D, lq4, lq4, 0, p_fc, seed_fc, 0, 0, None,
                                             b, None, 1, CF._stream()), "csn_outproj_ln_bwd_f32")
         # attention backward: gradients to the projected queries, keys and values
-        dscores = torch.empty_like(scores)
         delta = torch.empty((b, H, lq4), device=dev, dtype=torch.float32)
         q_lens, k_lens = ctx.lens
         varlen = q_lens is not None
@@ -131,19 +156,33 @@ class _CrossMHA(torch.autograd.Function):
         dq = alloc((b, D, lq4), device=dev, dtype=torch.float32)
         dk = alloc((b, D, lk4), device=dev, dtype=torch.float32)
         dv = alloc((b, D, lk4), device=dev, dtype=torch.float32)
-        work = scores.clone()                                        # the backward turns the scores into probabilities in place
-        if varlen:
-            _lib.check(L.csn_varlen_attn_bwd_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v), D * lq4,
-                                                 D * lk4, lq4, lk4, CF._ptr(work), CF._ptr(dscores), CF._ptr(lse), CF._ptr(delta),
-                                                 CF._ptr(dq), CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk,
-                                                 CF._ptr(q_lens), CF._ptr(k_lens), Tp, p_attn, seed_attn, CF._stream()),
-                       "csn_varlen_attn_bwd_f32")
+        if ctx.flash:                                                # nothing score-sized: S, P and dS are rebuilt tile by tile
+            if varlen:
+                _lib.check(L.csn_varlen_attn_bwd_flash_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v),
+                                                           D * lq4, D * lk4, lq4, lk4, CF._ptr(lse), CF._ptr(delta), CF._ptr(dq),
+                                                           CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk,
+                                                           CF._ptr(q_lens), CF._ptr(k_lens), Tp, p_attn, seed_attn, CF._stream()),
+                           "csn_varlen_attn_bwd_flash_f32")
+            else:
+                _lib.check(L.csn_cross_attn_bwd_flash_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v),
+                                                          D * lq4, D * lk4, lq4, lk4, CF._ptr(lse), CF._ptr(delta), CF._ptr(dq),
+                                                          CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk, Tp,
+                                                          p_attn, seed_attn, CF._stream()), "csn_cross_attn_bwd_flash_f32")
         else:
-            _lib.check(L.csn_cross_attn_bwd_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v), D * lq4,
-                                                D * lk4, lq4, lk4, CF._ptr(work), CF._ptr(dscores), CF._ptr(lse), CF._ptr(delta),
-                                                CF._ptr(dq), CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk, Tp,
-                                                p_attn, seed_attn, CF._stream()), "csn_cross_attn_bwd_f32")
-        del work, dscores
+            dscores = torch.empty_like(scores)
+            work = scores.clone()                                    # the backward turns the scores into probabilities in place
+            if varlen:
+                _lib.check(L.csn_varlen_attn_bwd_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v), D * lq4,
+                                                     D * lk4, lq4, lk4, CF._ptr(work), CF._ptr(dscores), CF._ptr(lse), CF._ptr(delta),
+                                                     CF._ptr(dq), CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk,
+                                                     CF._ptr(q_lens), CF._ptr(k_lens), Tp, p_attn, seed_attn, CF._stream()),
+                           "csn_varlen_attn_bwd_f32")
+            else:
+                _lib.check(L.csn_cross_attn_bwd_f32(CF._ptr(datt), CF._ptr(att), D * lq4, CF._ptr(q), CF._ptr(k), CF._ptr(v), D * lq4,
+                                                    D * lk4, lq4, lk4, CF._ptr(work), CF._ptr(dscores), CF._ptr(lse), CF._ptr(delta),
+                                                    CF._ptr(dq), CF._ptr(dk), CF._ptr(dv), D * lq4, D * lk4, b, H, d, lq4, lk, Tp,
+                                                    p_attn, seed_attn, CF._stream()), "csn_cross_attn_bwd_f32")
+            del work, dscores
         need = ctx.needs_input_grad
         dq /= temperature                                            # Qs = (xq Wq^T) / sqrt(d)
         dw_q = CF.project_wgrad(dq, xq_cm) if need[3] else None

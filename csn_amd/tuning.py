@@ -49,8 +49,25 @@ class Tuning:
         **{(2, d): FLASH for d in (32, 64, 96, 128)},     # config 5: 18.5 -> 17.1 (recompute) -> 15.4 ms (flash)
         **{(1, d): FLASH for d in (32, 64, 96)}, (1, 128): RECOMPUTE_DQ})
 
+    # cross-length / ragged attention (csn_amd.minkowski_attention._CrossMHA, hence MultiHeadAttention.forward, forward_varlen and
+    # SimCSNHead): the score-free backward (csn_cross_attn_bwd_flash_f32 / csn_varlen_attn_bwd_flash_f32) — the forward keeps only
+    # lse, nothing score-sized is saved or allocated.  False: never.  True: wherever csn_cross_attn_flash_available says so
+    # (CsnError where it does not).  None: only when the three score-sized tensors of the kept flow exceed cross_score_budget
+    # (cross_takes_score_free) — a call that fits keeps its flow, its bits and its memory
+    cross_score_free: Optional[bool] = None
+    # bytes for that automatic decision; None: what the device can still give at forward time (free device memory + what the
+    # caching allocator holds but has not handed out)
+    cross_score_budget: Optional[int] = None
+
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))
+
+
+def cross_takes_score_free(score_bytes: int, budget: int, available: bool) -> bool:
+    """The automatic rule of ``cross_score_free=None``: score-free when the flow has kernels for the call's mode and head width
+    AND the kept flow's score-sized tensors (``score_bytes`` = 3 * b * H * lq4 * Tp * 4: the scores, the backward's working copy
+    and dscores) exceed ``budget``.  Deliberately conservative: it counts the score tensors alone."""
+    return bool(available) and score_bytes > budget
 
 
 _current = Tuning()

@@ -324,6 +324,39 @@ CSN_API int csn_varlen_attn_bwd_f32(const float* dctx, const float* ctx, long lo
                             int max_queries, int max_keys, const int* n_queries, const int* n_keys, int score_pitch,
                             float dropout_p, unsigned long long seed, void* stream);
 
+/* ---- (3d) score-free backward of (3b) and (3c) ---------------------------------------------------------------------------
+ * The backward of the cross-length and the ragged attention WITHOUT any score-sized tensor, for batches whose scores do not
+ * fit the device (one score tensor is n_evals * n_heads * n_queries * score_pitch * 4 bytes; the kept flow holds three).
+ * The forward runs as it does in (3b) / (3c) with scores = NULL and keeps only lse.  Then
+ *   launch 1, query-stationary: rebuilds S = Qs K^T tile by tile from q and the fp32 k map (one more matrix product per
+ *             tile), forms delta = rowsum(dctx * ctx) and writes delta and dq;
+ *   launch 2, key-stationary:   a work-group keeps 128 keys of k and v in registers, streams q, dctx, lse and delta, rebuilds
+ *             P and dS and writes dk and dv; a work-group whose keys lie beyond n_keys[e] exits at once.
+ * Forward + backward cost 9 instead of 6 products of 2 * n_queries * n_keys * d_head; no P / dS is written or read.
+ * Arguments: those of csn_cross_attn_bwd_f32 / csn_varlen_attn_bwd_f32 without scores and dscores; q is required, lse is
+ * read, delta, dq, dk, dv are written.  Geometry, alignment and the WRITTEN REGIONS are those of (3b) / (3c): dq columns
+ * < n_queries[e], dk / dv columns < round-up-4(n_keys[e]) with exact zeros in n_keys[e] .. round-up-4(n_keys[e]), delta entries
+ * < n_queries[e]; nothing else.  The padding points of q, k, v, dctx, ctx, lse must be finite; delta is read back only where
+ * launch 1 wrote it.  score_pitch stays an argument although no score buffer exists: the dropout mask is indexed with the pitch
+ * max(n_queries, score_pitch) (max_queries for the ragged call), and both launches regenerate the forward's mask bit for bit
+ * only with the forward's value (% 4, >= round-up-4(n_keys)).
+ * Available in math mode 1 at d_head = 32, 64, 96, 128 (the instances of the recomputing kernels: three LDS images of two
+ * planes per stage fit one CU up to d_head = 128); modes 2 and 3 run as mode 1, like (3b) / (3c).  Math mode 0 and d_head = 256
+ * return CSN_E_ARG before any launch.  csn_cross_attn_flash_available: 1 where both launches have kernels for d_head in the
+ * calling thread's math mode, else 0; host only, launches nothing. */
+CSN_API int csn_cross_attn_flash_available(int d_head);
+CSN_API int csn_cross_attn_bwd_flash_f32(const float* dctx, const float* ctx, long long ctx_eval_stride, const float* q, const float* k,
+                                 const float* v, long long q_shape_stride, long long kv_shape_stride, int ld_q, int ld_kv,
+                                 const float* lse, float* delta, float* dq, float* dk, float* dv, long long dq_eval_stride,
+                                 long long dkv_eval_stride, int n_evals, int n_heads, int d_head, int n_queries, int n_keys,
+                                 int score_pitch, float dropout_p, unsigned long long seed, void* stream);
+CSN_API int csn_varlen_attn_bwd_flash_f32(const float* dctx, const float* ctx, long long ctx_eval_stride, const float* q, const float* k,
+                                  const float* v, long long q_shape_stride, long long kv_shape_stride, int ld_q, int ld_kv,
+                                  const float* lse, float* delta, float* dq, float* dk, float* dv, long long dq_eval_stride,
+                                  long long dkv_eval_stride, int n_evals, int n_heads, int d_head, int max_queries, int max_keys,
+                                  const int* n_queries, const int* n_keys, int score_pitch, float dropout_p,
+                                  unsigned long long seed, void* stream);
+
 /* ---- (4) output projection + residual + LayerNorm, forward -------------------------------------------
  * z[c][n] = sum_D wfc[c][D] ctx[e][D][n] + xres[res_index[e]][c][n];  xhat = (z - mean_c z) * rstd,
  * rstd = 1/sqrt(var_c z + eps).   Replaces fc + residual + LayerNorm (csa_models.py:52,57,114-118) up to the

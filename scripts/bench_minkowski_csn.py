@@ -6,12 +6,15 @@ the ragged retrieval measure (hrnet.py:472-490).  Development aid, not the headl
              backward with gradients to queries, keys and every parameter: SimCSNHead (one varlen launch chain) against the
              reference's structure — a Python loop of per-shape / per-pair MultiHeadAttention calls plus eager head math.
   retrieval  16 x 16 shapes of 4096 points against csn_retrieval_measure_f32 on the same data, and a ragged 16 x 16 case of
-             1000..5000 points in TFLOP/s counting only real point pairs (2 C n m per pair)."""
+             1000..5000 points in TFLOP/s counting only real point pairs (2 C n m per pair).
+  --flows    kept,free: SimCSNHead alone with the kept-scores backward against the score-free one (csn_amd.tuning.cross_score_free),
+             alternating in one process: ms per step and the step's peak memory for each.  --points LO,HI sets the shape sizes;
+             "auto" leaves the choice to the automatic rule (the capability run at 11000..12000 points)."""
 import argparse, os, sys, time
 import numpy as np, torch
 import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from csn_amd import _lib
+from csn_amd import _lib, tuning
 from csn_amd import functional as CF
 from csn_amd.minkowski_csn import SimCSNHead, retrieval_measure_ragged
 
@@ -52,7 +55,8 @@ def bench_head(a, mode, K):
     H, C = 4, 256
     torch.manual_seed(0)
     head = SimCSNHead(C, H, 20, K).cuda().train()
-    lens = lambda: rng.integers(3000, 5001, a.shapes).tolist()
+    lo, hi = (int(x) for x in a.points.split(","))
+    lens = lambda: rng.integers(lo, hi + 1, a.shapes).tolist()
     qs = [torch.randn((n, C), device="cuda", requires_grad=True) for n in lens()]
     keys = [[torch.randn((n, C), device="cuda", requires_grad=True) for n in lens()] for _ in range(K)]
     q = torch.cat([t.detach() for t in qs]).requires_grad_(True)
@@ -70,10 +74,42 @@ def bench_head(a, mode, K):
         head.zero_grad(set_to_none=True)
         loop_step(head, qs, keys).square().mean().backward()
 
+    if a.flows:
+        return bench_flows(a, mode, K, fused, (lo, hi))
     ms = timed(fused, a.warmup, a.steps)
     ms_loop = timed(loop, a.warmup, a.steps) if not a.no_loop else float("nan")
     print(f"head mode {'bf16x3' if mode else 'fp32'}: B={a.shapes} shapes of 3000..5000 points, K={K}, d_model={C}, n_head={H}, "
           f"train fwd+bwd: SimCSNHead {ms:8.2f} ms/step, per-pair loop {ms_loop:8.2f} ms/step ({ms_loop / ms:4.2f}x)", flush=True)
+
+
+FLOWS = {"kept": False, "free": True, "auto": None}
+
+
+def bench_flows(a, mode, K, fused, points):
+    flows = a.flows.split(",")
+    ms, peak, took = {f: [] for f in flows}, {}, {}
+    for _ in range(a.rounds):
+        for f in flows:
+            names = set()
+            with tuning.override(cross_score_free=FLOWS[f]):
+                for _ in range(a.warmup):
+                    fused()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                _lib.set_call_hook(lambda name, phase: names.add(name))
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fused()
+                torch.cuda.synchronize()
+                ms[f].append((time.perf_counter() - t0) / a.steps * 1e3)
+                _lib.set_call_hook(None)
+                peak[f] = max(peak.get(f, 0), torch.cuda.max_memory_allocated() - base)
+                took[f] = "score-free" if "csn_varlen_attn_bwd_flash_f32" in names else "kept scores"
+    for f in flows:
+        print(f"head mode {mode}: B={a.shapes} shapes of {points[0]}..{points[1]} points, K={K}, train fwd+bwd, flow {f:5s} (ran {took[f]}): "
+              f"{min(ms[f]):9.2f} ms/step (min of {a.rounds} alternations: {' '.join(f'{x:.1f}' for x in ms[f])}), "
+              f"step peak memory {peak[f] / 2 ** 30:7.2f} GiB", flush=True)
 
 
 def bench_retrieval(a):
@@ -109,11 +145,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-loop", action="store_true", help="time only SimCSNHead (e.g. under a profiler)")
     ap.add_argument("--no-retrieval", action="store_true")
+    ap.add_argument("--points", default="3000,5000", help="LO,HI: points per shape of the head benchmark")
+    ap.add_argument("--flows", default="", help="comma list of kept / free / auto: time these data flows of SimCSNHead, alternating")
+    ap.add_argument("--rounds", type=int, default=3, help="alternations of --flows")
     a = ap.parse_args()
     for mode in (int(m) for m in a.modes.split(",")):
         for K in (int(k) for k in a.ks.split(",")):
             bench_head(a, mode, K)
-    if not a.no_retrieval:
+    if not a.no_retrieval and not a.flows:
         bench_retrieval(a)
     _lib.lib().csn_set_math_mode(1)
 
