@@ -16,3 +16,7 @@ def set_math_mode(mode) -> None:
     _lib.check(lib().csn_set_math_mode(CF.mode_id(mode)), "csn_set_math_mode")
 
 __version__ = "0.1.0"
+
+# the MinkowskiNet head's loss, metrics and train / test steps (MinkowskiNet/lib/trainer_csn.py:188-224, 400-500)
+from .minkowski_training import (SegBatch, SegMeter, evaluate, load_me_head_state, neighbor_batches, seg_loss,  # noqa: E402,F401
+                                 train_iter)

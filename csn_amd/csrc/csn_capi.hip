@@ -1054,4 +1054,45 @@ int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, const in
   return csn_launch_ragged_retrieval_f32(f1, offsets1, s1, N1, f2, offsets2, s2, N2, (int)mx1, channels, out, ws, (hipStream_t)stream);
 }
 
+// ---- (12) loss, predictions and IoU counts of the MinkowskiNet head ----
+long long csn_ragged_seg_workspace_bytes(int n_rows) {
+  if (n_rows <= 0) return 0;
+  return csn_ragged_seg_blocks(n_rows) * 4 * (long long)sizeof(double);
+}
+
+static int ragged_seg_dims(int n_rows, int ld, int n_classes) {
+  if (n_rows <= 0 || n_classes < 2 || ld < n_classes) return CSN_E_ARG;
+  if (n_rows > 0x7fffffff - 256 || ld > (1 << 20)) return CSN_E_DIM;       // 32-bit row indices; 256 rows below a 2 GiB window
+  return 0;
+}
+
+int csn_ragged_seg_fwd_f32(const float* logits, int n_rows, int ld, const long long* labels, const int* offsets_host,
+                           const int* offsets, int n_segments, int n_classes, int ignore_label, float* lse, float* nll, int* pred,
+                           double* stats, int* counts, void* ws, long long ws_bytes, void* stream) {
+  if (!logits || !labels || !offsets || !lse || !nll || !pred || !stats || !counts || !ws) return CSN_E_ARG;
+  if (const int e = ragged_seg_dims(n_rows, ld, n_classes)) return e;
+  if (ragged_offsets_max(offsets_host, n_segments) < 1 || offsets_host[n_segments] != n_rows) return CSN_E_ARG;
+  if ((long long)n_segments * n_classes * 3 > 0x7fffffffLL) return CSN_E_DIM;
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || (reinterpret_cast<uintptr_t>(stats) & 7)) return CSN_E_PTR;
+  if (ws_bytes < csn_ragged_seg_workspace_bytes(n_rows)) return CSN_E_WORKSPACE;
+  CsnRaggedSegArgs a{};
+  a.logits = logits; a.n_rows = n_rows; a.ld = ld; a.labels = labels; a.offsets = offsets; a.n_segments = n_segments;
+  a.n_classes = n_classes; a.ignore_label = ignore_label; a.lse = lse; a.nll = nll; a.pred = pred; a.stats = stats; a.counts = counts;
+  a.partials = static_cast<double*>(ws);
+  return csn_launch_ragged_seg_fwd(a, (hipStream_t)stream);
+}
+
+int csn_ragged_seg_bwd_f32(const float* logits, int n_rows, int ld, const long long* labels, int n_classes, int ignore_label,
+                           const float* lse, const float* nll, const double* stats, const float* grad_out, float* dlogits, int dld,
+                           void* stream) {
+  if (!logits || !labels || !lse || !nll || !stats || !grad_out || !dlogits) return CSN_E_ARG;
+  if (const int e = ragged_seg_dims(n_rows, ld, n_classes)) return e;
+  if (const int e = ragged_seg_dims(n_rows, dld, n_classes)) return e;
+  if (reinterpret_cast<uintptr_t>(stats) & 7) return CSN_E_PTR;
+  CsnRaggedSegArgs a{};
+  a.logits = logits; a.n_rows = n_rows; a.ld = ld; a.labels = labels; a.n_classes = n_classes; a.ignore_label = ignore_label;
+  a.lse = const_cast<float*>(lse); a.nll = const_cast<float*>(nll); a.stats = const_cast<double*>(stats); a.grad_out = grad_out; a.dlogits = dlogits; a.dld = dld;
+  return csn_launch_ragged_seg_bwd(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

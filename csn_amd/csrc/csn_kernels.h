@@ -239,6 +239,23 @@ int csn_launch_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const fl
 int csn_launch_ragged_retrieval_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2, int s2,
                                     long long N2, int max_n1, int C, float* out, float* ws, hipStream_t st);
 
+// ---- loss, predictions and IoU counts of the MinkowskiNet head on point-major ragged rows (minkowski_seg.hip) ----
+struct CsnRaggedSegArgs {
+  const float* logits;  int n_rows;  int ld;                      // [row][ld], n_classes <= ld
+  const long long* labels;                                        // [row] int64
+  const int* offsets;  int n_segments;                            // device copy, [n_segments + 1]
+  int n_classes, ignore_label;
+  float* lse;  float* nll;  int* pred;                            // [row]; nll = the row's loss (0 for an uncounted row)
+  double* stats;                                                  // [4]: mean loss, counted, correct, bad rows
+  int* counts;                                                    // [segment][class][3]: inter, gt, pr
+  double* partials;                                               // forward: 4 per work-group (csn_ragged_seg_blocks)
+  const float* grad_out;  float* dlogits;  int dld;               // backward
+  int pitch = 0, vec = 0;                                         // set by the launcher
+};
+long long csn_ragged_seg_blocks(int n_rows);
+int csn_launch_ragged_seg_fwd(const CsnRaggedSegArgs& a, hipStream_t st);
+int csn_launch_ragged_seg_bwd(const CsnRaggedSegArgs& a, hipStream_t st);
+
 // ---- compatibility head (compat.hip): normalize(W_q y_0 + b), normalize(W_k y_k + b), dot, softmax over the K+1 keys ----
 int csn_launch_compat_fwd(const float* pooled, const float* wq_t, const float* bq, const float* wk_t, const float* bk, float* comp,
                           double* save_u, double* save_n, int B, int K1, int C, int reference_layout, hipStream_t st);

@@ -526,6 +526,43 @@ CSN_API int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, 
                              const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
                              long long ws_floats, void* stream);
 
+/* ---- (12) loss, predictions and IoU counts of the MinkowskiNet head (MinkowskiNet/lib/trainer_csn.py:188-224, 400-500;
+ *           lib/utils.py:64-176) -----------------------------------------------------------------------------------------------
+ * The reference's loop computes nn.CrossEntropyLoss(ignore_index) (trainer_csn.py:406, 471), the prediction
+ * torch.max(output[:, 1:], 1)[1] + 1 (:221, :466), precision_at_one_partnet (utils.py:64-75) and calculate_iou (utils.py:78-110)
+ * one after the other, the last two on the host.  Here ONE pass reads the logits where the head leaves them: POINT-MAJOR ragged
+ * rows logits[n_rows][ld] (fp32, n_classes <= ld, any ld and alignment: 16-byte accesses where ld <= 59 and the base is 16-byte
+ * aligned), labels[n_rows] int64, and segments offsets[n_segments + 1] passed twice as in (11) (every segment >= 1 row, from 0 to
+ * n_rows: the shapes of the batch for the per-shape metric, {0, n_rows} for the reference's grouping of a whole test batch as
+ * one "model", trainer_csn.py:474).  n_classes >= 2; ignore_label is any int (the reference's default is 255).
+ *   A row is COUNTED when label != ignore_label and 0 <= label < n_classes; BAD when its label is neither the ignore label nor
+ *   in [0, n_classes) (torch raises for these; here they enter nothing but stats[3], so a caller can raise without a
+ *   synchronisation per step); otherwise IGNORED.
+ * csn_ragged_seg_fwd_f32 writes
+ *   lse[n]      log sum_{c < n_classes} exp(z[n][c])                                    (every row)
+ *   nll[n]      the row's loss lse - z[label] of a counted row, 0 otherwise.  It is formed as log1p(sum of the exponentials
+ *               without the maximum's) + (max - z[label]): two non-negative terms, where lse - z[label] cancels for a confident
+ *               row (a loss of 1e-3 is below one part in 1e4 of an lse of 4).  The loss sums these; the backward reads them.
+ *   pred[n]     1 + argmax_{1 <= c < n_classes} z[n][c], the FIRST maximum on ties      (every row, int32)
+ *   stats[0]    mean over the counted rows of lse - z[label]  (none: 0 / 0 = nan, as torch gives)
+ *   stats[1..3] the number of counted rows, of counted rows with pred == label or label == 0 (utils.py:69-70), of bad rows
+ *               (DOUBLES, 8-byte aligned)
+ *   counts[s][i][0..2]  (int32, overwritten) with p' = (label == 0 ? 0 : pred) over the rows of segment s that are not bad:
+ *               inter = #(label == i and p' == i), gt = #(label == i), pr = #(p' == i); union = gt + pr - inter.  An IGNORED
+ *               row keeps its prediction and enters pr (hence the union), as calculate_iou has it: only ground == 0 is zeroed.
+ *   ws: csn_ragged_seg_workspace_bytes(n_rows) bytes, 8-byte aligned (per-work-group fp64 partial sums, added in a fixed order:
+ *   the loss is bitwise reproducible; the counts are integer atomics: exact in any order).
+ * csn_ragged_seg_bwd_f32  dlogits[n][c] = counted ? (exp(z[n][c] - lse[n]) - [c == label]) * grad_out[0] / stats[1] : 0 for
+ *   c < n_classes, rows dld floats apart (n_classes <= dld); the columns [n_classes, dld) are LEFT UNTOUCHED.  A logit of -inf is
+ *   a probability of zero, as in (10).  The label's own entry is expm1(-nll[n]) (exp(z - lse) - 1 cancels).  16-byte accesses where ld == dld == n_classes and both bases are 16-byte aligned. */
+CSN_API long long csn_ragged_seg_workspace_bytes(int n_rows);
+CSN_API int csn_ragged_seg_fwd_f32(const float* logits, int n_rows, int ld, const long long* labels, const int* offsets_host,
+                           const int* offsets, int n_segments, int n_classes, int ignore_label, float* lse, float* nll, int* pred,
+                           double* stats, int* counts, void* ws, long long ws_bytes, void* stream);
+CSN_API int csn_ragged_seg_bwd_f32(const float* logits, int n_rows, int ld, const long long* labels, int n_classes, int ignore_label,
+                           const float* lse, const float* nll, const double* stats, const float* grad_out, float* dlogits, int dld,
+                           void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

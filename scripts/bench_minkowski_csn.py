@@ -9,7 +9,12 @@ the ragged retrieval measure (hrnet.py:472-490).  Development aid, not the headl
              1000..5000 points in TFLOP/s counting only real point pairs (2 C n m per pair).
   --flows    kept,free: SimCSNHead alone with the kept-scores backward against the score-free one (csn_amd.tuning.cross_score_free),
              alternating in one process: ms per step and the step's peak memory for each.  --points LO,HI sets the shape sizes;
-             "auto" leaves the choice to the automatic rule (the capability run at 11000..12000 points)."""
+             "auto" leaves the choice to the automatic rule (the capability run at 11000..12000 points).
+  --loss     torch,fused: the head's train step (39 classes, ~10 % of the rows labelled 255) with F.cross_entropy(ignore_index=255)
+             against csn_amd.seg_loss, alternating step by step in one process: median and interquartile range of --steps
+             steps each (>= 20 asked for); then an evaluate loop of 64 single-shape batches (csn_amd.evaluate: no host sync per
+             batch) against the reference-style loop on the same logits (cross-entropy, .item(), .cpu().numpy(), calculate_iou
+             restated per label on the host)."""
 import argparse, os, sys, time
 import numpy as np, torch
 import torch.nn.functional as F
@@ -17,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from csn_amd import _lib, tuning
 from csn_amd import functional as CF
 from csn_amd.minkowski_csn import SimCSNHead, retrieval_measure_ragged
+from csn_amd.minkowski_training import evaluate, seg_loss
 
 
 def timed(fn, warmup, steps):
@@ -54,7 +60,7 @@ def bench_head(a, mode, K):
     rng = np.random.default_rng(0)
     H, C = 4, 256
     torch.manual_seed(0)
-    head = SimCSNHead(C, H, 20, K).cuda().train()
+    head = SimCSNHead(C, H, 39 if a.loss else 20, K).cuda().train()
     lo, hi = (int(x) for x in a.points.split(","))
     lens = lambda: rng.integers(lo, hi + 1, a.shapes).tolist()
     qs = [torch.randn((n, C), device="cuda", requires_grad=True) for n in lens()]
@@ -76,10 +82,115 @@ def bench_head(a, mode, K):
 
     if a.flows:
         return bench_flows(a, mode, K, fused, (lo, hi))
+    if a.loss:
+        return bench_loss(a, mode, K, head, q, qo, kb, rng)
     ms = timed(fused, a.warmup, a.steps)
     ms_loop = timed(loop, a.warmup, a.steps) if not a.no_loop else float("nan")
     print(f"head mode {'bf16x3' if mode else 'fp32'}: B={a.shapes} shapes of 3000..5000 points, K={K}, d_model={C}, n_head={H}, "
           f"train fwd+bwd: SimCSNHead {ms:8.2f} ms/step, per-pair loop {ms_loop:8.2f} ms/step ({ms_loop / ms:4.2f}x)", flush=True)
+
+
+def quartiles(v):
+    q1, med, q3 = np.percentile(np.asarray(v), [25, 50, 75])
+    return f"median {med:8.3f} ms, IQR {q3 - q1:6.3f} ms ({q1:.3f} .. {q3:.3f})"
+
+
+def bench_loss(a, mode, K, head, q, qo, kb, rng):
+    N, n_cls = q.shape[0], 39
+    t = rng.integers(0, n_cls, N)
+    t[rng.random(N) < 0.1] = 255
+    target = torch.from_numpy(t).cuda()
+    losses = {"torch": lambda z: F.cross_entropy(z, target, ignore_index=255), "fused": lambda z: seg_loss(z, target, qo, 255)[0]}
+    kinds = a.loss.split(",")
+    ms = {k: [] for k in kinds}
+
+    def step(kind):
+        head.zero_grad(set_to_none=True)
+        losses[kind](head(q, qo, kb)).backward()
+
+    for k in kinds:
+        for _ in range(a.warmup):
+            step(k)
+    for _ in range(a.steps):
+        for k in kinds:                                      # alternating: drift of the clocks falls on both alike
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step(k)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    for k in kinds:
+        print(f"head mode {'bf16x3' if mode else 'fp32'}: B={a.shapes} shapes, {N} rows, K={K}, {n_cls} classes, train step with the "
+              f"{k:5s} loss: {quartiles(ms[k])} over {a.steps} steps", flush=True)
+    # the loss pair alone on the head's logits (forward + backward to the logits)
+    with torch.no_grad():
+        z0 = head(q, qo, kb)
+    for k in kinds:
+        z = z0.clone().requires_grad_(True)
+        def pair():
+            z.grad = None
+            losses[k](z).backward()
+        print(f"  {k:5s} loss alone, forward + backward on ({N}, {n_cls}) logits: {timed(pair, a.warmup, max(a.steps, 20)):8.3f} ms", flush=True)
+
+
+def host_iou(ground, prediction, num_labels):
+    """calculate_iou (MinkowskiNet/lib/utils.py:78-110) restated: one host pass over the rows per label."""
+    prediction = np.copy(prediction)
+    prediction[ground == 0] = 0
+    inter, union = {}, {}
+    for i in range(1, num_labels):
+        u = np.sum((ground == i) | (prediction == i))
+        if u > 0:
+            inter[i], union[i] = float(np.sum((ground == i) & (prediction == i))), float(u)
+    return inter, union
+
+
+def bench_evaluate(a):
+    """64 single-shape test batches of 3000..5000 rows, 39 classes: csn_amd.evaluate against the loop of trainer_csn.py:429-475 on
+    the same logits (the model's forward is left out of both)."""
+    rng = np.random.default_rng(3)
+    n_cls = 39
+    batches = []
+    for n in rng.integers(3000, 5001, 64).tolist():
+        t = rng.integers(0, n_cls, n)
+        t[rng.random(n) < 0.1] = 255
+        batches.append(((torch.randn((n, n_cls), device="cuda"), [0, n]), torch.from_numpy(t).cuda()))
+
+    def fused():
+        return evaluate(lambda b: b, batches, n_cls)
+
+    def reference_style():
+        loss_sum = score_sum = rows = 0.0
+        inter, union, shape_ious = np.zeros(n_cls), np.zeros(n_cls), []
+        for (z, _), target in batches:
+            pred = torch.max(z[:, 1:], 1)[1] + 1
+            n = target.shape[0]
+            loss_sum += float(F.cross_entropy(z, target, ignore_index=255)) * n
+            ok = (pred.eq(target) | target.eq(0))[target != 255]
+            score_sum += ok.float().sum(0).mul(100.0 / ok.size(0)).item() * n
+            rows += n
+            i_s, u_s = host_iou(target.cpu().numpy(), pred.cpu().numpy(), n_cls)
+            for k in i_s:
+                inter[k] += i_s[k]
+                union[k] += u_s[k]
+            if i_s:
+                shape_ious.append(sum(i_s[k] / u_s[k] for k in i_s) / len(i_s))
+        part = sum(inter[k] / union[k] if union[k] > 0 else 0.0 for k in range(1, n_cls)) / (n_cls - 1)
+        return loss_sum / rows, score_sum / rows, part * 100, float(np.mean(shape_ious)) * 100
+
+    got, want = fused(), reference_style()
+    ms = {"evaluate": [], "reference-style": []}
+    for _ in range(max(a.steps, 20) // 4 + 1):
+        for name, fn in (("evaluate", fused), ("reference-style", reference_style)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    for name in ms:
+        print(f"evaluate loop, 64 single-shape batches of 3000..5000 rows, {n_cls} classes, {name:15s}: {quartiles(ms[name])} over "
+              f"{len(ms[name])} loops", flush=True)
+    print(f"  results (loss, precision, Part IoU, Shape IoU): evaluate {tuple(round(v, 6) for v in got)}, reference-style "
+          f"{tuple(round(v, 6) for v in want)}", flush=True)
 
 
 FLOWS = {"kept": False, "free": True, "auto": None}
@@ -148,11 +259,14 @@ def main():
     ap.add_argument("--points", default="3000,5000", help="LO,HI: points per shape of the head benchmark")
     ap.add_argument("--flows", default="", help="comma list of kept / free / auto: time these data flows of SimCSNHead, alternating")
     ap.add_argument("--rounds", type=int, default=3, help="alternations of --flows")
+    ap.add_argument("--loss", default="", help="comma list of torch / fused: time the head's train step under these losses, alternating")
     a = ap.parse_args()
     for mode in (int(m) for m in a.modes.split(",")):
         for K in (int(k) for k in a.ks.split(",")):
             bench_head(a, mode, K)
-    if not a.no_retrieval and not a.flows:
+    if a.loss:
+        bench_evaluate(a)
+    if not a.no_retrieval and not a.flows and not a.loss:
         bench_retrieval(a)
     _lib.lib().csn_set_math_mode(1)
 
