@@ -1095,4 +1095,66 @@ int csn_ragged_seg_bwd_f32(const float* logits, int n_rows, int ld, const long l
   return csn_launch_ragged_seg_bwd(a, (hipStream_t)stream);
 }
 
+// ---- (13) fc_layer of the MinkowskiNet head: 1x1 convolution + BatchNorm + ReLU on point-major rows ----
+static int rows_fc_dims(int n_rows, int c_in, int c_out) {
+  if (n_rows <= 0) return CSN_E_ARG;
+  if (c_in < 32 || c_in > 1024 || (c_in & 31) || !dim_ok(c_out)) return CSN_E_DIM;
+  return 0;
+}
+static int rows_fc_pitch(long long ld, int width) {
+  if (ld < width) return CSN_E_ARG;
+  if (ld > (1 << 20)) return CSN_E_DIM;
+  return (ld & 3) ? CSN_E_ALIGN : 0;
+}
+
+long long csn_rows_fc_workspace_bytes(int n_rows, int c_in, int c_out, int training, int backward) {
+  if (rows_fc_dims(n_rows, c_in, c_out)) return 0;
+  return csn_rows_fc_ws_bytes(n_rows, c_in, c_out, training != 0, backward != 0);
+}
+
+int csn_rows_fc_fwd_f32(const float* x, long long ld_x, int n_rows, int c_in, int c_out, const float* w, const float* bias,
+                        const float* gamma, const float* beta, float* running_mean, float* running_var, float eps, float momentum,
+                        int training, float* y, long long ld_y, float* z, long long ld_z, float* mean, float* invstd, void* ws,
+                        long long ws_bytes, void* stream) {
+  if (!x || !w || !gamma || !beta || !y) return CSN_E_ARG;
+  if (training ? (!z || !mean || !invstd || !ws) : (!running_mean || !running_var)) return CSN_E_ARG;
+  if (const int e = rows_fc_dims(n_rows, c_in, c_out)) return e;
+  if (const int e = rows_fc_pitch(ld_x, c_in)) return e;
+  if (const int e = rows_fc_pitch(ld_y, c_out)) return e;
+  if (training) if (const int e = rows_fc_pitch(ld_z, c_out)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (training && (mis16(z) || mis16(ws)))) return CSN_E_PTR;
+  if (training && n_rows == 1) return CSN_E_ARG;                  // a one-row batch has no variance (torch refuses it too)
+  if (ws_bytes < csn_rows_fc_ws_bytes(n_rows, c_in, c_out, training != 0, 0)) return CSN_E_WORKSPACE;
+  CsnRowsFcArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.w = w; a.bias = bias; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean;
+  a.running_var = running_var; a.eps = eps; a.momentum = momentum; a.training = training != 0; a.n_rows = n_rows; a.c_in = c_in;
+  a.c_out = c_out; a.y = y; a.ld_y = (int)ld_y; a.z = z; a.ld_z = (int)ld_z; a.mean = mean; a.invstd = invstd; a.ws = ws;
+  return csn_launch_rows_fc_fwd(a, mode(), (hipStream_t)stream);
+}
+
+int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const float* z, long long ld_z,
+                        const float* x, long long ld_x, int n_rows, int c_in, int c_out, const float* w, const float* bias,
+                        const float* gamma, const float* stat_mean, const float* stat_scale, float eps, int training, float* dx,
+                        long long ld_dx, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws, long long ws_bytes,
+                        void* stream) {
+  if (!dy || !y || !x || !w || !gamma || !stat_mean || !stat_scale || !dgamma || !dbeta || !ws) return CSN_E_ARG;
+  if (training && !z) return CSN_E_ARG;
+  if (const int e = rows_fc_dims(n_rows, c_in, c_out)) return e;
+  if (const int e = rows_fc_pitch(ld_dy, c_out)) return e;
+  if (const int e = rows_fc_pitch(ld_y, c_out)) return e;
+  if (const int e = rows_fc_pitch(ld_x, c_in)) return e;
+  if (training) if (const int e = rows_fc_pitch(ld_z, c_out)) return e;
+  if (dx) if (const int e = rows_fc_pitch(ld_dx, c_in)) return e;
+  if (mis16(dy) || mis16(y) || mis16(x) || mis16(w) || mis16(ws) || (training && mis16(z)) || (dx && mis16(dx)) || (dw && mis16(dw)))
+    return CSN_E_PTR;
+  if (training && n_rows == 1) return CSN_E_ARG;
+  if (ws_bytes < csn_rows_fc_ws_bytes(n_rows, c_in, c_out, training != 0, 1)) return CSN_E_WORKSPACE;
+  CsnRowsFcArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.w = w; a.bias = bias; a.gamma = gamma; a.eps = eps; a.training = training != 0; a.n_rows = n_rows;
+  a.c_in = c_in; a.c_out = c_out; a.y = const_cast<float*>(y); a.ld_y = (int)ld_y; a.z = const_cast<float*>(z); a.ld_z = (int)ld_z;
+  a.mean = const_cast<float*>(stat_mean); a.invstd = const_cast<float*>(stat_scale); a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx;
+  a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias; a.dgamma = dgamma; a.dbeta = dbeta; a.ws = ws;
+  return csn_launch_rows_fc_bwd(a, mode(), (hipStream_t)stream);
+}
+
 }  // extern "C"

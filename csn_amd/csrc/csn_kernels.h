@@ -262,3 +262,21 @@ int csn_launch_compat_fwd(const float* pooled, const float* wq_t, const float* b
 int csn_launch_compat_bwd(const float* dcomp, const float* comp, const double* save_u, const double* save_n, const float* pooled,
                           const float* wq, const float* wk, double* d_raw, double* dx, float* dpooled, float* dwq, float* dbq,
                           float* dwk, float* dbk, int B, int K1, int C, int reference_layout, hipStream_t st);
+
+// ---- fc_layer of the MinkowskiNet head on point-major rows: 1x1 convolution + BatchNorm + ReLU (rows_fc.hip) ----
+struct CsnRowsFcArgs {
+  const float* x;  int ld_x;                                      // [n_rows][ld_x], c_in <= ld_x
+  const float* w;  const float* bias;                             // [c_out][c_in] row-major; bias optional
+  const float* gamma;  const float* beta;
+  float* running_mean;  float* running_var;  float eps, momentum;
+  int training, n_rows, c_in, c_out;
+  float* y;  int ld_y;                                            // forward: written; backward: read (the ReLU mask is y > 0)
+  float* z;  int ld_z;                                            // training: x w^T + bias, kept for the backward
+  float* mean;  float* invstd;                                    // training: the batch's; eval backward: running mean / variance
+  const float* dy;  int ld_dy;
+  float* dx;  int ld_dx;  float* dw;  float* dbias;  float* dgamma;  float* dbeta;
+  void* ws;
+};
+long long csn_rows_fc_ws_bytes(long long n_rows, int c_in, int c_out, int training, int backward);
+int csn_launch_rows_fc_fwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);
+int csn_launch_rows_fc_bwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);

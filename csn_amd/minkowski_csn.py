@@ -29,7 +29,10 @@ which d comp, d gamma, d beta follow), the compatibility math's autograd, then `
 descriptors' share, added to S and written for T), then the attention backward.
 
 The sparse backbone (MinkowskiEngine) is out of scope: inputs are the backbone features after ``fc_layer``, packed
-point-major rows sorted by shape plus their offsets (``offsets_from_batch_index`` derives them from an ME batch column).
+point-major rows sorted by shape plus their offsets (``offsets_from_batch_index`` derives them from an ME batch column) — or,
+for a head built with ``backbone_channels``, the concatenated backbone map itself: the head then owns ``fc_layer``
+(``BackboneFC``: hrnet.py:332-339, the kernel-size-1 convolution + BatchNorm + ReLU on ``csn_rows_fc_fwd_f32`` / ``_bwd_f32``) and
+applies it to the query batch and to every key batch, one BatchNorm batch each, as hrnet.py:439 and :451 do.
 """
 from __future__ import annotations
 
@@ -239,6 +242,97 @@ class _RaggedHead(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------
+# fc_layer: kernel-size-1 convolution + BatchNorm + ReLU on point-major rows
+# ------------------------------------------------------------------------------------------------------
+class _RowsFC(torch.autograd.Function):
+    """y = relu(batch_norm(x w^T + b)) through ``csn_rows_fc_fwd_f32`` / ``csn_rows_fc_bwd_f32``; one call is one BatchNorm
+    batch.  Training updates ``running_mean`` / ``running_var`` in place."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, eps, momentum, training):
+        CF._need_cuda(x, w, b, gamma, beta, running_mean, running_var)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        x = x.contiguous()
+        w_c, b_c, g_c, be_c = (t.detach().contiguous() for t in (w, b, gamma, beta))
+        N, c_in = x.shape
+        C = w_c.shape[0]
+        dev = x.device
+        y = torch.empty((N, C), device=dev, dtype=torch.float32)
+        z = mean = invstd = ws = None
+        ws_n = 0
+        if training:
+            z = torch.empty((N, C), device=dev, dtype=torch.float32)
+            mean = torch.empty((C,), device=dev, dtype=torch.float32)
+            invstd = torch.empty((C,), device=dev, dtype=torch.float32)
+            ws_n = int(L.csn_rows_fc_workspace_bytes(N, c_in, C, 1, 0))
+            ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        _lib.check(L.csn_rows_fc_fwd_f32(CF._ptr(x), c_in, N, c_in, C, CF._ptr(w_c), CF._ptr(b_c), CF._ptr(g_c), CF._ptr(be_c),
+                                         CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum), int(training),
+                                         CF._ptr(y), C, CF._ptr(z), C, CF._ptr(mean), CF._ptr(invstd), CF._ptr(ws), ws_n,
+                                         CF._stream()), "csn_rows_fc_fwd_f32")
+        if training:
+            ctx.save_for_backward(x, w_c, b_c, g_c, y, z, mean, invstd)
+        else:
+            ctx.save_for_backward(x, w_c, b_c, g_c, y, None, running_mean.clone(), running_var.clone())
+        ctx.training, ctx.eps = bool(training), float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with CF.math_mode(CF.backward_mode(ctx.mode)):
+            x, w, b, gamma, y, z, s_mean, s_scale = ctx.saved_tensors
+            L = _lib.lib()
+            N, c_in = x.shape
+            C = w.shape[0]
+            dev = x.device
+            dy = dy.contiguous()
+            need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            db = torch.empty((C,), device=dev, dtype=torch.float32) if need_b else None
+            dgamma = torch.empty((C,), device=dev, dtype=torch.float32)
+            dbeta = torch.empty((C,), device=dev, dtype=torch.float32)
+            ws_n = int(L.csn_rows_fc_workspace_bytes(N, c_in, C, int(ctx.training), 1))
+            ws = torch.empty((ws_n,), device=dev, dtype=torch.uint8)
+            _lib.check(L.csn_rows_fc_bwd_f32(CF._ptr(dy), C, CF._ptr(y), C, CF._ptr(z), C, CF._ptr(x), c_in, N, c_in, C, CF._ptr(w),
+                                             CF._ptr(b), CF._ptr(gamma), CF._ptr(s_mean), CF._ptr(s_scale), ctx.eps,
+                                             int(ctx.training), CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db), CF._ptr(dgamma),
+                                             CF._ptr(dbeta), CF._ptr(ws), ws_n, CF._stream()), "csn_rows_fc_bwd_f32")
+            return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+
+
+class BackboneFC(nn.Sequential):
+    """``fc_layer`` of hrnet.py:332-339 on dense rows: ``nn.Linear(in_channels, d_model)`` (the kernel-size-1
+    MinkowskiConvolution with bias), ``nn.BatchNorm1d(d_model, momentum=bn_momentum)`` (lib/config.py:63 gives 0.02) and
+    ``nn.ReLU`` — as holders of parameters and buffers only: ``forward`` runs the three as one autograd node on the HIP kernels.
+    BatchNorm weight 1 and bias 0 at construction (hrnet.py:165-169).  One call is one BatchNorm batch over its (N, in_channels)
+    rows; a training call with one row raises ``ValueError`` as torch does."""
+
+    def __init__(self, in_channels: int, d_model: int, bn_momentum: float = 0.02, eps: float = 1e-5):
+        if d_model not in LN_WIDTHS:
+            raise ValueError(f"d_model {d_model} is not supported: the kernels are built for d_model in {LN_WIDTHS}")
+        if in_channels % 32 or not 32 <= in_channels <= 1024:
+            raise ValueError(f"in_channels {in_channels} is not supported: a multiple of 32 in [32, 1024]")
+        super().__init__(nn.Linear(in_channels, d_model, bias=True), nn.BatchNorm1d(d_model, eps=eps, momentum=bn_momentum), nn.ReLU())
+        nn.init.constant_(self[1].weight, 1.0)
+        nn.init.constant_(self[1].bias, 0.0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        fc, bn = self[0], self[1]
+        if not x.is_cuda:
+            raise _lib.CsnError("csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+        if x.dim() != 2 or x.shape[1] != fc.in_features:
+            raise ValueError(f"rows must be (N, {fc.in_features})")
+        if self.training and x.shape[0] == 1:
+            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+        if self.training:
+            bn.num_batches_tracked += 1
+        return _RowsFC.apply(x.float(), fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                             bn.momentum, self.training)
+
+
+# ------------------------------------------------------------------------------------------------------
 # the module
 # ------------------------------------------------------------------------------------------------------
 class SimCSNHead(nn.Module):
@@ -251,7 +345,8 @@ class SimCSNHead(nn.Module):
     keys a list of K (rows, offsets) pairs, one per neighbour rank (``get_neighbors``, csn_utils.py:114-130: key batch i holds
     the i-th neighbour of every query shape).  Returns (N, out_channels), or with ``return_ssa`` the SSA rows (N, d_model)."""
 
-    def __init__(self, d_model: int, n_head: int, out_channels: int, k_neighbors: int, dropout: float = 0.1):
+    def __init__(self, d_model: int, n_head: int, out_channels: int, k_neighbors: int, dropout: float = 0.1,
+                 backbone_channels: Optional[int] = None, bn_momentum: float = 0.02):
         super().__init__()
         if d_model not in LN_WIDTHS:
             raise ValueError(f"d_model {d_model} is not supported: the LayerNorm epilogues are built for d_model in {LN_WIDTHS}")
@@ -263,6 +358,9 @@ class SimCSNHead(nn.Module):
             self.linear_q = nn.Linear(d_model, d_model, bias=False)
             self.linear_k = nn.Linear(d_model, d_model, bias=False)
             self.sim = ScaledDotProduct(d_model ** 0.5)
+        self.backbone_channels = backbone_channels
+        if backbone_channels is not None:
+            self.fc_layer = BackboneFC(backbone_channels, d_model, bn_momentum=bn_momentum)
 
     @staticmethod
     def cosine_similarity(q: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
@@ -289,8 +387,9 @@ class SimCSNHead(nn.Module):
     def forward(self, q: torch.Tensor, q_offsets, keys: Optional[Sequence[Ragged]] = None, return_ssa: bool = False):
         if not q.is_cuda:
             raise _lib.CsnError("csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
-        if q.dim() != 2 or q.shape[1] != self.d_model:
-            raise ValueError(f"queries must be (N, {self.d_model}) rows")
+        c_rows = self.d_model if self.backbone_channels is None else self.backbone_channels
+        if q.dim() != 2 or q.shape[1] != c_rows:
+            raise ValueError(f"queries must be (N, {c_rows}) rows")
         K = 0 if (keys is None or return_ssa) else len(keys)
         if K > 0 and self.k_neighbors == 0:
             raise ValueError("this head was built with k_neighbors = 0 (no linear_q / linear_k): it takes no key batches")
@@ -300,6 +399,16 @@ class SimCSNHead(nn.Module):
         q = q.float()
         qo = _host_offsets(q_offsets, q.shape[0])
         B = len(qo) - 1
+        if self.backbone_channels is not None:
+            # fc_layer on the query batch, then on key batch 0 .. K-1 (hrnet.py:439, :451): the order of the running statistics
+            for rows, offs in (keys or [])[:K]:
+                if not rows.is_cuda:
+                    raise _lib.CsnError("csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+                if rows.dim() != 2 or rows.shape[1] != c_rows:
+                    raise ValueError(f"key batches must be (N, {c_rows}) rows")
+                _host_offsets(offs, rows.shape[0])
+            q = self.fc_layer(q)
+            keys = [(self.fc_layer(rows), offs) for rows, offs in (keys or [])[:K]]
         q_shapes = [q[a:b] for a, b in zip(qo, qo[1:])]
         k_shapes = []
         for rows, offs in (keys or [])[:K]:

@@ -222,7 +222,10 @@ def load_me_head_state(head: SimCSNHead, state_dict) -> SimCSNHead:
     """Copy the head of an ``HRNetSimCSN`` checkpoint (hrnet.py:341-357) into a ``SimCSNHead``: ``MHA.*`` and ``linear_q/k.weight``
     by name; ``output`` is a kernel-size-1 ``MinkowskiConvolution`` there and an ``nn.Linear`` here, so ``output.kernel`` —
     (2C, out) or (1, 2C, out) — is transposed into ``output.weight`` (out, 2C) and ``output.bias`` — (out,) or (1, out) — is
-    flattened.  Any other shape raises.  (The two layouts are MinkowskiEngine's documented ones; no ME tensor was read.)"""
+    flattened.  Any other shape raises.  (The two layouts are MinkowskiEngine's documented ones; no ME tensor was read.)
+    A head built with ``backbone_channels`` takes ``fc_layer`` too (hrnet.py:332-339): ``fc_layer.0.kernel`` — (c_in, C) or
+    (1, c_in, C) — transposed into ``fc_layer.0.weight``, ``fc_layer.0.bias`` flattened, and the ``fc_layer.1.bn.*`` tensors of the
+    MinkowskiBatchNorm wrapper into ``fc_layer.1.*``; a head without it ignores those keys."""
     own = head.state_dict()
     out_ch, two_c = head.output.weight.shape
     new = {}
@@ -245,6 +248,26 @@ def load_me_head_state(head: SimCSNHead, state_dict) -> SimCSNHead:
         raise ValueError(f"output.bias is {tuple(bias.shape)}; expected ({out_ch},) or (1, {out_ch})")
     new["output.weight"] = kernel.t()
     new["output.bias"] = bias
+    if getattr(head, "fc_layer", None) is not None:
+        C, c_in = head.fc_layer[0].weight.shape
+        for need in ("fc_layer.0.kernel", "fc_layer.0.bias"):
+            if need not in state_dict:
+                raise ValueError(f"checkpoint has no {need}")
+        kernel, bias = state_dict["fc_layer.0.kernel"], state_dict["fc_layer.0.bias"]
+        if tuple(kernel.shape) == (1, c_in, C):
+            kernel = kernel[0]
+        if tuple(kernel.shape) != (c_in, C):
+            raise ValueError(f"fc_layer.0.kernel is {tuple(kernel.shape)}; expected ({c_in}, {C}) or (1, {c_in}, {C})")
+        if tuple(bias.shape) == (1, C):
+            bias = bias[0]
+        if tuple(bias.shape) != (C,):
+            raise ValueError(f"fc_layer.0.bias is {tuple(bias.shape)}; expected ({C},) or (1, {C})")
+        new["fc_layer.0.weight"] = kernel.t()
+        new["fc_layer.0.bias"] = bias
+        for leaf in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
+            if f"fc_layer.1.bn.{leaf}" not in state_dict:
+                raise ValueError(f"checkpoint has no fc_layer.1.bn.{leaf}")
+            new[f"fc_layer.1.{leaf}"] = state_dict[f"fc_layer.1.bn.{leaf}"]
     with torch.no_grad():
         for name, v in new.items():
             if tuple(own[name].shape) != tuple(v.shape):

@@ -563,6 +563,48 @@ CSN_API int csn_ragged_seg_bwd_f32(const float* logits, int n_rows, int ld, cons
                            const float* lse, const float* nll, const double* stats, const float* grad_out, float* dlogits, int dld,
                            void* stream);
 
+/* ---- (13) fc_layer of the MinkowskiNet head: 1x1 convolution + BatchNorm + ReLU (MinkowskiNet/models/hrnet.py:332-339, applied
+ *           to the query batch at :439 and to every key batch at :451) -----------------------------------------------------------
+ * The reference's fc_layer is MinkowskiConvolution(kernel_size = 1, bias) + MinkowskiBatchNorm + MinkowskiReLU on the concatenated
+ * backbone map (416 / 480 / 992 channels) down to d_model.  On the dense feature rows this is nn.Linear + nn.BatchNorm1d + ReLU;
+ * ONE CALL IS ONE BatchNorm BATCH (the reference calls the layer once per batch).  Everything is POINT-MAJOR fp32:
+ *   x[n_rows][ld_x]  (c_in <= ld_x),  w[c_out][c_in] row-major (contiguous),  bias[c_out] (may be NULL),  gamma / beta /
+ *   running_mean / running_var / mean / invstd [c_out],  y[n_rows][ld_y],  z[n_rows][ld_z],  dy[n_rows][ld_dy],  dx[n_rows][ld_dx],
+ *   dw[c_out][c_in] (contiguous),  dbias / dgamma / dbeta [c_out].  Columns of a row beyond its width are neither read as data nor
+ *   written.
+ * Geometry: n_rows >= 1 (no % 4 requirement); c_in % 32 == 0, 32 <= c_in <= 1024; c_out in {32, 64, 96, 128, 256} (CSN_E_DIM);
+ * every pitch % 4 == 0 (CSN_E_ALIGN), >= its width (CSN_E_ARG) and <= 2^20 (CSN_E_DIM); x, w, y, z, dy, dx, dw, ws 16-byte aligned
+ * (CSN_E_PTR).  training != 0 with n_rows == 1 returns CSN_E_ARG (no variance; torch refuses it too).  All of this is checked on the
+ * host before any launch.  ws: csn_rows_fc_workspace_bytes(n_rows, c_in, c_out, training, backward) bytes (backward = 0 for the
+ * forward call, 1 for the backward call; 0 for an eval forward, which takes ws = NULL).
+ * csn_rows_fc_fwd_f32, training != 0:
+ *   z = x w^T + bias;  mean, var (biased) per column over the n_rows rows;  invstd = 1 / sqrt(var + eps);
+ *   y = max(0, gamma (z - mean) invstd + beta);  running_mean <- (1 - momentum) running_mean + momentum mean;
+ *   running_var <- (1 - momentum) running_var + momentum var n / (n - 1)   (either running pointer may be NULL: not tracked).
+ *   z, mean and invstd are written for the backward.  The column statistics are (mean, M2) pairs of 32-row tiles formed in the
+ *   product's epilogue and merged by Chan's formula in fp64 in a fixed order.
+ * csn_rows_fc_fwd_f32, training == 0: ONE launch; the product's epilogue applies s = gamma / sqrt(running_var + eps),
+ *   t = beta + (bias - running_mean) s and the ReLU: only y is written (z, mean, invstd, ws may be NULL).
+ * csn_rows_fc_bwd_f32: with g' = dy [y > 0] (y is the forward's output: the mask is the forward's own) and xhat = (z - mean) invstd,
+ *   dgamma = sum_n g' xhat,  dbeta = sum_n g'                                             (always written)
+ *   training: dz = gamma invstd (g' - mean_n g' - xhat mean_n (g' xhat));  stat_mean / stat_scale = the forward's mean / invstd
+ *   eval:     dz = g' gamma / sqrt(running_var + eps);  stat_mean / stat_scale = running_mean / running_var; z is not read (NULL):
+ *             the product x w^T + bias is formed again into ws
+ *   dx = dz w,  dw = dz^T x (split-K over the rows, slabs added in order),  dbias = sum_n dz — each skipped when its pointer is NULL.
+ *   Column sums are fp64 partials of 64-row chunks added in a fixed order.
+ * No floating-point atomics: two identical calls give the same bits.  Math mode 0 runs the three products on the exact fp32 matrix
+ * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (3b). */
+CSN_API long long csn_rows_fc_workspace_bytes(int n_rows, int c_in, int c_out, int training, int backward);
+CSN_API int csn_rows_fc_fwd_f32(const float* x, long long ld_x, int n_rows, int c_in, int c_out, const float* w, const float* bias,
+                        const float* gamma, const float* beta, float* running_mean, float* running_var, float eps, float momentum,
+                        int training, float* y, long long ld_y, float* z, long long ld_z, float* mean, float* invstd, void* ws,
+                        long long ws_bytes, void* stream);
+CSN_API int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const float* z, long long ld_z,
+                        const float* x, long long ld_x, int n_rows, int c_in, int c_out, const float* w, const float* bias,
+                        const float* gamma, const float* stat_mean, const float* stat_scale, float eps, int training, float* dx,
+                        long long ld_dx, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws, long long ws_bytes,
+                        void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
