@@ -20,3 +20,7 @@ __version__ = "0.1.0"
 # the MinkowskiNet head's loss, metrics and train / test steps (MinkowskiNet/lib/trainer_csn.py:188-224, 400-500)
 from .minkowski_training import (SegBatch, SegMeter, evaluate, load_me_head_state, neighbor_batches, seg_loss,  # noqa: E402,F401
                                  train_iter)
+
+# sparse 3D convolution on voxel rows: the primitive of the HRNet backbone (MinkowskiNet/models/hrnet.py:39-53, 89-111, 233-239)
+from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseConvTranspose3d, build_kernel_map,  # noqa: E402,F401
+                             sparse_conv3d)

@@ -123,6 +123,7 @@ int csn_dev_get(int key) {
     case CSN_DEV_WIDE_FORMS: return csn_gemm_wide_set;
     case CSN_DEV_WX: return csn_dev_wx;
     case CSN_DEV_LNB_GROUP: return csn_dev_lnb_group;
+    case CSN_DEV_SCONV_NB: return csn_dev_sconv_nb;
     default: return CSN_E_ARG;
   }
 }
@@ -137,6 +138,10 @@ int csn_dev_set(int key, int value) {
       csn_dev_wx = value;
       break;
     case CSN_DEV_LNB_GROUP: csn_dev_lnb_group = value < 0 ? 0 : value; break;
+    case CSN_DEV_SCONV_NB:
+      if (value < 0 || value > 4) return CSN_E_ARG;
+      csn_dev_sconv_nb = value;
+      break;
     default: return CSN_E_ARG;
   }
   return prev;
@@ -1155,6 +1160,60 @@ int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long l
   a.mean = const_cast<float*>(stat_mean); a.invstd = const_cast<float*>(stat_scale); a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx;
   a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias; a.dgamma = dgamma; a.dbeta = dbeta; a.ws = ws;
   return csn_launch_rows_fc_bwd(a, mode(), (hipStream_t)stream);
+}
+
+// ---- (14) sparse 3D convolution on voxel rows over a kernel map ----
+static int sparse_conv_dims(int n_in, int n_out, int kv, int c_in, int c_out) {
+  if (n_in <= 0 || n_out <= 0) return CSN_E_ARG;
+  if (kv != 1 && kv != 27 && kv != 125) return CSN_E_DIM;
+  if (c_in < 32 || c_in > 256 || (c_in & 31) || c_out < 32 || c_out > 256 || (c_out & 31)) return CSN_E_DIM;
+  return 0;
+}
+// a row-major map of n rows: pitch % 4, >= its width, and the whole map inside one 2 GiB buffer window
+static int sparse_conv_map(long long ld, int width, int n) {
+  if (ld < width) return CSN_E_ARG;
+  if (ld & 3) return CSN_E_ALIGN;
+  if (ld > (1 << 20) || (long long)n * ld * 4 > 0x7fffffffLL) return CSN_E_DIM;
+  return 0;
+}
+
+long long csn_sparse_conv_workspace_bytes(int n_in, int n_out, int kv, int c_in, int c_out, int backward) {
+  if (sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return 0;
+  return csn_sparse_conv_ws_bytes(n_in, n_out, kv, c_in, c_out, backward != 0);
+}
+
+int csn_sparse_conv_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
+                            const float* w, const float* bias, float* y, long long ld_y, void* stream) {
+  if (!x || !table || !w || !y) return CSN_E_ARG;
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
+  if (const int e = sparse_conv_map(ld_y, c_out, n_out)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  CsnSparseConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
+  a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
+  return csn_launch_sparse_conv_fwd(a, mode(), (hipStream_t)stream);
+}
+
+int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_in, int n_out, int kv, int c_in,
+                            int c_out, const int* fwd_table, const int* bwd_table, const float* w, float* dx, long long ld_dx,
+                            float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
+  if (!dy || !ws) return CSN_E_ARG;
+  if (dx && !w) return CSN_E_ARG;
+  if (dx && !bwd_table && (!fwd_table || n_in != n_out)) return CSN_E_ARG;   // NULL: the stride-1 identity on fwd_table
+  if (dw && (!fwd_table || !x)) return CSN_E_ARG;
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_dy, c_out, n_out)) return e;
+  if (dw) if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
+  if (dx) if (const int e = sparse_conv_map(ld_dx, c_in, n_in)) return e;
+  if (mis16(dy) || mis16(ws) || (dx && (mis16(dx) || mis16(w))) || (dw && (mis16(dw) || mis16(x)))) return CSN_E_PTR;
+  if ((reinterpret_cast<uintptr_t>(fwd_table) & 3) || (reinterpret_cast<uintptr_t>(bwd_table) & 3)) return CSN_E_PTR;
+  if (ws_bytes < csn_sparse_conv_ws_bytes(n_in, n_out, kv, c_in, c_out, 1)) return CSN_E_WORKSPACE;
+  CsnSparseConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = fwd_table; a.bwd_table = bwd_table; a.n_out = n_out; a.kv = kv;
+  a.c_in = c_in; a.c_out = c_out; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias;
+  a.ws = ws;
+  return csn_launch_sparse_conv_bwd(a, mode(), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -280,3 +280,19 @@ struct CsnRowsFcArgs {
 long long csn_rows_fc_ws_bytes(long long n_rows, int c_in, int c_out, int training, int backward);
 int csn_launch_rows_fc_fwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);
 int csn_launch_rows_fc_bwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);
+
+// ---- sparse 3D convolution on voxel rows over a kernel map (sparse_conv.hip) ----
+struct CsnSparseConvArgs {
+  const float* x;  int ld_x;  int n_in;                           // [n_in][ld_x], c_in <= ld_x
+  const int* fwd_table;  const int* bwd_table;                    // [kv][n_out] input row or -1; [kv][n_in] output row or -1 (NULL: fwd reversed)
+  int n_out, kv, c_in, c_out;
+  const float* w;  const float* bias;                             // [kv][c_in][c_out]; bias optional
+  float* y;  int ld_y;                                            // forward: [n_out][ld_y]
+  const float* dy;  int ld_dy;
+  float* dx;  int ld_dx;  float* dw;  float* dbias;               // each skipped when NULL
+  void* ws;
+};
+long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward);
+int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
+int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
+extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule

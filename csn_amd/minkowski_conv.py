@@ -1,0 +1,332 @@
+"""Sparse 3D convolution on voxel rows: the one primitive of MinkowskiNet's HRNet backbone, on the MI355X kernels.
+
+Reference (marios2019/CSN):
+  * the stem, the stride-2 / transposed convolutions between branches, the blocks   MinkowskiNet/models/hrnet.py:39-53, 89-111, 233-239
+  * ``BasicBlock``                                                                 MinkowskiNet/models/modules/resnet_block.py:22-57
+
+Features are point-major fp32 rows ``x (n, c)``; coordinates are integer rows ``coords (n, 4) = [b, x, y, z]``, unique, every
+x, y, z a multiple of the tensor stride ``ts``.  For an odd kernel size k (r = k // 2, KV = k^3) the offsets o = (ox, oy, oz) in
+[-r, r]^3 are numbered ``kidx = (ox + r) + k (oy + r) + k^2 (oz + r)`` (x fastest); the weight is ``(KV, c_in, c_out)``.
+
+  * stride 1:             out coords = in coords,                        y[c]  = sum_o x[c  + ts o] W[kidx(o)]
+  * stride 2, k = 3:      out coords = unique([b, floor(xyz / 2ts) 2ts]) sorted by (b, x, y, z), out stride 2ts,
+                                                                         y[c'] = sum_o x[c' + ts o] W[kidx(o)]
+  * transposed, k = 3:    from a coarse set at 2ts onto a GIVEN fine set at ts,
+                                                                         y[c]  = sum_o x[c  - ts o] W[kidx(o)]
+Offsets never cross batch indices.  The offset numbering and the sorted output order are this project's choice (MinkowskiEngine
+cannot be imported on this platform): parity unpinned against MinkowskiEngine's own checkpoints.
+
+``build_kernel_map`` turns the coordinates into the two int32 tables the kernels read (plumbing: a sort and ``searchsorted`` in
+torch, device or CPU tensors alike).  One map serves every layer at its level: build it once per batch and pass it in.
+``sparse_conv3d`` is one autograd node on ``csn_sparse_conv_fwd_f32`` / ``csn_sparse_conv_bwd_f32`` (include/csn_hip.h section
+14); ``SparseConv3d`` / ``SparseConvTranspose3d`` hold MinkowskiEngine's ``kernel`` parameter; ``SparseBasicBlock`` is the
+residual block with the reference's attribute names (its batch norms are ``nn.BatchNorm1d`` through ATen).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from . import functional as CF
+
+_B_BITS, _C_BITS = 15, 16
+_C_BIAS = 1 << (_C_BITS - 1)
+
+
+def _pack(coords: torch.Tensor) -> torch.Tensor:
+    """[b, x, y, z] -> one int64 key whose order is the lexicographic order of (b, x, y, z)."""
+    c = coords.long()
+    return (c[:, 0] << (3 * _C_BITS)) | ((c[:, 1] + _C_BIAS) << (2 * _C_BITS)) | ((c[:, 2] + _C_BIAS) << _C_BITS) | (c[:, 3] + _C_BIAS)
+
+
+def _unpack(keys: torch.Tensor) -> torch.Tensor:
+    m = (1 << _C_BITS) - 1
+    return torch.stack([keys >> (3 * _C_BITS), ((keys >> (2 * _C_BITS)) & m) - _C_BIAS, ((keys >> _C_BITS) & m) - _C_BIAS,
+                        (keys & m) - _C_BIAS], dim=1)
+
+
+def _check_coords(coords: torch.Tensor, ts: int, what: str) -> torch.Tensor:
+    if coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] < 1 or coords.dtype.is_floating_point:
+        raise ValueError(f"{what} must be a non-empty (n, 4) integer tensor [b, x, y, z]")
+    c = coords.long()
+    if int(c[:, 0].min()) < 0 or int(c[:, 0].max()) >= (1 << _B_BITS):
+        raise ValueError(f"{what}: batch indices must lie in [0, {1 << _B_BITS})")
+    if int(c[:, 1:].min()) < -_C_BIAS or int(c[:, 1:].max()) >= _C_BIAS:
+        raise ValueError(f"{what}: x, y, z must lie in [{-_C_BIAS}, {_C_BIAS})")
+    if bool((c[:, 1:] % ts != 0).any()):
+        raise ValueError(f"{what}: x, y, z must be multiples of the tensor stride {ts}")
+    return c
+
+
+class _Index:
+    """Sorted keys of a coordinate set: row lookup by coordinates."""
+
+    def __init__(self, coords: torch.Tensor, what: str):
+        self.keys, self.perm = torch.sort(_pack(coords))
+        if bool((self.keys[1:] == self.keys[:-1]).any()):
+            raise ValueError(f"{what} holds duplicate rows")
+
+    def rows(self, coords: torch.Tensor) -> torch.Tensor:
+        """int32 row of every coordinate, -1 where the set has none (or the coordinate leaves the packed range)."""
+        ok = ((coords[:, 1:] >= -_C_BIAS) & (coords[:, 1:] < _C_BIAS)).all(dim=1)
+        q = _pack(coords.clamp(min=-_C_BIAS, max=_C_BIAS - 1))
+        pos = torch.searchsorted(self.keys, q).clamp_(max=self.keys.numel() - 1)
+        hit = ok & (self.keys[pos] == q)
+        return torch.where(hit, self.perm[pos], torch.full_like(pos, -1)).int()
+
+
+def kernel_offsets(kernel_size: int, device=None) -> torch.Tensor:
+    """(KV, 3) offsets (ox, oy, oz) in kidx order: x fastest."""
+    r = kernel_size // 2
+    a = torch.arange(-r, r + 1, device=device)
+    oz, oy, ox = torch.meshgrid(a, a, a, indexing="ij")
+    return torch.stack([ox.reshape(-1), oy.reshape(-1), oz.reshape(-1)], dim=1)
+
+
+class KernelMap:
+    """The tables of one convolution geometry between two coordinate sets.
+
+    ``fwd (KV, n_out)`` int32: the input row that feeds output row j at offset k, or -1; ``bwd (KV, n_in)`` int32: the output row
+    that input row i feeds at offset k, or -1.  At stride 1 ``bwd[k] = fwd[KV - 1 - k]``: no second table is searched or kept —
+    ``bwd_table`` is None there, which the backward kernel takes as "walk ``fwd`` in reversed offset order"; ``bwd`` forms the
+    reversed copy for whoever wants to look at it (torch has no negative-stride view) and does not keep it.
+    ``transpose()`` is the map of the opposite direction over the same tables."""
+
+    def __init__(self, in_coords, out_coords, kernel_size, stride, in_tensor_stride, out_tensor_stride, transposed, fwd, bwd):
+        self.in_coords, self.out_coords = in_coords, out_coords
+        self.kernel_size, self.stride = kernel_size, stride
+        self.in_tensor_stride, self.out_tensor_stride = in_tensor_stride, out_tensor_stride
+        self.transposed = transposed
+        self.fwd = fwd
+        self.bwd_table = bwd                                           # None: the stride-1 identity on ``fwd``
+
+    @property
+    def bwd(self) -> torch.Tensor:
+        return self.fwd.flip(0) if self.bwd_table is None else self.bwd_table
+
+    @property
+    def KV(self) -> int:
+        return self.kernel_size ** 3
+
+    @property
+    def n_in(self) -> int:
+        return self.in_coords.shape[0]
+
+    @property
+    def n_out(self) -> int:
+        return self.out_coords.shape[0]
+
+    def transpose(self) -> "KernelMap":
+        """The map from ``out_coords`` back onto ``in_coords``: a stride-2 map becomes the transposed convolution's map (and the
+        other way round), sharing the tables.  A stride-1 map is its own transpose with the offsets reversed."""
+        if self.stride == 1:
+            return KernelMap(self.out_coords, self.in_coords, self.kernel_size, 1, self.out_tensor_stride, self.in_tensor_stride,
+                             False, self.bwd, None if self.bwd_table is None else self.fwd)
+        return KernelMap(self.out_coords, self.in_coords, self.kernel_size, self.stride, self.out_tensor_stride,
+                         self.in_tensor_stride, not self.transposed, self.bwd, self.fwd)
+
+    def to(self, device) -> "KernelMap":
+        mv = lambda t: None if t is None else t.to(device)
+        return KernelMap(mv(self.in_coords), mv(self.out_coords), self.kernel_size, self.stride, self.in_tensor_stride,
+                         self.out_tensor_stride, self.transposed, mv(self.fwd), mv(self.bwd_table))
+
+
+def build_kernel_map(coords: torch.Tensor, kernel_size: int = 3, stride: int = 1, tensor_stride: int = 1,
+                     out_coords: Optional[torch.Tensor] = None, transposed: bool = False) -> KernelMap:
+    """The kernel map of one convolution geometry (module docstring).  ``coords`` are the input rows' coordinates at
+    ``tensor_stride``.  ``stride == 2`` generates the coarser coordinates unless ``out_coords`` gives them; ``transposed`` goes from
+    ``coords`` (coarse, at ``tensor_stride``) onto the given ``out_coords`` at ``tensor_stride // 2``."""
+    if kernel_size < 1 or kernel_size % 2 == 0:
+        raise ValueError(f"kernel_size {kernel_size} is not supported: odd sizes only")
+    if kernel_size not in (1, 3, 5):
+        raise ValueError(f"kernel_size {kernel_size} is not supported: the kernels take 1, 3 and 5")
+    if stride not in (1, 2):
+        raise ValueError(f"stride {stride} is not supported: 1 or 2")
+    if stride == 2 and kernel_size != 3:
+        raise ValueError("stride 2 takes kernel_size 3 only")
+    if transposed and stride != 2:
+        raise ValueError("the transposed convolution is the kernel-3 stride-2 one")
+    if transposed and out_coords is None:
+        raise ValueError("the transposed convolution goes onto a given coordinate set: pass out_coords (coordinates are not generated)")
+    if tensor_stride < 1 or (transposed and tensor_stride % 2):
+        raise ValueError(f"tensor_stride {tensor_stride} is not valid here")
+    c_in = _check_coords(coords, tensor_stride, "coords")
+    idx_in = _Index(c_in, "coords")
+    if transposed:
+        ts, out_ts = tensor_stride // 2, tensor_stride // 2        # ts: the step of the offsets (the finer of the two strides)
+    else:
+        ts, out_ts = tensor_stride, tensor_stride * stride
+    if out_coords is not None:
+        if out_coords.device != coords.device:
+            raise ValueError("coords and out_coords must be on one device")
+        c_out = _check_coords(out_coords, out_ts, "out_coords")
+        idx_out = _Index(c_out, "out_coords")
+    elif stride == 1:
+        c_out, idx_out = c_in, idx_in
+    else:
+        down = c_in.clone()
+        down[:, 1:] = torch.div(c_in[:, 1:], out_ts, rounding_mode="floor") * out_ts      # floor, not truncation, for negatives
+        c_out = _unpack(torch.unique(_pack(down), sorted=True))
+        idx_out = _Index(c_out, "out_coords")
+    off = kernel_offsets(kernel_size, coords.device) * ts
+    sign = -1 if transposed else 1
+
+    def table(index, at, s):
+        rows = []
+        for o in off:
+            q = at.clone()
+            q[:, 1:] += s * o
+            rows.append(index.rows(q))
+        return torch.stack(rows).contiguous()
+
+    fwd = table(idx_in, c_out, sign)
+    bwd = None if (stride == 1 and out_coords is None) else table(idx_out, c_in, -sign)
+    return KernelMap(c_in, c_out, kernel_size, stride, tensor_stride, out_ts, transposed, fwd, bwd)
+
+
+# ------------------------------------------------------------------------------------------------------
+# the autograd node
+# ------------------------------------------------------------------------------------------------------
+class _SparseConv(torch.autograd.Function):
+    """y = gather-GEMM(x, kmap.fwd, w) + b through ``csn_sparse_conv_fwd_f32`` / ``csn_sparse_conv_bwd_f32``."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, kmap):
+        CF._need_cuda(x, w, b, kmap.fwd)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        x = x.contiguous()
+        w_c = w.detach().contiguous()
+        b_c = None if b is None else b.detach().reshape(-1).contiguous()
+        KV, c_in, c_out = w_c.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
+        _lib.check(L.csn_sparse_conv_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
+                                             CF._ptr(b_c), CF._ptr(y), c_out, CF._stream()), "csn_sparse_conv_fwd_f32")
+        ctx.save_for_backward(x, w_c)
+        ctx.kmap = kmap
+        ctx.b_shape = None if b is None else b.shape
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        with CF.math_mode(CF.backward_mode(ctx.mode)):
+            x, w = ctx.saved_tensors
+            kmap = ctx.kmap
+            L = _lib.lib()
+            KV, c_in, c_out = w.shape
+            n_in, n_out = kmap.n_in, kmap.n_out
+            dy = dy.contiguous()
+            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            need_b = ctx.b_shape is not None and ctx.needs_input_grad[2]
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            db = torch.empty((c_out,), device=x.device, dtype=torch.float32) if need_b else None
+            if not (need_x or need_w or need_b):
+                return None, None, None, None
+            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+            bwd = kmap.bwd_table if need_x else None                        # None at stride 1: the kernel reverses ``fwd``
+            _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
+                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw),
+                                                 CF._ptr(db), CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+            return dx, dw, None if db is None else db.reshape(ctx.b_shape), None
+
+
+def sparse_conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], kmap: KernelMap) -> torch.Tensor:
+    """``y (n_out, c_out)`` of the convolution ``kmap`` describes: ``x (n_in, c_in)``, ``weight (KV, c_in, c_out)``, ``bias``
+    ``(c_out,)`` / ``(1, c_out)`` or None.  An input width that is not a multiple of 32 (the stem's 3 colour channels) is
+    zero-padded to one, rows and weight alike; autograd slices the gradients back."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise _lib.CsnError("csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1]:
+        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out)")
+    if weight.shape[0] != kmap.KV:
+        raise ValueError(f"the weight holds {weight.shape[0]} offsets, the map {kmap.KV}")
+    if x.shape[0] != kmap.n_in:
+        raise ValueError(f"x has {x.shape[0]} rows, the map's input set {kmap.n_in}")
+    c_in, c_out = weight.shape[1], weight.shape[2]
+    if c_out % 32 or not 32 <= c_out <= 256:
+        raise ValueError(f"c_out {c_out} is not supported: a multiple of 32 in [32, 256]")
+    if bias is not None and bias.numel() != c_out:
+        raise ValueError(f"bias must hold {c_out} values")
+    pad = -c_in % 32
+    if c_in + pad > 256:
+        raise ValueError(f"c_in {c_in} is not supported: at most 256")
+    if pad:
+        x = F.pad(x, (0, pad))
+        weight = F.pad(weight, (0, 0, 0, pad))
+    return _SparseConv.apply(x.float(), weight, bias, kmap)
+
+
+# ------------------------------------------------------------------------------------------------------
+# modules
+# ------------------------------------------------------------------------------------------------------
+class SparseConv3d(nn.Module):
+    """``ME.MinkowskiConvolution(c_in, c_out, kernel_size, stride, dimension=3)`` on rows and a kernel map: parameter ``kernel``
+    ``(KV, c_in, c_out)`` and, when asked, ``bias (1, c_out)`` — MinkowskiEngine's names and shapes."""
+
+    transposed = False
+
+    def __init__(self, c_in: int, c_out: int, kernel_size: int = 3, stride: int = 1, bias: bool = False):
+        super().__init__()
+        if kernel_size not in (1, 3, 5):
+            raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 or 5")
+        if stride not in (1, 2) or (stride == 2 and kernel_size != 3):
+            raise ValueError("stride 1, or stride 2 with kernel_size 3")
+        if c_out % 32 or not 32 <= c_out <= 256 or not 1 <= c_in <= 256:
+            raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in in [1, 256]")
+        self.c_in, self.c_out, self.kernel_size, self.stride = c_in, c_out, kernel_size, stride
+        KV = kernel_size ** 3
+        self.kernel = nn.Parameter(torch.empty(KV, c_in, c_out))
+        self.bias = nn.Parameter(torch.zeros(1, c_out)) if bias else None
+        nn.init.normal_(self.kernel, std=(KV * c_in) ** -0.5)             # unit-variance outputs for unit-variance rows
+
+    def forward(self, x: torch.Tensor, kmap: KernelMap) -> torch.Tensor:
+        if kmap.kernel_size != self.kernel_size or kmap.stride != self.stride or kmap.transposed != self.transposed:
+            raise ValueError(f"the map (kernel {kmap.kernel_size}, stride {kmap.stride}, transposed {kmap.transposed}) does not fit "
+                             f"this layer (kernel {self.kernel_size}, stride {self.stride}, transposed {self.transposed})")
+        return sparse_conv3d(x, self.kernel, self.bias, kmap)
+
+    def extra_repr(self) -> str:
+        return f"{self.c_in}, {self.c_out}, kernel_size={self.kernel_size}, stride={self.stride}, bias={self.bias is not None}"
+
+
+class SparseConvTranspose3d(SparseConv3d):
+    """``ME.MinkowskiConvolutionTranspose(c_in, c_out, kernel_size=3, stride=2, dimension=3)`` onto a given finer coordinate set:
+    takes the ``transpose()`` of that level's stride-2 map (or a map built with ``transposed=True``)."""
+
+    transposed = True
+
+    def __init__(self, c_in: int, c_out: int, bias: bool = False):
+        super().__init__(c_in, c_out, kernel_size=3, stride=2, bias=bias)
+
+
+class SparseBasicBlock(nn.Module):
+    """``BasicBlock`` of resnet_block.py:22-57: conv1 - norm1 - relu - conv2 - norm2, plus the residual (through ``downsample`` if
+    given: a module of the rows), relu.  Both convolutions are kernel 3, stride 1 on the same map."""
+
+    expansion = 1
+
+    def __init__(self, inplanes: int, planes: int, bn_momentum: float = 0.02, downsample: Optional[nn.Module] = None):
+        super().__init__()
+        self.conv1 = SparseConv3d(inplanes, planes, kernel_size=3, stride=1)
+        self.norm1 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.conv2 = SparseConv3d(planes, planes, kernel_size=3, stride=1)
+        self.norm2 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.relu = nn.ReLU(inplace=False)
+        self.downsample = downsample
+
+    def forward(self, x: torch.Tensor, kmap: KernelMap) -> torch.Tensor:
+        residual = x
+        out = self.relu(self.norm1(self.conv1(x, kmap)))
+        out = self.norm2(self.conv2(out, kmap))
+        if self.downsample is not None:
+            residual = self.downsample(x)
+        return self.relu(out + residual)

@@ -605,6 +605,40 @@ CSN_API int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y
                         long long ld_dx, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws, long long ws_bytes,
                         void* stream);
 
+/* ---- (14) sparse 3D convolution on voxel rows (MinkowskiNet/models/hrnet.py:39-53 the stem, :89-111 the stride-2 and transposed
+ *           convolutions between branches, :233-239 the blocks; models/modules/resnet_block.py:22-57) ----------------------------
+ * Every convolution of the HRNet backbone is MinkowskiConvolution / MinkowskiConvolutionTranspose on voxel coordinates: kernel 3 or
+ * 5 at stride 1, kernel 3 at stride 2, and the transposed kernel 3 at stride 2.  All of them are ONE gather-GEMM over a KERNEL MAP
+ * the caller builds (csn_amd.minkowski_conv.build_kernel_map):
+ *   table[kv][n_out] int32 — table[k][j] is the input row that feeds output row j at kernel offset k, or -1 (no voxel there).
+ *   y[j] = sum_k x[table[k][j]] W[k] + bias
+ * Everything is POINT-MAJOR fp32: x[n_in][ld_x] (c_in <= ld_x), w[kv][c_in][c_out] (contiguous; MinkowskiEngine's `kernel`),
+ * bias[c_out] (may be NULL), y[n_out][ld_y], dy[n_out][ld_dy], dx[n_in][ld_dx], dw[kv][c_in][c_out] (contiguous), dbias[c_out].
+ * Columns of a row beyond its width are neither read as data nor written.  Any negative table entry reads as "no voxel".  An
+ * entry >= n_in is the caller's error: the buffer range check keeps it from being dereferenced outside x, its contribution is undefined.
+ * Geometry: n_in, n_out >= 1 (no % 4 requirement; CSN_E_ARG); kv in {1, 27, 125}, c_in % 32 == 0 and c_out % 32 == 0, both in
+ * [32, 256] (CSN_E_DIM); every pitch % 4 == 0 (CSN_E_ALIGN), >= its width (CSN_E_ARG), <= 2^20 and rows * pitch * 4 < 2 GiB, the
+ * buffer window of the gathers (CSN_E_DIM); x, w, y, dy, dx, dw, ws 16-byte aligned, the tables 4-byte (CSN_E_PTR).  All of this is
+ * checked on the host before any launch.  ws (backward only): csn_sparse_conv_workspace_bytes(..., backward = 1) bytes
+ * (CSN_E_WORKSPACE); the forward takes none (backward = 0 returns 0).
+ * csn_sparse_conv_fwd_f32: one launch.  Reads x, table, w, bias; writes y (every row by exactly one wave); nothing else.  An offset
+ *   at which no row of a work-group's 128-row tile has a neighbour is skipped whole by that work-group.
+ * csn_sparse_conv_bwd_f32: with fwd_table[kv][n_out] as above and bwd_table[kv][n_in] — bwd_table[k][i] is the output row that
+ *   input row i feeds at offset k, or -1; bwd_table NULL with n_in == n_out means the stride-1 identity bwd[k] = fwd[kv - 1 - k]:
+ *   the kernel walks fwd_table in reversed offset order and no second table exists (n_in != n_out: CSN_E_ARG) —
+ *   dx = sum_k dy[bwd_table[k][i]] W[k]^T    the forward kernel on (dy, bwd_table, W^T); reads dy, bwd_table, w
+ *   dw[k] = sum_j x[fwd_table[k][j]]^T dy[j]  split-K over chunks of output rows, slabs added in chunk order; reads x, fwd_table, dy
+ *   dbias = sum_j dy[j]                       fp64 partials of 64-row chunks added in chunk order; reads dy
+ *   — each skipped when its pointer is NULL (its own inputs may then be NULL too), the others are unchanged by that.
+ * No floating-point atomics: two identical calls give the same bits.  Math mode 0 runs the products on the exact fp32 matrix
+ * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (13). */
+CSN_API long long csn_sparse_conv_workspace_bytes(int n_in, int n_out, int kv, int c_in, int c_out, int backward);
+CSN_API int csn_sparse_conv_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
+                            const float* w, const float* bias, float* y, long long ld_y, void* stream);
+CSN_API int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_in, int n_out, int kv, int c_in,
+                            int c_out, const int* fwd_table, const int* bwd_table, const float* w, float* dx, long long ld_dx,
+                            float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
@@ -625,6 +659,8 @@ CSN_API int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y
 #define CSN_DEV_LNB_GROUP 5 /* default 0; G > 0: csn_outproj_ln_bwd_f32 runs its LayerNorm backward and its dCtx product over groups
                                of G evaluations (bf16x3, streaming dCtx; the same results) */
 /* (key 6 was the output-stationary dV / dK stream of round 5: the GEMM route is as fast over the step; profiles/r5_dkv_stream.txt) */
+#define CSN_DEV_SCONV_NB 7  /* default 0: csn_sparse_conv_* choose the 32-column blocks a wave owns by their launch rule; 1..4 pins
+                               them (capped at c / 32) so that every kernel instance can be reached at any size — the same sums */
 CSN_API int csn_dev_set(int key, int value);
 CSN_API int csn_dev_get(int key);
 
