@@ -191,6 +191,10 @@ _SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_float, c_ulonglong, c_int, c_longlong, c_void_p, c_int,
                                        c_void_p, c_int, c_void_p]),
+    "csn_outproj_lnb_workspace_floats": (c_longlong, [c_int, c_int, c_int, c_int, c_int]),
+    "csn_outproj_lnb_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_int, c_int, c_int, c_float, c_ulonglong, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_longlong, c_void_p]),
     "csn_project_wgrad_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_longlong, c_int, c_void_p, c_int, c_int,
                                       c_int, c_int, c_float, c_int, c_void_p, c_longlong, c_void_p]),
     "csn_retrieval_measure_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,

@@ -177,16 +177,17 @@ class MultiHeadAttention(nn.Module):
                 mix_q, mix_kv = (b * K1).reshape(-1), (b * K1 + k).reshape(-1)
                 nbr = (b * K1 + k)[:, 1:].reshape(-1)
                 own = ar * K1
-                cache[key] = CF.EvalPlan(np.concatenate((mix_q, nbr, own)), np.concatenate((mix_kv, nbr, own)), B * K1, dev)
+                cache[key] = CF.EvalPlan(np.concatenate((mix_q, nbr, own)), np.concatenate((mix_kv, nbr, own)), B * K1, dev,
+                                         mixed_not_pooled=True)
             elif kind == "self2":         # train mode, own shapes only: [b] mixed self, [B + b] pooled self (separate masks)
-                cache[key] = CF.EvalPlan(np.concatenate((ar, ar)), np.concatenate((ar, ar)), B, dev)
+                cache[key] = CF.EvalPlan(np.concatenate((ar, ar)), np.concatenate((ar, ar)), B, dev, mixed_not_pooled=True)
             elif kind == "csa_cross":
                 # the part of "csa" that needs neighbour data: [b*K + k-1] MHA(x_b, x_bk, x_bk) (mixed), then
                 # [B*K + b*K + k-1] MHA(x_bk, x_bk, x_bk) (only its mean is used); slots as in "csa"
                 b, k = np.meshgrid(ar, np.arange(K1), indexing="ij")
                 nbr = (b * K1 + k)[:, 1:].reshape(-1)
                 own = (b * K1)[:, 1:].reshape(-1)
-                cache[key] = CF.EvalPlan(np.concatenate((own, nbr)), np.concatenate((nbr, nbr)), B * K1, dev)
+                cache[key] = CF.EvalPlan(np.concatenate((own, nbr)), np.concatenate((nbr, nbr)), B * K1, dev, mixed_not_pooled=True)
             elif kind == "cross_only":
                 # descriptor reuse (multi-GPU): only [b*K + k-1] MHA(x_b, x_bk, x_bk) — the neighbours' own self-attention is
                 # their owners' work (csn_amd.sharding.PendingStack.gather_pooled); slots as in "csa"
@@ -195,7 +196,7 @@ class MultiHeadAttention(nn.Module):
                 own = (b * K1)[:, 1:].reshape(-1)
                 # Q is read of the own slots b*K1 only, K / V of the neighbour slots b*K1 + k only
                 cache[key] = CF.EvalPlan(own, nbr, B * K1, dev, q_ranges=[(0, K1, B)],
-                                         kv_ranges=[(k_, K1, B) for k_ in range(1, K1)])
+                                         kv_ranges=[(k_, K1, B) for k_ in range(1, K1)], mixed_not_pooled=True)
             else:
                 raise ValueError(kind)
         return cache[key]

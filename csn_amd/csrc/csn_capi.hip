@@ -886,6 +886,50 @@ int csn_outproj_ln_bwd_f32(const float* dxhat, const float* xhat, const float* r
                accumulate, ws, ws_floats, st, a16 ? CSN_FMT_16 : 0, a16 == 2 ? CSN_FMT_F16_TO_BF16 : (a16 ? CSN_FMT_16 : 0));
 }
 
+// the evaluations e_base .. e_base + n_evals - 1 on the fused kernel (wx_lnb.hip), or none at all
+static bool lnb_range_takes(int n_evals, int d_model, int d_inner, int ld, int n_points, long long eval_stride) {
+  if (n_evals <= 0 || n_points <= 0 || n_points > ld || mode() != 1 || act16()) return false;
+  CsnLnBwdArgs l{};
+  l.C = d_model; l.ld = ld; l.n_points = n_points; l.eval_stride = eval_stride; l.act16 = 0;
+  return csn_wx_takes(d_inner, d_model) && csn_wx_geometry_takes(n_evals, n_points, d_inner / 256) && csn_wx_lnb_takes(l, d_inner);
+}
+
+long long csn_outproj_lnb_workspace_floats(int n_evals, int d_model, int d_inner, int ld, int n_points) {
+  if (!lnb_range_takes(n_evals, d_model, d_inner, ld, n_points, (long long)d_model * ld)) return 0;
+  return csn_wx_lnb_red_floats(n_evals, n_points);
+}
+
+int csn_outproj_lnb_f32(const float* dxhat, const float* xhat, const float* rstd, long long eval_stride, const float* wfc_t,
+                        float* dz, float* dz_res, float* dctx, int e_base, int n_evals, int d_model, int d_inner, int ld,
+                        int n_points, float dropout_p, unsigned long long seed, const float* dxhat_rows, int n_dense_evals,
+                        const float* dxhat_scale, int dxhat_group, float* rowdot, float* rowsum, float* red_ws,
+                        long long red_ws_floats, void* stream) {
+  if (dropout_p < 0.f || dropout_p >= 1.f) return CSN_E_ARG;
+  if (dxhat_group < 0 || e_base < 0 || n_evals <= 0 || n_dense_evals < 0 || (n_dense_evals > 0 && !dxhat)) return CSN_E_ARG;
+  if (!xhat || !rstd || !wfc_t || !dz || !dctx) return CSN_E_ARG;
+  if (n_points <= 0 || d_inner <= 0 || d_model <= 0 || n_points > ld) return CSN_E_ARG;
+  if (dropout_p > 0.f && (long long)(d_model / 2 + 1) * ld >= (1ll << 32)) return CSN_E_ARG;   // 32-bit mask pair index
+  if ((ld & 3) || (d_inner & 3) || (d_model & 3) || (n_points & 3)) return CSN_E_ALIGN;
+  if (mis16(dxhat) || mis16(xhat) || mis16(wfc_t) || mis16(dz) || mis16(dz_res) || mis16(dctx) || mis16(red_ws)) return CSN_E_PTR;
+  if (eval_stride & 3) return CSN_E_STRIDE;
+  if (!lnb_range_takes(e_base + n_evals, d_model, d_inner, ld, n_points, eval_stride)) return CSN_E_DIM;
+  const int group = dxhat_group > 0 ? dxhat_group : 1;
+  const bool reduce = rowdot || rowsum || red_ws;
+  if (reduce) {
+    // the reductions: over a launch of whole groups of dense evaluations from evaluation 0 on
+    if (!rowdot || !rowsum || !red_ws || e_base != 0 || n_evals > n_dense_evals || n_evals % group) return CSN_E_ARG;
+    if (red_ws_floats < csn_wx_lnb_red_floats(n_evals, n_points)) return CSN_E_WORKSPACE;
+  }
+  CsnWxLnbArgs f{};
+  f.w = wfc_t; f.xhat = xhat; f.rstd = rstd; f.eval_stride = eval_stride; f.ld = ld;
+  f.dxhat = dxhat; f.dxhat_group = group; f.n_dense = n_dense_evals; f.dxhat_scale = dxhat_scale; f.dxhat_rows = dxhat_rows;
+  f.dz = dz; f.dz_res = dz_res; f.dctx = dctx; f.dctx_eval_stride = eval_stride;
+  f.n_items = n_evals; f.n_points = n_points; f.e_base = e_base; f.dropout_p = dropout_p; f.seed = seed;
+  if (reduce) { f.red_ws = red_ws; f.red_slots = csn_wx_ln_sum_slots(n_evals, n_points); f.rowdot = rowdot; f.rowsum = rowsum; }
+  const int rc = csn_launch_wx_lnb(f, (hipStream_t)stream);
+  return rc == CSN_NOT_TAKEN ? CSN_E_DIM : rc;
+}
+
 int csn_project_wgrad_f32(const float* dout, long long dout_shape_stride, int ld_dout, const float* x,
                           long long x_shape_stride, int ld_x, float* dw, int rows, int channels, int n_shapes,
                           int n_points, float scale, int accumulate, float* ws, long long ws_floats,

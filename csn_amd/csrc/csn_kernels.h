@@ -205,7 +205,12 @@ struct CsnWxLnbArgs {
   float* dctx; long long dctx_eval_stride;                     // [e][256][ld]
   int n_items, n_points, e_base;                               // evaluations e_base .. e_base + n_items - 1
   float dropout_p; unsigned long long seed;
+  // optional, e_base = 0 and every evaluation of the launch dense: the mix backward's reductions from the same pass —
+  // rowdot[e][256] = sum_n dxhat[e / group][c][n] xhat[e][c][n], rowsum[e / group][256] = sum_n dxhat[e / group][c][n] (raw
+  // dxhat, before scale and rows); red_ws: csn_wx_lnb_red_floats(n_items, n_points) floats, red_slots = csn_wx_ln_sum_slots(..)
+  float* red_ws; int red_slots; float* rowdot; float* rowsum;
 };
+long long csn_wx_lnb_red_floats(int n_items, int n_points);
 bool csn_wx_lnb_takes(const CsnLnBwdArgs& a, int d_inner);
 int csn_launch_wx_lnb(const CsnWxLnbArgs& a, hipStream_t st);
 

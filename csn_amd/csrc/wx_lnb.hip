@@ -15,6 +15,12 @@
 // Wait counts (hand-counted, see wx_stream.hip): the commit of chunk c + 2 waits for the dfeats request issued inside the commit
 // of the previous iteration; behind it: that commit's 4 (8 with dz_res) stores, this iteration's chunk request (4 + 1 loads)
 // and the 4 stores of its epilogue.
+// Optional (red_ws): the mix backward's two reductions over the points, on the raw dfeats values that the commit holds anyway:
+//   rowdot[e][c] = sum_n dfeats[e / group][c][n] xhat[e][c][n],   rowsum[e / group][c] = sum_n dfeats[e / group][c][n]
+// 4 points in the thread, the 8 lanes of a row by DPP, then one LDS cell per (channel, sum) that only the row's first lane
+// touches (no register lives across chunks); a stream writes its partials out when its run leaves the evaluation and at its end
+// (red_ws[e][slot][dot | sum][256], slots as the pooled sums of wx_stream.hip), csn_wx_lnb_sums_kernel adds them in fp64 in a
+// fixed order.  The flush's stores come between counted requests and stores: the hand-counted waits only get stricter.
 #include "csn_common.h"
 #include "csn_kernels.h"
 #include "wx_common.h"
@@ -33,6 +39,11 @@ CSN_DEVINL void lnb_arrived(f32x4* R) {
 // v summed over the 8 lanes l ^ {8, 16, 32} (the wave's 8 row groups of one point column), in every one of them — on the vector
 // pipe: a rotation by 8 inside the 16-lane rows, then the row-pair and half-wave swaps of gfx950 (three ds_bpermute per value
 // — 24 per chunk and thread — were LDS traffic and 3 x ~100 cycles of latency in a row)
+// one dword out through a descriptor (flushes of the mix reductions); the wait state as wx_store4
+CSN_DEVINL void lnb_store1(float v, u32x4 rsrc, unsigned voff) {
+  asm volatile("buffer_store_dword %0, %1, %2, 0 offen\n\ts_nop 1" :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
+}
+
 CSN_DEVINL float lnb_sum_row_groups(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128 /* row_ror:8 */, 0xf, 0xf, false));
   // (asm, not __builtin_amdgcn_permlane16_swap / 32_swap: hipcc 7.2 maps BOTH elements of the builtin's result to the first
@@ -45,10 +56,20 @@ CSN_DEVINL float lnb_sum_row_groups(float v) {
   return v + c;
 }
 
-template <bool DROP, bool RES>
+// v summed over the 8 lanes l ^ {1, 2, 4} (the 8 threads of one staging row), in every one of them: two quad permutes and the
+// mirror of the 8-lane half rows
+CSN_DEVINL float lnb_sum_row_lanes(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xb1 /* quad_perm:[1,0,3,2] */, 0xf, 0xf, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4e /* quad_perm:[2,3,0,1] */, 0xf, 0xf, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141 /* row_half_mirror */, 0xf, 0xf, false));
+  return v;
+}
+
+template <bool DROP, bool RES, bool RED>
 __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
-  // [dfeats chunk 32 KB | 3 stages 96 KB | 8 epilogue blocks 16 KB | row sums 2 KB | (scale, row constant) of the item's channels 2 KB]
-  __shared__ __attribute__((aligned(16))) short smem[LNB_G + WX_NS * WX_STAGE + 8 * LNB_EBW * 2 + 1024 + 1024];
+  // [dfeats chunk 32 KB | 3 stages 96 KB | 8 epilogue blocks 16 KB | row sums 2 KB | (scale, row constant) of the item's channels 2 KB
+  //  | (rowdot, rowsum) cells of the evaluation the run is in 2 KB]
+  __shared__ __attribute__((aligned(16))) short smem[LNB_G + WX_NS * WX_STAGE + 8 * LNB_EBW * 2 + 1024 + 1024 + 1024];
   short* xs = smem + LNB_G;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
@@ -56,6 +77,7 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
   float* red = reinterpret_cast<float*>(smem + LNB_G + WX_NS * WX_STAGE + 8 * LNB_EBW * 2);      // [wave][sum | sum x][32 points]
   const float* gbuf = reinterpret_cast<const float*>(smem) + 4 * tid;                              // this thread's piece i at + 2048 i
   float* ctab = red + 512;                                                                         // [channel][scale, row constant]
+  float* cells = ctab + 512;                                                                       // [channel][rowdot, rowsum]
 
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int n_streams = (int)gridDim.x;
@@ -112,7 +134,7 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
     int col0, valid; unsigned item;
     locate(cu, col0, valid, item);
     const unsigned e = (unsigned)p.e_base + item;
-    const bool dense = (int)e < p.n_dense;
+    const bool dense = RED || (int)e < p.n_dense;           // (RED: the launcher has checked that every evaluation is dense)
     const unsigned src = p.dxhat_group > 1 ? e / (unsigned)p.dxhat_group : e;
     const u32x4 Gr = wx_rsrc(dense ? p.dxhat + (long long)src * p.eval_stride + col0 : nullptr, dense ? ((long long)(WX_K - 1) * ld + valid) * 4 : 0);
     const unsigned off = 4 * c4 < valid ? x_voff : CSN_OOB;
@@ -177,11 +199,44 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
   const unsigned thr16 = csn_drop_threshold16(p.dropout_p);
   const float keep_scale = DROP ? 1.f / (1.f - p.dropout_p) : 1.f;
   unsigned cst_item = 0xffffffffu;                           // the item whose channel constants sit in ctab
+  // the mix reductions: cells of row 2 krow + (i & 1) + 128 (i >> 1) belong to the row's first lane (c4 == 0) alone
+  unsigned red_item = 0xffffffffu;                           // the item whose partial sums sit in the cells
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef f32x2 __attribute__((address_space(3))) * lds_f32x2;
+  const unsigned smem_lds = (unsigned)(unsigned long)((short __attribute__((address_space(3)))*)smem);
+  const unsigned cells_lds = (unsigned)(unsigned long)((float __attribute__((address_space(3)))*)cells);
+  // 16 tid from the address of the thread's dfeats piece, opaque to the compiler: what the reductions derive from it is computed
+  // where it is used — kept across the whole loop it would be registers this kernel does not have
+  auto tid16 = [&]() {
+    unsigned ga = (unsigned)(unsigned long)((const float __attribute__((address_space(3)))*)gbuf);
+    asm volatile("" : "+v"(ga));
+    return ga - smem_lds;
+  };
+  auto flush_red = [&]() __attribute__((always_inline)) {
+    const unsigned slot = (unsigned)stream - (red_item * cpi) / (unsigned)run;
+    const u32x4 Wr = wx_rsrc(p.red_ws + ((long long)red_item * p.red_slots + slot) * (2 * WX_K), 2 * WX_K * 4);
+    const unsigned t16 = tid16();
+    if ((t16 & 0x70u) == 0) {                                // c4 == 0; row 2 krow at cell 16 krow, at dst + 8 krow
+      const unsigned cell = cells_lds + ((t16 >> 7) << 4), voff = (t16 >> 7) << 3;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const lds_f32x2 c = (lds_f32x2)(unsigned long)(cell + 8 * (i & 1) + 1024 * (i >> 1));
+        const f32x2 v = *c;
+        *c = f32x2{0.f, 0.f};
+        lnb_store1(v.x, Wr, voff + 4 * (i & 1) + 512 * (i >> 1));
+        lnb_store1(v.y, Wr, voff + 4 * (i & 1) + 512 * (i >> 1) + 4 * WX_K);
+      }
+    }
+  };
+  if (RED && c4 == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<float2*>(&cells[2 * (2 * krow + (i & 1) + 128 * (i >> 1))]) = make_float2(0.f, 0.f);
+  }
   auto commit = [&](auto wait_c, int stage, f32x4* R, const Cursor& cu, const Cursor& cg) __attribute__((always_inline)) {
     int col0, valid; unsigned item;
     locate(cu, col0, valid, item);
     const unsigned e = (unsigned)p.e_base + item;
-    const bool dense = (int)e < p.n_dense;
+    const bool dense = RED || (int)e < p.n_dense;
     if (item != cst_item) {                                  // (work-group uniform; once per item and stream: every wave is past the
       cst_item = item;                                       //  barrier that ended the last commit, nobody reads the old table)
       if (tid < WX_K) {
@@ -191,7 +246,33 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
       }
       __syncthreads();
     }
+    const bool reduce = RED && cu.q < q_end;                 // (work-group uniform)
+    if (reduce && item != red_item) {
+      if (red_item != 0xffffffffu) flush_red();
+      red_item = item;
+    }
     lnb_arrived<decltype(wait_c)::value>(R);
+    if (reduce) {                                            // a pass of its own: nothing of it is live in the LayerNorm backward
+      const unsigned t16 = tid16();
+      const unsigned cell = cells_lds + ((t16 >> 7) << 4);   // the cells of row 2 krow
+      const bool first_lane = (t16 & 0x70u) == 0;            // c4 == 0
+      const bool in = (int)((t16 >> 2) & 0x1cu) < valid;     // 4 c4 < valid (points beyond the item: xhat is 0, the dfeats sum is switched off)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gbuf + 2048 * i);
+        float rd = fmaf(g[3], R[i][3], fmaf(g[2], R[i][2], fmaf(g[1], R[i][1], g[0] * R[i][0])));
+        float rs = in ? (g[0] + g[1]) + (g[2] + g[3]) : 0.f;
+        rd = lnb_sum_row_lanes(rd);
+        rs = lnb_sum_row_lanes(rs);
+        if (first_lane) {                                    // cells of row 2 krow + (i & 1) + 128 (i >> 1)
+          if (i == 0) asm volatile("ds_add_f32 %0, %1\n\tds_add_f32 %0, %2 offset:4" :: "v"(cell), "v"(rd), "v"(rs) : "memory");
+          if (i == 1) asm volatile("ds_add_f32 %0, %1 offset:8\n\tds_add_f32 %0, %2 offset:12" :: "v"(cell), "v"(rd), "v"(rs) : "memory");
+          if (i == 2) asm volatile("ds_add_f32 %0, %1 offset:1024\n\tds_add_f32 %0, %2 offset:1028" :: "v"(cell), "v"(rd), "v"(rs) : "memory");
+          if (i == 3) asm volatile("ds_add_f32 %0, %1 offset:1032\n\tds_add_f32 %0, %2 offset:1036" :: "v"(cell), "v"(rd), "v"(rs) : "memory");
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     float sc[4], rw[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -299,7 +380,24 @@ __global__ __launch_bounds__(512, 2) void csn_wx_lnb_kernel(CsnWxLnbArgs p) {
     if (ce.q >= q_end) break;
     iteration(std::integral_constant<int, 2>{}, R0, R1);
   }
+  if (RED && red_item != 0xffffffffu) flush_red();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// rowdot[e][c] and, from the first evaluation of every group, rowsum[e / group][c]: the sums of the slots of red_ws[e] that the
+// launch geometry wrote, in fp64 and in slot order (two runs give the same bits)
+__global__ __launch_bounds__(512) void csn_wx_lnb_sums_kernel(const float* __restrict__ ws, float* __restrict__ rowdot,
+                                                              float* __restrict__ rowsum, int cpi, int run, int slots, int group) {
+  const long long e = blockIdx.x;
+  const int c = threadIdx.x & (WX_K - 1);
+  const bool is_sum = threadIdx.x >= WX_K;
+  if (is_sum && e % group != 0) return;
+  const int first = (int)((e * cpi) / run), last = (int)(((e + 1) * cpi - 1) / run);
+  const float* src = ws + e * slots * (2 * WX_K) + threadIdx.x;
+  double s = 0.0;
+  for (int k = 0; k <= last - first; ++k) s += (double)src[(long long)k * (2 * WX_K)];
+  if (is_sum) rowsum[(e / group) * WX_K + c] = (float)s;
+  else rowdot[e * WX_K + c] = (float)s;
 }
 
 }  // namespace
@@ -308,13 +406,31 @@ bool csn_wx_lnb_takes(const CsnLnBwdArgs& a, int d_inner) {
   return (csn_dev_wx & 9) == 9 && a.C == WX_K && d_inner == WX_K && !a.act16 && !(a.ld & 3) && !(a.n_points & 3) && !(a.eval_stride & 3);
 }
 
+long long csn_wx_lnb_red_floats(int n_items, int n_points) {
+  return n_items > 0 && n_points > 0 ? (long long)n_items * csn_wx_ln_sum_slots(n_items, n_points) * (2 * WX_K) : 0;
+}
+
 int csn_launch_wx_lnb(const CsnWxLnbArgs& a, hipStream_t st) {
   if (a.n_items <= 0 || a.n_points <= 0) return 0;
   if ((long long)a.n_items * ((a.n_points + WX_CH - 1) / WX_CH + 16) * 2 >= (1ll << 31)) return CSN_NOT_TAKEN;
   const int grid = wx_grid();
+  if (a.red_ws) {
+    // the reductions cover the launch's own evaluations, all of them dense, in whole groups
+    if (!a.rowdot || !a.rowsum || a.e_base != 0 || a.n_items > a.n_dense || a.dxhat_group < 1 || a.n_items % a.dxhat_group) return -2;
+    if (a.red_slots != csn_wx_ln_sum_slots(a.n_items, a.n_points)) return -2;
+  }
   // (always the instance with the mask code: at p = 0 the threshold is 0 and the scale 1 — every element kept, times 1.0.  The
   //  instances without it compile to 90 spilled registers: the scheduler then hoists the whole commit's loads)
-  if (a.dz_res) hipLaunchKernelGGL((csn_wx_lnb_kernel<true, true>), dim3(grid), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((csn_wx_lnb_kernel<true, false>), dim3(grid), dim3(512), 0, st, a);
+  if (a.red_ws) {
+    if (a.dz_res) hipLaunchKernelGGL((csn_wx_lnb_kernel<true, true, true>), dim3(grid), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((csn_wx_lnb_kernel<true, false, true>), dim3(grid), dim3(512), 0, st, a);
+  } else if (a.dz_res) hipLaunchKernelGGL((csn_wx_lnb_kernel<true, true, false>), dim3(grid), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((csn_wx_lnb_kernel<true, false, false>), dim3(grid), dim3(512), 0, st, a);
+  if (a.red_ws) {
+    const int cpi = (a.n_points + WX_CH - 1) / WX_CH;
+    const int run = (int)(((long long)a.n_items * cpi + grid - 1) / grid);
+    hipLaunchKernelGGL(csn_wx_lnb_sums_kernel, dim3(a.n_items), dim3(512), 0, st, a.red_ws, a.rowdot, a.rowsum, cpi, run, a.red_slots,
+                       a.dxhat_group);
+  }
   return (int)hipGetLastError();
 }

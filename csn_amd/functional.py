@@ -111,8 +111,12 @@ class EvalPlan:
     a colour every output slot occurs once, so a colour is one launch that adds into the per-slot gradient
     maps without atomics and without per-evaluation temporaries."""
 
-    def __init__(self, q_slots, kv_slots, n_slots: int, device, v_shift: int = 0, q_ranges=None, kv_ranges=None):
-        """q_ranges / kv_ranges (optional): the slots whose Q / K,V projections the evaluations actually read, as arithmetic
+    def __init__(self, q_slots, kv_slots, n_slots: int, device, v_shift: int = 0, q_ranges=None, kv_ranges=None,
+                 mixed_not_pooled: bool = False):
+        """mixed_not_pooled: the plan's leading evaluations (the ones a linked mix consumes) are not also consumers of a
+        pooled mean — their only gradient is the mix's, so their LayerNorm backward may run before the pooled gradients exist
+        (tuning.fused_mix_bwd).  False where an evaluation is both ("csa": the k = 0 evaluation is mixed and pooled).
+        q_ranges / kv_ranges (optional): the slots whose Q / K,V projections the evaluations actually read, as arithmetic
         progressions [(first, step, count), ...] — a plan that reads Q of every (K+1)-th slot only (descriptor reuse: the own
         shapes) and K / V of the others then projects, and contracts weight gradients over, just those.  None = every slot."""
         import numpy as np
@@ -122,6 +126,7 @@ class EvalPlan:
         assert q.min() >= 0 and max(q.max(), kv.max() + v_shift) < n_slots
         self.E, self.S, self.v_shift = int(q.size), int(n_slots), int(v_shift)
         self.q_ranges, self.kv_ranges = q_ranges, kv_ranges
+        self.mixed_not_pooled = bool(mixed_not_pooled)
         if q_ranges is not None or kv_ranges is not None:
             assert v_shift == 0 and q_ranges is not None and kv_ranges is not None
             cover = lambda rs: set(int(f + st * i) for f, st, c in rs for i in range(c))
@@ -490,6 +495,10 @@ class _MHAEvals(torch.autograd.Function):
                                             _ptr(sums), _ptr(sum_ws), sum_ws_n, _stream()),
                    "csn_outproj_ln_fwd_f32")
         del sum_ws
+        if (keep_scores and link is not None and not a16 and tuning.current().fused_mix_bwd and plan.mixed_not_pooled
+                and n_head_evals > 0):
+            # the mix's backward may run the LayerNorm backward of the leading evaluations itself (_lnb_head)
+            link.pre = (xhat, rstd, w_fc, p_fc, seed_fc, n_head_evals, ctx.mode, bool(x_all.requires_grad))
         if keep_scores:
             ctx.save_for_backward(x_all, w_qkv, w_fc, qkv, att, lse, scores, xhat, rstd, kv)
             ctx.flow = flow
@@ -556,15 +565,21 @@ class _MHAEvals(torch.autograd.Function):
         # linked mix: the dense term of the leading maps is scale[e][c] * dfeats[e // group] — rebuilt inside the kernel
         scale, group = None, 1
         link, ctx.link = ctx.link, None
+        head_done = None                                                 # dz, dz_res, dCtx with the leading evaluations filled in
+        if link is not None:
+            head_done, link.head_done, link.pre = link.head_done, None, None
         if dhandle is not None and link is not None and link.dfeats is not None:
             if dense is None:
                 dense, scale, group, n_dense = link.dfeats, link.scale, link.group, ctx.n_head
-            else:                                                        # somebody also used the maps densely: materialise
+            else:
+                head_done = None                                         # (the launch below writes every evaluation again)                                                        # somebody also used the maps densely: materialise
                 dense = dense.clone() if dense.shape[0] == E else torch.cat(
                     (dense, dense.new_zeros((E - dense.shape[0],) + tuple(dense.shape[1:]))), dim=0)
                 dense[:ctx.n_head] += link.scale[:, :, None] * link.dfeats.repeat_interleave(link.group, dim=0)[:ctx.n_head]
                 n_dense = E
             link.dfeats = link.scale = None
+        else:
+            head_done = None
         temperature = geo.temperature or float(d) ** 0.5
         p_attn, seed_attn, p_fc, seed_fc = ctx.drop
         need_dx = ctx.needs_input_grad[0]
@@ -572,18 +587,30 @@ class _MHAEvals(torch.autograd.Function):
         # ---- LayerNorm + fc backward -------------------------------------------------------------------
         a16 = ctx.a16
         bwd16 = torch.bfloat16 if a16 else torch.float32               # type of the backward's maps dZ, dCtx
-        dz = torch.empty((E, C, NP), device=dev, dtype=bwd16)
-        dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and (p_fc > 0 or a16)) else None
-        datt = torch.empty((E, D, NP), device=dev, dtype=bwd16)
         dw_fc = torch.empty((C, D), device=dev, dtype=torch.float32)
         ws_n = L.csn_wgrad_workspace_floats(C, D, E, NP)
         ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
-        w_fc_t = w_fc.t().contiguous()
-        _lib.check(L.csn_outproj_ln_bwd_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(att), D * NP,
-                                            _ptr(w_fc_t), _ptr(dz), _ptr(dz_res), _ptr(datt), _ptr(dw_fc), _ptr(ws), ws_n,
-                                            E, C, D, NP, NP, 0, p_fc, seed_fc, 0, 0, _ptr(rows), n_dense, _ptr(scale), group,
-                                            _stream()),
-                   "csn_outproj_ln_bwd_f32")
+        if head_done is not None:
+            # the mix's backward has run the leading evaluations (and taken its reductions from them): the others with the row
+            # constants, then the W_fc gradient over all of dz — the pieces of csn_outproj_ln_bwd_f32, the same bits
+            dz, dz_res, datt, w_fc_t = head_done
+            if E > ctx.n_head:
+                _lib.check(L.csn_outproj_lnb_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
+                                                 _ptr(datt), ctx.n_head, E - ctx.n_head, C, D, NP, NP, p_fc, seed_fc, _ptr(rows),
+                                                 n_dense, _ptr(scale), group, None, None, None, 0, _stream()),
+                           "csn_outproj_lnb_f32")
+            _lib.check(L.csn_project_wgrad_f32(_ptr(dz), C * NP, NP, _ptr(att), D * NP, NP, _ptr(dw_fc), C, D, E, NP, 1.0, 0,
+                                               _ptr(ws), ws_n, _stream()), "csn_project_wgrad_f32")
+        else:
+            dz = torch.empty((E, C, NP), device=dev, dtype=bwd16)
+            dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and (p_fc > 0 or a16)) else None
+            datt = torch.empty((E, D, NP), device=dev, dtype=bwd16)
+            w_fc_t = w_fc.t().contiguous()
+            _lib.check(L.csn_outproj_ln_bwd_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(att), D * NP,
+                                                _ptr(w_fc_t), _ptr(dz), _ptr(dz_res), _ptr(datt), _ptr(dw_fc), _ptr(ws), ws_n,
+                                                E, C, D, NP, NP, 0, p_fc, seed_fc, 0, 0, _ptr(rows), n_dense, _ptr(scale), group,
+                                                _stream()),
+                       "csn_outproj_ln_bwd_f32")
         del ws
 
         # ---- attention backward, straight into per-slot gradient maps ---------------------------------------
@@ -710,11 +737,44 @@ class _MHAEvals(torch.autograd.Function):
 class MixLink:
     """What a linked mix leaves for the backward of the evaluations it consumed: the gradient of the mixed features
     (one map per query shape), the per-(evaluation, channel) factors comp * gamma, and the evaluations mixed per shape."""
-    __slots__ = ("dfeats", "scale", "group")
+    __slots__ = ("dfeats", "scale", "group", "pre", "head_done")
 
     def __init__(self):
         self.dfeats = self.scale = None
         self.group = 1
+        # fused_mix_bwd: `pre` = what the forward leaves for _lnb_head (None: the plan or the maps do not allow it), `head_done`
+        # = the buffers _lnb_head has filled for the leading evaluations
+        self.pre = self.head_done = None
+
+
+def _lnb_head(link: MixLink, dfeats: torch.Tensor, scale: torch.Tensor, group: int):
+    """LayerNorm backward + dCtx of the evaluations a linked mix consumed, run from the mix's backward: the kernel holds dfeats
+    and xhat of these evaluations anyway and returns the mix's reductions rowdot (n, C) / rowsum (n / group, C) on the way —
+    no separate pass over the maps (csn_mix_bwd_f32).  dz, dz_res and dCtx of ALL evaluations are allocated here and left in
+    the link; _MHAEvals._backward fills in the others.  None: not taken (nothing was launched)."""
+    if link is None or link.pre is None:
+        return None
+    xhat, rstd, w_fc, p_fc, seed_fc, n, mode, need_dx = link.pre
+    E, C, NP = xhat.shape
+    D = w_fc.shape[1]
+    L = _lib.lib()
+    dev = xhat.device
+    with math_mode(backward_mode(mode)), act16(0):
+        if n % group or L.csn_outproj_lnb_workspace_floats(E, C, D, NP, NP) <= 0:
+            return None
+        ws_n = int(L.csn_outproj_lnb_workspace_floats(n, C, D, NP, NP))
+        red_ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+        rowdot = torch.empty((n, C), device=dev, dtype=torch.float32)
+        rowsum = torch.empty((n // group, C), device=dev, dtype=torch.float32)
+        dz = torch.empty((E, C, NP), device=dev, dtype=torch.float32)
+        dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and p_fc > 0) else None
+        datt = torch.empty((E, D, NP), device=dev, dtype=torch.float32)
+        w_fc_t = w_fc.t().contiguous()
+        _lib.check(L.csn_outproj_lnb_f32(_ptr(dfeats), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
+                                         _ptr(datt), 0, n, C, D, NP, NP, p_fc, seed_fc, None, n, _ptr(scale), group, _ptr(rowdot),
+                                         _ptr(rowsum), _ptr(red_ws), ws_n, _stream()), "csn_outproj_lnb_f32")
+    link.head_done = (dz, dz_res, datt, w_fc_t)
+    return rowdot, rowsum
 
 
 class LinkedMaps:
@@ -872,11 +932,6 @@ class _CSAMixLinked(torch.autograd.Function):
         B, K1 = ctx.dims
         E, C, NP = xhat.shape
         dfeats = dfeats.contiguous()
-        rowdot = torch.empty((B, K1, C), device=xhat.device, dtype=torch.float32)
-        rowsum = torch.empty((B, C), device=xhat.device, dtype=torch.float32)
-        with act16(1 if xhat.dtype == torch.float16 else 0):
-            _lib.check(_lib.lib().csn_mix_bwd_f32(_ptr(dfeats), _ptr(xhat), _ptr(comp), _ptr(gamma), None, _ptr(rowdot),
-                                                  _ptr(rowsum), B, K1, C, NP, _ptr(xself), None, _stream()), "csn_mix_bwd_f32")
         factors = comp[:, :, None] * gamma                                           # (B, K1, C) = comp_k * gamma
         link, link_self = ctx.links
         if link_self is None:
@@ -884,6 +939,20 @@ class _CSAMixLinked(torch.autograd.Function):
         else:
             link_self.dfeats, link_self.scale, link_self.group = dfeats, factors[:, 0].contiguous(), 1
             link.dfeats, link.scale, link.group = dfeats, factors[:, 1:].reshape(B * (K1 - 1), C).contiguous(), K1 - 1
+        # the reductions: out of the LayerNorm backward of the mixed evaluations, which reads the same maps (tuning.fused_mix_bwd;
+        # dz and dCtx of these evaluations then wait in the links) — or by a pass of their own
+        rowdot = rowsum = None
+        if xhat.dtype == torch.float32 and link.pre is not None and (link_self is None or link_self.pre is not None):
+            head = [_lnb_head(l, dfeats, l.scale, l.group) for l in ((link,) if link_self is None else (link_self, link))]
+            if all(h is not None for h in head):
+                rowdot = torch.cat([h[0].view(B, -1, C) for h in head], dim=1) if len(head) > 1 else head[0][0].view(B, K1, C)
+                rowsum = head[0][1]
+        if rowdot is None:
+            rowdot = torch.empty((B, K1, C), device=xhat.device, dtype=torch.float32)
+            rowsum = torch.empty((B, C), device=xhat.device, dtype=torch.float32)
+            with act16(1 if xhat.dtype == torch.float16 else 0):
+                _lib.check(_lib.lib().csn_mix_bwd_f32(_ptr(dfeats), _ptr(xhat), _ptr(comp), _ptr(gamma), None, _ptr(rowdot),
+                                                      _ptr(rowsum), B, K1, C, NP, _ptr(xself), None, _stream()), "csn_mix_bwd_f32")
         rd, rs = rowdot.double(), rowsum.double()
         g64, b64, c64 = gamma.double(), beta.double(), comp.double()
         dcomp = (rd * g64).sum(dim=2) + (rs * b64).sum(dim=1, keepdim=True)          # (B, K1)

@@ -24,6 +24,10 @@ class Tuning:
     kv_tiles: bool = True            # 16-bit modes: K / V leave the projection as tile planes (csn_project_f32, out_split = 2)
     fused_point_sums: bool = True    # False: pooled sums by a streaming pass over the maps
     link_mix: bool = True            # False: the mix backward writes per-evaluation gradient maps
+    # linked mix, bf16x3 at d = 256, plans whose mixed evaluations are not pooled: the mix's reductions (d comp, d gamma, d beta)
+    # come out of the LayerNorm backward of the mixed evaluations, which the mix's backward launches itself.  False: a pass of
+    # their own over the maps (csn_mix_bwd_f32) and one LayerNorm backward launch over all evaluations
+    fused_mix_bwd: bool = True
     grouped_dkv: bool = True         # False: dK / dV by one read-modify-write launch per colour
     grouped_dq: bool = True          # False: dQ likewise
     grouped_fwd: bool = True         # 16-bit modes: the forward's evaluations grouped by query slot (the query operand staged once per group)

@@ -403,6 +403,26 @@ CSN_API int csn_outproj_ln_bwd_f32(const float* dxhat, const float* xhat, const 
                            const float* dxhat_rows, int n_dense_evals, const float* dxhat_scale, int dxhat_group,
                            void* stream);
 
+/* ---- (5b) the same LayerNorm backward and dctx over a RANGE of evaluations, without the weight gradient ----
+ * csn_outproj_lnb_f32 writes dz, dz_res (optional) and dctx of evaluations e_base .. e_base + n_evals - 1 of the maps — the
+ * arguments and the arithmetic of (5), evaluation indices absolute (the dropout masks are keyed on them), dctx with the stride of
+ * the maps.  A backward may so run in pieces, in any order, and finish with dwfc over all of dz through csn_project_wgrad_f32
+ * (dout = dz, x = ctx: the contraction (5) ends with); every piece gives the bits of the one call.
+ * It exists on the fused kernel only (math mode 1, fp32 maps, d_model = d_inner = 256): CSN_E_DIM elsewhere.
+ * csn_outproj_lnb_workspace_floats(n_evals, ...) is 0 where a call over evaluations 0 .. n_evals - 1 would be refused, else the
+ * floats of red_ws for the reductions below over that many evaluations.
+ * rowdot / rowsum / red_ws (all three or none; then e_base = 0 and n_evals <= n_dense_evals a multiple of dxhat_group): the
+ * reductions of csn_mix_bwd_f32 from the same pass over xhat and dxhat, on the raw dxhat (dfeats) values,
+ *   rowdot[e][c] = sum_n dxhat[e / dxhat_group][c][n] xhat[e][c][n]      [n_evals][256]
+ *   rowsum[g][c] = sum_n dxhat[g][c][n]                                  [n_evals / dxhat_group][256]
+ * fp32 partial sums per work-group and evaluation in red_ws, added in fp64 in a fixed order (two calls give the same bits). */
+CSN_API long long csn_outproj_lnb_workspace_floats(int n_evals, int d_model, int d_inner, int ld, int n_points);
+CSN_API int csn_outproj_lnb_f32(const float* dxhat, const float* xhat, const float* rstd, long long eval_stride,
+                        const float* wfc_t, float* dz, float* dz_res, float* dctx, int e_base, int n_evals, int d_model,
+                        int d_inner, int ld, int n_points, float dropout_p, unsigned long long seed,
+                        const float* dxhat_rows, int n_dense_evals, const float* dxhat_scale, int dxhat_group,
+                        float* rowdot, float* rowsum, float* red_ws, long long red_ws_floats, void* stream);
+
 /* ---- (6) projection weight gradient ----------------------------------------------------------------------
  * dw[r][c] (+)= scale * sum_{s,n} dout[s][r][n] * x[s][c][n]        (autograd of csa_models.py:103-105) */
 CSN_API int csn_project_wgrad_f32(const float* dout, long long dout_shape_stride, int ld_dout, const float* x,
