@@ -24,3 +24,8 @@ from .minkowski_training import (SegBatch, SegMeter, evaluate, load_me_head_stat
 # sparse 3D convolution on voxel rows: the primitive of the HRNet backbone (MinkowskiNet/models/hrnet.py:39-53, 89-111, 233-239)
 from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseConvTranspose3d, build_kernel_map,  # noqa: E402,F401
                              sparse_conv3d)
+
+# the HRNet backbone and HRNetSimCSN on voxel rows, on the fused convolution + BatchNorm kernels (MinkowskiNet/models/hrnet.py:31-163,
+# 296-454)
+from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetSimCSN3S, HRNetSimCSN4S, VoxelPyramid,  # noqa: E402,F401
+                              bn_act, build_pyramid, conv_stats, load_me_hrnet_state)

@@ -300,4 +300,30 @@ struct CsnSparseConvArgs {
 long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward);
 int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
+// forward with the BatchNorm statistics epilogue (no bias): a.y = z, a.ws = csn_sparse_conv_stats_ws_bytes(n_out, c_out) bytes
+long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out);
+int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
+                                     float eps, float momentum, int mode, hipStream_t st);
 extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule
+
+// ---- BatchNorm apply + branch sum + residual + ReLU on point-major rows, forward and backward (rows_bn_act.hip) ----
+struct CsnRowsBnActArgs {
+  // the terms (include/csn_hip.h section 15: CsnBnTerms, copied by the C ABI)
+  const float* z[3];  int ld_z[3];
+  const float* mean[3];  const float* scale[3];  const float* gamma[3];  const float* beta[3];
+  float* dz[3];  int ld_dz[3];  float* dgamma[3];  float* dbeta[3];
+  int n_terms;
+  int n_rows, C, training, relu;  float eps;
+  const float* r;  int ld_r;                                      // residual, optional
+  float* y;  int ld_y;                                            // forward: written; backward: read (the ReLU mask is y > 0)
+  const float* dy;  int ld_dy;
+  float* dr;  int ld_dr;
+  void* ws;
+};
+// the Chan merge of [tile][2][C] (mean, M2) partials of 32-row tiles (the statistics epilogue of sparse_conv.hip): mean, invstd,
+// running statistics (either may be NULL)
+int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, float* mean, float* invstd,
+                              float* running_mean, float* running_var, hipStream_t st);
+long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms);
+int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, hipStream_t st);
+int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, hipStream_t st);

@@ -10,7 +10,9 @@
 //                      the work-group's 128-row tile has a neighbour is dropped from the work-group's offset list before the loop
 //                      (wave ballots, merged through LDS: uniform over the work-group).  Forward: A = x, table = fwd, B[k] =
 //                      W[k] ([c_in][c_out], B_KN).  dx: A = dy, table = bwd, B[k] = W[k]^T (the same memory read [J][K]).
-//                      Every output row is written by exactly one wave.
+//                      Every output row is written by exactly one wave.  With a partials pointer the epilogue also forms the
+//                      (mean, M2) of each wave's <= 32 rows from the accumulators (the BatchNorm statistics of the backbone's
+//                      convolutions, csn_sparse_conv_stats_fwd_f32); the stored values are the same bits either way.
 //   sconv_wgrad        dW[k][ci][co] = sum_j x[fwd[k][j]][ci] dy[j][co] over the output rows of one split-K chunk: rows_fc_wgrad
 //                      with one gathered operand (a lane's 8 contraction steps are 8 looked-up rows of one column: a half wave
 //                      reads one contiguous 128-byte run per row).  A 16-row step in which the wave finds no neighbour is skipped
@@ -38,6 +40,7 @@ struct SconvGemmP {
   float* c; int ldc;                   // C[M][J]
   int M, K, J, KV;
   const float* bias;
+  float* part;                         // non-NULL: the (mean, M2) of each wave's rows, [tile][2][J], tile = 32 rows (rows_fc.hip)
 };
 
 template <int NB, int MODE, bool B_KN>
@@ -179,10 +182,31 @@ __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
     const int col = j0 + nb * 32 + li;
     if (j0 + nb * 32 >= p.J) continue;                                // wave-uniform: J % 32 == 0
     const float bv = p.bias ? p.bias[col] : 0.f;
+    float sum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int rr = csn_acc_row(r, h);
-      if (rr < cnt) p.c[(row_w + rr) * p.ldc + col] = acc[nb][r] + bv;
+      const float v = acc[nb][r] + bv;
+      acc[nb][r] = v;
+      if (rr < cnt) { p.c[(row_w + rr) * p.ldc + col] = v; sum += v; }
+    }
+    if (p.part) {
+      // (mean, M2) of the wave's cnt rows, two passes over the registers (rows_gemm_kernel's epi == 1): the stored values are
+      // untouched, the epilogue only adds
+      sum += csn_xhalf(sum);
+      const float mu = cnt > 0 ? sum / (float)cnt : 0.f;
+      float m2 = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float d = acc[nb][r] - mu;
+        if (csn_acc_row(r, h) < cnt) m2 = fmaf(d, d, m2);
+      }
+      m2 += csn_xhalf(m2);
+      if (h == 0) {
+        const long long tile = (long long)rg * 4 + wave;
+        p.part[(tile * 2) * p.J + col] = mu;
+        p.part[(tile * 2 + 1) * p.J + col] = m2;
+      }
     }
   }
 }
@@ -457,6 +481,23 @@ int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = a.bias;
   return launch_gemm<true>(p, mode, st);
+}
+
+long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out) {
+  return up256(((n_out + 127) / 128) * 4 * 2 * c_out * (long long)sizeof(float));
+}
+
+// the forward product with the statistics epilogue, then the tiles' (mean, M2) merged in fp64 in a fixed order (rows_bn_act.hip)
+int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
+                                     float eps, float momentum, int mode, hipStream_t st) {
+  mode = mode != 0;
+  SconvGemmP p{};
+  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
+  p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = nullptr;
+  p.part = static_cast<float*>(a.ws);
+  if (const int e = launch_gemm<true>(p, mode, st)) return e;
+  const int n_tiles = (int)(((long long)a.n_out + 127) / 128) * 4;
+  return csn_launch_bn_stats_merge(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, mean, invstd, running_mean, running_var, st);
 }
 
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {

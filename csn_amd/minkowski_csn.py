@@ -28,7 +28,7 @@ Backward: ``csn_ragged_mix_bwd_f32`` (the mixed maps' gradients and the fp64 per
 which d comp, d gamma, d beta follow), the compatibility math's autograd, then ``csn_ragged_pool_bwd_f32`` (the pooled
 descriptors' share, added to S and written for T), then the attention backward.
 
-The HRNet assembly is not built yet; its convolution is ``minkowski_conv.py``: inputs are the backbone features after ``fc_layer``, packed
+The HRNet backbone is ``minkowski_hrnet.py`` (``HRNetSimCSN2S`` / ``3S`` feed this head): inputs are the backbone features after ``fc_layer``, packed
 point-major rows sorted by shape plus their offsets (``offsets_from_batch_index`` derives them from an ME batch column) — or,
 for a head built with ``backbone_channels``, the concatenated backbone map itself: the head then owns ``fc_layer``
 (``BackboneFC``: hrnet.py:332-339, the kernel-size-1 convolution + BatchNorm + ReLU on ``csn_rows_fc_fwd_f32`` / ``_bwd_f32``) and

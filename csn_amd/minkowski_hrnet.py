@@ -1,0 +1,522 @@
+"""MinkowskiNet's HRNet backbone and ``HRNetSimCSN`` on voxel rows, on the MI355X kernels.
+
+Reference (marios2019/CSN):
+  * ``HRNetBase.backbone_initialization`` / ``forward_backbone``        MinkowskiNet/models/hrnet.py:31-163
+  * final transitions, the concatenation, ``fc_layer``, the head        MinkowskiNet/models/hrnet.py:308-357, 425-454
+  * ``BasicBlock``                                                      MinkowskiNet/models/modules/resnet_block.py:22-57
+
+Every convolution of the backbone is followed by a BatchNorm, and every BatchNorm by a ReLU, a residual add or a sum over branches.
+With ``fused=True`` each such pair is two autograd nodes on include/csn_hip.h section 15:
+
+  * ``conv_stats``  (15a) the gather-GEMM with the BatchNorm statistics formed in its epilogue: z, mean, invstd, running statistics;
+  * ``bn_act``      (15b) y = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + r) for up to three terms, whose backward is the
+                    COMPLETE BatchNorm gradient of every term (the statistics are constants of the autograd graph, as in
+                    ``_RowsFC``).
+In eval mode the convolution is the plain ``sparse_conv3d`` and ``bn_act`` takes the running statistics.  With ``fused=False`` the same
+graph runs on ``sparse_conv3d`` + ``F.batch_norm`` + ATen add / ReLU: the timing baseline and the error yardstick of the tests.
+
+The three or four maps that the reference joins with ``me.cat`` are joined with ``torch.cat`` here (the kernels' output pitch would
+let them be written straight into one buffer; that is not built).
+
+``VoxelPyramid`` holds the coordinate sets and kernel maps of one batch, built once (``build_pyramid``): level l's coordinates are
+``down^l(coords)`` by the stride-2 rule of ``build_kernel_map``; per level the stride-1 kernel-3 map, at level 0 the stem's map,
+between neighbouring levels the stride-2 map whose ``transpose()`` serves the up direction.
+
+Offset numbering and the sorted order of the coarse levels are this project's choice (minkowski_conv.py): parity unpinned against
+MinkowskiEngine's own checkpoints.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from . import functional as CF
+from .minkowski_conv import KernelMap, SparseConv3d, SparseConvTranspose3d, build_kernel_map, sparse_conv3d
+from .minkowski_csn import SimCSNHead, offsets_from_batch_index
+
+_NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
+
+
+# ------------------------------------------------------------------------------------------------------
+# the pyramid
+# ------------------------------------------------------------------------------------------------------
+class VoxelPyramid:
+    """Coordinates and kernel maps of one batch for an ``n_levels``-branch HRNet.
+
+    ``coords[l]`` (n_l, 4) at tensor stride 2^l; ``s1[l]`` the kernel-3 stride-1 map of level l; ``stem`` the kernel-``stem_kernel``
+    stride-1 map of level 0; ``down[l]`` the kernel-3 stride-2 map from level l onto level l + 1; ``up(l)`` its transpose (from level
+    l + 1 onto level l)."""
+
+    def __init__(self, coords: List[torch.Tensor], s1: List[KernelMap], stem: KernelMap, down: List[KernelMap], stem_kernel: int):
+        self.coords, self.s1, self.stem, self.down, self.stem_kernel = coords, s1, stem, down, stem_kernel
+        self._up = [d.transpose() for d in down]
+
+    @property
+    def n_levels(self) -> int:
+        return len(self.coords)
+
+    def up(self, level: int) -> KernelMap:
+        return self._up[level]
+
+    def to(self, device) -> "VoxelPyramid":
+        return VoxelPyramid([c.to(device) for c in self.coords], [m.to(device) for m in self.s1], self.stem.to(device),
+                            [m.to(device) for m in self.down], self.stem_kernel)
+
+
+def build_pyramid(coords: torch.Tensor, n_levels: int, stem_kernel: int = 5) -> VoxelPyramid:
+    """The pyramid of ``coords`` (n, 4) = [b, x, y, z] at tensor stride 1 (device or CPU tensor; the maps live where it does)."""
+    if n_levels < 1:
+        raise ValueError("n_levels must be at least 1")
+    levels, s1, down = [coords.long()], [], []
+    for l in range(n_levels):
+        ts = 1 << l
+        s1.append(build_kernel_map(levels[l], kernel_size=3, stride=1, tensor_stride=ts))
+        if l + 1 < n_levels:
+            d = build_kernel_map(levels[l], kernel_size=3, stride=2, tensor_stride=ts)
+            down.append(d)
+            levels.append(d.out_coords)
+    stem = s1[0] if stem_kernel == 3 else build_kernel_map(levels[0], kernel_size=stem_kernel, stride=1, tensor_stride=1)
+    return VoxelPyramid(levels, s1, stem, down, stem_kernel)
+
+
+# ------------------------------------------------------------------------------------------------------
+# autograd nodes on section 15
+# ------------------------------------------------------------------------------------------------------
+class _ConvStats(torch.autograd.Function):
+    """(z, mean, invstd) = ``csn_sparse_conv_stats_fwd_f32``; updates the running statistics in place.  mean / invstd are constants
+    of the graph; the backward is ``csn_sparse_conv_bwd_f32``."""
+
+    @staticmethod
+    def forward(ctx, x, w, kmap, running_mean, running_var, eps, momentum):
+        CF._need_cuda(x, w, kmap.fwd, running_mean, running_var)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        x = x.contiguous()
+        w_c = w.detach().contiguous()
+        KV, c_in, c_out = w_c.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        dev = x.device
+        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
+        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        _lib.check(L.csn_sparse_conv_stats_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
+                                                   CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
+                                                   CF._ptr(running_var), float(eps), float(momentum), CF._ptr(ws), ws_n,
+                                                   CF._stream()), "csn_sparse_conv_stats_fwd_f32")
+        ctx.save_for_backward(x, w_c)
+        ctx.kmap = kmap
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dmean, _dinvstd):
+        with CF.math_mode(CF.backward_mode(ctx.mode)):
+            x, w = ctx.saved_tensors
+            kmap = ctx.kmap
+            L = _lib.lib()
+            KV, c_in, c_out = w.shape
+            n_in, n_out = kmap.n_in, kmap.n_out
+            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_x or need_w):
+                return (None,) * 7
+            dz = dz.contiguous()
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+            bwd = kmap.bwd_table if need_x else None
+            _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
+                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
+                                                 CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+            return dx, dw, None, None, None, None, None
+
+
+def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_mean: Optional[torch.Tensor],
+               running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``z (n_out, c_out)``, ``mean``, ``invstd`` of the convolution ``kmap`` describes and of its output's BatchNorm batch; the
+    running statistics (either may be None) are updated in place.  An input width that is no multiple of 32 is zero-padded as in
+    ``sparse_conv3d``.  A one-row output raises ``ValueError`` (no variance), as torch does."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
+        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out) for the map's KV and n_in")
+    c_in, c_out = weight.shape[1], weight.shape[2]
+    if c_out % 32 or not 32 <= c_out <= 256 or c_in > 256:
+        raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in at most 256")
+    if kmap.n_out == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    pad = -c_in % 32
+    if pad:
+        x = F.pad(x, (0, pad))
+        weight = F.pad(weight, (0, 0, 0, pad))
+    return _ConvStats.apply(x.float(), weight, kmap, running_mean, running_var, eps, momentum)
+
+
+class _BnAct(torch.autograd.Function):
+    """y = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + r) through ``csn_rows_bn_act_fwd_f32`` / ``_bwd_f32``.
+    Arguments after the fixed ones: (z, mean, scale, gamma, beta) per term."""
+
+    @staticmethod
+    def forward(ctx, relu, training, eps, r, *flat):
+        M = len(flat) // 5
+        CF._need_cuda(r, *flat)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        zs = [flat[5 * m].contiguous() for m in range(M)]
+        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
+        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
+        if not training:                                                    # the running statistics may move before the backward
+            means, scales = [t.clone() for t in means], [t.clone() for t in scales]
+        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
+        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+        N, C = zs[0].shape
+        r_c = None if r is None else r.contiguous()
+        y = torch.empty((N, C), device=zs[0].device, dtype=torch.float32)
+        t = _lib.BnTerms()
+        for m in range(M):
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
+            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
+        _lib.check(L.csn_rows_bn_act_fwd_f32(ctypes.addressof(t), M, N, C, int(training), float(eps), CF._ptr(r_c), C, int(relu),
+                                             CF._ptr(y), C, CF._stream()), "csn_rows_bn_act_fwd_f32")
+        ctx.save_for_backward(y if relu else None, *zs, *means, *scales, *gammas)
+        ctx.M, ctx.relu, ctx.training, ctx.eps, ctx.has_r = M, bool(relu), bool(training), float(eps), r is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        M = ctx.M
+        saved = ctx.saved_tensors
+        y = saved[0]
+        zs, means, scales, gammas = (saved[1 + k * M:1 + (k + 1) * M] for k in range(4))
+        L = _lib.lib()
+        N, C = zs[0].shape
+        dev = dy.device
+        dy = dy.contiguous()
+        need = ctx.needs_input_grad
+        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[3]) else None
+        t = _lib.BnTerms()
+        outs = []
+        for m in range(M):
+            nz, ng, nb = need[4 + 5 * m], need[4 + 5 * m + 3], need[4 + 5 * m + 4]
+            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
+            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
+            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
+            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
+            outs += [dz, None, None, dg, db]
+        ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        _lib.check(L.csn_rows_bn_act_bwd_f32(CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C, int(ctx.training), ctx.eps,
+                                             int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),
+                   "csn_rows_bn_act_bwd_f32")
+        return (None, None, None, dr, *outs)
+
+
+Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
+
+
+def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu: bool = True, training: bool = True,
+           eps: float = 1e-5) -> torch.Tensor:
+    """``y (N, C) = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + residual)`` for 1 to 3 terms ``(z, mean, scale, gamma, beta)``:
+    training takes ``scale = invstd`` (of ``conv_stats``), eval the running mean / variance and ``eps``."""
+    if not 1 <= len(terms) <= 3:
+        raise ValueError("bn_act takes 1 to 3 terms")
+    flat = []
+    N, C = terms[0][0].shape
+    for z, mean, scale, gamma, beta in terms:
+        if not z.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if tuple(z.shape) != (N, C) or any(v.numel() != C for v in (mean, scale, gamma, beta)):
+            raise ValueError("every term needs an (N, C) map and four (C,) vectors")
+        flat += [z.float(), mean, scale, gamma, beta]
+    if C % 32 or not 32 <= C <= 256:
+        raise ValueError(f"width {C} is not supported: a multiple of 32 in [32, 256]")
+    if residual is not None:
+        if not residual.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if tuple(residual.shape) != (N, C):
+            raise ValueError("the residual must be (N, C)")
+        residual = residual.float()
+    return _BnAct.apply(bool(relu), bool(training), float(eps), residual, *flat)
+
+
+# ------------------------------------------------------------------------------------------------------
+# conv + norm as a term; combining terms
+# ------------------------------------------------------------------------------------------------------
+def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, fused: bool):
+    """fused: the term (z, mean, scale, gamma, beta) of ``bn_act``; else the normalised map through ATen."""
+    if kmap.kernel_size != conv.kernel_size or kmap.stride != conv.stride or kmap.transposed != conv.transposed:
+        raise ValueError("the map does not fit this layer")
+    training = norm.training
+    if not x.is_cuda:
+        raise _lib.CsnError(_NO_CPU)
+    if training and kmap.n_out == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    if not fused:
+        return norm(sparse_conv3d(x, conv.kernel, None, kmap))
+    if training:
+        norm.num_batches_tracked += 1
+        z, mean, invstd = conv_stats(x, conv.kernel, kmap, norm.running_mean, norm.running_var, norm.eps, norm.momentum)
+        return (z, mean, invstd, norm.weight, norm.bias)
+    return (sparse_conv3d(x, conv.kernel, None, kmap), norm.running_mean, norm.running_var, norm.weight, norm.bias)
+
+
+def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5) -> torch.Tensor:
+    """relu(sum of ``parts``) where a part is a term / normalised map of ``_conv_bn`` or ("r", map) for a plain map.  The ATen path
+    adds in the order given (the reference's, hrnet.py:157-161)."""
+    if fused:
+        terms = [p for p in parts if not (isinstance(p, tuple) and p[0] == "r")]
+        res = [p[1] for p in parts if isinstance(p, tuple) and p[0] == "r"]
+        if not terms:
+            # the finest branch after stage 0 has no incoming path: the reference's ReLU of a block's output, itself a ReLU
+            # output — the same values, and the same gradient (the block's own mask zeroes the same elements): no launch
+            return res[0]
+        return bn_act(terms, res[0] if res else None, True, training, eps)
+    maps = [p[1] if isinstance(p, tuple) else p for p in parts]
+    buf = maps[0]
+    for m in maps[1:]:
+        buf = buf + m
+    return F.relu(buf)
+
+
+def _keep(trace: Optional[Dict[str, torch.Tensor]], name: str, y: torch.Tensor) -> torch.Tensor:
+    if trace is not None:
+        trace[name] = y.detach()
+    return y
+
+
+class HRBasicBlock(nn.Module):
+    """``BasicBlock`` of resnet_block.py:22-57 without a downsample (the backbone has none), on the fused nodes.  State-dict keys
+    are those of ``SparseBasicBlock``: ``conv1.kernel``, ``norm1.*``, ``conv2.kernel``, ``norm2.*``.  ``trace`` (a dict) receives the
+    two ReLU outputs under ``prefix + "norm1"`` / ``prefix + "norm2"``."""
+
+    expansion = 1
+
+    def __init__(self, inplanes: int, planes: int, bn_momentum: float = 0.02, fused: bool = True):
+        super().__init__()
+        if inplanes != planes:
+            raise ValueError("the backbone's blocks keep their width (no downsample)")
+        self.conv1 = SparseConv3d(inplanes, planes, kernel_size=3, stride=1)
+        self.norm1 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.conv2 = SparseConv3d(planes, planes, kernel_size=3, stride=1)
+        self.norm2 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.fused = fused
+
+    def forward(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "") -> torch.Tensor:
+        f, tr = self.fused, self.training
+        out = _keep(trace, prefix + "norm1", _combine([_conv_bn(self.conv1, self.norm1, x, kmap, f)], f, tr, self.norm1.eps))
+        t2 = _conv_bn(self.conv2, self.norm2, out, kmap, f)
+        return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps))
+
+
+# ------------------------------------------------------------------------------------------------------
+# the backbone
+# ------------------------------------------------------------------------------------------------------
+class HRNetBackbone(nn.Module):
+    """``HRNetBase.backbone_initialization`` + ``forward_backbone`` + the final transitions + the concatenation (hrnet.py:31-163,
+    308-326, 433-437) with the reference's module names: ``conv0s1``, ``bn0s1``, ``conv1s1``, ``bn1s1``, ``stages.i.j.b``,
+    ``exchange_blocks.i.j.k.*`` (sequential indices with the ReLUs counted: a two-step path has conv 0, norm 1, relu 2, conv 3, norm
+    4), ``final_transitions.i.*`` (conv 3s, norm 3s + 1, relu 3s + 2).
+
+    ``forward(feats, pyramid, trace=None)``: ``feats (N, in_channels)`` on the pyramid's level-0 rows; returns the
+    ``(N, init_dim + sum of the branch widths)`` rows [out_init | branch 0 | transition 1 | ...].  ``trace``: a dict that receives
+    every ReLU's output, keyed ``bn0s1``, ``bn1s1``, ``stages.i.j.b.norm1`` / ``.norm2``, ``exchange_blocks.i.j.k.<norm index>``
+    (the inner steps of a multi-step path), ``sum.i.k`` (the branch sums after stage i) and ``final_transitions.i.<norm index>``."""
+
+    NUM_BLOCKS = 3
+
+    def __init__(self, in_channels: int = 3, num_stages: int = 3, feat_factor: int = 2, init_dim: int = 32, conv1_kernel_size: int = 5,
+                 bn_momentum: float = 0.02, fused: bool = True):
+        super().__init__()
+        D = init_dim * feat_factor
+        if D * 2 ** (num_stages - 1) > 256:
+            raise NotImplementedError(f"the coarsest branch would be {D * 2 ** (num_stages - 1)} wide: the convolution kernels "
+                                      "(include/csn_hip.h section 14) take widths up to 256")
+        self.num_stages, self.init_dim, self.init_stage_dims, self.fused = num_stages, init_dim, D, fused
+        self.conv1_kernel_size = conv1_kernel_size
+        bn = lambda c: nn.BatchNorm1d(c, momentum=bn_momentum)
+        self.conv0s1 = SparseConv3d(in_channels, init_dim, kernel_size=conv1_kernel_size)
+        self.bn0s1 = bn(init_dim)
+        self.conv1s1 = SparseConv3d(init_dim, D, kernel_size=3)
+        self.bn1s1 = bn(D)
+        self.stages, self.exchange_blocks = nn.ModuleList(), nn.ModuleList()
+        for i in range(num_stages):
+            self.stages.append(nn.ModuleList(
+                nn.ModuleList(HRBasicBlock(D * 2 ** j, D * 2 ** j, bn_momentum, fused) for _ in range(self.NUM_BLOCKS))
+                for j in range(i + 1)))
+            if i == num_stages - 1:
+                break
+            depth = i + 1
+            ex = nn.ModuleList()
+            for j in range(depth):
+                row = nn.ModuleList()
+                c0 = D * 2 ** j
+                for k in range(depth + 1):
+                    path = nn.ModuleList()
+                    for s in range(abs(k - j)):
+                        if s:
+                            path.append(nn.ReLU())
+                        if k > j:
+                            path.append(SparseConv3d(c0 * 2 ** s, c0 * 2 ** (s + 1), kernel_size=3, stride=2))
+                            path.append(bn(c0 * 2 ** (s + 1)))
+                        else:
+                            path.append(SparseConvTranspose3d(c0 // 2 ** s, c0 // 2 ** (s + 1)))
+                            path.append(bn(c0 // 2 ** (s + 1)))
+                    row.append(path)
+                ex.append(row)
+            self.exchange_blocks.append(ex)
+        self.final_transitions = nn.ModuleList()
+        for i in range(1, num_stages):
+            c = D * 2 ** i
+            block = nn.ModuleList()
+            for _ in range(i):
+                block += [SparseConvTranspose3d(c, c), bn(c), nn.ReLU()]
+            self.final_transitions.append(block)
+        self.out_channels = init_dim + sum(D * 2 ** s for s in range(num_stages))
+        for m in self.modules():                                            # hrnet.py:165-169
+            if isinstance(m, nn.BatchNorm1d):
+                nn.init.constant_(m.weight, 1.0)
+                nn.init.constant_(m.bias, 0.0)
+
+    def forward(self, feats: torch.Tensor, pyramid: VoxelPyramid, trace: Optional[dict] = None) -> torch.Tensor:
+        if not feats.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if pyramid.n_levels < self.num_stages or pyramid.stem_kernel != self.conv1_kernel_size:
+            raise ValueError(f"the pyramid needs {self.num_stages} levels and a kernel-{self.conv1_kernel_size} stem map")
+        if feats.dim() != 2 or feats.shape[0] != pyramid.coords[0].shape[0]:
+            raise ValueError("feats must be (N, in_channels) rows of the pyramid's level 0")
+        f, tr = self.fused, self.training
+        act1 = lambda name, t: _keep(trace, name, _combine([t], f, tr))
+        out_init = act1("bn0s1", _conv_bn(self.conv0s1, self.bn0s1, feats.float(), pyramid.stem, f))
+        out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f))
+        stage_input = [out]
+        for i in range(self.num_stages):
+            stage_output = []
+            for j in range(i + 1):
+                x = stage_input[j]
+                for b, blk in enumerate(self.stages[i][j]):
+                    x = blk(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.")
+                stage_output.append(x)
+            if i == self.num_stages - 1:
+                break
+            depth = i + 1
+            stage_input = []
+            for k in range(depth + 1):
+                parts = []
+                for j in range(depth):
+                    if j == k:
+                        parts.append(("r", stage_output[j]))
+                        continue
+                    path, x, steps = self.exchange_blocks[i][j][k], stage_output[j], abs(k - j)
+                    for s in range(steps):
+                        level = j + s if k > j else j - s                  # the level the step starts from
+                        kmap = pyramid.down[level] if k > j else pyramid.up(level - 1)
+                        t = _conv_bn(path[3 * s], path[3 * s + 1], x, kmap, f)
+                        if s + 1 < steps:
+                            x = act1(f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", t)
+                        else:
+                            parts.append(t)
+                stage_input.append(_keep(trace, f"sum.{i}.{k}", _combine(parts, f, tr)))
+        outs = [out_init, stage_output[0]]
+        for i in range(1, self.num_stages):
+            x, block = stage_output[i], self.final_transitions[i - 1]
+            for s in range(i):
+                x = act1(f"final_transitions.{i - 1}.{3 * s + 1}", _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f))
+            outs.append(x)
+        return torch.cat(outs, dim=1)
+
+
+# ------------------------------------------------------------------------------------------------------
+# the models
+# ------------------------------------------------------------------------------------------------------
+Batch = Tuple[torch.Tensor, torch.Tensor]         # (coords (n, 4) sorted by shape — or a VoxelPyramid —, feats (n, in_channels))
+
+
+class HRNetSimCSN(nn.Module):
+    """``HRNetSimCSN`` (hrnet.py:296-454): ``backbone`` (``HRNetBackbone``) and ``head`` (``SimCSNHead`` with its ``fc_layer``).
+
+    ``forward((coords, feats), keys=None, return_ssa=False)``: ``coords (N, 4)`` rows [b, x, y, z] sorted by shape (or a
+    ``VoxelPyramid`` built for them), ``feats (N, in_channels)``; ``keys`` a list of K such batches, batch i holding the i-th
+    neighbour of every query shape.  The backbone runs on the queries first and then on key batches 0 .. K-1, each its own
+    BatchNorm batch, and so does ``fc_layer`` inside the head: per layer the running statistics see the batches in the reference's
+    order (hrnet.py:425-454).  Returns the (N, out_channels) logits, or the SSA rows with ``return_ssa``."""
+
+    NUM_STAGES = 1
+    FEAT_FACTOR = 1
+
+    def __init__(self, in_channels: int, out_channels: int, d_model: int = 256, n_head: int = 4, k_neighbors: int = 1,
+                 dropout: float = 0.1, bn_momentum: float = 0.02, conv1_kernel_size: int = 5, init_dim: int = 32, fused: bool = True):
+        super().__init__()
+        self.backbone = HRNetBackbone(in_channels, self.NUM_STAGES, self.FEAT_FACTOR, init_dim, conv1_kernel_size, bn_momentum, fused)
+        self.head = SimCSNHead(d_model, n_head, out_channels, k_neighbors, dropout=dropout,
+                               backbone_channels=self.backbone.out_channels, bn_momentum=bn_momentum)
+
+    def backbone_rows(self, batch: Batch):
+        """(rows (N, backbone channels), offsets (B + 1)) of one batch."""
+        where, feats = batch
+        pyr = where if isinstance(where, VoxelPyramid) else build_pyramid(where, self.NUM_STAGES, self.backbone.conv1_kernel_size)
+        if not feats.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if pyr.coords[0].device != feats.device:
+            pyr = pyr.to(feats.device)
+        return self.backbone(feats, pyr), offsets_from_batch_index(pyr.coords[0][:, 0])
+
+    def forward(self, queries: Batch, keys: Optional[Sequence[Batch]] = None, return_ssa: bool = False):
+        q, qo = self.backbone_rows(queries)
+        ks = [self.backbone_rows(b) for b in (keys or [])]
+        return self.head(q, qo, keys=ks or None, return_ssa=return_ssa)
+
+
+class HRNetSimCSN2S(HRNetSimCSN):
+    NUM_STAGES, FEAT_FACTOR = 2, 4            # 32 + 128 + 256 = 416 backbone channels
+
+
+class HRNetSimCSN3S(HRNetSimCSN):
+    NUM_STAGES, FEAT_FACTOR = 3, 2            # 32 + 64 + 128 + 256 = 480 backbone channels
+
+
+class HRNetSimCSN4S(HRNetSimCSN):
+    NUM_STAGES, FEAT_FACTOR = 4, 2
+
+    def __init__(self, *a, **kw):
+        raise NotImplementedError("HRNetSimCSN4S needs 512-wide convolutions; the kernels (include/csn_hip.h section 14) take "
+                                  "widths up to 256")
+
+
+def load_me_hrnet_state(model: HRNetSimCSN, state_dict) -> HRNetSimCSN:
+    """Copy an ``HRNetSimCSN`` checkpoint of the reference into ``model``.  The backbone's modules keep the reference's names
+    (under ``backbone.`` here, at the top level there); a ``MinkowskiBatchNorm`` wraps its norm, so ``<name>.bn.weight`` etc. map
+    to ``<name>.weight``; a convolution's ``<name>.kernel`` is (KV, c_in, c_out) on both sides.  The sequential indices of the
+    exchange and transition blocks count the ReLUs on both sides.  The head goes through ``load_me_head_state``.  A missing key or
+    a wrong shape raises ``ValueError``.  The order of the KV axis (the offset numbering of minkowski_conv.py) is this project's
+    choice: parity unpinned against MinkowskiEngine."""
+    from .minkowski_training import load_me_head_state
+    new = {}
+    for name, mod in model.backbone.named_modules():
+        if isinstance(mod, SparseConv3d):
+            pairs = [(f"{name}.kernel", f"{name}.kernel", mod.kernel)]
+        elif isinstance(mod, nn.BatchNorm1d):
+            pairs = [(f"{name}.{p}", f"{name}.bn.{p}", getattr(mod, p))
+                     for p in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+        else:
+            continue
+        for own, ref, cur in pairs:
+            if ref not in state_dict:
+                raise ValueError(f"checkpoint has no {ref}")
+            v = state_dict[ref]
+            if tuple(v.shape) != tuple(cur.shape):
+                raise ValueError(f"{ref} is {tuple(v.shape)}; expected {tuple(cur.shape)}")
+            new[own] = v
+    model.backbone.load_state_dict(new, strict=True)
+    load_me_head_state(model.head, state_dict)
+    return model

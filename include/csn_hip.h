@@ -659,6 +659,56 @@ CSN_API int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const floa
                             int c_out, const int* fwd_table, const int* bwd_table, const float* w, float* dx, long long ld_dx,
                             float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
 
+/* ---- (15) the HRNet backbone's fused tail: convolution with a BatchNorm statistics epilogue, and normalise + sum + add + activate
+ *           (MinkowskiNet/models/hrnet.py:124-131 the stem, :157-161 the branch sums, :308-326 the final transitions;
+ *           models/modules/resnet_block.py:40-57 the block) --------------------------------------------------------------------
+ * Every normalised convolution of the backbone (47 in HRNetSimCSN3S) is followed by a ReLU, a residual add or a sum over branches.
+ * Two entry points cover all of it.  Everything is POINT-MAJOR fp32 with pitches as in (14): widths % 32 == 0 in [32, 256]
+ * (CSN_E_DIM); every pitch % 4 == 0 (CSN_E_ALIGN), >= the width (CSN_E_ARG), <= 2^20 and rows * pitch * 4 < 2 GiB (CSN_E_DIM); maps
+ * and ws 16-byte aligned (CSN_E_PTR); per-column vectors [channels] fp32.  All of this is checked on the host before any launch.
+ * No floating-point atomics: every reduction has a fixed order, two identical calls give the same bits.
+ *
+ * (15a) csn_sparse_conv_stats_fwd_f32: z = gather-GEMM(x, table, w) exactly as csn_sparse_conv_fwd_f32 with bias = NULL — the SAME
+ *   bits in the same math mode; the epilogue only adds — plus the BatchNorm statistics of z over its n_out rows:
+ *   mean[c], invstd[c] = 1 / sqrt(var_biased + eps);  running_mean <- (1 - momentum) running_mean + momentum mean;
+ *   running_var <- (1 - momentum) running_var + momentum var n / (n - 1)   (either running pointer may be NULL: not tracked).
+ *   The product's epilogue forms (mean, M2) of each wave's <= 32 rows from the accumulators in two passes over the registers; the
+ *   partials are merged by Chan's formula in fp64 in a fixed order, as in (13).  n_out == 1: CSN_E_ARG (no variance).
+ *   ws: csn_sparse_conv_stats_workspace_bytes(n_out, c_out) bytes (CSN_E_WORKSPACE).  Math modes as in (14).
+ *   Its backward is csn_sparse_conv_bwd_f32 (the statistics are taken up by (15b)'s dz).
+ *
+ * (15b) csn_rows_bn_act_fwd_f32:  y = act( sum_{m < n_terms} (gamma_m (z_m - mean_m) s_m + beta_m) + r ),  n_terms in {1, 2, 3}
+ *   (CSN_E_ARG otherwise), r an optional residual map (NULL: none), act = ReLU (relu != 0) or the identity.  The terms cross the
+ *   ABI as ONE host struct of arrays, CsnBnTerms: entry m of every array belongs to term m, entries >= n_terms are ignored.
+ *   training != 0: s_m = scale[m] is the invstd of (15a), mean[m] its mean.  training == 0: mean[m] / scale[m] are the running mean
+ *   / variance and s_m = 1 / sqrt(scale[m] + eps), as in (13).  Forward reads z, ld_z, mean, scale, gamma, beta of each term.
+ *   y may be a column block of a wider buffer (ld_y > channels): columns outside [0, channels) of a row are not written.
+ * csn_rows_bn_act_bwd_f32: g' = dy [y > 0] with the forward's own y (relu == 0: g' = dy, y may be NULL);
+ *   dr = g';  per term dgamma[m] = sum_n g' xhat_m,  dbeta[m] = sum_n g',  xhat_m = (z_m - mean_m) s_m;
+ *   training: dz[m] = gamma_m s_m (g' - mean_n g' - xhat_m mean_n(g' xhat_m))  — the complete BatchNorm gradient;
+ *   eval:     dz[m] = g' gamma_m s_m.
+ *   Any output whose pointer is NULL (dr, dz[m], dgamma[m], dbeta[m]) is skipped; beta is not read.  Pass 1 reads dy and y ONCE for
+ *   all terms; column sums are fp64 partials of 64-row chunks added in a fixed order.
+ *   ws: csn_rows_bn_act_workspace_bytes(n_rows, channels, n_terms) bytes (backward only; the forward takes none). */
+typedef struct CsnBnTerms {
+  const float* z[3];      long long ld_z[3];   /* the maps [n_rows][ld_z] */
+  const float* mean[3];   const float* scale[3];
+  const float* gamma[3];  const float* beta[3];
+  float* dz[3];           long long ld_dz[3];  /* backward outputs, each may be NULL */
+  float* dgamma[3];       float* dbeta[3];
+} CsnBnTerms;
+CSN_API long long csn_sparse_conv_stats_workspace_bytes(int n_out, int c_out);
+CSN_API int csn_sparse_conv_stats_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                  float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
+                                  void* stream);
+CSN_API long long csn_rows_bn_act_workspace_bytes(int n_rows, int channels, int n_terms);
+CSN_API int csn_rows_bn_act_fwd_f32(const CsnBnTerms* terms, int n_terms, int n_rows, int channels, int training, float eps,
+                            const float* r, long long ld_r, int relu, float* y, long long ld_y, void* stream);
+CSN_API int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* terms,
+                            int n_terms, int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr,
+                            void* ws, long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

@@ -1,0 +1,124 @@
+"""Time the HRNet3S backbone (csn_amd.minkowski_hrnet.HRNetBackbone), training forward + backward, with the fused BatchNorm kernels
+(``fused=True``: include/csn_hip.h section 15) beside the same graph on ``sparse_conv3d`` + ATen batch norm / add / ReLU
+(``fused=False``) on the same device in the same process; and one ``HRBasicBlock`` beside ``SparseBasicBlock`` at 64 / 128 / 256
+channels on the voxel set of the branch that has that width.
+
+Voxels: ``--voxels`` (32768) from 8 synthetic ellipsoid shells (scripts/bench_sparse_conv.py).  The pyramid is built once outside
+the timed window, as a training loop would per batch.  HIP events around each forward + backward; every variant is warmed up, then
+timed in ``--rounds`` alternating rounds of ``--iters`` steps: the figure is the median over the rounds of each round's median,
+``spread`` its min and max over the rounds.  ``fused_is_faster`` is true only when the fused median lies below the unfused one by more
+than both spreads.  ``--only fused|unfused`` runs one variant (a profiler pass wants one).  Prints one JSON line.
+
+    python scripts/bench_hrnet.py --out profiles/hrnet_bench.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scripts.bench_sparse_conv import shell_shapes  # noqa: E402
+
+
+def timed(step, iters):
+    ms = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def compare(variants, warmup, iters, rounds):
+    """variants: name -> step().  Alternating rounds (round 0 is the warm-up); medians of the rounds' medians and their spread."""
+    samples = {v: [] for v in variants}
+    for rnd in range(rounds + 1):
+        for v, step in variants.items():
+            t = timed(step, warmup if rnd == 0 else iters)
+            if rnd:
+                samples[v].append(t)
+    out = {}
+    for v, s in samples.items():
+        out[f"{v}_ms"] = statistics.median(s)
+        out[f"{v}_spread_ms"] = [min(s), max(s)]
+    if "unfused_ms" in out and "fused_ms" in out:
+        gap = out["unfused_ms"] - out["fused_ms"]
+        noise = max(out["fused_spread_ms"][1] - out["fused_spread_ms"][0], out["unfused_spread_ms"][1] - out["unfused_spread_ms"][0])
+        out["speedup"] = out["unfused_ms"] / out["fused_ms"]
+        out["fused_is_faster"] = bool(gap > noise and out["fused_spread_ms"][1] < out["unfused_spread_ms"][0])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voxels", type=int, default=32768)
+    ap.add_argument("--shapes", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--mode", default="bf16x3", help="math mode of the products: fp32 or bf16x3 (the library's default)")
+    ap.add_argument("--only", default="", help="fused or unfused: run that variant alone")
+    ap.add_argument("--skip-blocks", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import csn_amd
+    csn_amd.build()
+    from csn_amd import HRBasicBlock, HRNetBackbone, SparseBasicBlock, build_pyramid
+    from csn_amd import functional as CF
+    torch.manual_seed(0)
+    coords = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
+    pyr = build_pyramid(coords, 3)
+    n = coords.shape[0]
+    res = {"voxels": int(n), "level_rows": [int(c.shape[0]) for c in pyr.coords], "shapes": a.shapes, "warmup": a.warmup,
+           "iters": a.iters, "rounds": a.rounds, "mode": a.mode, "device": torch.cuda.get_device_name(0)}
+    feats = torch.randn(n, 3, device="cuda")
+    want = [v for v in ("fused", "unfused") if not a.only or v == a.only]
+
+    with CF.math_mode(CF.mode_id(a.mode)):
+        nets = {v: HRNetBackbone(3, 3, 2, fused=(v == "fused")).cuda().train() for v in want}
+        for v in want[1:]:
+            nets[v].load_state_dict(nets[want[0]].state_dict())
+        dy = torch.randn(n, nets[want[0]].out_channels, device="cuda")
+
+        def step_of(net):
+            def step():
+                for p in net.parameters():
+                    p.grad = None
+                net(feats, pyr).backward(dy)
+            return step
+        res["backbone_3S_train_fwd_bwd"] = compare({v: step_of(nets[v]) for v in want}, a.warmup, a.iters, a.rounds)
+        del nets
+        if not a.skip_blocks:
+            res["blocks_train_fwd_bwd"] = {}
+            for level, c in enumerate((64, 128, 256)):
+                kmap, rows = pyr.s1[level], pyr.coords[level].shape[0]
+                x = torch.randn(rows, c, device="cuda", requires_grad=True)
+                dyb = torch.randn(rows, c, device="cuda")
+                blocks = {"fused": HRBasicBlock(c, c).cuda().train(), "unfused": SparseBasicBlock(c, c).cuda().train()}
+                blocks["unfused"].load_state_dict(blocks["fused"].state_dict())
+
+                def bstep_of(blk):
+                    def step():
+                        x.grad = None
+                        for p in blk.parameters():
+                            p.grad = None
+                        blk(x, kmap).backward(dyb)
+                    return step
+                r = compare({v: bstep_of(blocks[v]) for v in want}, a.warmup, 2 * a.iters, a.rounds)
+                r["rows"] = int(rows)
+                res["blocks_train_fwd_bwd"][f"{c}_wide"] = r
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
