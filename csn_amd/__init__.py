@@ -29,3 +29,7 @@ from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseCo
 # 296-454)
 from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetSimCSN3S, HRNetSimCSN4S, VoxelPyramid,  # noqa: E402,F401
                               bn_act, build_pyramid, conv_stats, load_me_hrnet_state)
+
+# point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
+# (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))
+from .minkowski_field import PointField, batch_points  # noqa: E402,F401

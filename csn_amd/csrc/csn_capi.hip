@@ -1338,4 +1338,47 @@ int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, lo
   return csn_launch_rows_bn_act_bwd(a, (hipStream_t)stream);
 }
 
+// ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
+static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
+
+int csn_voxel_mean_f32(const float* feats, long long ld_feats, int n_points, const int* vox_ptr, const int* vox_pts, int n_voxels,
+                       int channels, float* out, long long ld_out, void* stream) {
+  if (!feats || !vox_ptr || !vox_pts || !out) return CSN_E_ARG;
+  if (n_points < 1 || n_voxels < 1 || n_voxels > n_points) return CSN_E_ARG;
+  if (channels < 1 || channels > 64) return CSN_E_DIM;
+  if (ld_feats < channels || ld_out < channels) return CSN_E_ARG;
+  if (mis4(feats) || mis4(out) || mis4(vox_ptr) || mis4(vox_pts)) return CSN_E_PTR;
+  CsnPointFieldArgs a{};
+  a.dy = feats; a.ld_dy = ld_feats; a.n_points = n_points; a.vox_ptr = vox_ptr; a.vox_pts = vox_pts; a.n_voxels = n_voxels;
+  a.C = channels; a.dz = out; a.ld_dz = ld_out;
+  return csn_launch_voxel_mean(a, (hipStream_t)stream);
+}
+
+int csn_point_interp_fwd_f32(const float* z, long long ld_z, int n_voxels, const float* coords, const int* home, const int* table,
+                             int n_points, int channels, float* y, long long ld_y, void* stream) {
+  if (!z || !coords || !home || !table || !y) return CSN_E_ARG;
+  if (n_points < 1 || n_voxels < 1) return CSN_E_ARG;
+  if (channels < 1 || channels > 1024) return CSN_E_DIM;
+  if (ld_z < channels || ld_y < channels) return CSN_E_ARG;
+  if (mis16(coords) || mis4(z) || mis4(y) || mis4(home) || mis4(table)) return CSN_E_PTR;
+  CsnPointFieldArgs a{};
+  a.z = z; a.ld_z = ld_z; a.n_voxels = n_voxels; a.coords = coords; a.home = home; a.table = table; a.n_points = n_points;
+  a.C = channels; a.y = y; a.ld_y = ld_y;
+  return csn_launch_point_interp_fwd(a, (hipStream_t)stream);
+}
+
+int csn_point_interp_bwd_f32(const float* dy, long long ld_dy, int n_points, const float* coords, const int* vox_ptr,
+                             const int* vox_pts, const int* table, int n_voxels, int channels, float* dz, long long ld_dz,
+                             void* stream) {
+  if (!dy || !coords || !vox_ptr || !vox_pts || !table || !dz) return CSN_E_ARG;
+  if (n_points < 1 || n_voxels < 1) return CSN_E_ARG;
+  if (channels < 1 || channels > 1024) return CSN_E_DIM;
+  if (ld_dy < channels || ld_dz < channels) return CSN_E_ARG;
+  if (mis16(coords) || mis4(dy) || mis4(dz) || mis4(vox_ptr) || mis4(vox_pts) || mis4(table)) return CSN_E_PTR;
+  CsnPointFieldArgs a{};
+  a.dy = dy; a.ld_dy = ld_dy; a.n_points = n_points; a.coords = coords; a.vox_ptr = vox_ptr; a.vox_pts = vox_pts; a.table = table;
+  a.n_voxels = n_voxels; a.C = channels; a.dz = dz; a.ld_dz = ld_dz;
+  return csn_launch_point_interp_bwd(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -327,3 +327,19 @@ int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C,
 long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms);
 int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, hipStream_t st);
 int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, hipStream_t st);
+
+// ---- point fields: voxel means, trilinear interpolation onto points and its adjoint (point_field.hip) ----
+struct CsnPointFieldArgs {
+  const float* coords;                                            // [n_points][4] = [b, x, y, z] in voxel units, 16-byte aligned
+  const int* home;                                                // [n_points] the voxel row of floor(xyz)
+  const int* vox_ptr;  const int* vox_pts;                        // the points of every voxel as a CSR: [n_voxels + 1], [n_points]
+  const int* table;                                               // [27][n_voxels]: the kernel-3 stride-1 map, -1 = no voxel
+  int n_points, n_voxels, C;
+  const float* z;  long long ld_z;                                // forward: the voxel map, read
+  float* y;  long long ld_y;                                      // forward: the point map, written
+  const float* dy;  long long ld_dy;                              // backward: read (voxel_mean: the point features)
+  float* dz;  long long ld_dz;                                    // backward: written (voxel_mean: the means)
+};
+int csn_launch_voxel_mean(const CsnPointFieldArgs& a, hipStream_t st);
+int csn_launch_point_interp_fwd(const CsnPointFieldArgs& a, hipStream_t st);
+int csn_launch_point_interp_bwd(const CsnPointFieldArgs& a, hipStream_t st);

@@ -709,6 +709,38 @@ CSN_API int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const floa
                             int n_terms, int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr,
                             void* ws, long long ws_bytes, void* stream);
 
+/* ---- (16) point fields: voxelised features, interpolation of a voxel map onto points and its adjoint (MinkowskiNet/lib/
+ *           trainer_csn.py:236-260 ME.TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field)) ----------------
+ * The reference's loss and metrics live on POINTS: a batch's points are quantised to voxels, the network runs on the voxel rows
+ * and its logits are interpolated back.  csn_amd.minkowski_field.PointField builds the index arrays (plumbing); the three entry
+ * points below are the arithmetic.  Everything is POINT-MAJOR fp32 in every math mode (there is no matrix product here):
+ *   coords[n_points][4] = [b, x, y, z] in voxel units (contiguous, 16-byte aligned: CSN_E_PTR);
+ *   home[n_points] int32: the voxel row of [b, floor(x), floor(y), floor(z)];
+ *   vox_ptr[n_voxels + 1], vox_pts[n_points] int32: the points of every voxel as a CSR, ascending inside a voxel;
+ *   table[27][n_voxels] int32: the kernel-3 stride-1 map of (14) on the voxel set (-1: no voxel) — the row of v + c is
+ *   table[13 + cx + 3 cy + 9 cz][v], the row of v - c is table[13 - cx - 3 cy - 9 cz][v], c in {0, 1}^3;
+ *   z[n_voxels][ld_z], y[n_points][ld_y], dy[n_points][ld_dy], dz[n_voxels][ld_dz], feats[n_points][ld_feats], out[n_voxels][ld_out].
+ * Any pitch >= its width; columns of a row beyond the width are neither read nor written.  16-byte accesses where both maps of a
+ * call are 16-byte aligned and both pitches % 4 == 0 (a width % 4 != 0 then ends in a scalar tail), one element per access
+ * otherwise.  Host-side checks before any launch: a NULL pointer, n_points < 1, n_voxels < 1 or a pitch below its width:
+ * CSN_E_ARG; channels outside [1, 1024] ([1, 64] for the mean): CSN_E_DIM; a map or index array off 4 bytes: CSN_E_PTR.
+ * An index outside its array is never dereferenced: it reads as "no voxel" / is skipped (its contribution is the caller's error).
+ * (16a) csn_voxel_mean_f32: out[v] = (sum_{p in voxel v, ascending} feats[p]) / count   (n_voxels <= n_points).
+ * (16b) csn_point_interp_fwd_f32: t = xyz - floor(xyz) (the fp32 difference) and
+ *   y[p] = sum_{c in {0,1}^3} w_c(p) z[row(home[p] + c)],  w_c = ((cx ? tx : 1 - tx) (cy ? ty : 1 - ty)) (cz ? tz : 1 - tz),
+ *   added in the order c = cx + 2 cy + 4 cz = 0 .. 7.  A corner with no voxel contributes nothing; the weights are NOT renormalised.
+ * (16c) csn_point_interp_bwd_f32: the exact adjoint dz[v] = sum_c sum_{p : home[p] = v - c} w_c(p) dy[p], output-stationary over
+ *   the voxel rows: per voxel the corners in the order c = 0 .. 7, per corner the points of row(v - c) in CSR order.  EVERY dz row
+ *   is written.  No floating-point atomics: two identical calls give the same bits.  One voxel's sum is serial in its G lanes: a
+ *   voxel with thousands of points paces its wave (correct for any list length). */
+CSN_API int csn_voxel_mean_f32(const float* feats, long long ld_feats, int n_points, const int* vox_ptr, const int* vox_pts,
+                       int n_voxels, int channels, float* out, long long ld_out, void* stream);
+CSN_API int csn_point_interp_fwd_f32(const float* z, long long ld_z, int n_voxels, const float* coords, const int* home,
+                             const int* table, int n_points, int channels, float* y, long long ld_y, void* stream);
+CSN_API int csn_point_interp_bwd_f32(const float* dy, long long ld_dy, int n_points, const float* coords, const int* vox_ptr,
+                             const int* vox_pts, const int* table, int n_voxels, int channels, float* dz, long long ld_dz,
+                             void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
