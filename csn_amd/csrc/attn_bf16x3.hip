@@ -79,10 +79,14 @@ constexpr bool csn_attn_x3fwd96(int npl, int dt, bool bwd) { return npl == 2 && 
 constexpr int csn_attn_waves(int npl, int dt, bool bwd, bool rc_f32 = false) {
   return (!rc_f32 && ((npl == 1 ? dt <= 3 : dt <= 2) || csn_attn_x3fwd96(npl, dt, bwd))) ? 4 : 2;
 }
-template <typename PR, int DT, bool BWD, bool KVP, bool RC = false>
+// NOP (kept scores, two planes, sc_tiles == 2): the dS planes leave as with sc_tiles == 1, but P is neither split nor stored —
+// the scores stay as the forward wrote them, for the dV kernel that rebuilds P from them (attn_dv_scores.hip).  A compile-time
+// property: the split and the two plane stores are gone from the instance, not branched around in every tile.
+template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, bool NOP = false>
 __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
   static_assert(PR::NT == 3 || KVP, "single-product modes take K / V as tile planes");
   static_assert(!RC || BWD, "score recomputation: backward kernel");
+  static_assert(!NOP || (BWD && KVP && !RC && PR::NPL == 2), "no P planes: the kept-scores backward in two planes");
   constexpr int NPL = PR::NPL;                          // planes: hi (+ lo)
   constexpr int D = 32 * DT;
   constexpr int UPR = KVP ? 4 * NPL : 8;                // 16-byte pieces per tile row (tile planes: 4 per plane; fp32: 8)
@@ -609,10 +613,12 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
       // P and dS leave as tile planes, per query row 16 tiles of [hi: 32 keys | lo: 32 keys] — the k-major operand
       // the dV / dK products stage without conversion work; keys beyond the block end are written as zeros.
       s16x8 qh, ql;
+      if constexpr (!NOP) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        qh[r] = to16<PR::HALF>(sv[r]);
-        ql[r] = PR::NT == 3 ? to16<PR::HALF>(sv[r] - from16<PR::HALF>(qh[r])) : qh[r];
+        for (int r = 0; r < 8; ++r) {
+          qh[r] = to16<PR::HALF>(sv[r]);
+          ql[r] = PR::NT == 3 ? to16<PR::HALF>(sv[r] - from16<PR::HALF>(qh[r])) : qh[r];
+        }
       }
       if constexpr (NPL == 2) {
         // two planes: a row of 16 tiles is exactly the bytes of the fp32 score row — P overwrites the scores of this tile
@@ -620,8 +626,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
         const unsigned tv = !q_ok ? CSN_OOB
                             : tile_major ? (unsigned)(kt * Tq + qrow) * 128u + (unsigned)(16 * kq)
                                          : (unsigned)(qrow * Tp) * 4u + (unsigned)(kt * 128 + 16 * kq);
-        csn_bstore4_stream(__builtin_bit_cast(f32x4, qh), Sr, tv);
-        csn_bstore4_stream(__builtin_bit_cast(f32x4, ql), Sr, tv, 64u);
+        if constexpr (!NOP) {
+          csn_bstore4_stream(__builtin_bit_cast(f32x4, qh), Sr, tv);
+          csn_bstore4_stream(__builtin_bit_cast(f32x4, ql), Sr, tv, 64u);
+        }
         csn_bstore4_stream(__builtin_bit_cast(f32x4, ph), dSr, tv);
         csn_bstore4_stream(__builtin_bit_cast(f32x4, pl), dSr, tv, 64u);
       } else {
@@ -750,6 +758,10 @@ int launch_dt(const CsnAttnArgs& a, bool bwd, hipStream_t st) {
           if constexpr (csn_attn_recompute_fits(PR::NPL, DT))
             hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, true>), grid, dim3(512), 0, st, a);
           else return -1;
+        } else if (a.sc_tiles == 2) {                               // kept scores, dS planes only (the instance that is built)
+          if constexpr (csn_attn_dv_scores_fits(PR::NT == 3 ? 1 : 2, 32 * DT))
+            hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, true>), grid, dim3(512), 0, st, a);
+          else return -1;
         } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true>), grid, dim3(512), 0, st, a);
       } else return -1;                                             // fp16: forward only (gradients underflow fp16)
     } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, false, true>), grid, dim3(512), 0, st, a);
@@ -776,6 +788,7 @@ int launch_any(const CsnAttnArgs& a, int d, bool bwd, hipStream_t st) {
   if (a.sc_layout && (PR::NPL != 2 || !a.kv_planes || a.Tq > 0 || a.tq_arr || a.t_arr || a.Tp < (a.T + 31) / 32 * 32 || (bwd && !a.sc_tiles)))
     return -1;                                                      // tile-major scores: block mode, two planes, tile-plane K / V
   if (a.q2 && (!bwd || (a.q2_shape_stride & 3))) return -1;
+  if (a.sc_tiles == 2 && (!bwd || !a.kv_planes || a.q2 || a.Tq > 0 || a.tq_arr || a.t_arr)) return -1;   // block mode, kept scores
   if (a.q2 && !a.kv_planes && (a.sc_tiles || a.grp_off)) return -1;     // fp32 K / V maps: nothing score-sized leaves, one evaluation per launch unit
   if ((a.r_fmt || a.ctx_fmt || a.q2_fmt || a.out_fmt) && (PR::NPL != 1 || !a.kv_planes)) return -1;   // 16-bit maps: single-product modes
   if (a.out_fmt && a.accumulate) return -1;

@@ -384,6 +384,11 @@ static int attn_bwd_dq_impl(const float* dctx, const float* ctx, long long ctx_e
   if (group_offsets && (n_groups <= 0 || !eval_ids || !(csn_attn_bwd_grouping(d_head, block) & 1))) return CSN_E_ARG;
   if ((block & 3) && (block_q == 0 || kv_split)) return CSN_E_ALIGN;
   if (probs_tiles && (mode() == 0 || score_pitch < (block + 31) / 32 * 32)) return CSN_E_ARG;
+  // probs_tiles == 2: dS planes only, the scores stay untouched (kept scores, where the dV-from-scores kernel exists)
+  if (probs_tiles < 0 || probs_tiles > 2) return CSN_E_ARG;
+  if (probs_tiles == 2 && (q || !kv_split || block_q != 0 || tq_arr || t_arr || act16() ||
+                           !csn_attn_bwd_dv_scores_available(d_head, block)))
+    return CSN_E_ARG;
   if (dropout_p < 0.f || dropout_p >= 1.f) return CSN_E_ARG;
   if (dctx_split) return CSN_E_ARG;                                  // reserved (see header)
   if (kv_split && mode() == 0) return CSN_E_ARG;
@@ -491,8 +496,10 @@ static int attn_bwd_dkv_impl(const float* dctx, long long ctx_eval_stride, const
   if (mode() == 3 || (mode() == 2 && !probs_tiles)) return CSN_E_ARG;
   if (dctx_split || q_split) return CSN_E_ARG;                       // reserved (see header)
   if (group_offsets && (n_groups <= 0 || !eval_ids || !(csn_attn_bwd_grouping(d_head, block) & 2))) return CSN_E_ARG;
-  if (!dctx || !q || !dscores || !dk || !dv) return CSN_E_ARG;
-  if (!probs && !(probs_tiles && mode() == 2)) return CSN_E_ARG;       // (one plane: P and dS are both read from dscores)
+  // probs == NULL && dv == NULL: dK alone (the dV product is somebody else's: csn_block_attn_bwd_dv_scores_f32)
+  const bool dk_only = !probs && !dv;
+  if (!dctx || !q || !dscores || !dk || (!dv && !dk_only)) return CSN_E_ARG;
+  if (!probs && !dk_only && !(probs_tiles && mode() == 2)) return CSN_E_ARG;   // (one plane: P and dS are both read from dscores)
   if (n_launch_evals <= 0 || n_heads <= 0 || block <= 0 || n_blocks <= 0) return CSN_E_ARG;
   if (!dim_ok(d_head)) return CSN_E_DIM;
   if ((ld & 3) || (score_pitch & 3) || score_pitch < bk4) return CSN_E_ALIGN;
@@ -533,7 +540,7 @@ static int attn_bwd_dkv_impl(const float* dctx, long long ctx_eval_stride, const
   if (g16 && accumulate) return CSN_E_ARG;                            // a 16-bit gradient map is written once (grouped calls)
   g.C = operand(dv, block, (long long)d_head * lk, dkv_slot_stride, dv_index, lk);
   if (g16) g.C.planes = 1;
-  rc = launch_gemm(g, 0, n_blocks * n_heads * n_batch, st);
+  if (!dk_only) rc = launch_gemm(g, 0, n_blocks * n_heads * n_batch, st);
   if (rc) return rc;
   g.A = operand(q, bq, (long long)d_head * ld, q_shape_stride, q_index, ld);
   g.A.planes = q_split; g.A.plane_stride = q_plane_stride;
@@ -565,6 +572,39 @@ int csn_attn_bwd_grouping(int d_head, int block) {
   const bool flash = recompute && csn_attn_dkv_flash_fits(d_head / 32);
   const bool tm = mode() == 1 && tiles_ok && csn_gemm_tile_major_planes(d_head, (block + 3) / 4 * 4);
   return 1 | (csn_gemm_bf16x3_big_tiles(d_head, (block + 3) / 4 * 4) ? 2 : 0) | (recompute ? 4 : 0) | (flash ? 8 : 0) | (tm ? 16 : 0);
+}
+
+int csn_attn_bwd_dv_scores_available(int d_head, int block) {
+  return block > 0 && block <= 512 && !(block & 3) && csn_attn_dv_scores_fits(mode(), d_head);
+}
+
+int csn_block_attn_bwd_dv_scores_f32(const float* dctx, long long ctx_eval_stride, int ld, const float* scores, const float* lse,
+                                     float* dv, long long dkv_slot_stride, const int* dv_index, const int* eval_ids,
+                                     int n_launch_evals, int n_heads, int d_head, int block, int n_blocks, int score_pitch,
+                                     float dropout_p, unsigned long long seed, const int* group_offsets, int n_groups,
+                                     void* stream) {
+  if (!dctx || !scores || !lse || !dv) return CSN_E_ARG;
+  if (n_launch_evals <= 0 || n_heads <= 0 || block <= 0 || n_blocks <= 0) return CSN_E_ARG;
+  if (!dim_ok(d_head)) return CSN_E_DIM;
+  if (!csn_attn_bwd_dv_scores_available(d_head, block)) return CSN_E_ARG;
+  if (group_offsets && (n_groups <= 0 || !eval_ids)) return CSN_E_ARG;
+  if (dropout_p < 0.f || dropout_p >= 1.f) return CSN_E_ARG;
+  if (act16()) return CSN_E_ARG;                                      // fp32 scores, fp32 maps
+  if (t_score_layout && (!(csn_attn_bwd_grouping(d_head, block) & 16) || score_pitch < (block + 31) / 32 * 32)) return CSN_E_ARG;
+  const int t_last = last_block_points(block, n_blocks, ld, 0);
+  if (t_last < 0) return t_last;
+  if ((ld & 3) || (score_pitch & 3) || score_pitch < block) return CSN_E_ALIGN;
+  if (mis16(dctx) || mis16(scores) || mis16(dv)) return CSN_E_PTR;
+  if ((ctx_eval_stride & 3) || (dkv_slot_stride & 3)) return CSN_E_STRIDE;
+  CsnAttnDvArgs a;
+  a.dctx = dctx; a.ctx_eval_stride = ctx_eval_stride;
+  a.scores = scores; a.lse = lse;
+  a.dv = dv; a.dkv_slot_stride = dkv_slot_stride; a.dv_index = dv_index;
+  a.eval_ids = eval_ids; a.grp_off = group_offsets; a.n_groups = group_offsets ? n_groups : n_launch_evals;
+  a.ld = ld; a.H = n_heads; a.T = block; a.Tp = score_pitch; a.n_blocks = n_blocks; a.T_last = t_last;
+  a.dropout_p = dropout_p; a.seed = seed;
+  a.sc_layout = t_score_layout != 0;
+  return csn_launch_attn_dv_scores(a, d_head, mode(), (hipStream_t)stream);
 }
 
 int csn_block_attn_bwd_dkv_flash_f32(const float* dctx, long long ctx_eval_stride, const float* q, long long q_shape_stride,

@@ -137,6 +137,20 @@ struct CsnAttnDkvArgs {
 int csn_launch_attn_dkv_flash(const CsnAttnDkvArgs& a, int d, int mode, hipStream_t st);
 constexpr bool csn_attn_dkv_flash_fits(int dt) { return dt <= 4; }         // K^T, V^T, dK^T, dV^T of 16 keys in one wave's registers
 
+// ---- dV from the kept scores (attn_dv_scores.hip; math mode 1, block mode, d = 256) ----------------------------------
+struct CsnAttnDvArgs {
+  const float* dctx;  long long ctx_eval_stride;                          // dO^T [evaluation][H*d][ld]
+  const float* scores;                                                    // the forward's S [evaluation][H][blk][T][Tp] (row- or tile-major), untouched
+  const float* lse;                                                       // [evaluation][H][n_blocks * T]
+  float* dv;  long long dkv_slot_stride;  const int* dv_index;            // fp32 gradient maps [slot][..][ld], evaluation -> slot
+  const int* eval_ids;  const int* grp_off;  int n_groups;                // group g = eval_ids[grp_off[g] .. grp_off[g+1]); no offsets: one evaluation each
+  int ld, H, T, Tp, n_blocks, T_last;
+  float dropout_p;  unsigned long long seed;
+  int sc_layout = 0;                                                      // 1: tile-major scores (CsnAttnArgs::sc_layout), Tp >= round-up-32(T)
+};
+int csn_launch_attn_dv_scores(const CsnAttnDvArgs& a, int d, int mode, hipStream_t st);
+constexpr bool csn_attn_dv_scores_fits(int mode, int d) { return mode == 1 && d == 256; }   // the instance that is built
+
 int csn_launch_attn_fwd_f32(const CsnAttnArgs& a, int d, hipStream_t st);
 int csn_launch_attn_bwd_f32(const CsnAttnArgs& a, int d, hipStream_t st);
 int csn_launch_attn_fwd_bf16x3(const CsnAttnArgs& a, int d, int mode, hipStream_t st);     // attn_bf16x3.hip; mode 1..3 (2, 3: tile-plane K/V only)

@@ -656,6 +656,10 @@ class _MHAEvals(torch.autograd.Function):
             v_ptr = q_ptr + 4 * (2 * D * NP + plan.v_shift * kv_stride)
         grouping = L.csn_attn_bwd_grouping(d, T)
         tune = ctx.tune                                              # the forward's snapshot
+        # kept scores in two planes, both grouped calls (either score layout): dV from the scores, dK alone on the plane product
+        dv_scores = bool(tune.dv_from_scores and flow == tuning.KEEP_SCORES and ctx.mode == 1 and pt == 1 and kv_flag == 1
+                         and not a16 and not ctx.g16 and tune.grouped_dq and tune.grouped_dkv and (grouping & 3) == 3
+                         and L.csn_attn_bwd_dv_scores_available(d, T))
         if flow != tuning.KEEP_SCORES:
             # one grouped call, scores rebuilt from the pre-scaled queries of the evaluation's query slot
             _lib.check(L.csn_block_attn_bwd_dq_recompute_f32(_ptr(datt), _ptr(att), D * NP, q_ptr, q_stride, _ptr(plan.q_slots),
@@ -667,11 +671,13 @@ class _MHAEvals(torch.autograd.Function):
                        "csn_block_attn_bwd_dq_recompute_f32")
         elif tune.grouped_dq and (grouping & 1):
             # one call: the evaluations of a query slot run one after the other into the same dQ accumulators
+            # (dV from the scores: the call leaves the dS planes only and the scores as the forward wrote them)
             _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, k_ptr, v_ptr, kv_stride,
                                                    _ptr(plan.kv_slots), NP, _ptr(scores), _ptr(dscores), _ptr(lse),
                                                    _ptr(delta), gbase, slot_stride, _ptr(plan.q_slots), 0,
                                                    _ptr(plan.q_group_items), E, H, d, T, nb, Tp, p_attn, seed_attn, 0, 0,
-                                                   kv_flag + kv_f16, kv_pitch, pt, _ptr(plan.q_group_off), plan.n_q_groups, _stream()),
+                                                   kv_flag + kv_f16, kv_pitch, 2 if dv_scores else pt, _ptr(plan.q_group_off),
+                                                   plan.n_q_groups, _stream()),
                        "csn_block_attn_bwd_dq_f32")
         else:
             for ci, ids in enumerate(plan.dq_colors):
@@ -691,6 +697,18 @@ class _MHAEvals(torch.autograd.Function):
                                                           _ptr(plan.kv_slots), _ptr(plan.v_slots), 0, _ptr(plan.kv_group_items),
                                                           E, H, d, T, nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off),
                                                           plan.n_kv_groups, _stream()), "csn_block_attn_bwd_dkv_flash_f32")
+        elif dv_scores:
+            # dV: key-stationary, P rebuilt from the untouched scores; then the grouped plane product for dK alone
+            _lib.check(L.csn_block_attn_bwd_dv_scores_f32(_ptr(datt), D * NP, NP, _ptr(scores), _ptr(lse), gbase + 2 * ges * D * NP,
+                                                          slot_stride, _ptr(plan.v_slots), _ptr(plan.kv_group_items), E, H, d, T,
+                                                          nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off), plan.n_kv_groups,
+                                                          _stream()), "csn_block_attn_bwd_dv_scores_f32")
+            _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), NP,
+                                                    None, _ptr(dscores), gbase + ges * D * NP, None,
+                                                    slot_stride, _ptr(plan.kv_slots), None, 0,
+                                                    _ptr(plan.kv_group_items), E, H, d, T, nb, Tp, 0, 0, 0, 0, pt,
+                                                    _ptr(plan.kv_group_off), plan.n_kv_groups, _stream()),
+                       "csn_block_attn_bwd_dkv_f32")
         elif tune.grouped_dkv and (grouping & 2):
             # one call: the evaluations of a key/value slot are contracted one after the other into the same accumulators
             _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), NP,

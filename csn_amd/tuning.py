@@ -43,6 +43,11 @@ class Tuning:
     # faster: the launch alone 1.96 ms against 0.54 + 1.06 + launch gap = 1.78 for the two calls, the config-3 step 26.95 against
     # 26.99 ms (profiles/r4t_qkv_one_pass.txt).  Off; kept as the measured form (tests/test_gpu_wx.py holds it bit for bit)
     qkv_one_pass: bool = False
+    # bf16x3 at d = 256, kept scores, grouped dQ and dK / dV: the dQ kernel leaves the scores untouched (no P planes written over
+    # them), a key-stationary kernel forms dV from the scores (csn_block_attn_bwd_dv_scores_f32) and the plane product runs for dK
+    # alone — the dQ launch writes 5.2 GB less per config-3 step (the dV kernel reads S where the product read P).  dQ and dK keep their bits; dV is the same three products summed in another
+    # order.  Taken in either score layout where csn_attn_bwd_dv_scores_available says so; the default is what profiles/dv_scores_ab_step.txt measured
+    dv_from_scores: bool = True
     # attention backward data flow by (math mode of the backward: 1 bf16x3, 2 bf16 — fp16 forwards run their backward in 2;
     # head width), or by mode alone; taken where the kernels have an instance for it (csn_attn_bwd_grouping bits 2 / 3),
     # KEEP_SCORES otherwise.  Measured per mode and width, DESIGN.md §4 "data flow A/B": at d = 256 the extra matrix products

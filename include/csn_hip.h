@@ -200,12 +200,21 @@ CSN_API int csn_block_attn_fwd_grouped_f32(const float* q, const float* k, const
  * block) region of block * score_pitch floats: [P: block rows | dS: block rows] of pitch score_pitch bf16 elements — and
  * `scores` is left untouched; the dkv call reads both from its `dscores` argument (`probs` is ignored).  Mode 2 REQUIRES
  * kv_split and probs_tiles.
+ * probs_tiles == 2 (csn_block_attn_bwd_dq_f32 only; mode 1, kv_split, either score layout, where
+ * csn_attn_bwd_dv_scores_available says so): the dq call leaves the dS planes in `dscores` as with probs_tiles = 1 and does NOT touch `scores` — P is neither split
+ * nor stored; dq, delta and the dS planes are bit for bit those of probs_tiles = 1.  dV then comes from
+ * csn_block_attn_bwd_dv_scores_f32 (below), which rebuilds P from the untouched scores, and dK from a
+ * csn_block_attn_bwd_dkv_f32 call with probs = NULL and dv = NULL (probs_tiles = 1): that call runs the dK product alone and
+ * writes the bits the two-product call writes.  probs_tiles takes the values 0, 1 and 2; anything else is CSN_E_ARG.
  * GROUPED calls (group_offsets != NULL): eval_ids lists the n_launch_evals evaluations ordered so that evaluations sharing
  * an output slot are adjacent, group g = entries group_offsets[g] .. group_offsets[g+1] (n_groups + 1 offsets); a group's
  * results are accumulated in registers and its slot is written once — one call for all evaluations instead of one
  * read-modify-write pass per colour.  csn_attn_bwd_grouping() says where that is available in the current math mode:
  * bit 0 = the dq call, bit 1 = the dkv call, bit 2 = csn_block_attn_bwd_dq_recompute_f32, bit 3 =
  * csn_block_attn_bwd_dkv_flash_f32 (both below), bit 4 = tile-major score storage (csn_set_thread_score_layout).
+ * csn_attn_bwd_dv_scores_available() != 0: csn_block_attn_bwd_dv_scores_f32 and probs_tiles = 2 of the dq call have an instance
+ * in the current math mode (mode 1, d_head = 256, block <= 512 and % 4 == 0) — a query of its own, so that the bits above keep
+ * their values.
  *
  * csn_block_attn_bwd_dq_recompute_f32 — the dq call WITHOUT saved scores ("flash" data flow; math modes 1 and 2, K / V as tile
  * planes, block mode): the forward is run with scores = NULL (only lse is kept) and this call rebuilds S = Qs K^T tile by tile
@@ -265,6 +274,21 @@ CSN_API int csn_block_attn_bwd_dkv_flash_f32(const float* dctx, long long ctx_ev
                                      int n_launch_evals, int n_heads, int d_head, int block, int n_blocks, int score_pitch,
                                      float dropout_p, unsigned long long seed, const int* group_offsets, int n_groups,
                                      void* stream);
+
+/* csn_block_attn_bwd_dv_scores_f32 — dV from the KEPT scores (where csn_attn_bwd_dv_scores_available != 0): per (value slot, head, block,
+ * 128 keys) a work-group streams the forward's scores [evaluation][head][block][block][score_pitch] (fp32, in the thread's score layout, as the
+ * forward wrote them — run the dq call with probs_tiles = 2), lse and dctx of every evaluation of its group, rebuilds
+ * P_drop = exp(S - lse) mask / (1 - dropout_p) in registers with the mask of (dropout_p, seed), and writes
+ *   dv[dv_index[e]] = P_drop^T dctx
+ * once per group (no accumulate: every listed evaluation belongs to exactly one group; without group_offsets every listed
+ * evaluation is its own group).  Geometry as csn_block_attn_bwd_dkv_f32 in block mode: block % 4 == 0, score_pitch >= block,
+ * a row may end inside the last block (n_blocks * block > ld). */
+CSN_API int csn_attn_bwd_dv_scores_available(int d_head, int block);
+CSN_API int csn_block_attn_bwd_dv_scores_f32(const float* dctx, long long ctx_eval_stride, int ld, const float* scores,
+                                     const float* lse, float* dv, long long dkv_slot_stride, const int* dv_index,
+                                     const int* eval_ids, int n_launch_evals, int n_heads, int d_head, int block, int n_blocks,
+                                     int score_pitch, float dropout_p, unsigned long long seed, const int* group_offsets,
+                                     int n_groups, void* stream);
 
 /* ---- (3b) cross-length attention: one unchunked block per evaluation, n_queries != n_keys -------------
  * The MinkowskiNet variant of the layer (MinkowskiNet/models/attention.py:31-75, used per shape pair by

@@ -20,7 +20,9 @@ CONFIGS = {2: dict(B=4, K=2, N=10000, C=256, nb=20), 3: dict(B=32, K=3, N=10000,
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", type=int, default=3)
 ap.add_argument("--math", default="bf16x3")
-ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--rounds", type=int, default=3, help="alternations: every variant runs once per round")
+ap.add_argument("--steps", type=int, default=5, help="timed steps per variant and round (their median is the round's number)")
+ap.add_argument("--warmup", type=int, default=2, help="untimed steps per variant and round, before the timed ones")
 ap.add_argument("--variants", default="tiled:3=0;streaming:3=1", help="name:key=value,key=value;name:...")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -60,17 +62,17 @@ for r in range(a.rounds):
             L.csn_dev_set(k, v)
         for k, v in kvs:
             L.csn_dev_set(k, v)
-        for _ in range(2):
+        for _ in range(max(1, a.warmup)):
             losses[name] = step()
         grads[name] = [p.grad.clone() for p in model.parameters() if p.grad is not None]
         torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-        for i in range(5):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        for i in range(a.steps):
             ev[i].record()
             step()
-        ev[5].record()
+        ev[a.steps].record()
         torch.cuda.synchronize()
-        res[name].append(float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(5)])))
+        res[name].append(float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)])))
 for k, v in defaults.items():
     L.csn_dev_set(k, v)
 first = variants[0][0]

@@ -20,7 +20,7 @@ def main():
         m = re.match(r"(csn_attn_\w+)<([^>]*?)(?:>\S*)?\s+(FETCH_SIZE|WRITE_SIZE)\s+n=\s*\d+\s+mean=\s*([0-9.]+)", line)
         if m:
             args = [a.strip() for a in m.group(2).split(",")]          # attention: <mode, DT, BWD, KVP[, RC]> (names may be cut short)
-            which = "dkv" if m.group(1) == "csn_attn_dkv_kernel" else ("bwd" if len(args) > 2 and args[2] == "true" else "fwd")
+            which = "dkv" if m.group(1) == "csn_attn_dkv_kernel" else "dv" if m.group(1) == "csn_attn_dv_scores_kernel" else ("bwd" if len(args) > 2 and args[2] == "true" else "fwd")
             vals.setdefault(which, {})[m.group(3)] = float(m.group(4))
     names = {}
     if len(sys.argv) > 5:
@@ -32,7 +32,7 @@ def main():
             if not m:
                 continue
             args = [a.strip() for a in m.group(2).split(",")]
-            which = "dkv" if m.group(1) == "csn_attn_dkv_kernel" else ("bwd" if len(args) > 2 and args[2] == "true" else "fwd")
+            which = "dkv" if m.group(1) == "csn_attn_dkv_kernel" else "dv" if m.group(1) == "csn_attn_dv_scores_kernel" else ("bwd" if len(args) > 2 and args[2] == "true" else "fwd")
             if which not in names or float(row["TotalDurationNs"]) > names[which][2]:
                 names[which] = (nm, float(row["AverageNs"]) * 1e-6, float(row["TotalDurationNs"]), stats_label)
     out_path = os.path.join(ROOT, "profiles", "attn_hbm_traffic.json")
