@@ -299,6 +299,10 @@ struct CsnRowsFcArgs {
 long long csn_rows_fc_ws_bytes(long long n_rows, int c_in, int c_out, int training, int backward);
 int csn_launch_rows_fc_fwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);
 int csn_launch_rows_fc_bwd(const CsnRowsFcArgs& a, int mode, hipStream_t st);
+// fp64 column sums of [n_rows][C] rows in a fixed order (the bias gradients): part[chunk][C] of 64-row chunks (four waves each
+// taking every fourth row, added in wave order), then the chunks in 32 segments added in segment order; C % 32 == 0
+int csn_launch_rows_colsum(const float* x, int ldx, long long n_rows, int C, double* part, hipStream_t st);
+int csn_launch_rows_colsum_merge(const double* part, int n_chunks, int C, float* out, hipStream_t st);
 
 // ---- sparse 3D convolution on voxel rows over a kernel map (sparse_conv.hip) ----
 struct CsnSparseConvArgs {

@@ -12,11 +12,13 @@
 //                       fixed tree): dbeta_m = sum g' (the same for every term), dgamma_m = sum g' xhat_m, the means of the dz formula.
 //   rows_bn_act_bwd<2>  dz_m = gamma_m s_m (g' - mean g' - xhat_m mean(g' xhat_m)) (training) or g' gamma_m s_m (eval).
 //   bn_stats_merge      (15a) the (mean, M2) pairs that the convolution's epilogue leaves per 32-row tile, merged by Chan's formula in
-//                       fp64 in a fixed order: mean, invstd, running statistics.
+//                       fp64 in a fixed order: mean, invstd, running statistics (the merge, the tile walk and the finish are
+//                       rows_mma.h's, shared with rows_fc_stats; the segment count and the tree are this kernel's).
 // No floating-point atomics anywhere: every reduction has a fixed order, two calls give the same bits.
-#include "csn_kernels.h"
+#include "rows_mma.h"
 
 namespace {
+using namespace rows_mma;
 
 constexpr int MAXT = 3;
 
@@ -169,15 +171,6 @@ __global__ __launch_bounds__(256) void rows_bn_act_bwd_kernel(const BnActP p) {
   }
 }
 
-// Chan's merge of (n, mean, M2) pairs
-__device__ __forceinline__ void chan_merge(double& n, double& mu, double& m2, double nb, double mb, double qb) {
-  if (nb <= 0.0) return;
-  const double nn = n + nb, d = mb - mu;
-  mu += d * (nb / nn);
-  m2 += qb + d * d * (n * nb / nn);
-  n = nn;
-}
-
 // The tiles' (mean, M2) of a convolution's statistics epilogue -> mean, invstd, running statistics: 16 columns x 64 segments of the
 // tile list per work-group; a thread merges its segment's tiles in tile order, the segments are merged pairwise in a fixed tree
 // (neighbours first, the lower tiles on the left).
@@ -191,23 +184,14 @@ __global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_kernel(const floa
   const int per = (n_tiles + SSEG - 1) / SSEG;
   const int t0 = seg * per, t1 = min(n_tiles, t0 + per);
   double n = 0.0, mu = 0.0, m2 = 0.0;
-  for (int t = t0; t < t1; ++t) {
-    const long long left = (long long)n_rows - (long long)t * 32;
-    if (left <= 0) break;
-    chan_merge(n, mu, m2, left < 32 ? (double)left : 32.0, (double)part[((long long)t * 2) * C + col],
-               (double)part[((long long)t * 2 + 1) * C + col]);
-  }
+  chan_walk(n, mu, m2, part, t0, t1, n_rows, C, col);
   for (int stride = 1; stride < SSEG; stride <<= 1) {
     sh[0][seg][lc] = n; sh[1][seg][lc] = mu; sh[2][seg][lc] = m2;
     __syncthreads();
     if (seg % (2 * stride) == 0) chan_merge(n, mu, m2, sh[0][seg + stride][lc], sh[1][seg + stride][lc], sh[2][seg + stride][lc]);
     __syncthreads();
   }
-  if (seg != 0) return;
-  mean[col] = (float)mu;
-  invstd[col] = (float)(1.0 / sqrt(m2 / n + (double)eps));
-  if (rmean) rmean[col] = (float)((1.0 - (double)momentum) * (double)rmean[col] + (double)momentum * mu);
-  if (rvar) rvar[col] = (float)((1.0 - (double)momentum) * (double)rvar[col] + (double)momentum * (m2 / (n - 1.0)));
+  if (seg == 0) bn_finish(n, mu, m2, col, eps, momentum, mean, invstd, rmean, rvar);
 }
 
 struct BnSumsP {
@@ -241,8 +225,6 @@ __global__ __launch_bounds__(SCOLS * SSEG) void rows_bn_act_sums_kernel(const Bn
     if (q == 1 + m && p.dgamma[m]) p.dgamma[m][col] = (float)s;
   }
 }
-
-inline long long up256(long long b) { return (b + 255) & ~255LL; }
 
 struct WsLayout { long long part, coef, total; };
 WsLayout ws_layout(long long n_rows, int C, int M) {
