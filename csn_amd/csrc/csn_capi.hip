@@ -1421,4 +1421,33 @@ int csn_point_interp_bwd_f32(const float* dy, long long ld_dy, int n_points, con
   return csn_launch_point_interp_bwd(a, (hipStream_t)stream);
 }
 
+// ---- (17) kernel maps: packed keys, the coarser level's keys, the offset tables ----
+static bool mis8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+int csn_coord_keys_i64(const long long* coords, int n, int tensor_stride, long long* keys, int* status, void* stream) {
+  if (!coords || !keys || !status) return CSN_E_ARG;
+  if (n < 1 || tensor_stride < 1) return CSN_E_ARG;
+  if (mis8(coords) || mis8(keys) || mis4(status)) return CSN_E_PTR;
+  return csn_launch_coord_keys(coords, n, tensor_stride, keys, status, (hipStream_t)stream);
+}
+
+int csn_coord_down_i64(const long long* keys, int n, int out_tensor_stride, long long* down_keys, void* stream) {
+  if (!keys || !down_keys) return CSN_E_ARG;
+  if (n < 1 || out_tensor_stride < 1) return CSN_E_ARG;
+  if (mis8(keys) || mis8(down_keys)) return CSN_E_PTR;
+  return csn_launch_coord_down(keys, n, out_tensor_stride, down_keys, (hipStream_t)stream);
+}
+
+int csn_kernel_map_i32(const long long* set_keys, const int* set_rows, int n_set, const long long* query_keys, int n_query,
+                       int kernel_size, int step, int* table, int* status, void* stream) {
+  if (!set_keys || !query_keys || !table || !status) return CSN_E_ARG;
+  if (n_set < 1 || n_query < 1 || step == 0) return CSN_E_ARG;
+  if (kernel_size != 1 && kernel_size != 3 && kernel_size != 5) return CSN_E_DIM;
+  if (mis8(set_keys) || mis8(query_keys) || mis4(table) || mis4(status) || (set_rows && mis4(set_rows))) return CSN_E_PTR;
+  CsnKernelMapArgs a{};
+  a.set_keys = set_keys; a.set_rows = set_rows; a.n_set = n_set; a.query_keys = query_keys; a.n_query = n_query;
+  a.kernel_size = kernel_size; a.step = step; a.table = table; a.status = status;
+  return csn_launch_kernel_map(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

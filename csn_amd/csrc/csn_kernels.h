@@ -361,3 +361,16 @@ struct CsnPointFieldArgs {
 int csn_launch_voxel_mean(const CsnPointFieldArgs& a, hipStream_t st);
 int csn_launch_point_interp_fwd(const CsnPointFieldArgs& a, hipStream_t st);
 int csn_launch_point_interp_bwd(const CsnPointFieldArgs& a, hipStream_t st);
+
+// ---- kernel maps: packed coordinate keys, the coarser level's keys, the offset tables by binary search (kernel_map.hip) ----
+struct CsnKernelMapArgs {
+  const long long* set_keys;                                      // [n_set] ascending packed keys of the searched set
+  const int* set_rows;                                            // [n_set] the row of every sorted key, or NULL: the position itself
+  const long long* query_keys;                                    // [n_query] packed keys of the rows the table is indexed by
+  int n_set, n_query, kernel_size, step;                          // step: sign * offset step, non-zero
+  int* table;                                                     // [kernel_size^3][n_query], written
+  int* status;                                                    // one word, or-ed into (8: the set is not strictly ascending)
+};
+int csn_launch_coord_keys(const long long* coords, int n, int tensor_stride, long long* keys, int* status, hipStream_t st);
+int csn_launch_coord_down(const long long* keys, int n, int out_tensor_stride, long long* down_keys, hipStream_t st);
+int csn_launch_kernel_map(const CsnKernelMapArgs& a, hipStream_t st);

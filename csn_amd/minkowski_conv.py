@@ -16,8 +16,11 @@ x, y, z a multiple of the tensor stride ``ts``.  For an odd kernel size k (r = k
 Offsets never cross batch indices.  The offset numbering and the sorted output order are this project's choice (MinkowskiEngine
 cannot be imported on this platform): parity unpinned against MinkowskiEngine's own checkpoints.
 
-``build_kernel_map`` turns the coordinates into the two int32 tables the kernels read (plumbing: a sort and ``searchsorted`` in
-torch, device or CPU tensors alike).  One map serves every layer at its level: build it once per batch and pass it in.
+``build_kernel_map`` turns the coordinates into the two int32 tables the kernels read.  One map serves every layer at its level:
+build it once per batch and pass it in.  Two backends give the same integers: ``"torch"`` (the default; plumbing: a sort and
+``searchsorted`` per offset in torch, device or CPU tensors alike) and ``"hip"`` (device tensors only: the packing, the coarser keys
+and one lookup kernel per table of include/csn_hip.h section 17 around ``torch.sort`` / ``torch.unique``);
+``tuning.override(native_kernel_maps=True)`` makes ``"hip"`` what ``backend=None`` means for device tensors.
 ``sparse_conv3d`` is one autograd node on ``csn_sparse_conv_fwd_f32`` / ``csn_sparse_conv_bwd_f32`` (include/csn_hip.h section
 14); ``SparseConv3d`` / ``SparseConvTranspose3d`` hold MinkowskiEngine's ``kernel`` parameter; ``SparseBasicBlock`` is the
 residual block with the reference's attribute names (its batch norms are ``nn.BatchNorm1d`` through ATen).
@@ -33,7 +36,10 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import functional as CF
+from . import tuning
 
+_NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
+BACKENDS = ("torch", "hip")
 _B_BITS, _C_BITS = 15, 16
 _C_BIAS = 1 << (_C_BITS - 1)
 
@@ -50,9 +56,13 @@ def _unpack(keys: torch.Tensor) -> torch.Tensor:
                         (keys & m) - _C_BIAS], dim=1)
 
 
-def _check_coords(coords: torch.Tensor, ts: int, what: str) -> torch.Tensor:
+def _check_shape(coords: torch.Tensor, what: str) -> None:
     if coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] < 1 or coords.dtype.is_floating_point:
         raise ValueError(f"{what} must be a non-empty (n, 4) integer tensor [b, x, y, z]")
+
+
+def _check_coords(coords: torch.Tensor, ts: int, what: str) -> torch.Tensor:
+    _check_shape(coords, what)
     c = coords.long()
     if int(c[:, 0].min()) < 0 or int(c[:, 0].max()) >= (1 << _B_BITS):
         raise ValueError(f"{what}: batch indices must lie in [0, {1 << _B_BITS})")
@@ -137,10 +147,15 @@ class KernelMap:
 
 
 def build_kernel_map(coords: torch.Tensor, kernel_size: int = 3, stride: int = 1, tensor_stride: int = 1,
-                     out_coords: Optional[torch.Tensor] = None, transposed: bool = False) -> KernelMap:
+                     out_coords: Optional[torch.Tensor] = None, transposed: bool = False, backend: Optional[str] = None) -> KernelMap:
     """The kernel map of one convolution geometry (module docstring).  ``coords`` are the input rows' coordinates at
     ``tensor_stride``.  ``stride == 2`` generates the coarser coordinates unless ``out_coords`` gives them; ``transposed`` goes from
-    ``coords`` (coarse, at ``tensor_stride``) onto the given ``out_coords`` at ``tensor_stride // 2``."""
+    ``coords`` (coarse, at ``tensor_stride``) onto the given ``out_coords`` at ``tensor_stride // 2``.
+
+    ``backend``: ``"torch"`` builds the tables with torch ops (device or CPU tensors); ``"hip"`` with the kernels of include/csn_hip.h
+    section 17 — device tensors only (``CsnError`` otherwise), the same attributes, dtypes and integers, the same ``ValueError``
+    messages (raised after the launches: one status word is read back per call).  None takes ``"hip"`` for device tensors when
+    ``tuning.current().native_kernel_maps`` is set and ``"torch"`` otherwise; any other value raises ``ValueError``."""
     if kernel_size < 1 or kernel_size % 2 == 0:
         raise ValueError(f"kernel_size {kernel_size} is not supported: odd sizes only")
     if kernel_size not in (1, 3, 5):
@@ -155,12 +170,17 @@ def build_kernel_map(coords: torch.Tensor, kernel_size: int = 3, stride: int = 1
         raise ValueError("the transposed convolution goes onto a given coordinate set: pass out_coords (coordinates are not generated)")
     if tensor_stride < 1 or (transposed and tensor_stride % 2):
         raise ValueError(f"tensor_stride {tensor_stride} is not valid here")
-    c_in = _check_coords(coords, tensor_stride, "coords")
-    idx_in = _Index(c_in, "coords")
+    backend = resolve_backend(backend, coords, out_coords)
     if transposed:
         ts, out_ts = tensor_stride // 2, tensor_stride // 2        # ts: the step of the offsets (the finer of the two strides)
     else:
         ts, out_ts = tensor_stride, tensor_stride * stride
+    if backend == "hip":
+        if out_coords is not None and out_coords.device != coords.device:
+            raise ValueError("coords and out_coords must be on one device")
+        return _build_kernel_map_hip(coords, kernel_size, stride, tensor_stride, out_coords, transposed, ts, out_ts)
+    c_in = _check_coords(coords, tensor_stride, "coords")
+    idx_in = _Index(c_in, "coords")
     if out_coords is not None:
         if out_coords.device != coords.device:
             raise ValueError("coords and out_coords must be on one device")
@@ -187,6 +207,104 @@ def build_kernel_map(coords: torch.Tensor, kernel_size: int = 3, stride: int = 1
     fwd = table(idx_in, c_out, sign)
     bwd = None if (stride == 1 and out_coords is None) else table(idx_out, c_in, -sign)
     return KernelMap(c_in, c_out, kernel_size, stride, tensor_stride, out_ts, transposed, fwd, bwd)
+
+
+# ------------------------------------------------------------------------------------------------------
+# the native backend (include/csn_hip.h section 17)
+# ------------------------------------------------------------------------------------------------------
+def resolve_backend(backend: Optional[str], *tensors: Optional[torch.Tensor]) -> str:
+    """``"torch"`` or ``"hip"`` for a call on ``tensors``.  None follows ``tuning.current().native_kernel_maps`` for device tensors;
+    CPU tensors keep the torch backend under the switch and raise ``CsnError`` where ``"hip"`` is asked for by name."""
+    if backend is not None and backend not in BACKENDS:
+        raise ValueError(f"backend {backend!r} is not known: one of {BACKENDS}, or None for the tuning switch")
+    on_device = all(t.is_cuda for t in tensors if t is not None)
+    if backend is None:
+        return "hip" if tuning.current().native_kernel_maps and on_device else "torch"
+    if backend == "hip" and not on_device:
+        raise _lib.CsnError(_NO_CPU)
+    return backend
+
+
+class _KeySet:
+    """A coordinate set for the native lookups: ``coords (n, 4)`` int64, ``keys (n,)`` in row order, ``sorted (n,)`` ascending,
+    ``rows (n,)`` int32 the row of every sorted key — None where the rows are in key order already."""
+
+    def __init__(self, coords, keys, sorted_keys, rows):
+        self.coords, self.keys, self.sorted, self.rows = coords, keys, sorted_keys, rows
+
+
+def _new_status(device) -> torch.Tensor:
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def _read_status(status: torch.Tensor) -> int:
+    """The one host read of a native build."""
+    return int(status.item())
+
+
+def _coord_keys(c: torch.Tensor, ts: int, status: torch.Tensor) -> torch.Tensor:
+    """(17a): the packed keys of ``c (n, 4)`` int64; range and tensor-stride failures go into ``status``."""
+    cc = c.contiguous()
+    keys = torch.empty(cc.shape[0], dtype=torch.int64, device=cc.device)
+    _lib.check(_lib.lib().csn_coord_keys_i64(CF._ptr(cc), cc.shape[0], ts, CF._ptr(keys), CF._ptr(status), CF._stream()),
+               "csn_coord_keys_i64")
+    return keys
+
+
+def _key_set(coords: torch.Tensor, ts: int, what: str, status: torch.Tensor) -> _KeySet:
+    """(17a) and one sort: what ``_check_coords`` + ``_Index`` are to the torch backend."""
+    _check_shape(coords, what)
+    c = coords.long()
+    keys = _coord_keys(c, ts, status)
+    skeys, perm = torch.sort(keys)
+    return _KeySet(c, keys, skeys, perm.int())
+
+
+def _coarse_set(fine: _KeySet, out_ts: int) -> _KeySet:
+    """(17b), then the sorted unique keys: the coarser level of ``fine``, its rows in key order."""
+    down = torch.empty_like(fine.keys)
+    n = down.numel()
+    _lib.check(_lib.lib().csn_coord_down_i64(CF._ptr(fine.keys), n, out_ts, CF._ptr(down), CF._stream()), "csn_coord_down_i64")
+    uniq = torch.unique(down, sorted=True)
+    return _KeySet(_unpack(uniq), uniq, uniq, None)
+
+
+def _lookup(where: _KeySet, at: _KeySet, kernel_size: int, step: int, status: torch.Tensor) -> torch.Tensor:
+    """(17c): ``table (KV, n_at)`` int32, the row in ``where`` of "row j of ``at`` + step * offset", or -1; a set that is not
+    strictly ascending (a duplicate row) goes into ``status``."""
+    n_set, n_query = where.sorted.numel(), at.keys.numel()
+    table = torch.empty((kernel_size ** 3, n_query), dtype=torch.int32, device=at.keys.device)
+    _lib.check(_lib.lib().csn_kernel_map_i32(CF._ptr(where.sorted), CF._ptr(where.rows), n_set, CF._ptr(at.keys), n_query, kernel_size,
+                                             step, CF._ptr(table), CF._ptr(status), CF._stream()), "csn_kernel_map_i32")
+    return table
+
+
+def _raise_for_status(word: int, sets) -> None:
+    """A non-zero status word of a native build.  The word says THAT a set is bad; which one, and the torch backend's own message for
+    it, come from that backend's checks on ``sets`` = [(coords, tensor stride, name)] in its order (the failing call's price)."""
+    if word == 0:
+        return
+    for coords, ts, what in sets:
+        _Index(_check_coords(coords, ts, what), what)
+    raise ValueError(f"the coordinates are not valid (kernel-map status {word})")
+
+
+def _build_kernel_map_hip(coords, kernel_size, stride, tensor_stride, out_coords, transposed, ts, out_ts) -> KernelMap:
+    status = _new_status(coords.device)
+    s_in = _key_set(coords, tensor_stride, "coords", status)
+    sets = [(coords, tensor_stride, "coords")]
+    if out_coords is not None:
+        s_out = _key_set(out_coords, out_ts, "out_coords", status)
+        sets.append((out_coords, out_ts, "out_coords"))
+    elif stride == 1:
+        s_out = s_in
+    else:
+        s_out = _coarse_set(s_in, out_ts)
+    step = -ts if transposed else ts
+    fwd = _lookup(s_in, s_out, kernel_size, step, status)
+    bwd = None if (stride == 1 and out_coords is None) else _lookup(s_out, s_in, kernel_size, -step, status)
+    _raise_for_status(_read_status(status), sets)
+    return KernelMap(s_in.coords, s_out.coords, kernel_size, stride, tensor_stride, out_ts, transposed, fwd, bwd)
 
 
 # ------------------------------------------------------------------------------------------------------

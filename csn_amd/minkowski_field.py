@@ -214,11 +214,12 @@ class PointField:
                 self._voxel_feats = total / (self.vox_ptr[1:] - self.vox_ptr[:-1]).float()[:, None]
         return self._voxel_feats
 
-    def pyramid(self, n_levels: int, stem_kernel: int = 5) -> VoxelPyramid:
-        """The ``VoxelPyramid`` of ``voxel_coords``, built once and kept (a different request rebuilds it)."""
+    def pyramid(self, n_levels: int, stem_kernel: int = 5, backend: Optional[str] = None) -> VoxelPyramid:
+        """The ``VoxelPyramid`` of ``voxel_coords``, built once and kept (a different request rebuilds it).  ``backend`` as in
+        ``build_pyramid`` (both give the same pyramid, so it is no part of the request)."""
         p = self._pyramid
         if p is None or p.n_levels != n_levels or p.stem_kernel != stem_kernel:
-            self._pyramid = p = build_pyramid(self.voxel_coords, n_levels, stem_kernel)
+            self._pyramid = p = build_pyramid(self.voxel_coords, n_levels, stem_kernel, backend=backend)
             self._table = p.s1[0].fwd
         return p
 
@@ -227,10 +228,11 @@ class PointField:
         take as it stands (the pyramid once ``pyramid()`` was called, the coordinates otherwise)."""
         return (self._pyramid if self._pyramid is not None else self.voxel_coords), self.voxel_feats
 
-    def corner_table(self) -> torch.Tensor:
-        """(27, Nv) int32: the kernel-3 stride-1 map of the voxel rows — the pyramid's if one was built, else built once here."""
+    def corner_table(self, backend: Optional[str] = None) -> torch.Tensor:
+        """(27, Nv) int32: the kernel-3 stride-1 map of the voxel rows — the pyramid's if one was built, else built once here
+        (``backend`` as in ``build_kernel_map``)."""
         if self._table is None:
-            self._table = build_kernel_map(self.voxel_coords, kernel_size=3, stride=1, tensor_stride=1).fwd
+            self._table = build_kernel_map(self.voxel_coords, kernel_size=3, stride=1, tensor_stride=1, backend=backend).fwd
         return self._table
 
     # ---- the point side ----

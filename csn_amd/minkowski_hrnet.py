@@ -37,6 +37,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import functional as CF
+from . import minkowski_conv as _mc
 from .minkowski_conv import KernelMap, SparseConv3d, SparseConvTranspose3d, build_kernel_map, sparse_conv3d
 from .minkowski_csn import SimCSNHead, offsets_from_batch_index
 
@@ -69,20 +70,57 @@ class VoxelPyramid:
                             [m.to(device) for m in self.down], self.stem_kernel)
 
 
-def build_pyramid(coords: torch.Tensor, n_levels: int, stem_kernel: int = 5) -> VoxelPyramid:
-    """The pyramid of ``coords`` (n, 4) = [b, x, y, z] at tensor stride 1 (device or CPU tensor; the maps live where it does)."""
+def build_pyramid(coords: torch.Tensor, n_levels: int, stem_kernel: int = 5, backend: Optional[str] = None) -> VoxelPyramid:
+    """The pyramid of ``coords`` (n, 4) = [b, x, y, z] at tensor stride 1 (device or CPU tensor; the maps live where it does).
+    ``backend`` as in ``build_kernel_map``: ``"torch"``, ``"hip"`` (device tensors only) or None for the tuning switch
+    ``native_kernel_maps``; both give the same pyramid."""
     if n_levels < 1:
         raise ValueError("n_levels must be at least 1")
+    backend = _mc.resolve_backend(backend, coords)
+    if backend == "hip":
+        return _build_pyramid_hip(coords, n_levels, stem_kernel)
     levels, s1, down = [coords.long()], [], []
     for l in range(n_levels):
         ts = 1 << l
-        s1.append(build_kernel_map(levels[l], kernel_size=3, stride=1, tensor_stride=ts))
+        s1.append(build_kernel_map(levels[l], kernel_size=3, stride=1, tensor_stride=ts, backend=backend))
         if l + 1 < n_levels:
-            d = build_kernel_map(levels[l], kernel_size=3, stride=2, tensor_stride=ts)
+            d = build_kernel_map(levels[l], kernel_size=3, stride=2, tensor_stride=ts, backend=backend)
             down.append(d)
             levels.append(d.out_coords)
-    stem = s1[0] if stem_kernel == 3 else build_kernel_map(levels[0], kernel_size=stem_kernel, stride=1, tensor_stride=1)
+    stem = s1[0] if stem_kernel == 3 else build_kernel_map(levels[0], kernel_size=stem_kernel, stride=1, tensor_stride=1,
+                                                           backend=backend)
     return VoxelPyramid(levels, s1, stem, down, stem_kernel)
+
+
+def _build_pyramid_hip(coords: torch.Tensor, n_levels: int, stem_kernel: int) -> VoxelPyramid:
+    """The same pyramid on include/csn_hip.h section 17.  Level l's keys and their sort are formed once and serve ``s1[l]``, the stem
+    and ``down[l]``; a coarser level leaves ``torch.unique`` sorted, so it is never sorted again.  Level 0 takes one key launch; a
+    coarser level takes one launch for the floored keys and one key launch on its unpacked coordinates, which computes nothing new
+    (its keys equal the unique ones) and is there as the level's range and tensor-stride check, the torch backend's
+    ``_check_coords`` of that level; one lookup launch per table; one status word for the whole pyramid, read once at the end."""
+    if stem_kernel < 1 or stem_kernel % 2 == 0:
+        raise ValueError(f"kernel_size {stem_kernel} is not supported: odd sizes only")
+    if stem_kernel not in (1, 3, 5):
+        raise ValueError(f"kernel_size {stem_kernel} is not supported: the kernels take 1, 3 and 5")
+    status = _mc._new_status(coords.device)
+    sets, s1, down = [_mc._key_set(coords, 1, "coords", status)], [], []
+    for l in range(n_levels):
+        ts, here = 1 << l, sets[l]
+        fwd = _mc._lookup(here, here, 3, ts, status)
+        s1.append(KernelMap(here.coords, here.coords, 3, 1, ts, ts, False, fwd, None))
+        if l + 1 < n_levels:
+            up = _mc._coarse_set(here, 2 * ts)
+            up.keys = _mc._coord_keys(up.coords, 2 * ts, status)
+            sets.append(up)
+            down.append(KernelMap(here.coords, up.coords, 3, 2, ts, 2 * ts, False, _mc._lookup(here, up, 3, ts, status),
+                                  _mc._lookup(up, here, 3, -ts, status)))
+    if stem_kernel == 3:
+        stem = s1[0]
+    else:
+        stem = KernelMap(sets[0].coords, sets[0].coords, stem_kernel, 1, 1, 1, False,
+                         _mc._lookup(sets[0], sets[0], stem_kernel, 1, status), None)
+    _mc._raise_for_status(_mc._read_status(status), [(coords, 1, "coords")])
+    return VoxelPyramid([s.coords for s in sets], s1, stem, down, stem_kernel)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -67,6 +67,12 @@ class Tuning:
     # bytes for that automatic decision; None: what the device can still give at forward time (free device memory + what the
     # caching allocator holds but has not handed out)
     cross_score_budget: Optional[int] = None
+    # kernel maps and voxel pyramids of DEVICE tensors (csn_amd.minkowski_conv.build_kernel_map, csn_amd.minkowski_hrnet.build_pyramid
+    # with backend=None, hence PointField.pyramid and HRNetSimCSN.forward on bare coordinates) through the kernels of include/csn_hip.h
+    # section 17 instead of one searchsorted per offset in torch ops.  The same integers (tests/test_gpu_kernel_map.py), so every launch
+    # downstream is the same launch.  CPU tensors keep the torch backend whatever this says.  Off: opt-in until the default is flipped
+    # on its own (timing: DESIGN.md "Kernel maps", scripts/bench_kernel_map.py)
+    native_kernel_maps: bool = False
 
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))

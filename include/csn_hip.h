@@ -765,6 +765,38 @@ CSN_API int csn_point_interp_bwd_f32(const float* dy, long long ld_dy, int n_poi
                              const int* vox_pts, const int* table, int n_voxels, int channels, float* dz, long long ld_dz,
                              void* stream);
 
+/* ---- (17) kernel maps: the coordinate manager of (14) — packed keys, the coarser level's keys, the offset tables ------------
+ * MinkowskiEngine builds its kernel maps in native code; csn_amd.minkowski_conv.build_kernel_map(backend="hip") and
+ * csn_amd.minkowski_hrnet.build_pyramid(backend="hip") build theirs here.  The sort and the unique of the keys stay the caller's.
+ * PACKED KEY (part of this ABI): a coordinate [b, x, y, z] is the int64
+ *   key = b << 48 | (x + 2^15) << 32 | (y + 2^15) << 16 | (z + 2^15),   b in [0, 2^15), x, y, z in [-2^15, 2^15):
+ * three 16-bit fields biased by 2^15 below a 15-bit batch field, so that the order of the keys is the lexicographic order of
+ * (b, x, y, z) and every valid key is non-negative.
+ * STATUS WORD: one int32 on the device, zeroed by the caller, or-ed into by (17a) and (17c) and read by the caller when it likes:
+ *   1 a batch index outside [0, 2^15);  2 an x, y or z outside [-2^15, 2^15);  4 an x, y or z that is no multiple of tensor_stride;
+ *   8 two neighbours of set_keys equal or descending (a duplicate row, or a set that was not sorted).
+ * Nothing is dereferenced through a bad value: a flagged call's outputs are merely not meaningful.
+ * Host-side checks before any launch: a NULL pointer (set_rows may be NULL), n < 1, tensor_stride < 1 or step == 0: CSN_E_ARG;
+ * kernel_size not in {1, 3, 5}: CSN_E_DIM; a key or coordinate array off 8 bytes, an int32 array or the status word off 4 bytes:
+ * CSN_E_PTR.
+ * (17a) csn_coord_keys_i64: keys[i] = key(coords[i]) for coords[n][4] int64 (contiguous rows), and the flags 1, 2, 4.  "Multiple of"
+ *   in the sense of a floored remainder (-4 is a multiple of 2, -3 is not).
+ * (17b) csn_coord_down_i64: down_keys[i] = the key of [b, floor(x / s) s, floor(y / s) s, floor(z / s) s], s = out_tensor_stride.
+ *   Floor, not truncation: -1 -> -2 at s = 2.  The batch field is kept.  down_keys may be keys.
+ * (17c) csn_kernel_map_i32: set_keys[n_set] ascending, set_rows[n_set] the row number of every sorted key (NULL: its position),
+ *   query_keys[n_query] in row order.  With r = kernel_size / 2, o = (ox, oy, oz) in [-r, r]^3 and kidx = (ox + r) + k (oy + r) +
+ *   k^2 (oz + r) as in (14): table[kidx][j] = the row of the coordinate "query j + step o" in the set, or -1.  step is signed
+ *   (sign x offset step: +ts for the tables indexed by output rows of a convolution, -ts for those indexed by its input rows, the
+ *   opposite for the transposed convolution).  The offset is added per field after unpacking: a field that leaves its 16 bits gives
+ *   -1, it never carries into the neighbouring field, and the batch field is never touched (offsets cannot cross shapes).  A row
+ *   number outside [0, n_set) in set_rows reads as -1.  The same launch raises flag 8.  One thread per query row; per pair (ox, oy) one
+ *   lower-bound search and a forward walk over the k keys that differ in z alone; table offsets are 64-bit (kernel_size^3 n_query
+ *   may exceed 2^31). */
+CSN_API int csn_coord_keys_i64(const long long* coords, int n, int tensor_stride, long long* keys, int* status, void* stream);
+CSN_API int csn_coord_down_i64(const long long* keys, int n, int out_tensor_stride, long long* down_keys, void* stream);
+CSN_API int csn_kernel_map_i32(const long long* set_keys, const int* set_rows, int n_set, const long long* query_keys, int n_query,
+                       int kernel_size, int step, int* table, int* status, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
