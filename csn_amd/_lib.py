@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libcsn_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "csn_capi.hip"]
-HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", os.path.join("..", "..", "include", "csn_hip.h")]
+HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
 ARCH = "gfx950"
 BUILD_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"]
 
@@ -127,6 +127,8 @@ _SIGNATURES = {
     "csn_get_thread_math_mode": (c_int, []),
     "csn_set_thread_act16": (c_int, [c_int]),
     "csn_get_thread_act16": (c_int, []),
+    "csn_set_thread_rows16": (c_int, [c_int]),
+    "csn_get_thread_rows16": (c_int, []),
     "csn_set_thread_score_layout": (c_int, [c_int]),
     "csn_get_thread_score_layout": (c_int, []),
     "csn_status_string": (c_char_p, [c_int]),

@@ -20,6 +20,10 @@ inline bool grad16() { return (t_act16 & 4) != 0; }
 // forward entry points: the flag has to name the type of the mode that runs; backward: mode 2 takes either
 inline bool act16_fwd_ok() { return act16() == 0 || (act16() == 1 && mode() == 2) || (act16() == 2 && mode() == 3); }
 inline bool act16_bwd_ok() { return act16() == 0 || mode() == 2; }
+// single-product row products of sections 13 / 14 / 15a (csn_set_thread_rows16): 0 = modes 2 / 3 run as mode 1 there, 1 = they
+// run the bf16 / fp16 instances
+thread_local int t_rows16 = 0;
+inline int rows_mode() { return mode() >= 2 && !t_rows16 ? 1 : mode(); }
 // score storage of the block-attention entry points (csn_set_thread_score_layout): 0 = [query][key] rows, 1 = tile-major
 thread_local int t_score_layout = 0;
 inline int planes_of(int m) { return m == 1 ? 2 : 1; }          // tile-plane / split-tensor planes of a 16-bit mode
@@ -165,6 +169,12 @@ int csn_set_thread_act16(int fmt) {
   return 0;
 }
 int csn_get_thread_act16(void) { return t_act16; }
+int csn_set_thread_rows16(int on) {
+  if (on != 0 && on != 1) return CSN_E_ARG;
+  t_rows16 = on;
+  return 0;
+}
+int csn_get_thread_rows16(void) { return t_rows16; }
 int csn_set_thread_score_layout(int layout) {
   if (layout < 0 || layout > 1) return CSN_E_ARG;
   t_score_layout = layout;
@@ -1218,7 +1228,7 @@ int csn_rows_fc_fwd_f32(const float* x, long long ld_x, int n_rows, int c_in, in
   a.x = x; a.ld_x = (int)ld_x; a.w = w; a.bias = bias; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean;
   a.running_var = running_var; a.eps = eps; a.momentum = momentum; a.training = training != 0; a.n_rows = n_rows; a.c_in = c_in;
   a.c_out = c_out; a.y = y; a.ld_y = (int)ld_y; a.z = z; a.ld_z = (int)ld_z; a.mean = mean; a.invstd = invstd; a.ws = ws;
-  return csn_launch_rows_fc_fwd(a, mode(), (hipStream_t)stream);
+  return csn_launch_rows_fc_fwd(a, rows_mode(), (hipStream_t)stream);
 }
 
 int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const float* z, long long ld_z,
@@ -1228,6 +1238,7 @@ int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long l
                         void* stream) {
   if (!dy || !y || !x || !w || !gamma || !stat_mean || !stat_scale || !dgamma || !dbeta || !ws) return CSN_E_ARG;
   if (training && !z) return CSN_E_ARG;
+  if (rows_mode() == 3) return CSN_E_ARG;                         // fp16 single product: forward only — run the backward in mode 2
   if (const int e = rows_fc_dims(n_rows, c_in, c_out)) return e;
   if (const int e = rows_fc_pitch(ld_dy, c_out)) return e;
   if (const int e = rows_fc_pitch(ld_y, c_out)) return e;
@@ -1243,7 +1254,7 @@ int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y, long l
   a.c_in = c_in; a.c_out = c_out; a.y = const_cast<float*>(y); a.ld_y = (int)ld_y; a.z = const_cast<float*>(z); a.ld_z = (int)ld_z;
   a.mean = const_cast<float*>(stat_mean); a.invstd = const_cast<float*>(stat_scale); a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx;
   a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias; a.dgamma = dgamma; a.dbeta = dbeta; a.ws = ws;
-  return csn_launch_rows_fc_bwd(a, mode(), (hipStream_t)stream);
+  return csn_launch_rows_fc_bwd(a, rows_mode(), (hipStream_t)stream);
 }
 
 // ---- (14) sparse 3D convolution on voxel rows over a kernel map ----
@@ -1276,7 +1287,7 @@ int csn_sparse_conv_fwd_f32(const float* x, long long ld_x, int n_in, const int*
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
-  return csn_launch_sparse_conv_fwd(a, mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_fwd(a, rows_mode(), (hipStream_t)stream);
 }
 
 int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_in, int n_out, int kv, int c_in,
@@ -1284,6 +1295,7 @@ int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, lo
                             float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
   if (!dy || !ws) return CSN_E_ARG;
   if (dx && !w) return CSN_E_ARG;
+  if (rows_mode() == 3) return CSN_E_ARG;                         // fp16 single product: forward only — run the backward in mode 2
   if (dx && !bwd_table && (!fwd_table || n_in != n_out)) return CSN_E_ARG;   // NULL: the stride-1 identity on fwd_table
   if (dw && (!fwd_table || !x)) return CSN_E_ARG;
   if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
@@ -1297,7 +1309,7 @@ int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, lo
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = fwd_table; a.bwd_table = bwd_table; a.n_out = n_out; a.kv = kv;
   a.c_in = c_in; a.c_out = c_out; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias;
   a.ws = ws;
-  return csn_launch_sparse_conv_bwd(a, mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_bwd(a, rows_mode(), (hipStream_t)stream);
 }
 
 // ---- (15) the HRNet backbone's fused tail ----
@@ -1320,7 +1332,7 @@ int csn_sparse_conv_stats_fwd_f32(const float* x, long long ld_x, int n_in, cons
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
-  return csn_launch_sparse_conv_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, rows_mode(), (hipStream_t)stream);
 }
 
 static int bn_act_dims(int n_terms, int n_rows, int channels) {

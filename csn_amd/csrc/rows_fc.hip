@@ -20,6 +20,9 @@
 //                      buffer range check (never a lane mask).  The four waves of a work-group contract a quarter of its row
 //                      chunk each and are added through LDS in wave order; chunks are split-K slabs added by csn_launch_slab_reduce.
 //                      The 16-row step and the reduction are rows_mma.h's; the kernel keeps its addressing.
+//   rows_gemm16 / rows_fc_wgrad16   the same bodies with ONE 16-bit product per operand pair (math modes 2 bf16 / 3 fp16 behind
+//                      csn_set_thread_rows16; fp16: the forward products alone): operands rounded once, the weight converted when it
+//                      is stored to LDS.
 // No floating-point atomics anywhere: every reduction has a fixed order, two calls give the same bits.
 #include "rows_mma.h"
 
@@ -37,9 +40,10 @@ struct RowsGemmP {
   const float* gamma; const float* beta; const float* rmean; const float* rvar; float eps;
 };
 
+// the body of rows_gemm_kernel (MODE 0 / 1) and rows_gemm16_kernel (MODE 2 bf16 / 3 fp16: one product, the tile holds shorts)
 template <int NB, int MODE, bool B_KN>
-__global__ __launch_bounds__(256) void rows_gemm_kernel(const RowsGemmP p) {
-  __shared__ __attribute__((aligned(16))) float Bs[NB * 32 * BS_PITCH];
+__device__ __forceinline__ void rows_gemm_body(const RowsGemmP p) {
+  __shared__ __attribute__((aligned(16))) bs_t<MODE> Bs[NB * 32 * bs_pitch<MODE>];
   const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
   const int ncg = (p.J + NB * 32 - 1) / (NB * 32);
   const int cg = blockIdx.x % ncg, rg = blockIdx.x / ncg;
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void rows_gemm_kernel(const RowsGemmP p) {
   load_b<NB, B_KN>(bn, p.b, p.ldb, 0, j0, p.J, tid);
   for (int k0 = 0; k0 < p.K; k0 += 32) {
     __syncthreads();                                                  // the previous step's reads of Bs are done
-    store_b<NB, B_KN>(Bs, bn, tid);
+    store_b<NB, B_KN, MODE>(Bs, bn, tid);
     f32x4 af[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) af[g] = an[g];
@@ -89,6 +93,13 @@ __global__ __launch_bounds__(256) void rows_gemm_kernel(const RowsGemmP p) {
     store_tile(acc[nb], p.bias ? p.bias[col] : 0.f, p.c, p.ldc, row_w, cnt, col, h, p.epi == 1, p.part, tile, p.J);
   }
 }
+
+template <int NB, int MODE, bool B_KN>
+__global__ __launch_bounds__(256) void rows_gemm_kernel(const RowsGemmP p) { rows_gemm_body<NB, MODE, B_KN>(p); }
+
+// the single-product instances: H16 = fp16 operands (forward only), else bf16
+template <int NB, bool H16, bool B_KN>
+__global__ __launch_bounds__(256) void rows_gemm16_kernel(const RowsGemmP p) { rows_gemm_body<NB, H16 ? 3 : 2, B_KN>(p); }
 
 // one thread per (column, segment of the tiles): 32 columns x NSEG segments per work-group, segments merged in order by segment 0
 constexpr int NSEG = 32;
@@ -239,9 +250,10 @@ __global__ __launch_bounds__(32 * NSEG) void rows_colsum_merge_kernel(const doub
 }
 
 // dw[co][ci] = sum_n dz[n][co] x[n][ci] over the rows of one split-K chunk; see the file header
+// the body of rows_fc_wgrad_kernel (MODE 0 / 1) and rows_fc_wgrad16_kernel (MODE 2: one bf16 product)
 template <int TA, int MODE>
-__global__ __launch_bounds__(256) void rows_fc_wgrad_kernel(const float* __restrict__ dz, int ldz, const float* __restrict__ x, int ldx,
-                                                            float* __restrict__ out, long long n_rows, int c_out, int c_in, int chunk) {
+__device__ __forceinline__ void rows_fc_wgrad_body(const float* __restrict__ dz, int ldz, const float* __restrict__ x, int ldx,
+                                                   float* __restrict__ out, long long n_rows, int c_out, int c_in, int chunk) {
   __shared__ float red[TA * WG_TB * 16 * 64];
   const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
   const int ci0 = blockIdx.x * 64, co0 = blockIdx.y * 32 * TA;
@@ -279,6 +291,18 @@ __global__ __launch_bounds__(256) void rows_fc_wgrad_kernel(const float* __restr
     wgrad_step<TA, MODE, false>(acc, af, bf, nbv);
   }
   wgrad_reduce_store<TA>(acc, red, out + (long long)blockIdx.z * c_out * c_in, c_in, co0, ci0, nbv, wave, l);
+}
+
+template <int TA, int MODE>
+__global__ __launch_bounds__(256) void rows_fc_wgrad_kernel(const float* __restrict__ dz, int ldz, const float* __restrict__ x, int ldx,
+                                                            float* __restrict__ out, long long n_rows, int c_out, int c_in, int chunk) {
+  rows_fc_wgrad_body<TA, MODE>(dz, ldz, x, ldx, out, n_rows, c_out, c_in, chunk);
+}
+
+template <int TA>
+__global__ __launch_bounds__(256) void rows_fc_wgrad16_kernel(const float* __restrict__ dz, int ldz, const float* __restrict__ x, int ldx,
+                                                              float* __restrict__ out, long long n_rows, int c_out, int c_in, int chunk) {
+  rows_fc_wgrad_body<TA, 2>(dz, ldz, x, ldx, out, n_rows, c_out, c_in, chunk);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -319,7 +343,10 @@ WsLayout ws_layout(long long n_rows, int c_in, int c_out, int training, int back
 
 template <int NB, bool B_KN>
 int launch_gemm_nb(const RowsGemmP& p, int mode, hipStream_t st) {
-  return launch_row_product(rows_gemm_kernel<NB, 0, B_KN>, rows_gemm_kernel<NB, 1, B_KN>, p, NB, mode, st);
+  // the fp16 product exists for the forward ([J][K] weights) alone
+  void (*const k[4])(RowsGemmP) = {rows_gemm_kernel<NB, 0, B_KN>, rows_gemm_kernel<NB, 1, B_KN>, rows_gemm16_kernel<NB, false, B_KN>,
+                                   B_KN ? nullptr : rows_gemm16_kernel<NB, true, false>};
+  return launch_row_product(k, p, NB, mode, st);
 }
 
 // forward products: the wave owns every column up to 128, two column groups at 256
@@ -331,8 +358,8 @@ template <int TA>
 int launch_wgrad_ta(const float* dz, const float* x, int ldx, float* out, long long n_rows, int c_in, int c_out, int splits, int chunk,
                     int mode, hipStream_t st) {
   const dim3 grid((unsigned)((c_in + 63) / 64), (unsigned)(c_out / (32 * TA)), (unsigned)splits), block(256);
-  if (mode == 0) hipLaunchKernelGGL((rows_fc_wgrad_kernel<TA, 0>), grid, block, 0, st, dz, c_out, x, ldx, out, n_rows, c_out, c_in, chunk);
-  else hipLaunchKernelGGL((rows_fc_wgrad_kernel<TA, 1>), grid, block, 0, st, dz, c_out, x, ldx, out, n_rows, c_out, c_in, chunk);
+  auto* const k = mode == 0 ? rows_fc_wgrad_kernel<TA, 0> : (mode == 1 ? rows_fc_wgrad_kernel<TA, 1> : rows_fc_wgrad16_kernel<TA>);
+  hipLaunchKernelGGL(k, grid, block, 0, st, dz, c_out, x, ldx, out, n_rows, c_out, c_in, chunk);
   return (int)hipGetLastError();
 }
 
@@ -352,8 +379,8 @@ int csn_launch_rows_colsum_merge(const double* part, int n_chunks, int C, float*
   return (int)hipGetLastError();
 }
 
+// mode: 0 fp32, 1 bf16x3, 2 bf16 / 3 fp16 single product (csn_capi.hip resolves the thread's math mode and rows16 flag)
 int csn_launch_rows_fc_fwd(const CsnRowsFcArgs& a, int mode, hipStream_t st) {
-  mode = mode != 0;
   const WsLayout L = ws_layout(a.n_rows, a.c_in, a.c_out, a.training, 0);
   RowsGemmP p{};
   p.a = a.x; p.lda = a.ld_x; p.b = a.w; p.ldb = a.c_in; p.M = a.n_rows; p.K = a.c_in; p.J = a.c_out;
@@ -376,7 +403,7 @@ int csn_launch_rows_fc_fwd(const CsnRowsFcArgs& a, int mode, hipStream_t st) {
 }
 
 int csn_launch_rows_fc_bwd(const CsnRowsFcArgs& a, int mode, hipStream_t st) {
-  mode = mode != 0;
+  if (mode == 3) return -1;                                           // fp16 is forward only
   const WsLayout L = ws_layout(a.n_rows, a.c_in, a.c_out, a.training, 1);
   char* ws = static_cast<char*>(a.ws);
   double* part = reinterpret_cast<double*>(ws + L.part);

@@ -3,13 +3,16 @@
 // rows_bn_act.hip).  A kernel keeps where its rows come from, its pipeline order and its launch rule; what it does with a
 // staged tile is here.
 //
-//   row product      a wave owns 32 rows x NB * 32 columns; a lane owns one row and 4 (fp32) / 8 (bf16x3) consecutive k of every
+//   row product      a wave owns 32 rows x NB * 32 columns; a lane owns one row and 4 (fp32) / 8 (16-bit) consecutive k of every
 //                    32-k step (a_kofs); B — [J][K] or [K][J] (B_KN) — is staged through LDS once per work-group (load_b,
 //                    store_b); mma_step contracts one step; store_tile adds the bias, stores the wave's rows and forms their
 //                    (mean, M2) from the accumulators.
 //   weight gradient  both operands are k-major (the contraction runs over the rows): a lane holds 8 rows of one column per 16-row
 //                    step (wgrad_row) and splits them in registers (wgrad_step); the four waves of a work-group contract a
 //                    quarter of its row chunk each and are added through LDS in wave order (wgrad_reduce_store).
+//   MODE              0 fp32, 1 bf16x3 (hi / lo split in registers, three products), 2 bf16 / 3 fp16: ONE product of operands
+//                    rounded once to 16 bits (to16x4: nearest even) — A in registers, B when it is stored to LDS, so the tile
+//                    holds shorts and a lane's B fragment is one 16-byte read.
 //   statistics       chan_merge / chan_walk / bn_finish: [tile][2][C] (mean, M2) partials of 32-row tiles -> mean, invstd,
 //                    running statistics, in fp64.
 // Every reduction has a fixed order.
@@ -22,6 +25,10 @@ namespace rows_mma {
 using namespace csn_mode;
 
 constexpr int BS_PITCH = 36;          // floats per LDS row of the B tile: 32 k + 4 (16-byte reads of 16 lanes hit 16 x 4 distinct banks)
+constexpr int BS16_PITCH = 40;        // shorts per row of the single-product tile: 32 k + 8 (20 li mod 64 is a distinct multiple of 4 dwords
+                                      // over each 16-lane group of a 16-byte read)
+template <int MODE> using bs_t = std::conditional_t<(MODE >= 2), short, float>;
+template <int MODE> constexpr int bs_pitch = MODE >= 2 ? BS16_PITCH : BS_PITCH;
 constexpr int WG_TB = 2;              // 32-column blocks of the weight gradient's second operand per work-group
 
 // k of a lane's g-th 16-byte A read inside a 32-k step, before its half-wave offset (4 h fp32, 8 h 16-bit):
@@ -47,27 +54,43 @@ __device__ __forceinline__ void load_b(f32x4 (&bn)[NB], const float* b, int ldb,
   }
 }
 
-// ... and from there into the LDS tile Bs[column][BS_PITCH]
-template <int NB, bool B_KN>
-__device__ __forceinline__ void store_b(float* Bs, const f32x4 (&bn)[NB], int tid) {
+// ... and from there into the LDS tile Bs[column][bs_pitch]: floats, or (single product) the values rounded to 16 bits
+template <int NB, bool B_KN, int MODE>
+__device__ __forceinline__ void store_b(bs_t<MODE>* Bs, const f32x4 (&bn)[NB], int tid) {
+  constexpr int P = bs_pitch<MODE>;
 #pragma unroll
   for (int u = 0; u < NB; ++u) {
     const int idx = tid + 256 * u;
     if constexpr (!B_KN) {
       const int j = idx >> 3, kq = idx & 7;
-      *reinterpret_cast<f32x4*>(&Bs[j * BS_PITCH + 4 * kq]) = bn[u];
+      if constexpr (MODE >= 2) *reinterpret_cast<s16x4*>(&Bs[j * P + 4 * kq]) = to16x4<MODE == 3>(bn[u]);
+      else *reinterpret_cast<f32x4*>(&Bs[j * P + 4 * kq]) = bn[u];
     } else {
       const int k = idx / (NB * 8), jq = idx % (NB * 8);
+      if constexpr (MODE >= 2) {
+        const s16x4 v = to16x4<MODE == 3>(bn[u]);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) Bs[(4 * jq + e) * BS_PITCH + k] = bn[u][e];
+        for (int e = 0; e < 4; ++e) Bs[(4 * jq + e) * P + k] = v[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) Bs[(4 * jq + e) * P + k] = bn[u][e];
+      }
     }
   }
 }
 
 // one 32-k step: the lane's A reads af[g] (a_kofs) against the staged tile
 template <int NB, int MODE>
-__device__ __forceinline__ void mma_step(f32x16 (&acc)[NB], const f32x4 (&af)[4], const float* Bs, int li, int h) {
-  if constexpr (MODE == 0) {
+__device__ __forceinline__ void mma_step(f32x16 (&acc)[NB], const f32x4 (&af)[4], const bs_t<MODE>* Bs, int li, int h) {
+  if constexpr (MODE >= 2) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const s16x8 a = join8(to16x4<MODE == 3>(af[2 * s2]), to16x4<MODE == 3>(af[2 * s2 + 1]));
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        acc[nb] = mfma32<MODE == 3>(a, *reinterpret_cast<const s16x8*>(&Bs[(nb * 32 + li) * BS16_PITCH + 16 * s2 + 8 * h]), acc[nb]);
+    }
+  } else if constexpr (MODE == 0) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -141,6 +164,12 @@ __device__ __forceinline__ int wgrad_steps(long long left, int quarter) {
   return left <= 0 ? 0 : (int)((left < quarter ? left : quarter) + 15) / 16;
 }
 
+// 8 floats rounded to 16 bits (nearest even) as one matrix-core fragment
+template <bool H16>
+__device__ __forceinline__ s16x8 pack8(const float (&v)[8]) {
+  return join8(to16x4<H16>(f32x4{v[0], v[1], v[2], v[3]}), to16x4<H16>(f32x4{v[4], v[5], v[6], v[7]}));
+}
+
 // one 16-row step: acc[ta][tb] += af[ta]^T bf[tb] over the lane's 8 rows, for the nbv column blocks that exist.  SPLIT_ALL: bf16x3
 // splits an absent block of bf too (never read) instead of branching round it: the gathered kernel is 8 % faster so, the dense one
 // a wave per SIMD poorer at TA 2
@@ -154,6 +183,18 @@ __device__ __forceinline__ void wgrad_step(f32x16 (&acc)[TA][WG_TB], const float
 #pragma unroll
         for (int tb = 0; tb < WG_TB; ++tb)
           if (tb < nbv) acc[ta][tb] = csn_mfma(af[ta][e], bf[tb][e], acc[ta][tb]);
+  } else if constexpr (MODE >= 2) {
+    // one conversion of the lane's 8 rows per operand (an absent block of bf is converted too: it is never read), one product
+    s16x8 b16[WG_TB];
+#pragma unroll
+    for (int tb = 0; tb < WG_TB; ++tb) b16[tb] = pack8<MODE == 3>(bf[tb]);
+#pragma unroll
+    for (int ta = 0; ta < TA; ++ta) {
+      const s16x8 a16 = pack8<MODE == 3>(af[ta]);
+#pragma unroll
+      for (int tb = 0; tb < WG_TB; ++tb)
+        if (tb < nbv) acc[ta][tb] = mfma32<MODE == 3>(a16, b16[tb], acc[ta][tb]);
+    }
   } else {
     s16x8 bhi[WG_TB], blo[WG_TB];
 #pragma unroll
@@ -254,13 +295,14 @@ __device__ __forceinline__ void bn_finish(double n, double mu, double m2, int co
 // ---- host side ---------------------------------------------------------------------------------------------------------
 inline long long up256(long long b) { return (b + 255) & ~255LL; }
 
-// a row product's grid: one work-group per (128 rows, NB * 32 columns), column groups fastest; k0 / k1 are the kernel's fp32 and
-// bf16x3 instances of that NB
+// a row product's grid: one work-group per (128 rows, NB * 32 columns), column groups fastest; k[mode] are the kernel's fp32,
+// bf16x3, bf16 and fp16 instances of that NB (the last may be NULL: a backward product has no fp16 form, -1 = CSN_E_ARG)
 template <typename P>
-int launch_row_product(void (*k0)(P), void (*k1)(P), const P& p, int NB, int mode, hipStream_t st) {
+int launch_row_product(void (*const (&k)[4])(P), const P& p, int NB, int mode, hipStream_t st) {
   const long long groups = (long long)((p.J + NB * 32 - 1) / (NB * 32)) * ((p.M + 127) / 128);
   if (groups > 0x7fffffffLL) return -5;
-  hipLaunchKernelGGL(mode == 0 ? k0 : k1, dim3((unsigned)groups), dim3(256), 0, st, p);
+  if (mode < 0 || mode > 3 || !k[mode]) return -1;
+  hipLaunchKernelGGL(k[mode], dim3((unsigned)groups), dim3(256), 0, st, p);
   return (int)hipGetLastError();
 }
 

@@ -19,6 +19,8 @@
 //                      (wave ballot).  The four waves contract a quarter of the chunk each and are added through LDS in wave
 //                      order; the chunks are slabs added in order by csn_launch_slab_reduce.
 //   dbias = sum_j dy[j]: csn_launch_rows_colsum / _merge (rows_fc.hip), fp64 sums of 64-row chunks added in chunk order.
+//   sconv_gemm16 / sconv_wgrad16   the same bodies with ONE 16-bit product per operand pair (math modes 2 bf16 / 3 fp16 behind
+//                      csn_set_thread_rows16; fp16: the forward alone): operands rounded once, W converted when it is stored to LDS.
 // No floating-point atomics anywhere: every reduction has a fixed order, two calls give the same bits.
 #include "rows_mma.h"
 
@@ -44,89 +46,23 @@ struct SconvGemmP {
 
 template <int NB, int MODE, bool B_KN>
 __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
-  __shared__ __attribute__((aligned(16))) float Bs[NB * 32 * BS_PITCH];
-  __shared__ int s_flag[MAX_KV];
-  __shared__ int s_act[MAX_KV];
-  __shared__ int s_nact;
-  const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
-  const int ncg = (p.J + NB * 32 - 1) / (NB * 32);
-  const int cg = blockIdx.x % ncg, rg = blockIdx.x / ncg;
-  const int j0 = cg * NB * 32;
-  const long long row_g = (long long)rg * 128;                        // first output row of the work-group
-  const long long row_l = row_g + wave * 32 + li;                     // the lane's output row
-  const bool row_ok = row_l < p.M;
-  const csn_rsrc_t ar = csn_make_rsrc(p.a, ((long long)(p.n_src - 1) * p.lda + p.K) * 4LL);
-  const unsigned a_in = (unsigned)((MODE == 0 ? 4 : 8) * h * 4);      // byte offset of the lane's channels inside a 32-channel step
-  const int ks = p.K >> 5;                                            // channel steps per offset
+#include "sconv_gemm_body.inc"
+}
 
-  // the offsets at which some row of the tile has a neighbour, in ascending order
-  for (int k = tid; k < p.KV; k += 256) s_flag[k] = 0;
-  __syncthreads();
-  for (int k = 0; k < p.KV; ++k) {
-    const int r = row_ok ? p.table[(long long)(p.rev ? p.KV - 1 - k : k) * p.M + row_l] : -1;
-    if (__ballot(r >= 0) != 0ULL && l == 0) s_flag[k] = 1;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int n = 0;
-    for (int k = 0; k < p.KV; ++k)
-      if (s_flag[k]) s_act[n++] = k;
-    s_nact = n;
-  }
-  __syncthreads();
-  const int S = s_nact * ks;                                          // contraction steps of this work-group
-
-  f32x16 acc[NB] = {};
-  // step s = (offset s / ks of the list, channels 32 (s % ks) ..): the lane's source row of a step, two steps ahead of its use
-  auto row_of = [&](int s) -> int {
-    if (s >= S || !row_ok) return -1;
-    const int k = s_act[s / ks];
-    return p.table[(long long)(p.rev ? p.KV - 1 - k : k) * p.M + row_l];
-  };
-  f32x4 an[4], bn[NB];
-  auto load_a = [&](int s, int src) {
-    const unsigned off = src < 0 ? CSN_OOB : (unsigned)src * (unsigned)p.lda * 4u + a_in + (unsigned)((s % ks) * 128);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) an[g] = csn_bload4(ar, off + (unsigned)(a_kofs<MODE>(g) * 4));
-  };
-  auto load_w = [&](int s) {
-    load_b<NB, B_KN>(bn, p.b + (long long)s_act[s / ks] * p.c_in * p.c_out, p.c_out, (s % ks) * 32, j0, p.J, tid);
-  };
-
-  int r1 = row_of(0);
-  if (S > 0) { load_a(0, r1); load_w(0); }
-  r1 = row_of(1);
-  int r2 = row_of(2);
-  for (int s = 0; s < S; ++s) {
-    __syncthreads();                                                  // the previous step's reads of Bs are done
-    store_b<NB, B_KN>(Bs, bn, tid);
-    f32x4 af[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) af[g] = an[g];
-    __syncthreads();
-    if (s + 1 < S) { load_a(s + 1, r1); load_w(s + 1); }
-    r1 = r2;
-    r2 = row_of(s + 3);
-    mma_step<NB, MODE>(acc, af, Bs, li, h);
-  }
-
-  const long long row_w = row_g + wave * 32;                          // first row of the wave's tile
-  const int cnt = (int)(p.M - row_w < 32 ? (p.M - row_w < 0 ? 0 : p.M - row_w) : 32);
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const int col = j0 + nb * 32 + li;
-    if (j0 + nb * 32 >= p.J) continue;                                // wave-uniform: J % 32 == 0
-    store_tile(acc[nb], p.bias ? p.bias[col] : 0.f, p.c, p.ldc, row_w, cnt, col, h, p.part != nullptr, p.part, (long long)rg * 4 + wave,
-               p.J);
-  }
+// the single-product instances: H16 = fp16 operands (forward only), else bf16
+template <int NB, bool H16, bool B_KN>
+__global__ __launch_bounds__(256) void sconv_gemm16_kernel(const SconvGemmP p) {
+  constexpr int MODE = H16 ? 3 : 2;
+#include "sconv_gemm_body.inc"
 }
 
 // dW[k][ci][co] = sum_j x[fwd[k][j]][ci] dy[j][co] over the rows of one split-K chunk; see the file header.
 // grid: x = 64-column blocks of c_out, y = 32 TA-row blocks of c_in, z = KV * splits (offset fastest)
+// the body of sconv_wgrad_kernel (MODE 0 / 1) and sconv_wgrad16_kernel (MODE 2: one bf16 product)
 template <int TA, int MODE>
-__global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restrict__ x, int ldx, int n_in, const int* __restrict__ table,
-                                                          const float* __restrict__ dy, int ldy, float* __restrict__ out, int n_out,
-                                                          int c_in, int c_out, int KV, int chunk) {
+__device__ __forceinline__ void sconv_wgrad_body(const float* __restrict__ x, int ldx, int n_in, const int* __restrict__ table,
+                                                 const float* __restrict__ dy, int ldy, float* __restrict__ out, int n_out, int c_in,
+                                                 int c_out, int KV, int chunk) {
   __shared__ float red[TA * WG_TB * 16 * 64];
   const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
   const int co0 = blockIdx.x * 64, ci0 = blockIdx.y * 32 * TA;
@@ -191,6 +127,20 @@ __global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restric
   wgrad_reduce_store<TA>(acc, red, out + ((long long)split * KV + kv) * c_in * c_out, c_out, ci0, co0, nbv, wave, l);
 }
 
+template <int TA, int MODE>
+__global__ __launch_bounds__(256) void sconv_wgrad_kernel(const float* __restrict__ x, int ldx, int n_in, const int* __restrict__ table,
+                                                          const float* __restrict__ dy, int ldy, float* __restrict__ out, int n_out,
+                                                          int c_in, int c_out, int KV, int chunk) {
+  sconv_wgrad_body<TA, MODE>(x, ldx, n_in, table, dy, ldy, out, n_out, c_in, c_out, KV, chunk);
+}
+
+template <int TA>
+__global__ __launch_bounds__(256) void sconv_wgrad16_kernel(const float* __restrict__ x, int ldx, int n_in, const int* __restrict__ table,
+                                                            const float* __restrict__ dy, int ldy, float* __restrict__ out, int n_out,
+                                                            int c_in, int c_out, int KV, int chunk) {
+  sconv_wgrad_body<TA, 2>(x, ldx, n_in, table, dy, ldy, out, n_out, c_in, c_out, KV, chunk);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // rows of 32 c_in channels a work-group of the weight gradient owns: 4 where they divide c_in / 32, else the largest divisor
 inline int wgrad_ta_for(int c_in) {
@@ -223,7 +173,10 @@ WsLayout ws_layout(long long n_out, int kv, int c_in, int c_out) {
 
 template <int NB, bool B_KN>
 int launch_gemm_nb(const SconvGemmP& p, int mode, hipStream_t st) {
-  return launch_row_product(sconv_gemm_kernel<NB, 0, B_KN>, sconv_gemm_kernel<NB, 1, B_KN>, p, NB, mode, st);
+  // the fp16 product exists for the forward (B_KN) alone
+  void (*const k[4])(SconvGemmP) = {sconv_gemm_kernel<NB, 0, B_KN>, sconv_gemm_kernel<NB, 1, B_KN>, sconv_gemm16_kernel<NB, false, B_KN>,
+                                    B_KN ? sconv_gemm16_kernel<NB, true, true> : nullptr};
+  return launch_row_product(k, p, NB, mode, st);
 }
 
 // the wave owns every column up to 128; wider outputs take two column groups of the smallest width that covers them.  Where
@@ -243,12 +196,8 @@ int launch_gemm(const SconvGemmP& p, int mode, hipStream_t st) {
 template <int TA>
 int launch_wgrad_ta(const CsnSparseConvArgs& a, float* out, int splits, int chunk, int mode, hipStream_t st) {
   const dim3 grid((unsigned)((a.c_out + 63) / 64), (unsigned)(a.c_in / (32 * TA)), (unsigned)(splits * a.kv)), block(256);
-  if (mode == 0)
-    hipLaunchKernelGGL((sconv_wgrad_kernel<TA, 0>), grid, block, 0, st, a.x, a.ld_x, a.n_in, a.fwd_table, a.dy, a.ld_dy, out, a.n_out,
-                       a.c_in, a.c_out, a.kv, chunk);
-  else
-    hipLaunchKernelGGL((sconv_wgrad_kernel<TA, 1>), grid, block, 0, st, a.x, a.ld_x, a.n_in, a.fwd_table, a.dy, a.ld_dy, out, a.n_out,
-                       a.c_in, a.c_out, a.kv, chunk);
+  auto* const k = mode == 0 ? sconv_wgrad_kernel<TA, 0> : (mode == 1 ? sconv_wgrad_kernel<TA, 1> : sconv_wgrad16_kernel<TA>);
+  hipLaunchKernelGGL(k, grid, block, 0, st, a.x, a.ld_x, a.n_in, a.fwd_table, a.dy, a.ld_dy, out, a.n_out, a.c_in, a.c_out, a.kv, chunk);
   return (int)hipGetLastError();
 }
 
@@ -261,8 +210,8 @@ long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int 
   return backward ? ws_layout(n_out, kv, c_in, c_out).total : 0;
 }
 
+// mode: 0 fp32, 1 bf16x3, 2 bf16 / 3 fp16 single product (csn_capi.hip resolves the thread's math mode and rows16 flag)
 int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {
-  mode = mode != 0;
   SconvGemmP p{};
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = a.bias;
@@ -276,7 +225,6 @@ long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out) {
 // the forward product with the statistics epilogue, then the tiles' (mean, M2) merged in fp64 in a fixed order (rows_bn_act.hip)
 int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
                                      float eps, float momentum, int mode, hipStream_t st) {
-  mode = mode != 0;
   SconvGemmP p{};
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = nullptr;
@@ -287,7 +235,7 @@ int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, fl
 }
 
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {
-  mode = mode != 0;
+  if (mode == 3) return -1;                                           // fp16 is forward only
   const WsLayout L = ws_layout(a.n_out, a.kv, a.c_in, a.c_out);
   char* ws = static_cast<char*>(a.ws);
   if (a.dx) {

@@ -253,6 +253,25 @@ class act16:
         return False
 
 
+class rows16:
+    """``with rows16(flag):`` — the calling thread's row products of the MinkowskiNet side (fc_layer, sparse convolution and its
+    statistics form; include/csn_hip.h sections 13, 14, 15a) run their single-product instances in math modes 2 / 3 inside the block
+    (csn_set_thread_rows16); False / 0: those modes run there as bf16x3 (the default).  The previous value returns on exit."""
+
+    def __init__(self, flag):
+        self.flag = int(bool(flag))
+
+    def __enter__(self):
+        L = _lib.lib()
+        self.prev = L.csn_get_thread_rows16()
+        _lib.check(L.csn_set_thread_rows16(self.flag))
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().csn_set_thread_rows16(self.prev)
+        return False
+
+
 class score_layout:
     """Bracket: the block-attention calls inside store their scores / P / dS planes tile-major (csn_set_thread_score_layout)."""
 

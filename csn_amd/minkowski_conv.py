@@ -318,14 +318,16 @@ class _SparseConv(torch.autograd.Function):
         CF._need_cuda(x, w, b, kmap.fwd)
         L = _lib.lib()
         ctx.mode = CF.current_mode()
+        ctx.rows16 = tuning.current().rows_single_product
         x = x.contiguous()
         w_c = w.detach().contiguous()
         b_c = None if b is None else b.detach().reshape(-1).contiguous()
         KV, c_in, c_out = w_c.shape
         n_in, n_out = kmap.n_in, kmap.n_out
         y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
-        _lib.check(L.csn_sparse_conv_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
-                                             CF._ptr(b_c), CF._ptr(y), c_out, CF._stream()), "csn_sparse_conv_fwd_f32")
+        with CF.rows16(ctx.rows16):
+            _lib.check(L.csn_sparse_conv_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
+                                                 CF._ptr(b_c), CF._ptr(y), c_out, CF._stream()), "csn_sparse_conv_fwd_f32")
         ctx.save_for_backward(x, w_c)
         ctx.kmap = kmap
         ctx.b_shape = None if b is None else b.shape
@@ -334,7 +336,7 @@ class _SparseConv(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        with CF.math_mode(CF.backward_mode(ctx.mode)):
+        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
             x, w = ctx.saved_tensors
             kmap = ctx.kmap
             L = _lib.lib()

@@ -45,6 +45,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import functional as CF
+from . import tuning
 from .minkowski_attention import MultiHeadAttention, ScaledDotProduct, _CrossMHA, _up
 
 LN_WIDTHS = (32, 64, 96, 128, 256)          # d_model instances of the LayerNorm epilogues (DESIGN §1 "Not supported")
@@ -253,6 +254,7 @@ class _RowsFC(torch.autograd.Function):
         CF._need_cuda(x, w, b, gamma, beta, running_mean, running_var)
         L = _lib.lib()
         ctx.mode = CF.current_mode()
+        ctx.rows16 = tuning.current().rows_single_product
         x = x.contiguous()
         w_c, b_c, g_c, be_c = (t.detach().contiguous() for t in (w, b, gamma, beta))
         N, c_in = x.shape
@@ -267,10 +269,11 @@ class _RowsFC(torch.autograd.Function):
             invstd = torch.empty((C,), device=dev, dtype=torch.float32)
             ws_n = int(L.csn_rows_fc_workspace_bytes(N, c_in, C, 1, 0))
             ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
-        _lib.check(L.csn_rows_fc_fwd_f32(CF._ptr(x), c_in, N, c_in, C, CF._ptr(w_c), CF._ptr(b_c), CF._ptr(g_c), CF._ptr(be_c),
-                                         CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum), int(training),
-                                         CF._ptr(y), C, CF._ptr(z), C, CF._ptr(mean), CF._ptr(invstd), CF._ptr(ws), ws_n,
-                                         CF._stream()), "csn_rows_fc_fwd_f32")
+        with CF.rows16(ctx.rows16):                                        # training and eval (the folded epilogue) alike
+            _lib.check(L.csn_rows_fc_fwd_f32(CF._ptr(x), c_in, N, c_in, C, CF._ptr(w_c), CF._ptr(b_c), CF._ptr(g_c), CF._ptr(be_c),
+                                             CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum), int(training),
+                                             CF._ptr(y), C, CF._ptr(z), C, CF._ptr(mean), CF._ptr(invstd), CF._ptr(ws), ws_n,
+                                             CF._stream()), "csn_rows_fc_fwd_f32")
         if training:
             ctx.save_for_backward(x, w_c, b_c, g_c, y, z, mean, invstd)
         else:
@@ -280,7 +283,7 @@ class _RowsFC(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        with CF.math_mode(CF.backward_mode(ctx.mode)):
+        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
             x, w, b, gamma, y, z, s_mean, s_scale = ctx.saved_tensors
             L = _lib.lib()
             N, c_in = x.shape

@@ -38,6 +38,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import functional as CF
 from . import minkowski_conv as _mc
+from . import tuning
 from .minkowski_conv import KernelMap, SparseConv3d, SparseConvTranspose3d, build_kernel_map, sparse_conv3d
 from .minkowski_csn import SimCSNHead, offsets_from_batch_index
 
@@ -135,6 +136,7 @@ class _ConvStats(torch.autograd.Function):
         CF._need_cuda(x, w, kmap.fwd, running_mean, running_var)
         L = _lib.lib()
         ctx.mode = CF.current_mode()
+        ctx.rows16 = tuning.current().rows_single_product
         x = x.contiguous()
         w_c = w.detach().contiguous()
         KV, c_in, c_out = w_c.shape
@@ -145,10 +147,11 @@ class _ConvStats(torch.autograd.Function):
         invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
         ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out))
         ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
-        _lib.check(L.csn_sparse_conv_stats_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
-                                                   CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
-                                                   CF._ptr(running_var), float(eps), float(momentum), CF._ptr(ws), ws_n,
-                                                   CF._stream()), "csn_sparse_conv_stats_fwd_f32")
+        with CF.rows16(ctx.rows16):
+            _lib.check(L.csn_sparse_conv_stats_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
+                                                       CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
+                                                       CF._ptr(running_var), float(eps), float(momentum), CF._ptr(ws), ws_n,
+                                                       CF._stream()), "csn_sparse_conv_stats_fwd_f32")
         ctx.save_for_backward(x, w_c)
         ctx.kmap = kmap
         ctx.mark_non_differentiable(mean, invstd)
@@ -157,7 +160,7 @@ class _ConvStats(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, _dmean, _dinvstd):
-        with CF.math_mode(CF.backward_mode(ctx.mode)):
+        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
             x, w = ctx.saved_tensors
             kmap = ctx.kmap
             L = _lib.lib()

@@ -1,9 +1,10 @@
 """Data-flow switches of the step and the bench's event hook — kept out of the product modules.
 
 Every switch selects between two forms of the SAME arithmetic (a fused pass and the plain pass it replaced, or two data
-flows of the attention backward); the defaults are the measured-faster forms.  Nothing here changes results
-beyond fp32 rounding; `tests/test_gpu_module.py::test_fused_data_flow_equals_the_unfused_one` and
-`tests/test_gpu_flash.py` flip them through ``override`` to check one form against the other (`bench.py` times the launches
+flows of the attention backward); the defaults are the measured-faster forms.  With ONE exception nothing here
+changes results beyond fp32 rounding: ``rows_single_product`` selects arithmetic — with it the bf16 / fp16 math modes round the
+operands of the MinkowskiNet row products to 16 bits instead of running them as bf16x3 (off by default).
+`tests/test_gpu_module.py::test_fused_data_flow_equals_the_unfused_one` and `tests/test_gpu_flash.py` flip the others through ``override`` to check one form against the other (`bench.py` times the launches
 through csn_amd._lib.set_call_hook, not through anything here).  The state is process-wide on purpose: autograd runs the backward on its own threads, and a step must see the
 same switches in both passes.
 """
@@ -73,6 +74,12 @@ class Tuning:
     # downstream is the same launch.  CPU tensors keep the torch backend whatever this says.  Off: opt-in until the default is flipped
     # on its own (timing: DESIGN.md "Kernel maps", scripts/bench_kernel_map.py)
     native_kernel_maps: bool = False
+    # math modes "bf16" / "fp16" on the MinkowskiNet side: fc_layer, the sparse convolutions and their statistics form (_RowsFC,
+    # _SparseConv, _ConvStats) run ONE 16-bit product per operand pair (csn_set_thread_rows16; an fp16 forward runs its backward in
+    # bf16) instead of bf16x3.  Unlike every other switch here this one selects ARITHMETIC: operands are rounded to 16 bits, the
+    # results leave the 1e-4 contract of bf16x3 as those modes do on the attention side.  Modes fp32 / bf16x3 never see it.  Off:
+    # opt-in until the default is flipped in a change of its own (errors and timing: DESIGN.md "Single-product row products")
+    rows_single_product: bool = False
 
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))

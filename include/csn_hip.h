@@ -58,6 +58,15 @@ CSN_API int csn_version(void);
  *                      (csn_amd does: "fp16 forward / bf16 backward").
  * The retrieval measure (7) always runs in exact fp32 (bit-exact kNN indices).  The cross-length entry points (3b) have no
  * single-product kernels: in modes 2 / 3 they run as mode 1.
+ * The row products of the MinkowskiNet side — (13) csn_rows_fc_*, (14) csn_sparse_conv_*, (15a) csn_sparse_conv_stats_fwd_f32 —
+ * have single-product instances behind a per-thread, opt-in flag, csn_set_thread_rows16(on): on = 0 (THE DEFAULT) runs modes 2 / 3
+ * as mode 1 there, as before the instances existed; on = 1 runs mode 2 in every forward and backward entry point of those sections
+ * (the folded eval epilogue of csn_rows_fc_fwd_f32 included) and mode 3 in their FORWARD entry points (csn_sparse_conv_fwd_f32,
+ * csn_sparse_conv_stats_fwd_f32, csn_rows_fc_fwd_f32) with every operand rounded once to 16 bits (nearest even), one
+ * v_mfma_f32_32x32x16_{bf16,f16} per product, fp32 accumulation, fp32 maps in memory as ever; mode 3 then makes
+ * csn_sparse_conv_bwd_f32 and csn_rows_fc_bwd_f32 return CSN_E_ARG before any launch (callers run them in mode 2).  Modes 0 and 1
+ * do not see the flag.  Any other value of `on` returns CSN_E_ARG and leaves the flag; csn_get_thread_rows16 returns it.
+ * What the matrix instruction does with fp16 SUBNORMAL operands (|v| < 2^-14) is not pinned.
  * csn_set_math_mode sets the PROCESS default; csn_set_thread_math_mode overrides it for the calling thread only (-1 clears the
  * override), which is how a module selects its own mode per call without touching other threads (csn_amd brackets every
  * forward / backward with it; autograd's backward threads set their own).  csn_get_math_mode returns the mode in effect for
@@ -104,6 +113,9 @@ CSN_API int csn_version(void);
  * bf16 anyway — the weight gradients are the same bits. */
 CSN_API int csn_set_thread_act16(int fmt);
 CSN_API int csn_get_thread_act16(void);
+/* single-product row products of (13), (14), (15a) for the calling thread: see the math-mode comment above */
+CSN_API int csn_set_thread_rows16(int on);
+CSN_API int csn_get_thread_rows16(void);
 /* SCORE STORAGE of the block-attention entry points (3), (3c), per calling thread.  0 (default): the scores of a block are
  * [query][key] rows of pitch score_pitch — what a caller that reads probabilities expects.  1: TILE-MAJOR — per block
  * [key tile of 32][query][32 keys]: the forward's scores, and the P / dS tile planes the backward hands from its dQ call to its
@@ -637,7 +649,8 @@ CSN_API int csn_ragged_seg_bwd_f32(const float* logits, int n_rows, int ld, cons
  *   dx = dz w,  dw = dz^T x (split-K over the rows, slabs added in order),  dbias = sum_n dz — each skipped when its pointer is NULL.
  *   Column sums are fp64 partials of 64-row chunks added in a fixed order.
  * No floating-point atomics: two identical calls give the same bits.  Math mode 0 runs the three products on the exact fp32 matrix
- * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (3b). */
+ * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (3b), unless csn_set_thread_rows16(1) selects their single-product
+ * instances (mode 3: the forward only; csn_rows_fc_bwd_f32 then returns CSN_E_ARG). */
 CSN_API long long csn_rows_fc_workspace_bytes(int n_rows, int c_in, int c_out, int training, int backward);
 CSN_API int csn_rows_fc_fwd_f32(const float* x, long long ld_x, int n_rows, int c_in, int c_out, const float* w, const float* bias,
                         const float* gamma, const float* beta, float* running_mean, float* running_var, float eps, float momentum,
@@ -675,7 +688,8 @@ CSN_API int csn_rows_fc_bwd_f32(const float* dy, long long ld_dy, const float* y
  *   dbias = sum_j dy[j]                       fp64 partials of 64-row chunks added in chunk order; reads dy
  *   — each skipped when its pointer is NULL (its own inputs may then be NULL too), the others are unchanged by that.
  * No floating-point atomics: two identical calls give the same bits.  Math mode 0 runs the products on the exact fp32 matrix
- * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (13). */
+ * instruction, mode 1 as bf16x3; modes 2 / 3 run as mode 1, like (13), unless csn_set_thread_rows16(1) selects their single-product
+ * instances (mode 3: the forward only; csn_sparse_conv_bwd_f32 then returns CSN_E_ARG). */
 CSN_API long long csn_sparse_conv_workspace_bytes(int n_in, int n_out, int kv, int c_in, int c_out, int backward);
 CSN_API int csn_sparse_conv_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
                             const float* w, const float* bias, float* y, long long ld_y, void* stream);

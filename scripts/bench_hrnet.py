@@ -7,7 +7,10 @@ Voxels: ``--voxels`` (32768) from 8 synthetic ellipsoid shells (scripts/bench_sp
 the timed window, as a training loop would per batch.  HIP events around each forward + backward; every variant is warmed up, then
 timed in ``--rounds`` alternating rounds of ``--iters`` steps: the figure is the median over the rounds of each round's median,
 ``spread`` its min and max over the rounds.  ``fused_is_faster`` is true only when the fused median lies below the unfused one by more
-than both spreads.  ``--only fused|unfused`` runs one variant (a profiler pass wants one).  Prints one JSON line.
+than both spreads.  ``--only fused|unfused`` runs one variant (a profiler pass wants one).  ``--variants`` names the variants
+outright and adds ``mode2`` (bf16 forward + backward) and ``mode3`` (fp16 forward, bf16 backward): the fused network on the
+single-product row products (``tuning.rows_single_product`` on), whatever ``--mode`` says; ``--mode bf16`` / ``fp16`` runs ``fused`` and
+``unfused`` so too.  Prints one JSON line.
 
     python scripts/bench_hrnet.py --out profiles/hrnet_bench.json
 """
@@ -62,8 +65,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--mode", default="bf16x3", help="math mode of the products: fp32 or bf16x3 (the library's default)")
+    ap.add_argument("--mode", default="bf16x3", help="math mode of fused / unfused: fp32, bf16x3 (the library's default), bf16 or fp16")
     ap.add_argument("--only", default="", help="fused or unfused: run that variant alone")
+    ap.add_argument("--variants", default="", help="comma-separated: fused, unfused, mode2, mode3 (default: fused,unfused)")
     ap.add_argument("--skip-blocks", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -71,6 +75,7 @@ def main():
     csn_amd.build()
     from csn_amd import HRBasicBlock, HRNetBackbone, SparseBasicBlock, build_pyramid
     from csn_amd import functional as CF
+    from csn_amd import tuning
     torch.manual_seed(0)
     coords = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
     pyr = build_pyramid(coords, 3)
@@ -78,23 +83,29 @@ def main():
     res = {"voxels": int(n), "level_rows": [int(c.shape[0]) for c in pyr.coords], "shapes": a.shapes, "warmup": a.warmup,
            "iters": a.iters, "rounds": a.rounds, "mode": a.mode, "device": torch.cuda.get_device_name(0)}
     feats = torch.randn(n, 3, device="cuda")
-    want = [v for v in ("fused", "unfused") if not a.only or v == a.only]
+    want = [v for v in a.variants.split(",") if v] or [v for v in ("fused", "unfused") if not a.only or v == a.only]
+    # a variant's math mode, and whether it runs the single-product row products
+    arith = {v: {"mode2": (2, True), "mode3": (3, True)}.get(v, (CF.mode_id(a.mode), CF.mode_id(a.mode) >= 2)) for v in want}
 
-    with CF.math_mode(CF.mode_id(a.mode)):
-        nets = {v: HRNetBackbone(3, 3, 2, fused=(v == "fused")).cuda().train() for v in want}
+    with CF.math_mode(CF.mode_id(a.mode)), tuning.override(rows_single_product=CF.mode_id(a.mode) >= 2):
+        nets = {v: HRNetBackbone(3, 3, 2, fused=(v != "unfused")).cuda().train() for v in want}
         for v in want[1:]:
             nets[v].load_state_dict(nets[want[0]].state_dict())
         dy = torch.randn(n, nets[want[0]].out_channels, device="cuda")
 
-        def step_of(net):
+        def step_of(v):
+            net, (mode, single) = nets[v], arith[v]
+
             def step():
                 for p in net.parameters():
                     p.grad = None
-                net(feats, pyr).backward(dy)
+                with CF.math_mode(mode), tuning.override(rows_single_product=single):
+                    net(feats, pyr).backward(dy)
             return step
-        res["backbone_3S_train_fwd_bwd"] = compare({v: step_of(nets[v]) for v in want}, a.warmup, a.iters, a.rounds)
+        res["backbone_3S_train_fwd_bwd"] = compare({v: step_of(v) for v in want}, a.warmup, a.iters, a.rounds)
         del nets
-        if not a.skip_blocks:
+        want = [v for v in want if v in ("fused", "unfused")]
+        if not a.skip_blocks and want:
             res["blocks_train_fwd_bwd"] = {}
             for level, c in enumerate((64, 128, 256)):
                 kmap, rows = pyr.s1[level], pyr.coords[level].shape[0]

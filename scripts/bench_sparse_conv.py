@@ -12,7 +12,8 @@ matrix products of existing (offset, row) pairs: forward 2 P c_in c_out, backwar
 implementation has to move once: forward x, table, W, y; backward dy, x, both tables, W, dx, dW — a lower bound computed from the
 shapes, not measured traffic.  The forward call is one launch; the backward call is the sum of its launches (dx, dW, the slab
 sum, the two dbias kernels when there is a bias).  Per-launch times and memory-side bytes come from profiler passes over
-``--layers NAME --variants mode1`` (profiles/sparse_conv_launches.txt).  Prints one JSON line.
+``--layers NAME --variants mode1`` (profiles/sparse_conv_launches.txt).  ``mode2`` (bf16 forward + backward) and ``mode3`` (fp16
+forward, bf16 backward) are the single-product row products: both run with ``tuning.rows_single_product`` on.  Prints one JSON line.
 
     python scripts/bench_sparse_conv.py --out profiles/sparse_conv_bench.json
 """
@@ -67,12 +68,14 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", default="", help="comma-separated substrings of the layer names to run (default: all)")
-    ap.add_argument("--variants", default="mode0,mode1,eager", help="which of mode0, mode1, eager to run (a profiler pass wants one)")
+    ap.add_argument("--variants", default="mode0,mode1,eager",
+                    help="which of mode0, mode1, mode2, mode3, eager to run (a profiler pass wants one)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import csn_amd
     csn_amd.build()
     from csn_amd import functional as CF
+    from csn_amd import tuning
     from csn_amd.minkowski_conv import build_kernel_map, sparse_conv3d
     torch.manual_seed(0)
     c1 = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
@@ -109,7 +112,7 @@ def main():
             x.grad = w.grad = None
             y.backward(dy)
 
-        variants = {"mode0": (0, ours), "mode1": (1, ours), "eager": (None, eager)}
+        variants = {"mode0": (0, ours), "mode1": (1, ours), "mode2": (2, ours), "mode3": (3, ours), "eager": (None, eager)}
         variants = {v: variants[v] for v in a.variants.split(",")}
         cip = -(-ci // 32) * 32
         mb_f = (n * cip + KV * n + KV * cip * co + n * co) * 4 / 1e6
@@ -120,7 +123,7 @@ def main():
         for rnd in range(a.rounds + 1):                                          # round 0 is the warm-up
             it = a.warmup if rnd == 0 else a.iters
             for v, (mode, fn) in variants.items():
-                with CF.math_mode(mode):
+                with CF.math_mode(mode), tuning.override(rows_single_product=v in ("mode2", "mode3")):
                     tf = timed(lambda: None, fn, it)
                     tb = timed(fn, back, it)
                 if rnd:
