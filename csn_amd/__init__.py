@@ -33,3 +33,7 @@ from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetS
 # point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
 # (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))
 from .minkowski_field import PointField, batch_points  # noqa: E402,F401
+
+# resident point collections: a category's points on the device, normalised once, augmented and collated per batch
+# (MinkowskiNet/lib/dataset.py:104-126, 221-252, lib/transforms.py:12-89, 195-225, lib/voxelizer.py:34-45)
+from .minkowski_points import AugmentParams, AugmentSpec, PointBatch, PointCollection  # noqa: E402,F401

@@ -1462,4 +1462,62 @@ int csn_kernel_map_i32(const long long* set_keys, const int* set_rows, int n_set
   return csn_launch_kernel_map(a, (hipStream_t)stream);
 }
 
+// ---- (18) resident point collections: normalise, bound, augment + collate + key; a PointField's index arrays ----
+static int points_collection(const float* points, const long long* offsets, int n_shapes, long long n_total, const int* status) {
+  if (!points || !offsets || !status) return CSN_E_ARG;
+  if (n_shapes < 1 || n_total < 1) return CSN_E_ARG;
+  if (mis4(points) || mis8(offsets) || mis4(status)) return CSN_E_PTR;
+  return 0;
+}
+
+int csn_points_normalize_f32(const float* points, const long long* offsets, int n_shapes, long long n_total, int method, float* out,
+                             int* status, void* stream) {
+  if (const int e = points_collection(points, offsets, n_shapes, n_total, status)) return e;
+  if (!out || (method != 0 && method != 1)) return CSN_E_ARG;
+  if (mis4(out)) return CSN_E_PTR;
+  CsnPointsArgs a{};
+  a.points = points; a.offsets = offsets; a.n_shapes = n_shapes; a.n_total = n_total; a.method = method; a.out = out; a.status = status;
+  return csn_launch_points_normalize(a, (hipStream_t)stream);
+}
+
+int csn_points_bounds_f64(const float* points, const long long* offsets, int n_shapes, long long n_total, const long long* idx,
+                          const double* params, int n_items, double* bounds, int* status, void* stream) {
+  if (const int e = points_collection(points, offsets, n_shapes, n_total, status)) return e;
+  if (!idx || !params || !bounds || n_items < 1) return CSN_E_ARG;
+  if (mis8(idx) || mis8(params) || mis8(bounds)) return CSN_E_PTR;
+  CsnPointsArgs a{};
+  a.points = points; a.offsets = offsets; a.n_shapes = n_shapes; a.n_total = n_total; a.idx = idx; a.params = params;
+  a.n_items = n_items; a.bounds = bounds; a.status = status;
+  return csn_launch_points_bounds(a, (hipStream_t)stream);
+}
+
+int csn_points_batch_f32(const float* points, const int* labels, const long long* offsets, int n_shapes, long long n_total,
+                         const long long* idx, const long long* out_offsets, const double* params, const double* bounds, int n_items,
+                         int max_points, double sigma, double clip, double voxel_size, float* coords, float* feats, long long* labels_out,
+                         long long* keys, long long n_out, int* status, void* stream) {
+  if (const int e = points_collection(points, offsets, n_shapes, n_total, status)) return e;
+  if (!idx || !out_offsets || !params || !bounds || !coords || !feats || !keys || (labels && !labels_out)) return CSN_E_ARG;
+  if (n_items < 1 || max_points < 1 || n_out < 1) return CSN_E_ARG;
+  if (!(sigma >= 0.0) || !(clip > 0.0) || !(voxel_size > 0.0)) return CSN_E_ARG;               // (a NaN fails all three)
+  if (n_items > 65535) return CSN_E_DIM;                                                         // one grid row per item
+  if (mis8(idx) || mis8(out_offsets) || mis8(params) || mis8(bounds) || mis16(coords) || mis4(feats) || mis8(keys) ||
+      (labels && (mis4(labels) || mis8(labels_out)))) return CSN_E_PTR;
+  CsnPointsArgs a{};
+  a.points = points; a.labels = labels; a.offsets = offsets; a.n_shapes = n_shapes; a.n_total = n_total; a.idx = idx;
+  a.out_offsets = out_offsets; a.params = params; a.bounds = const_cast<double*>(bounds); a.n_items = n_items; a.max_points = max_points;
+  a.sigma = sigma; a.clip = clip; a.voxel_size = voxel_size; a.coords = coords; a.feats = feats; a.labels_out = labels_out; a.keys = keys;
+  a.n_out = n_out; a.status = status;
+  return csn_launch_points_batch(a, (hipStream_t)stream);
+}
+
+int csn_field_index_i32(const long long* skeys, const long long* order, const long long* vid, int n_points, int n_voxels, int* home,
+                        int* vox_ptr, int* vox_pts, long long* uniq_keys, int* status, void* stream) {
+  if (!skeys || !order || !vid || !home || !vox_ptr || !vox_pts || !uniq_keys || !status) return CSN_E_ARG;
+  if (n_points < 1 || n_voxels < 1) return CSN_E_ARG;
+  if (n_voxels > n_points) return CSN_E_DIM;
+  if (mis8(skeys) || mis8(order) || mis8(vid) || mis8(uniq_keys) || mis4(home) || mis4(vox_ptr) || mis4(vox_pts) || mis4(status))
+    return CSN_E_PTR;
+  return csn_launch_field_index(skeys, order, vid, n_points, n_voxels, home, vox_ptr, vox_pts, uniq_keys, status, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -374,3 +374,26 @@ struct CsnKernelMapArgs {
 int csn_launch_coord_keys(const long long* coords, int n, int tensor_stride, long long* keys, int* status, hipStream_t st);
 int csn_launch_coord_down(const long long* keys, int n, int out_tensor_stride, long long* down_keys, hipStream_t st);
 int csn_launch_kernel_map(const CsnKernelMapArgs& a, hipStream_t st);
+
+// ---- resident point collections: normalise, bound, augment + collate + key, and a PointField's index arrays (points.hip) ----
+constexpr int CSN_POINTS_NPARAM = 9;                              // per item: cos, sin, shift_z[3], jitter[3], scale
+struct CsnPointsArgs {
+  const float* points;                                            // [n_total][3] the collection, flat
+  const int* labels;                                              // [n_total] or NULL
+  const long long* offsets;                                       // [n_shapes + 1] the rows of every shape
+  int n_shapes;  long long n_total;
+  float* out;  int method;                                        // normalize: [n_total][3] written (may be points); 0 sphere, 1 box
+  const long long* idx;                                           // [n_items] the shape of every batch item
+  const long long* out_offsets;                                   // [n_items] the first output row of every item
+  const double* params;                                           // [n_items][CSN_POINTS_NPARAM]
+  double* bounds;                                                 // [n_items][6] min xyz, max xyz of the rotated points (bounds: written)
+  int n_items, max_points;                                        // max_points: the longest shape among the items
+  double sigma, clip, voxel_size;
+  float* coords;  float* feats;  long long* labels_out;  long long* keys;  long long n_out;      // batch: written, n_out rows
+  int* status;                                                    // one word, or-ed into
+};
+int csn_launch_points_normalize(const CsnPointsArgs& a, hipStream_t st);
+int csn_launch_points_bounds(const CsnPointsArgs& a, hipStream_t st);
+int csn_launch_points_batch(const CsnPointsArgs& a, hipStream_t st);
+int csn_launch_field_index(const long long* skeys, const long long* order, const long long* vid, int n_points, int n_voxels, int* home,
+                           int* vox_ptr, int* vox_pts, long long* uniq_keys, int* status, hipStream_t st);

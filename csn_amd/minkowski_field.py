@@ -183,6 +183,62 @@ class PointField:
         self._pyramid: Optional[VoxelPyramid] = None
         self._table: Optional[torch.Tensor] = None
 
+    @classmethod
+    def from_keys(cls, coords: torch.Tensor, feats: torch.Tensor, keys: torch.Tensor, status: torch.Tensor, offsets,
+                  quantization_mode: str = "random_subsample") -> "PointField":
+        """The field ``PointField(coords, feats, quantization_mode)`` builds — every attribute equal — from what a
+        ``csn_amd.minkowski_points.PointBatch`` already knows: ``keys (Np,)`` int64 the packed key of every point's home voxel,
+        ``status (1,)`` int32 the device word the batch kernels flagged bad points in, ``offsets (B + 1,)`` the point rows of every
+        shape on the host.  One stable sort and one scan in torch, ONE host read (the status word, the voxel count and the voxel rows
+        of every shape), then ``csn_field_index_i32`` (include/csn_hip.h section 18d) writes ``home``, ``vox_ptr``, ``vox_pts`` and
+        the unique keys.  A non-zero status raises ``ValueError`` with the constructor's own message; device tensors only."""
+        if quantization_mode not in QUANTIZATION_MODES:
+            raise ValueError(f"quantization_mode must be one of {QUANTIZATION_MODES}")
+        if coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] < 1 or coords.dtype != torch.float32:
+            raise ValueError("coords must be a non-empty (Np, 4) float32 tensor [b, x, y, z] in voxel units")
+        if feats.dim() != 2 or feats.shape[0] != coords.shape[0] or feats.shape[1] < 1 or feats.dtype != torch.float32:
+            raise ValueError("feats must be (Np, Cf) float32, one row per point")
+        n_pts = coords.shape[0]
+        if keys.dim() != 1 or keys.shape[0] != n_pts or keys.dtype != torch.int64:
+            raise ValueError("keys must be (Np,) int64, one packed key per point")
+        if status.numel() != 1 or status.dtype != torch.int32:
+            raise ValueError("status must be one int32 word")
+        if len({coords.device, feats.device, keys.device, status.device}) != 1:
+            raise ValueError("coords, feats, keys and status must be on one device")
+        off = torch.as_tensor(offsets).reshape(-1).to("cpu", torch.int64)
+        if off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != n_pts or bool((off[1:] <= off[:-1]).any()):
+            raise ValueError("offsets must start at 0, increase strictly (every shape >= 1 point) and end at the point count")
+        if off.numel() - 1 > (1 << _B_BITS):
+            raise ValueError(f"batch indices must be integers in [0, {1 << _B_BITS})")
+        if not coords.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        CF._need_cuda(coords, feats, status)
+        dev = coords.device
+        skeys, order = torch.sort(keys, stable=True)                # stable: ascending point numbers inside a voxel
+        vid = torch.cat([skeys.new_zeros(1), (skeys[1:] != skeys[:-1]).cumsum(0)])
+        starts = off[:-1].to(dev)
+        word = torch.cat([status.reshape(1).long(), vid[-1:] + 1, vid[starts]]).tolist()       # the one host read
+        if word[0] != 0:
+            cls(coords, feats, quantization_mode)                   # the constructor's checks and message, the failing call's price
+            raise ValueError(f"the points are not valid (point-batch status {word[0]})")
+        n_vox = word[1]
+        f = object.__new__(cls)
+        f.quantization_mode = quantization_mode
+        f.coords, f.feats = coords.contiguous(), feats.contiguous()
+        f.home = torch.empty(n_pts, dtype=torch.int32, device=dev)
+        f.vox_ptr = torch.empty(n_vox + 1, dtype=torch.int32, device=dev)
+        f.vox_pts = torch.empty(n_pts, dtype=torch.int32, device=dev)
+        uniq = torch.empty(n_vox, dtype=torch.int64, device=dev)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)       # (raised only by arrays that are no sort and scan: not read)
+        _lib.check(_lib.lib().csn_field_index_i32(CF._ptr(skeys), CF._ptr(order), CF._ptr(vid), n_pts, n_vox, CF._ptr(f.home),
+                                                  CF._ptr(f.vox_ptr), CF._ptr(f.vox_pts), CF._ptr(uniq), CF._ptr(flags), CF._stream()),
+                   "csn_field_index_i32")
+        f.voxel_coords = _unpack(uniq)
+        f.offsets = off
+        f.voxel_offsets = torch.tensor(word[2:] + [n_vox], dtype=torch.int64)
+        f._voxel_feats = f._pyramid = f._table = None
+        return f
+
     # ---- sizes ----
     @property
     def n_points(self) -> int:

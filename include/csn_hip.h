@@ -811,6 +811,54 @@ CSN_API int csn_coord_down_i64(const long long* keys, int n, int out_tensor_stri
 CSN_API int csn_kernel_map_i32(const long long* set_keys, const int* set_rows, int n_set, const long long* query_keys, int n_query,
                        int kernel_size, int step, int* table, int* status, void* stream);
 
+/* ---- (18) resident point collections: normalise, augment, collate and key a batch of shapes on the device (MinkowskiNet/lib/
+ *           dataset.py:104-126, 221-252, lib/transforms.py:12-89, 195-225, lib/voxelizer.py:34-45) ---------------------------------
+ * The reference keeps a category's points in host memory and runs a numpy chain per item and step; csn_amd.minkowski_points keeps
+ * them on the device and builds a batch with the entry points below.  Additive to ABI version 17.
+ * COLLECTION: points[n_total][3] fp32 (contiguous), offsets[n_shapes + 1] int64 on the DEVICE: shape s is the rows
+ *   [offsets[s], offsets[s + 1]), at least one; labels[n_total] int32 or NULL.
+ * ITEMS of a batch: idx[n_items] int64 the shape of every item (repeats, any order); params[n_items][9] float64 =
+ *   cos, sin, shift_z[3], jitter[3], scale (the cosine and sine of the rotation angle come from the host: no trigonometry here);
+ *   out_offsets[n_items] int64 the first output row of every item; bounds[n_items][6] float64 = min x, y, z, max x, y, z.
+ * ARITHMETIC: float64 on the fp32 inputs, every operation rounded on its own (no fused multiply-add between a product and an add;
+ *   division and square root correctly rounded), sums of three terms as (a + b) + c.  No floating-point atomics: two calls give
+ *   the same bits.
+ * STATUS WORD, as in (17): one int32 on the device, zeroed by the caller, or-ed into:
+ *   1 an item number >= 2^15;  2 a floor(x), floor(y) or floor(z) outside [-2^15, 2^15);  16 a non-finite parameter or coordinate
+ *   (then 2 is not raised for that point);  32 a shape index, a CSR offset pair, an output row, a sort position or a voxel number
+ *   outside its array: that item or point is SKIPPED (csn_points_bounds_f64 writes zeros for it).  4 and 8 keep their meaning of (17)
+ *   and are never raised here.  Nothing is dereferenced through a bad value.  The arrays live on the device, so a bad shape index
+ *   cannot be a host-side error here: csn_amd checks its index lists on the host (ValueError) before any launch.
+ * Host-side checks before any launch: a NULL pointer (labels may be NULL, labels_out with it), a count < 1, method not 0 or 1,
+ *   sigma < 0, clip <= 0, voxel_size <= 0 or any of them NaN: CSN_E_ARG; n_items > 65535 (one grid row per item), n_voxels >
+ *   n_points: CSN_E_DIM; an fp32 / int32 array or the status word off 4 bytes, an int64 / float64 array off 8 bytes, coords off 16
+ *   bytes: CSN_E_PTR.
+ * (18a) csn_points_normalize_f32: per shape c = (sum p) / n and a radius r: method 0 (sphere) r = sqrt(max |p - c|^2), method 1 (box)
+ *   r = the diagonal of the bounding box of p - c; r = max(r, 2^-22) (2 eps_fp32); out = fp32((p - c) / r).  out may be points.  One
+ *   work-group of 256 threads per shape; the sum is thread t's partial over the rows t, t + 256, ... in that order, then a binary
+ *   tree over the 256 partials (partial t + partial t + w, w = 128 .. 1).
+ * (18b) csn_points_bounds_f64: per item the minimum and maximum per axis of r = (c x + s z, y, (-s) x + c z): each product rounded,
+ *   then one add.  Exact and order-free.  One work-group per item.
+ * (18c) csn_points_batch_f32: per point of every item i (grid: chunks of max_points x items), with e = max - min of (18b):
+ *   diag = sqrt((ex ex + ey ey) + ez ez);  t = clip((sigma diag) shift_z, -clip, +clip);  q = ((r + t) + jitter) scale;
+ *   feats[row] = fp32(q);  coords[row] = [fp32(i), fp32(q / voxel_size)] (a division);  keys[row] = the packed key of (17) of
+ *   [i, floor of the three STORED fp32 coordinates], -1 for a point that raised 1, 2 or 16;  labels_out[row] = labels[...] (int64);
+ *   row = out_offsets[i] + the point's number inside its shape, inside [0, n_out).  max_points >= the longest shape among the items
+ *   (points beyond it are not written).
+ * (18d) csn_field_index_i32: skeys[n_points] the ascending keys of a stable sort, order[n_points] its permutation, vid[n_points] the
+ *   number of the run of equal keys that position j belongs to (all int64): home[order[j]] = vid[j]; at every run head
+ *   vox_ptr[vid[j]] = j and uniq_keys[vid[j]] = skeys[j]; vox_ptr[n_voxels] = n_points; vox_pts[j] = order[j] (int32). */
+CSN_API int csn_points_normalize_f32(const float* points, const long long* offsets, int n_shapes, long long n_total, int method,
+                             float* out, int* status, void* stream);
+CSN_API int csn_points_bounds_f64(const float* points, const long long* offsets, int n_shapes, long long n_total, const long long* idx,
+                          const double* params, int n_items, double* bounds, int* status, void* stream);
+CSN_API int csn_points_batch_f32(const float* points, const int* labels, const long long* offsets, int n_shapes, long long n_total,
+                         const long long* idx, const long long* out_offsets, const double* params, const double* bounds, int n_items,
+                         int max_points, double sigma, double clip, double voxel_size, float* coords, float* feats,
+                         long long* labels_out, long long* keys, long long n_out, int* status, void* stream);
+CSN_API int csn_field_index_i32(const long long* skeys, const long long* order, const long long* vid, int n_points, int n_voxels,
+                        int* home, int* vox_ptr, int* vox_pts, long long* uniq_keys, int* status, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
