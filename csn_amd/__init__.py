@@ -29,6 +29,9 @@ from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseCo
 # 296-454)
 from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetSimCSN3S, HRNetSimCSN4S, VoxelPyramid,  # noqa: E402,F401
                               bn_act, build_pyramid, conv_stats, load_me_hrnet_state)
+# the plain segmentation networks (hrnet.py:214-293) and the backbone's one-launch-per-convolution inference primitive
+from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
+                              sparse_conv_bn_act)
 
 # point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
 # (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))

@@ -258,6 +258,9 @@ _SIGNATURES = {
                                         c_longlong, c_void_p]),
     "csn_rows_bn_act_bwd_f32": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                         c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p]),
+    "csn_sparse_conv_bn_act_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_longlong, c_int, c_void_p,
+                                               c_longlong, c_void_p]),
     "csn_voxel_mean_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "csn_point_interp_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong,
                                          c_void_p]),

@@ -1390,6 +1390,27 @@ int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, lo
   return csn_launch_rows_bn_act_bwd(a, (hipStream_t)stream);
 }
 
+// ---- (19) the gather-GEMM with a BatchNorm + residual + ReLU epilogue (inference) ----
+int csn_sparse_conv_bn_act_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
+                                   const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
+                                   long long ld_y, void* stream) {
+  if (!x || !table || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
+  if (const int e = sparse_conv_map(ld_y, c_out, n_out)) return e;
+  if (r) if (const int e = sparse_conv_map(ld_r, c_out, n_out)) return e;
+  if (r == y && ld_r != ld_y) return CSN_E_ARG;                   // y as its own residual: element for element, or not at all
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  CsnSparseConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
+  a.w = w; a.y = y; a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
+  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
+  return csn_launch_sparse_conv_bn_act_fwd(a, n, rows_mode(), (hipStream_t)stream);
+}
+
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
 static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 

@@ -322,6 +322,13 @@ int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t
 long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out);
 int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
                                      float eps, float momentum, int mode, hipStream_t st);
+// forward with the inference epilogue (no bias): a.y = act(z s + t + r), s = gamma / sqrt(running_var + eps), t = beta -
+// running_mean s; r optional, may be a.y itself with ld_r == a.ld_y.  One launch, no workspace
+struct CsnSconvBnArgs {
+  const float* gamma;  const float* beta;  const float* running_mean;  const float* running_var;  float eps;
+  const float* r;  int ld_r;  int relu;
+};
+int csn_launch_sparse_conv_bn_act_fwd(const CsnSparseConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule
 
 // ---- BatchNorm apply + branch sum + residual + ReLU on point-major rows, forward and backward (rows_bn_act.hip) ----

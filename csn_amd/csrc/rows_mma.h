@@ -6,7 +6,7 @@
 //   row product      a wave owns 32 rows x NB * 32 columns; a lane owns one row and 4 (fp32) / 8 (16-bit) consecutive k of every
 //                    32-k step (a_kofs); B — [J][K] or [K][J] (B_KN) — is staged through LDS once per work-group (load_b,
 //                    store_b); mma_step contracts one step; store_tile adds the bias, stores the wave's rows and forms their
-//                    (mean, M2) from the accumulators.
+//                    (mean, M2) from the accumulators; store_tile_bn stores act(acc * s + t + r) instead (inference).
 //   weight gradient  both operands are k-major (the contraction runs over the rows): a lane holds 8 rows of one column per 16-row
 //                    step (wgrad_row) and splits them in registers (wgrad_step); the four waves of a work-group contract a
 //                    quarter of its row chunk each and are added through LDS in wave order (wgrad_reduce_store).
@@ -150,6 +150,25 @@ __device__ __forceinline__ void store_tile(f32x16& acc, float bv, float* c, int 
       part[(tile * 2) * J + col] = mu;
       part[(tile * 2 + 1) * J + col] = m2;
     }
+  }
+}
+
+// The same block through an inference epilogue: y = act(acc * s + t + r) with the lane's column constants s, t (a BatchNorm on its
+// running statistics), an optional residual map r (pitch ldr) and act = ReLU or the identity; nothing but y is written.  r is read
+// through the same address form as the store, and each element is read and then written by the same lane: r may be c itself (with
+// ldr == ldc), which is how a sum over branches accumulates in one buffer.
+__device__ __forceinline__ void store_tile_bn(const f32x16& acc, float s, float t, const float* r, int ldr, bool relu, float* c, int ldc,
+                                              long long row_w, int cnt, int col, int h) {
+  float* cw = c + row_w * ldc;
+  const int lane = 4 * h * ldc + col;
+  const float* rw = r ? r + row_w * ldr : nullptr;
+  const int lane_r = 4 * h * ldr + col;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    if (csn_acc_row(q, h) >= cnt) continue;
+    float v = fmaf(acc[q], s, t);
+    if (rw) v += (rw + csn_acc_row(q, 0) * ldr)[lane_r];
+    (cw + csn_acc_row(q, 0) * ldc)[lane] = relu ? fmaxf(0.f, v) : v;
   }
 }
 

@@ -1,5 +1,7 @@
 // The body of the gather-GEMM kernels of sparse_conv.hip, included into sconv_gemm_kernel (MODE 0 fp32 / 1 bf16x3) and
-// sconv_gemm16_kernel (MODE 2 bf16 / 3 fp16: one product, the tile holds shorts) with NB, MODE, B_KN and the argument p in scope.
+// sconv_gemm16_kernel (MODE 2 bf16 / 3 fp16: one product, the tile holds shorts) with NB, MODE, B_KN, BN and the argument p in scope.
+// BN (sconv_gemm_bn_kernel / sconv_gemm16_bn_kernel: forward instances, p a SconvBnP) takes the BatchNorm + residual + ReLU epilogue
+// of store_tile_bn in place of store_tile.  The loop is the same text either way: the same sums in the same order.
 // It is text and not a __device__ function on purpose: called through a function (by reference, by value or field by field) the
 // fp32 NB = 4 dx instance takes 106 vector registers instead of 104 and loses a wave per SIMD.
   __shared__ __attribute__((aligned(16))) bs_t<MODE> Bs[NB * 32 * bs_pitch<MODE>];
@@ -70,10 +72,17 @@
 
   const long long row_w = row_g + wave * 32;                          // first row of the wave's tile
   const int cnt = (int)(p.M - row_w < 32 ? (p.M - row_w < 0 ? 0 : p.M - row_w) : 32);
+  // BN: the epilogue's arguments are read from the kernel-argument segment here, after the loop (bn_args_late, sparse_conv.hip)
+  [[maybe_unused]] const auto* q = [&] { if constexpr (BN) return bn_args_late(); else return &p; }();
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int col = j0 + nb * 32 + li;
     if (j0 + nb * 32 >= p.J) continue;                                // wave-uniform: J % 32 == 0
-    store_tile(acc[nb], p.bias ? p.bias[col] : 0.f, p.c, p.ldc, row_w, cnt, col, h, p.part != nullptr, p.part, (long long)rg * 4 + wave,
-               p.J);
+    if constexpr (BN) {
+      // the lane's column of the block: its two constants, formed here from the four vectors (no preparation launch)
+      const float sc = q->gamma[col] / sqrtf(q->rvar[col] + q->eps);
+      store_tile_bn(acc[nb], sc, q->beta[col] - q->rmean[col] * sc, q->r, q->ldr, q->relu != 0, p.c, p.ldc, row_w, cnt, col, h);
+    } else
+      store_tile(acc[nb], p.bias ? p.bias[col] : 0.f, p.c, p.ldc, row_w, cnt, col, h, p.part != nullptr, p.part, (long long)rg * 4 + wave,
+                 p.J);
   }

@@ -13,6 +13,8 @@
 //                      Every output row is written by exactly one wave.  With a partials pointer the epilogue also forms the
 //                      (mean, M2) of each wave's <= 32 rows from the accumulators (the BatchNorm statistics of the backbone's
 //                      convolutions, csn_sparse_conv_stats_fwd_f32); the stored values are the same bits either way.
+//                      The BN forward instances (csn_sparse_conv_bn_act_fwd_f32, inference) store act(acc * s + t + r) instead:
+//                      a BatchNorm on its running statistics, an optional residual and the ReLU in the product's epilogue.
 //   sconv_wgrad        dW[k][ci][co] = sum_j x[fwd[k][j]][ci] dy[j][co] over the output rows of one split-K chunk: the weight
 //                      gradient of rows_mma.h with one gathered operand (a lane's 8 contraction steps are 8 looked-up rows of one column: a half wave
 //                      reads one contiguous 128-byte run per row).  A 16-row step in which the wave finds no neighbour is skipped
@@ -44,8 +46,29 @@ struct SconvGemmP {
   float* part;                         // non-NULL: the (mean, M2) of each wave's rows, [tile][2][J], tile = 32 rows
 };
 
+// the inference epilogue's arguments on top of the product's (bias and part stay unused): y = act(acc * s + t + r),
+// s = gamma / sqrt(rvar + eps), t = beta - rmean * s
+struct SconvBnP : SconvGemmP {
+  const float* gamma; const float* beta; const float* rmean; const float* rvar; float eps;
+  const float* r; int ldr;             // residual [M][ldr], optional; may be c itself with ldr == ldc
+  int relu;
+};
+// The epilogue's own arguments, read from the kernel-argument segment (the by-value argument is its first and only entry) at the
+// point of the call instead of at kernel entry, where the compiler reads a by-value argument: read there they stay in scalar
+// registers across the contraction loop, the NB >= 2 instances have none to spare, 16 of them spill into vector registers and the
+// fp32 NB = 4 instance (105 + 64 accumulator registers) loses a wave per SIMD.  The empty asm keeps the reads below it.
+typedef const SconvBnP __attribute__((address_space(4)))* SconvBnLateP;
+__device__ __forceinline__ SconvBnLateP bn_args_late() {
+  SconvBnLateP k = (SconvBnLateP)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
+// (BN is stated in terms of NB so that the body's choice between the two epilogues is made per instance: the epilogue an
+// instance does not take is never instantiated for its argument type)
 template <int NB, int MODE, bool B_KN>
 __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
+  constexpr bool BN = NB < 0;
 #include "sconv_gemm_body.inc"
 }
 
@@ -53,6 +76,22 @@ __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
 template <int NB, bool H16, bool B_KN>
 __global__ __launch_bounds__(256) void sconv_gemm16_kernel(const SconvGemmP p) {
   constexpr int MODE = H16 ? 3 : 2;
+  constexpr bool BN = NB < 0;
+#include "sconv_gemm_body.inc"
+}
+
+// the forward instances with the inference epilogue: the same body, kernels of their own (the instances above keep their names,
+// arguments and code)
+template <int NB, int MODE>
+__global__ __launch_bounds__(256) void sconv_gemm_bn_kernel(const SconvBnP p) {
+  constexpr bool B_KN = true, BN = NB > 0;
+#include "sconv_gemm_body.inc"
+}
+
+template <int NB, bool H16>
+__global__ __launch_bounds__(256) void sconv_gemm16_bn_kernel(const SconvBnP p) {
+  constexpr int MODE = H16 ? 3 : 2;
+  constexpr bool B_KN = true, BN = NB > 0;
 #include "sconv_gemm_body.inc"
 }
 
@@ -179,12 +218,21 @@ int launch_gemm_nb(const SconvGemmP& p, int mode, hipStream_t st) {
   return launch_row_product(k, p, NB, mode, st);
 }
 
+// the instances with the inference epilogue (forward only)
+template <int NB, bool B_KN>
+int launch_gemm_nb(const SconvBnP& p, int mode, hipStream_t st) {
+  static_assert(B_KN, "the inference epilogue belongs to the forward product");
+  void (*const k[4])(SconvBnP) = {sconv_gemm_bn_kernel<NB, 0>, sconv_gemm_bn_kernel<NB, 1>, sconv_gemm16_bn_kernel<NB, false>,
+                                  sconv_gemm16_bn_kernel<NB, true>};
+  return launch_row_product(k, p, NB, mode, st);
+}
+
 // the wave owns every column up to 128; wider outputs take two column groups of the smallest width that covers them.  Where
 // that leaves fewer than TARGET_GROUPS work-groups (the coarse levels: few rows, wide rows), the column groups are halved
 // until it does not: more work-groups gather the same rows (from L2), each contracts a narrower slice.  The sums are the same.
 // csn_dev_set(CSN_DEV_SCONV_NB, 1..4) pins the column blocks per wave instead (tests reach every instance at small sizes).
-template <bool B_KN>
-int launch_gemm(const SconvGemmP& p, int mode, hipStream_t st) {
+template <bool B_KN, typename P>
+int launch_gemm(const P& p, int mode, hipStream_t st) {
   const int t = p.J / 32;
   int nb = t <= 4 ? t : (t + 1) / 2;
   const long long row_groups = ((long long)p.M + 127) / 128;
@@ -215,6 +263,16 @@ int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t
   SconvGemmP p{};
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = a.bias;
+  return launch_gemm<true>(p, mode, st);
+}
+
+// the forward product with the inference epilogue: one launch, no workspace
+int csn_launch_sparse_conv_bn_act_fwd(const CsnSparseConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st) {
+  SconvBnP p{};
+  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
+  p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv;
+  p.gamma = n.gamma; p.beta = n.beta; p.rmean = n.running_mean; p.rvar = n.running_var; p.eps = n.eps;
+  p.r = n.r; p.ldr = n.ld_r; p.relu = n.relu;
   return launch_gemm<true>(p, mode, st);
 }
 

@@ -15,8 +15,12 @@ With ``fused=True`` each such pair is two autograd nodes on include/csn_hip.h se
 In eval mode the convolution is the plain ``sparse_conv3d`` and ``bn_act`` takes the running statistics.  With ``fused=False`` the same
 graph runs on ``sparse_conv3d`` + ``F.batch_norm`` + ATen add / ReLU: the timing baseline and the error yardstick of the tests.
 
-The three or four maps that the reference joins with ``me.cat`` are joined with ``torch.cat`` here (the kernels' output pitch would
-let them be written straight into one buffer; that is not built).
+The three or four maps that the reference joins with ``me.cat`` are joined with ``torch.cat`` here.
+
+Inference (``tuning.override(eval_epilogue=True)``, a fused backbone in eval mode with autograd disabled): every convolution + norm is
+ONE launch of include/csn_hip.h section 19 (``sparse_conv_bn_act``: the BatchNorm on its running statistics, the residual and the
+ReLU in the product's epilogue), a branch sum is a chain of such launches into one buffer, and the concatenated result is
+allocated once and written in place through the kernels' output pitch: no ``torch.cat``.  Off by default.
 
 ``VoxelPyramid`` holds the coordinate sets and kernel maps of one batch, built once (``build_pyramid``): level l's coordinates are
 ``down^l(coords)`` by the stride-2 rule of ``build_kernel_map``; per level the stride-1 kernel-3 map, at level 0 the stem's map,
@@ -40,7 +44,7 @@ from . import functional as CF
 from . import minkowski_conv as _mc
 from . import tuning
 from .minkowski_conv import KernelMap, SparseConv3d, SparseConvTranspose3d, build_kernel_map, sparse_conv3d
-from .minkowski_csn import SimCSNHead, offsets_from_batch_index
+from .minkowski_csn import BackboneFC, SimCSNHead, offsets_from_batch_index
 
 _NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
 
@@ -266,6 +270,82 @@ class _BnAct(torch.autograd.Function):
 Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
 
 
+# ------------------------------------------------------------------------------------------------------
+# inference: convolution + BatchNorm + residual + ReLU as one launch (section 19)
+# ------------------------------------------------------------------------------------------------------
+_WINDOW = 0x7fffffff                                  # bytes of a map (rows * pitch * 4) the kernels' gathers can address
+
+
+def _pitched(t: torch.Tensor) -> bool:
+    """Whether the kernels can take the fp32 rows ``t (n, c)`` where they lie: unit column stride, a row pitch that is a multiple
+    of 4 floats and at least the width, a 16-byte aligned first element."""
+    return (t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1]
+            and t.data_ptr() % 16 == 0)
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    t = t.detach().float()
+    return t if _pitched(t) else t.contiguous()
+
+
+def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, norm: nn.BatchNorm1d,
+                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y (n_out, c_out) = act(conv(x) s + t + residual)`` in one launch (``csn_sparse_conv_bn_act_fwd_f32``): ``conv`` the
+    convolution ``kmap`` describes without a bias, ``s = gamma / sqrt(running_var + eps)``, ``t = beta - running_mean s`` from
+    ``norm``'s running statistics, ``act`` the ReLU or the identity.  Inference only: no autograd node, the result has no ``grad_fn``.
+
+    ``x``, ``residual`` and ``out`` may be row-pitched views of a wider buffer (``stride(1) == 1``, ``stride(0) % 4 == 0``, a
+    16-byte aligned data pointer); ``x`` and ``residual`` are made contiguous otherwise, ``out`` raises ``ValueError``.  With
+    ``out`` the result is written there (a column block of a wider buffer keeps its other columns) and ``out`` is returned;
+    ``residual`` may be ``out`` itself — a sum that accumulates in place — and must not overlap it in any other way.  An input width
+    that is no multiple of 32 is zero-padded as in ``sparse_conv3d``."""
+    if not (x.is_cuda and weight.is_cuda) or (residual is not None and not residual.is_cuda) or (out is not None and not out.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
+        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out) for the map's KV and n_in")
+    KV, c_in, c_out = weight.shape
+    if c_out % 32 or not 32 <= c_out <= 256 or c_in > 256:
+        raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in at most 256")
+    if not isinstance(norm, nn.BatchNorm1d) or norm.num_features != c_out or norm.running_mean is None or norm.weight is None:
+        raise ValueError(f"norm must be an affine nn.BatchNorm1d({c_out}) that tracks running statistics")
+    n_in, n_out = kmap.n_in, kmap.n_out
+    for name, t in (("residual", residual), ("out", out)):
+        if t is not None and tuple(t.shape) != (n_out, c_out):
+            raise ValueError(f"{name} must be ({n_out}, {c_out})")
+    CF._need_cuda(kmap.fwd, norm.weight, norm.bias, norm.running_mean, norm.running_var)
+    same = residual is not None and out is not None and residual.data_ptr() == out.data_ptr() and residual.stride() == out.stride()
+    w = weight.detach().float()
+    x = x.detach().float()
+    pad = -c_in % 32
+    if pad:
+        x, w, c_in = F.pad(x, (0, pad)), F.pad(w, (0, 0, 0, pad)), c_in + pad
+    x, w = _rows(x), w.contiguous()
+    if out is None:
+        y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
+    else:
+        y = out.detach()
+        if not _pitched(y):
+            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer")
+    r = None if residual is None else (y if same else _rows(residual))
+    vec = [v.detach().float().contiguous() for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+    with CF.rows16(tuning.current().rows_single_product):
+        _lib.check(_lib.lib().csn_sparse_conv_bn_act_fwd_f32(
+            CF._ptr(x), x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w), *(CF._ptr(v) for v in vec),
+            float(norm.eps), CF._ptr(r), 0 if r is None else r.stride(0), int(bool(relu)), CF._ptr(y), y.stride(0), CF._stream()),
+            "csn_sparse_conv_bn_act_fwd_f32")
+    return y if out is None else out
+
+
+def _fits(layer: SparseConv3d, kmap: KernelMap) -> None:
+    if kmap.kernel_size != layer.kernel_size or kmap.stride != layer.stride or kmap.transposed != layer.transposed:
+        raise ValueError("the map does not fit this layer")
+
+
+def _conv_bn_act(conv: SparseConv3d, norm: nn.BatchNorm1d, x, kmap: KernelMap, residual=None, relu=True, out=None) -> torch.Tensor:
+    _fits(conv, kmap)
+    return sparse_conv_bn_act(x, conv.kernel, kmap, norm, residual, relu, out)
+
+
 def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu: bool = True, training: bool = True,
            eps: float = 1e-5) -> torch.Tensor:
     """``y (N, C) = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + residual)`` for 1 to 3 terms ``(z, mean, scale, gamma, beta)``:
@@ -296,8 +376,7 @@ def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu:
 # ------------------------------------------------------------------------------------------------------
 def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, fused: bool):
     """fused: the term (z, mean, scale, gamma, beta) of ``bn_act``; else the normalised map through ATen."""
-    if kmap.kernel_size != conv.kernel_size or kmap.stride != conv.stride or kmap.transposed != conv.transposed:
-        raise ValueError("the map does not fit this layer")
+    _fits(conv, kmap)
     training = norm.training
     if not x.is_cuda:
         raise _lib.CsnError(_NO_CPU)
@@ -359,6 +438,12 @@ class HRBasicBlock(nn.Module):
         t2 = _conv_bn(self.conv2, self.norm2, out, kmap, f)
         return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps))
 
+    def infer(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The block on the inference launches: two, the second with ``x`` as its residual (written to ``out`` when given)."""
+        h = _keep(trace, prefix + "norm1", _conv_bn_act(self.conv1, self.norm1, x, kmap))
+        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, kmap, residual=x, out=out))
+
 
 # ------------------------------------------------------------------------------------------------------
 # the backbone
@@ -372,7 +457,10 @@ class HRNetBackbone(nn.Module):
     ``forward(feats, pyramid, trace=None)``: ``feats (N, in_channels)`` on the pyramid's level-0 rows; returns the
     ``(N, init_dim + sum of the branch widths)`` rows [out_init | branch 0 | transition 1 | ...].  ``trace``: a dict that receives
     every ReLU's output, keyed ``bn0s1``, ``bn1s1``, ``stages.i.j.b.norm1`` / ``.norm2``, ``exchange_blocks.i.j.k.<norm index>``
-    (the inner steps of a multi-step path), ``sum.i.k`` (the branch sums after stage i) and ``final_transitions.i.<norm index>``."""
+    (the inner steps of a multi-step path), ``sum.i.k`` (the branch sums after stage i) and ``final_transitions.i.<norm index>``.
+
+    Under ``tuning.override(eval_epilogue=True)`` a fused backbone in eval mode, called with autograd disabled, runs the inference
+    graph (``_forward_infer``); in every other case the switch changes nothing."""
 
     NUM_BLOCKS = 3
 
@@ -437,6 +525,8 @@ class HRNetBackbone(nn.Module):
         if feats.dim() != 2 or feats.shape[0] != pyramid.coords[0].shape[0]:
             raise ValueError("feats must be (N, in_channels) rows of the pyramid's level 0")
         f, tr = self.fused, self.training
+        if tuning.current().eval_epilogue and f and not tr and not torch.is_grad_enabled():
+            return self._forward_infer(feats, pyramid, trace)
         act1 = lambda name, t: _keep(trace, name, _combine([t], f, tr))
         out_init = act1("bn0s1", _conv_bn(self.conv0s1, self.bn0s1, feats.float(), pyramid.stem, f))
         out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f))
@@ -475,6 +565,57 @@ class HRNetBackbone(nn.Module):
                 x = act1(f"final_transitions.{i - 1}.{3 * s + 1}", _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f))
             outs.append(x)
         return torch.cat(outs, dim=1)
+
+    def _forward_infer(self, feats: torch.Tensor, pyramid: VoxelPyramid, trace: Optional[dict]) -> torch.Tensor:
+        """The same network with one launch per convolution + norm (``sparse_conv_bn_act``).  Every ReLU output is a stored map.
+        A branch sum is a chain into one buffer, over the incoming paths in ascending source branch j: the first launch writes
+        ``z s + t + own`` (``own``: the branch's own map, when it has one) without a ReLU, every further one adds its ``z s + t``
+        to that buffer in place, the last applies the ReLU — ((own + p_0) + p_1) + ..., a summation order of its own.  The
+        (N, out_channels) result is allocated once; ``bn0s1``, branch 0's last block and the last step of every final transition
+        write their column blocks of it, and ``conv1s1`` reads ``out_init`` from there through the row pitch.  Where that pitch
+        would take the result past the kernels' 2 GiB window, the maps stay separate and are joined with ``torch.cat``."""
+        n, D, S = feats.shape[0], self.init_stage_dims, self.num_stages
+        widths = [self.init_dim] + [D * 2 ** s for s in range(S)]
+        wide = torch.empty((n, self.out_channels), device=feats.device, dtype=torch.float32) \
+            if n * self.out_channels * 4 <= _WINDOW else None
+        col = lambda m: None if wide is None else wide[:, sum(widths[:m]):sum(widths[:m + 1])]
+        out_init = _keep(trace, "bn0s1", _conv_bn_act(self.conv0s1, self.bn0s1, feats, pyramid.stem, out=col(0)))
+        stage_input = [_keep(trace, "bn1s1", _conv_bn_act(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0]))]
+        for i in range(S):
+            stage_output = []
+            for j in range(i + 1):
+                x, blocks = stage_input[j], self.stages[i][j]
+                for b, blk in enumerate(blocks):
+                    last = i == S - 1 and j == 0 and b == len(blocks) - 1
+                    x = blk.infer(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", out=col(1) if last else None)
+                stage_output.append(x)
+            if i == S - 1:
+                break
+            depth = i + 1
+            stage_input = []
+            for k in range(depth + 1):
+                buf = stage_output[k] if k < depth else None                # the branch's own map: the first launch's residual
+                sources = [j for j in range(depth) if j != k]
+                for j in sources:
+                    path, x, steps = self.exchange_blocks[i][j][k], stage_output[j], abs(k - j)
+                    for s in range(steps):
+                        level = j + s if k > j else j - s                  # the level the step starts from
+                        kmap = pyramid.down[level] if k > j else pyramid.up(level - 1)
+                        if s + 1 < steps:
+                            x = _keep(trace, f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", _conv_bn_act(path[3 * s], path[3 * s + 1], x, kmap))
+                        else:
+                            buf = _conv_bn_act(path[3 * s], path[3 * s + 1], x, kmap, residual=buf, relu=j == sources[-1],
+                                               out=None if j == sources[0] else buf)
+                # (no incoming path — the finest branch after stage 0 — is the block's own ReLU output: no launch, as in _combine)
+                stage_input.append(_keep(trace, f"sum.{i}.{k}", buf))
+        outs = [out_init, stage_output[0]]
+        for i in range(1, S):
+            x, block = stage_output[i], self.final_transitions[i - 1]
+            for s in range(i):
+                x = _keep(trace, f"final_transitions.{i - 1}.{3 * s + 1}",
+                          _conv_bn_act(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), out=col(i + 1) if s == i - 1 else None))
+            outs.append(x)
+        return torch.cat(outs, dim=1) if wide is None else wide
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -534,16 +675,66 @@ class HRNetSimCSN4S(HRNetSimCSN):
                                   "widths up to 256")
 
 
-def load_me_hrnet_state(model: HRNetSimCSN, state_dict) -> HRNetSimCSN:
-    """Copy an ``HRNetSimCSN`` checkpoint of the reference into ``model``.  The backbone's modules keep the reference's names
-    (under ``backbone.`` here, at the top level there); a ``MinkowskiBatchNorm`` wraps its norm, so ``<name>.bn.weight`` etc. map
-    to ``<name>.weight``; a convolution's ``<name>.kernel`` is (KV, c_in, c_out) on both sides.  The sequential indices of the
-    exchange and transition blocks count the ReLUs on both sides.  The head goes through ``load_me_head_state``.  A missing key or
-    a wrong shape raises ``ValueError``.  The order of the KV axis (the offset numbering of minkowski_conv.py) is this project's
-    choice: parity unpinned against MinkowskiEngine."""
-    from .minkowski_training import load_me_head_state
+class SegFinal(BackboneFC):
+    """``final`` of ``HRNetSeg`` (hrnet.py:246-262) with the reference's sequential indices: 0 / 1 / 2 the kernel-size-1
+    convolution, BatchNorm and ReLU of ``BackboneFC`` (one autograd node on the fc_layer kernels), 3 the kernel-size-1 output
+    convolution as an ``nn.Linear``."""
+
+    WIDTH = 256
+
+    def __init__(self, backbone_channels: int, out_channels: int, bn_momentum: float = 0.02):
+        super().__init__(backbone_channels, self.WIDTH, bn_momentum=bn_momentum)
+        self.append(nn.Linear(self.WIDTH, out_channels, bias=True))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return F.linear(super().forward(x), self[3].weight, self[3].bias)
+
+
+class HRNetSeg(nn.Module):
+    """``HRNetSeg`` (hrnet.py:214-275), the plain segmentation network: ``backbone`` (``HRNetBackbone``) and ``final``
+    (``SegFinal``: ``final.0`` / ``.1`` / ``.2`` the 256-wide fc layer, ``final.3`` the output layer).
+
+    ``forward((coords, feats))``: ``coords (N, 4)`` rows [b, x, y, z] (or a ``VoxelPyramid`` built for them), ``feats (N,
+    in_channels)``; returns the (N, out_channels) logits, in training and eval."""
+
+    NUM_STAGES = 1
+    FEAT_FACTOR = 2
+
+    def __init__(self, in_channels: int, out_channels: int, bn_momentum: float = 0.02, conv1_kernel_size: int = 5, init_dim: int = 32,
+                 fused: bool = True):
+        super().__init__()
+        self.backbone = HRNetBackbone(in_channels, self.NUM_STAGES, self.FEAT_FACTOR, init_dim, conv1_kernel_size, bn_momentum, fused)
+        self.final = SegFinal(self.backbone.out_channels, out_channels, bn_momentum)
+
+    def forward(self, batch: Batch) -> torch.Tensor:
+        where, feats = batch
+        pyr = where if isinstance(where, VoxelPyramid) else build_pyramid(where, self.NUM_STAGES, self.backbone.conv1_kernel_size)
+        if not feats.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if pyr.coords[0].device != feats.device:
+            pyr = pyr.to(feats.device)
+        return self.final(self.backbone(feats, pyr))
+
+
+class HRNetSeg2S(HRNetSeg):
+    NUM_STAGES = 2                            # 32 + 64 + 128 = 224 backbone channels
+
+
+class HRNetSeg3S(HRNetSeg):
+    NUM_STAGES = 3                            # 32 + 64 + 128 + 256 = 480 backbone channels
+
+
+class HRNetSeg4S(HRNetSeg):
+    NUM_STAGES = 4
+
+    def __init__(self, *a, **kw):
+        raise NotImplementedError("HRNetSimCSN4S needs 512-wide convolutions; the kernels (include/csn_hip.h section 14) take "
+                                  "widths up to 256")
+
+
+def _load_me_backbone(backbone: HRNetBackbone, state_dict) -> None:
     new = {}
-    for name, mod in model.backbone.named_modules():
+    for name, mod in backbone.named_modules():
         if isinstance(mod, SparseConv3d):
             pairs = [(f"{name}.kernel", f"{name}.kernel", mod.kernel)]
         elif isinstance(mod, nn.BatchNorm1d):
@@ -558,6 +749,52 @@ def load_me_hrnet_state(model: HRNetSimCSN, state_dict) -> HRNetSimCSN:
             if tuple(v.shape) != tuple(cur.shape):
                 raise ValueError(f"{ref} is {tuple(v.shape)}; expected {tuple(cur.shape)}")
             new[own] = v
-    model.backbone.load_state_dict(new, strict=True)
+    backbone.load_state_dict(new, strict=True)
+
+
+def load_me_seg_state(model: HRNetSeg, state_dict) -> HRNetSeg:
+    """Copy an ``HRNetSeg`` checkpoint of the reference into ``model``: the backbone as ``load_me_hrnet_state`` does; ``final`` as
+    ``load_me_head_state`` maps ``fc_layer`` / ``output``: ``final.0.kernel`` and ``final.3.kernel`` — (c_in, c_out) or (1, c_in,
+    c_out) — transposed into the ``nn.Linear`` weights, ``final.0.bias`` / ``final.3.bias`` — (c_out,) or (1, c_out) — flattened,
+    ``final.1.bn.*`` into ``final.1.*``.  A missing key or a wrong shape raises ``ValueError`` before ``final`` is touched.  Parity
+    of the KV-axis order is unpinned against MinkowskiEngine, as for every checkpoint here."""
+    new = {}
+    for i in (0, 3):
+        c_out, c_in = model.final[i].weight.shape
+        for need in (f"final.{i}.kernel", f"final.{i}.bias"):
+            if need not in state_dict:
+                raise ValueError(f"checkpoint has no {need}")
+        kernel, bias = state_dict[f"final.{i}.kernel"], state_dict[f"final.{i}.bias"]
+        if tuple(kernel.shape) == (1, c_in, c_out):
+            kernel = kernel[0]
+        if tuple(kernel.shape) != (c_in, c_out):
+            raise ValueError(f"final.{i}.kernel is {tuple(kernel.shape)}; expected ({c_in}, {c_out}) or (1, {c_in}, {c_out})")
+        if tuple(bias.shape) == (1, c_out):
+            bias = bias[0]
+        if tuple(bias.shape) != (c_out,):
+            raise ValueError(f"final.{i}.bias is {tuple(bias.shape)}; expected ({c_out},) or (1, {c_out})")
+        new[f"{i}.weight"], new[f"{i}.bias"] = kernel.t(), bias
+    for leaf in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
+        ref = f"final.1.bn.{leaf}"
+        if ref not in state_dict:
+            raise ValueError(f"checkpoint has no {ref}")
+        cur = getattr(model.final[1], leaf)
+        if tuple(state_dict[ref].shape) != tuple(cur.shape):
+            raise ValueError(f"{ref} is {tuple(state_dict[ref].shape)}; expected {tuple(cur.shape)}")
+        new[f"1.{leaf}"] = state_dict[ref]
+    _load_me_backbone(model.backbone, state_dict)
+    model.final.load_state_dict(new, strict=True)
+    return model
+
+
+def load_me_hrnet_state(model: HRNetSimCSN, state_dict) -> HRNetSimCSN:
+    """Copy an ``HRNetSimCSN`` checkpoint of the reference into ``model``.  The backbone's modules keep the reference's names
+    (under ``backbone.`` here, at the top level there); a ``MinkowskiBatchNorm`` wraps its norm, so ``<name>.bn.weight`` etc. map
+    to ``<name>.weight``; a convolution's ``<name>.kernel`` is (KV, c_in, c_out) on both sides.  The sequential indices of the
+    exchange and transition blocks count the ReLUs on both sides.  The head goes through ``load_me_head_state``.  A missing key or
+    a wrong shape raises ``ValueError``.  The order of the KV axis (the offset numbering of minkowski_conv.py) is this project's
+    choice: parity unpinned against MinkowskiEngine."""
+    from .minkowski_training import load_me_head_state
+    _load_me_backbone(model.backbone, state_dict)
     load_me_head_state(model.head, state_dict)
     return model

@@ -80,6 +80,12 @@ class Tuning:
     # results leave the 1e-4 contract of bf16x3 as those modes do on the attention side.  Modes fp32 / bf16x3 never see it.  Off:
     # opt-in until the default is flipped in a change of its own (errors and timing: DESIGN.md "Single-product row products")
     rows_single_product: bool = False
+    # HRNetBackbone in eval mode with autograd disabled (validation, construct_shape_graph, test-time prediction; fused=True only):
+    # every convolution + BatchNorm (+ residual, + ReLU) is ONE launch of include/csn_hip.h section 19 instead of sparse_conv3d +
+    # bn_act, a branch sum accumulates in one buffer, and the concatenated result is written in place (no torch.cat).  A branch sum
+    # is added in an order of its own, so results differ from the two-launch path by fp32 rounding.  Training, grad-enabled and
+    # fused=False calls never see it.  Off: opt-in (bytes and timing: DESIGN.md "Inference backbone", scripts/bench_hrnet.py)
+    eval_epilogue: bool = False
 
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))

@@ -859,6 +859,37 @@ CSN_API int csn_points_batch_f32(const float* points, const int* labels, const l
 CSN_API int csn_field_index_i32(const long long* skeys, const long long* order, const long long* vid, int n_points, int n_voxels,
                         int* home, int* vox_ptr, int* vox_pts, long long* uniq_keys, int* status, void* stream);
 
+/* ---- (19) inference: the gather-GEMM with a BatchNorm + residual + ReLU epilogue (MinkowskiNet/models/hrnet.py:124-131 the stem,
+ *           :157-161 the branch sums, :308-326 the final transitions; models/modules/resnet_block.py:40-57 the block) ------------
+ * In eval mode the statistics of every normalised convolution of the backbone are constants, so (15)'s two launches per
+ * convolution — (14) writes z, (15b) reads z (and a residual) back and writes y — need no round trip through memory: ONE launch
+ * forms the product of (14) and applies the BatchNorm, the residual and the activation to the accumulators, as (13) does for
+ * fc_layer with training == 0.  Additive to ABI version 17.  Everything is POINT-MAJOR fp32 as in (14):
+ *   x[n_in][ld_x], table[kv][n_out], w[kv][c_in][c_out] (contiguous), gamma / beta / running_mean / running_var [c_out],
+ *   r[n_out][ld_r] (optional: NULL, ld_r then ignored), y[n_out][ld_y].  ld_x, ld_r and ld_y are independent pitches.
+ *   acc[j][c] = sum_k x[table[k][j]] W[k]      exactly the sum of csn_sparse_conv_fwd_f32 with bias = NULL: the same contraction
+ *                                              order in the same math mode (the same kernel text up to the epilogue)
+ *   s[c] = gamma[c] / sqrt(running_var[c] + eps),  t[c] = beta[c] - running_mean[c] s[c]                      (fp32)
+ *   y[j][c] = act(acc s + t + r[j][c])         act = ReLU (relu != 0) or the identity; acc s + t is one fused multiply-add
+ * A lane owns one column per 32-column block, so s and t are two registers per block formed in the epilogue from the four vectors:
+ * no preparation launch, no workspace, no atomics; two identical calls give the same bits.  Nothing but y is written, and y may be
+ * a column block of a wider buffer (ld_y > c_out): columns outside [0, c_out) of a row are not written; the same holds for reading
+ * x and r.
+ * ALIASING: r may be y itself (the same pointer AND ld_r == ld_y): every element is read and then written by the same lane, which
+ * is how a sum over branches accumulates in one buffer.  r == y with ld_r != ld_y returns CSN_E_ARG.  Any other overlap of y with
+ * r, x, w or the vectors is the caller's error: it is not detected and its result is undefined.
+ * Geometry, alignment and window checks and their codes are exactly those of (14), made on the host before any launch, with r (when
+ * given) checked like y: n_in, n_out >= 1 (CSN_E_ARG); kv in {1, 27, 125}, c_in % 32 == 0 and c_out % 32 == 0, both in [32, 256]
+ * (CSN_E_DIM); every pitch % 4 == 0 (CSN_E_ALIGN), >= its width (CSN_E_ARG), <= 2^20 and rows * pitch * 4 < 2 GiB (CSN_E_DIM); x, w, y,
+ * r 16-byte aligned, the table 4-byte (CSN_E_PTR); x, table, w, gamma, beta, running_mean, running_var or y NULL: CSN_E_ARG.
+ * Math modes as in (14): mode 0 the exact fp32 matrix instruction, mode 1 bf16x3; modes 2 / 3 run as mode 1 unless
+ * csn_set_thread_rows16(1) selects their single-product instances (this is a forward: mode 3 has one).  The launch rule for the
+ * column blocks a wave owns and CSN_DEV_SCONV_NB apply as in (14). */
+CSN_API int csn_sparse_conv_bn_act_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                   int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
+                                   long long ld_y, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

@@ -13,6 +13,14 @@ single-product row products (``tuning.rows_single_product`` on), whatever ``--mo
 ``unfused`` so too.  Prints one JSON line.
 
     python scripts/bench_hrnet.py --out profiles/hrnet_bench.json
+
+``--infer`` times the eval variants instead and nothing else: the 3S backbone forward in eval mode under ``torch.no_grad()`` with
+``tuning.eval_epilogue`` off (``two_launch``: ``sparse_conv3d`` + ``bn_act`` per convolution, then ``torch.cat``) against on
+(``one_launch``: include/csn_hip.h section 19, the result written in place), in math modes fp32 and bf16x3, the same rounds.
+``counted_bytes`` is the traffic of the output maps alone that the two graphs differ in (``infer_bytes``); the gathers and the
+weights are the same reads in both.
+
+    python scripts/bench_hrnet.py --infer --out profiles/hrnet_infer_bench.json
 """
 import argparse
 import json
@@ -58,6 +66,76 @@ def compare(variants, warmup, iters, rounds):
     return out
 
 
+def infer_bytes(num_stages, D, init_dim, rows):
+    """Bytes of the maps written and read back between a convolution's accumulators and the next convolution's gather, per forward:
+    (two_launch, one_launch).  With e = 4 n c for an (n, c) map — two launches: a convolution writes z (e), ``bn_act`` reads every
+    z of its sum and the residual or own map and writes y; ``torch.cat`` reads and writes the result once.  One launch: every
+    launch writes y and reads its residual (the own map, or the running sum)."""
+    two = one = 0
+    e = lambda level, c: 4 * rows[level] * c
+
+    def conv(level, c, paths=1, res=0):
+        nonlocal two, one
+        two += (2 * paths + res + 1) * e(level, c)                          # z written and read per path, r read, y written
+        one += (2 * paths - 1 + res) * e(level, c)                          # y written per launch, r / the running sum read
+    conv(0, init_dim)
+    conv(0, D)
+    for i in range(num_stages):
+        for j in range(i + 1):
+            for _ in range(3):
+                conv(j, D * 2 ** j)
+                conv(j, D * 2 ** j, res=1)
+        if i == num_stages - 1:
+            break
+        depth = i + 1
+        for k in range(depth + 1):
+            sources = [j for j in range(depth) if j != k]
+            for j in sources:
+                for s in range(abs(k - j) - 1):                             # the inner steps of a multi-step path
+                    level = j + s + 1 if k > j else j - s - 1
+                    conv(level, D * 2 ** level)
+            if sources:
+                conv(k, D * 2 ** k, paths=len(sources), res=int(k < depth))
+    for i in range(1, num_stages):
+        for s in range(i):
+            conv(i - s - 1, D * 2 ** i)
+    two += 2 * 4 * rows[0] * (init_dim + sum(D * 2 ** s for s in range(num_stages)))      # torch.cat: read + write
+    return two, one
+
+
+def infer(a):
+    import csn_amd
+    csn_amd.build()
+    from csn_amd import HRNetBackbone, build_pyramid
+    from csn_amd import functional as CF
+    from csn_amd import tuning
+    torch.manual_seed(0)
+    coords = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
+    pyr = build_pyramid(coords, 3)
+    n = coords.shape[0]
+    rows = [int(c.shape[0]) for c in pyr.coords]
+    two, one = infer_bytes(3, 64, 32, rows)
+    res = {"voxels": int(n), "level_rows": rows, "shapes": a.shapes, "warmup": a.warmup, "iters": a.iters, "rounds": a.rounds,
+           "device": torch.cuda.get_device_name(0), "what": "HRNetBackbone 3S forward, eval, no_grad",
+           "counted_bytes": {"two_launch": two, "one_launch": one}}
+    feats = torch.randn(n, 3, device="cuda")
+    net = HRNetBackbone(3, 3, 2).cuda().eval()
+
+    def step_of(mode, on):
+        def step():
+            with torch.no_grad(), CF.math_mode(mode), tuning.override(eval_epilogue=on):
+                net(feats, pyr)
+        return step
+    for mode in ("fp32", "bf16x3"):
+        r = compare({"two_launch": step_of(mode, False), "one_launch": step_of(mode, True)}, a.warmup, a.iters, a.rounds)
+        gap = r["two_launch_ms"] - r["one_launch_ms"]
+        noise = max(r[f"{v}_spread_ms"][1] - r[f"{v}_spread_ms"][0] for v in ("two_launch", "one_launch"))
+        r["speedup"] = r["two_launch_ms"] / r["one_launch_ms"]
+        r["one_launch_is_faster"] = bool(gap > noise and r["one_launch_spread_ms"][1] < r["two_launch_spread_ms"][0])
+        res[f"backbone_3S_eval_fwd_{mode}"] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--voxels", type=int, default=32768)
@@ -69,8 +147,16 @@ def main():
     ap.add_argument("--only", default="", help="fused or unfused: run that variant alone")
     ap.add_argument("--variants", default="", help="comma-separated: fused, unfused, mode2, mode3 (default: fused,unfused)")
     ap.add_argument("--skip-blocks", action="store_true")
+    ap.add_argument("--infer", action="store_true", help="time the eval variants (eval_epilogue off against on, fp32 and bf16x3) instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.infer:
+        line = json.dumps(infer(a))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     import csn_amd
     csn_amd.build()
     from csn_amd import HRBasicBlock, HRNetBackbone, SparseBasicBlock, build_pyramid
