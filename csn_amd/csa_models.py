@@ -459,6 +459,10 @@ class CrossShapeAt(nn.Module):
         return CF.retrieval_measure(f1, f2)
 
     def get_knn_graph(self, ssa_feats_1, ssa_feats_2, K):
+        if tuning.current().retrieval_screen:
+            # the same (S1, K + 1) indices with only the candidates an fp16 screen cannot rule out scored in fp32
+            from .minkowski_csn import knn_graph_screened
+            return knn_graph_screened(ssa_feats_1.to(device, torch.float32), ssa_feats_2.to(device, torch.float32), K)[0]
         scores, knn_graph = self.get_retrieval_measure(ssa_feats_1, ssa_feats_2).topk(K + 1, -1)
         return knn_graph
 
@@ -509,6 +513,23 @@ class CrossShapeAt(nn.Module):
         return torch.cat(rows, dim=0)
 
     def get_knn_graph_big(self, query_loader, candidate_loader, candidate_shape_indices, K):
+        if tuning.current().retrieval_screen:
+            from .minkowski_csn import knn_graph_screened
+            candidate_shape_indices.sort()
+            cand = self.get_candidate_ssa_feats(candidate_loader, candidate_shape_indices).contiguous()
+            # query batches are gathered 32 shapes at a time: one screen (one fp16 image of the candidates, one host read) per chunk
+            rows, chunk, held = [], [], 0
+            for feats, label in query_loader:
+                feats = torch.squeeze(feats, dim=1)
+                with torch.no_grad():
+                    chunk.append(self._ssa_cm(feats).permute(0, 2, 1).contiguous())
+                held += chunk[-1].shape[0]
+                if held >= 32:
+                    rows.append(knn_graph_screened(torch.cat(chunk, dim=0), cand, K)[0])
+                    chunk, held = [], 0
+            if chunk:
+                rows.append(knn_graph_screened(torch.cat(chunk, dim=0), cand, K)[0])
+            return torch.cat(rows, dim=0)
         measure = self.get_retrieval_measure_big(query_loader, candidate_loader, candidate_shape_indices)
         scores, knn_graph = measure.topk(K + 1, -1)
         return knn_graph

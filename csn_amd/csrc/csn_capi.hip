@@ -1153,6 +1153,68 @@ int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, const in
   return csn_launch_ragged_retrieval_f32(f1, offsets1, s1, N1, f2, offsets2, s2, N2, (int)mx1, channels, out, ws, (hipStream_t)stream);
 }
 
+// ---- (11b) fp16 screen and pair-list form of the ragged retrieval measure ----
+static int ragged_retrieval_args(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                                 const int* offsets2_host, const int* offsets2, int s2, int channels, const float* out, const float* ws,
+                                 long long* mx1) {
+  if (!f1 || !f2 || !offsets1 || !offsets2 || !out || !ws || s1 <= 0 || s2 <= 0 || channels <= 0) return CSN_E_ARG;
+  *mx1 = ragged_offsets_max(offsets1_host, s1);
+  if (*mx1 < 1 || ragged_offsets_max(offsets2_host, s2) < 1) return CSN_E_ARG;
+  if ((long long)s1 * s2 > 0x7fffffffLL) return CSN_E_ARG;
+  if (channels & 3) return CSN_E_ALIGN;
+  if (mis16(f1) || mis16(f2) || mis16(ws)) return CSN_E_PTR;
+  return 0;
+}
+
+long long csn_retrieval_screen_workspace_floats(long long n1_rows, long long n2_rows, int s1, int s2, int max_n1, int channels) {
+  if (n1_rows <= 0 || n2_rows <= 0 || s1 <= 0 || s2 <= 0 || max_n1 <= 0 || channels <= 0) return 0;
+  return (n1_rows + n2_rows) * (csn_screen_padded_channels(channels) / 2) + (long long)s1 * s2 * ((max_n1 + 127) / 128);
+}
+
+int csn_ragged_retrieval_screen_f16(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                                    const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
+                                    long long ws_floats, void* stream) {
+  long long mx1 = 0;
+  const int bad = ragged_retrieval_args(f1, offsets1_host, offsets1, s1, f2, offsets2_host, offsets2, s2, channels, out, ws, &mx1);
+  if (bad) return bad;
+  if (csn_screen_padded_channels(channels) > CSN_SCREEN_MAX_CP) return CSN_E_DIM;
+  const long long N1 = offsets1_host[s1], N2 = offsets2_host[s2];
+  if (ws_floats < csn_retrieval_screen_workspace_floats(N1, N2, s1, s2, (int)mx1, channels)) return CSN_E_WORKSPACE;
+  return csn_launch_ragged_retrieval_screen_f16(f1, offsets1, s1, N1, f2, offsets2, s2, N2, (int)mx1, channels, out, ws,
+                                                (hipStream_t)stream);
+}
+
+int csn_ragged_retrieval_pairs_f32(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                                   const int* offsets2_host, const int* offsets2, int s2, int channels, const int* pairs,
+                                   long long n_pairs, float* out, float* ws, long long ws_floats, void* stream) {
+  long long mx1 = 0;
+  const int bad = ragged_retrieval_args(f1, offsets1_host, offsets1, s1, f2, offsets2_host, offsets2, s2, channels, out, ws, &mx1);
+  if (bad) return bad;
+  if (!pairs || n_pairs <= 0 || ((uintptr_t)pairs & 3)) return CSN_E_ARG;
+  const long long N1 = offsets1_host[s1], N2 = offsets2_host[s2];
+  if (ws_floats < N1 + N2 + n_pairs * ((mx1 + 127) / 128)) return CSN_E_WORKSPACE;
+  return csn_launch_ragged_retrieval_pairs_f32(f1, offsets1, s1, N1, f2, offsets2, s2, N2, (int)mx1, channels, pairs, n_pairs, out, ws,
+                                               (hipStream_t)stream);
+}
+
+// |screen - exact| <= eps for every pair (derivation: DESIGN.md "fp16 screen of the shape graph"; tests/retrieval_screen_ref.py
+// restates it).  u = 2^-24 (fp32), h = 2^-11 (fp16), Cp = channels padded to 32.
+float csn_retrieval_screen_eps(int channels) {
+  if (channels <= 0) return 0.f;
+  const double C = channels, Cp = csn_screen_padded_channels(channels);
+  const double u = 1.0 / 16777216.0, h = 1.0 / 2048.0;
+  const double d = h + (C + 8.0) * u;                                // one image element against the real unit row, relative
+  const double operands = 2.0 * d + d * d;                           // both operands, Cauchy-Schwarz on unit rows
+  const double subnormal = 2.0 * (1.0 / 2097152.0) * sqrt(Cp) * (1.0 + d);   // |element| < 2^-21 of a unit row: flushed or kept
+  const double accumulate = Cp * 2.0 * u * (1.0 + d) * (1.0 + d);    // fp32 accumulation in the matrix unit, any order, truncating
+  const double exact_path = (2.0 * C + 8.0) * u;                     // the fp32 measure against real arithmetic
+  const double means = 256.0 * u;                                    // both means: fp32 trees of <= 61 000 points per shape, fp64 tile sums
+  const double eps = (operands + subnormal + accumulate + exact_path + means) * (1.0 + 1.0 / 1048576.0);
+  float e = (float)eps;
+  if ((double)e < eps) e = nextafterf(e, 1.f);
+  return e;
+}
+
 // ---- (12) loss, predictions and IoU counts of the MinkowskiNet head ----
 long long csn_ragged_seg_workspace_bytes(int n_rows) {
   if (n_rows <= 0) return 0;

@@ -257,6 +257,17 @@ int csn_launch_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const fl
                                   float* dxhat, double* rowdot, double* rowsum, double* ws, hipStream_t st);
 int csn_launch_ragged_retrieval_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2, int s2,
                                     long long N2, int max_n1, int C, float* out, float* ws, hipStream_t st);
+int csn_launch_ragged_mean_f32(const float* part, const int* off1, float* out, int pairs, int s2, int tiles, hipStream_t st);
+// the same arithmetic for a device list of (i, j) pairs: out[p] (retrieval.hip)
+int csn_launch_ragged_retrieval_pairs_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2,
+                                          int s2, long long N2, int max_n1, int C, const int* pairs, long long n_pairs, float* out,
+                                          float* ws, hipStream_t st);
+// fp16 screen of the ragged retrieval measure (retrieval_screen.hip): the sweep keeps 128 query rows and two 64-row candidate
+// tiles of Cp + 8 halves in LDS, 512 (Cp + 8) bytes of the CU's 160 KB
+#define CSN_SCREEN_MAX_CP 288
+int csn_screen_padded_channels(int C);
+int csn_launch_ragged_retrieval_screen_f16(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2,
+                                           int s2, long long N2, int max_n1, int C, float* out, float* ws, hipStream_t st);
 
 // ---- loss, predictions and IoU counts of the MinkowskiNet head on point-major ragged rows (minkowski_seg.hip) ----
 struct CsnRaggedSegArgs {

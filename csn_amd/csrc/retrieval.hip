@@ -149,17 +149,17 @@ __global__ __launch_bounds__(256) void csn_row_mean_kernel(const float* __restri
 // one pair and exits at once past its query shape's points; the candidate sweep stops at the candidate's own points, and its
 // last tile's rows beyond them fall outside the buffer window (zeros) and are never compared.  Instead of per-point maxima
 // the work-group leaves ONE partial sum (its 128 maxima added in a fixed tree): part[pair][tile], O(pairs x tiles).
-__global__ __launch_bounds__(256, 2) void csn_ragged_rowmax_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
-                                                                   const float* __restrict__ inv1, const float* __restrict__ inv2,
-                                                                   const int* __restrict__ off1, const int* __restrict__ off2,
-                                                                   float* __restrict__ part, int s2, int tiles, int C) {
+// The body is stated once: the all-pairs kernel takes (i, j) from the pair's position in the s1 x s2 matrix, the pair-list
+// kernel looks them up.  A work-group's sums depend on its own pair only, so a listed pair gets the all-pairs bits.
+__device__ __forceinline__ void csn_ragged_rowmax_body(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                       const float* __restrict__ inv1, const float* __restrict__ inv2,
+                                                       const int* __restrict__ off1, const int* __restrict__ off2,
+                                                       float* __restrict__ part, int i, int j, int nq0, int C) {
   __shared__ __attribute__((aligned(16))) float As[128 * LDK];      // candidate points (rows m)
   __shared__ __attribute__((aligned(16))) float Bs[128 * LDK];      // query points (rows n)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
-  const int pair = blockIdx.x / tiles, i = pair / s2, j = pair % s2;
-  const int nq0 = (blockIdx.x % tiles) * 128;
   const int r1 = off1[i], n1 = off1[i + 1] - r1;
   const int r2 = off2[j], n2 = off2[j + 1] - r2;
   if (nq0 >= n1) return;                                   // past the query shape: nothing to do (uniform over the work-group)
@@ -250,6 +250,26 @@ __global__ __launch_bounds__(256, 2) void csn_ragged_rowmax_kernel(const float* 
   if (tid == 0) part[blockIdx.x] = sum[0];
 }
 
+__global__ __launch_bounds__(256, 2) void csn_ragged_rowmax_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                                   const float* __restrict__ inv1, const float* __restrict__ inv2,
+                                                                   const int* __restrict__ off1, const int* __restrict__ off2,
+                                                                   float* __restrict__ part, int s2, int tiles, int C) {
+  const int pair = blockIdx.x / tiles;
+  csn_ragged_rowmax_body(f1, f2, inv1, inv2, off1, off2, part, pair / s2, pair % s2, (blockIdx.x % tiles) * 128, C);
+}
+
+// pairs[p] = {i, j}: the same work-group for a LISTED pair, part[p][tile]
+__global__ __launch_bounds__(256, 2) void csn_ragged_rowmax_pairs_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                                         const float* __restrict__ inv1, const float* __restrict__ inv2,
+                                                                         const int* __restrict__ off1, const int* __restrict__ off2,
+                                                                         const int* __restrict__ pairs, float* __restrict__ part,
+                                                                         int s1, int s2, int tiles, int C) {
+  const int p = blockIdx.x / tiles;
+  const int i = pairs[2 * p], j = pairs[2 * p + 1];
+  if ((unsigned)i >= (unsigned)s1 || (unsigned)j >= (unsigned)s2) return;    // not a pair: nothing is read, the mean writes nan
+  csn_ragged_rowmax_body(f1, f2, inv1, inv2, off1, off2, part, i, j, (blockIdx.x % tiles) * 128, C);
+}
+
 // out[pair] = (1 / n_i) sum over the query shape's own tiles of part[pair][tile], in tile order (fp64)
 __global__ __launch_bounds__(256) void csn_ragged_mean_kernel(const float* __restrict__ part, const int* __restrict__ off1,
                                                               float* __restrict__ out, int pairs, int s2, int tiles) {
@@ -260,6 +280,24 @@ __global__ __launch_bounds__(256) void csn_ragged_mean_kernel(const float* __res
   double s = 0.0;
   for (int t = 0; t < nt; ++t) s += (double)part[(long long)pair * tiles + t];
   out[pair] = (float)(s / (double)n1);
+}
+
+// the same mean for a listed pair p: the query shape is pairs[p][0]
+__global__ __launch_bounds__(256) void csn_ragged_mean_pairs_kernel(const float* __restrict__ part, const int* __restrict__ off1,
+                                                                    const int* __restrict__ pairs, float* __restrict__ out,
+                                                                    long long n_pairs, int s1, int s2, int tiles) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_pairs) return;
+  const int i = pairs[2 * p];
+  if ((unsigned)i >= (unsigned)s1 || (unsigned)pairs[2 * p + 1] >= (unsigned)s2) {
+    out[p] = __builtin_nanf("");
+    return;
+  }
+  const int n1 = off1[i + 1] - off1[i];
+  const int nt = (n1 + 127) / 128;
+  double s = 0.0;
+  for (int t = 0; t < nt; ++t) s += (double)part[p * tiles + t];
+  out[p] = (float)(s / (double)n1);
 }
 }  // namespace
 
@@ -279,6 +317,13 @@ int csn_launch_retrieval_f32(const float* f1, const float* f2, float* out, int s
   return (int)hipGetLastError();
 }
 
+// the per-(pair, tile) partial sums of an all-pairs sweep -> out[pair] (also the fp16 screen's: retrieval_screen.hip)
+int csn_launch_ragged_mean_f32(const float* part, const int* off1, float* out, int pairs, int s2, int tiles, hipStream_t st) {
+  hipLaunchKernelGGL(csn_ragged_mean_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, part, off1, out, pairs, s2,
+                     tiles);
+  return (int)hipGetLastError();
+}
+
 int csn_launch_ragged_retrieval_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2, int s2,
                                     long long N2, int max_n1, int C, float* out, float* ws, hipStream_t st) {
   float* inv1 = ws;
@@ -291,8 +336,23 @@ int csn_launch_ragged_retrieval_f32(const float* f1, const int* off1, int s1, lo
   hipLaunchKernelGGL(csn_row_inv_norm_kernel, dim3((unsigned)((N2 + 3) / 4)), dim3(256), 0, st, f2, inv2, N2, C, 1e-12f);
   hipLaunchKernelGGL(csn_ragged_rowmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f1, f2, inv1, inv2, off1, off2, part, s2,
                      tiles, C);
-  const int pairs = s1 * s2;
-  hipLaunchKernelGGL(csn_ragged_mean_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, part, off1, out, pairs, s2,
-                     tiles);
+  return csn_launch_ragged_mean_f32(part, off1, out, s1 * s2, s2, tiles, st);
+}
+
+int csn_launch_ragged_retrieval_pairs_f32(const float* f1, const int* off1, int s1, long long N1, const float* f2, const int* off2,
+                                          int s2, long long N2, int max_n1, int C, const int* pairs, long long n_pairs, float* out, float* ws,
+                                          hipStream_t st) {
+  float* inv1 = ws;
+  float* inv2 = ws + N1;
+  float* part = inv2 + N2;
+  const int tiles = (max_n1 + 127) / 128;
+  const long long blocks = (long long)tiles * n_pairs;
+  if (blocks > 0x7fffffffLL) return -1;                    // CSN_E_ARG: list fewer pairs per call
+  hipLaunchKernelGGL(csn_row_inv_norm_kernel, dim3((unsigned)((N1 + 3) / 4)), dim3(256), 0, st, f1, inv1, N1, C, 1e-12f);
+  hipLaunchKernelGGL(csn_row_inv_norm_kernel, dim3((unsigned)((N2 + 3) / 4)), dim3(256), 0, st, f2, inv2, N2, C, 1e-12f);
+  hipLaunchKernelGGL(csn_ragged_rowmax_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, f1, f2, inv1, inv2, off1, off2, pairs,
+                     part, s1, s2, tiles, C);
+  hipLaunchKernelGGL(csn_ragged_mean_pairs_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, part, off1, pairs, out,
+                     n_pairs, s1, s2, tiles);
   return (int)hipGetLastError();
 }

@@ -151,6 +151,189 @@ def retrieval_measure_ragged(f1: torch.Tensor, offsets1, f2: torch.Tensor, offse
 
 
 # ------------------------------------------------------------------------------------------------------
+# exact top-K retrieval behind an fp16 screen
+# ------------------------------------------------------------------------------------------------------
+SCREEN_MAX_CHANNELS = 288                    # round-up-32(C) the screen kernel's LDS images hold (include/csn_hip.h, section 11b)
+# An element beyond this magnitude (or a non-finite one) can overflow the fp32 measure's own sums: screen_eps bounds the distance
+# to the fp32 measure only where that measure stays in range.  Such a shape is never screened out, its own row is scored in full,
+# and its screen scores never enter another row's threshold (screen_shortlist).
+_SCREEN_SAFE_MAX = 2.0 ** 55
+
+
+def screen_eps(C: int) -> float:
+    """The DERIVED bound of the fp16 screen: |retrieval_screen_ragged - retrieval_measure_ragged| <= screen_eps(C) for every pair
+    (``csn_retrieval_screen_eps``; derivation in DESIGN.md "fp16 screen of the shape graph")."""
+    return float(_lib.lib().csn_retrieval_screen_eps(int(C)))
+
+
+def _ragged_args(f1, offsets1, f2, offsets2):
+    CF._need_cuda(f1, f2)
+    f1, f2 = f1.contiguous(), f2.contiguous()
+    o1, o2 = _host_offsets(offsets1, f1.shape[0]), _host_offsets(offsets2, f2.shape[0])
+    if f2.shape[1] != f1.shape[1]:
+        raise ValueError("both feature sets need the same channel count")
+    return f1, o1, f2, o2
+
+
+def _row_chunks(lens1: Sequence[int], S2: int, pair_budget: int):
+    """Query rows [i, j) whose pair tiles (S2 x tiles of the longest of them) stay within the budget, at least one row each."""
+    i, S1 = 0, len(lens1)
+    while i < S1:
+        j, mx = i + 1, lens1[i]
+        while j < S1 and (j + 1 - i) * S2 * ((max(mx, lens1[j]) + 127) // 128) <= pair_budget:
+            mx = max(mx, lens1[j])
+            j += 1
+        yield i, j, mx
+        i = j
+
+
+def retrieval_screen_ragged(f1: torch.Tensor, offsets1, f2: torch.Tensor, offsets2, pair_budget: int = 2 ** 26) -> torch.Tensor:
+    """The fp16 SCREEN of ``retrieval_measure_ragged``: the same (S1, S2) fp32 matrix within ``screen_eps(C)`` of it, from unit
+    rows rounded once to fp16 on the 16-bit matrix cores (``csn_ragged_retrieval_screen_f16``).  It ranks nothing: it tells
+    ``topk_retrieval_ragged`` which pairs need no exact score."""
+    f1, o1, f2, o2 = _ragged_args(f1, offsets1, f2, offsets2)
+    S1, S2, C = len(o1) - 1, len(o2) - 1, f1.shape[1]
+    if (C + 31) // 32 * 32 > SCREEN_MAX_CHANNELS:
+        raise _lib.CsnError(f"the retrieval screen holds up to {SCREEN_MAX_CHANNELS} channels (got {C}); score exactly instead")
+    dev, L = f1.device, _lib.lib()
+    out = torch.empty((S1, S2), device=dev, dtype=torch.float32)
+    h2, d2 = _int32_pair(o2, dev)
+    lens1 = [b - a for a, b in zip(o1, o1[1:])]
+    for i, j, mx in _row_chunks(lens1, S2, pair_budget):
+        sub = [o - o1[i] for o in o1[i:j + 1]]
+        h1, d1 = _int32_pair(sub, dev)
+        ws_n = int(L.csn_retrieval_screen_workspace_floats(sub[-1], o2[-1], j - i, S2, mx, C))
+        ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+        _lib.check(L.csn_ragged_retrieval_screen_f16(CF._ptr(f1[o1[i]:o1[j]]), h1.data_ptr(), CF._ptr(d1), j - i, CF._ptr(f2),
+                                                     h2.data_ptr(), CF._ptr(d2), S2, C, CF._ptr(out[i:j]), CF._ptr(ws), ws_n,
+                                                     CF._stream()), "csn_ragged_retrieval_screen_f16")
+    return out
+
+
+def retrieval_pairs_ragged(f1: torch.Tensor, offsets1, f2: torch.Tensor, offsets2, pairs: torch.Tensor,
+                           pair_budget: int = 2 ** 26) -> torch.Tensor:
+    """The exact fp32 measure of the listed pairs only: ``pairs`` (P, 2) integer (i, j) on the device, any order, repeats allowed
+    -> (P,) fp32 with the bits ``retrieval_measure_ragged(...)[i, j]`` has (``csn_ragged_retrieval_pairs_f32``: the same
+    work-groups, the pair looked up)."""
+    f1, o1, f2, o2 = _ragged_args(f1, offsets1, f2, offsets2)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype not in (torch.int32, torch.int64):
+        raise ValueError("pairs must be a (P, 2) int32 / int64 tensor of (query shape, key shape) indices")
+    if not pairs.is_cuda:
+        raise _lib.CsnError("csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    S1, S2, C = len(o1) - 1, len(o2) - 1, f1.shape[1]
+    dev, L = f1.device, _lib.lib()
+    pairs = pairs.to(torch.int32).contiguous()
+    P = pairs.shape[0]
+    out = torch.empty((P,), device=dev, dtype=torch.float32)
+    if P == 0:
+        return out
+    h1, d1 = _int32_pair(o1, dev)
+    h2, d2 = _int32_pair(o2, dev)
+    tiles = (max(b - a for a, b in zip(o1, o1[1:])) + 127) // 128
+    step = max(1, pair_budget // tiles)
+    for p0 in range(0, P, step):
+        n = min(step, P - p0)
+        ws_n = o1[-1] + o2[-1] + n * tiles
+        ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+        _lib.check(L.csn_ragged_retrieval_pairs_f32(CF._ptr(f1), h1.data_ptr(), CF._ptr(d1), S1, CF._ptr(f2), h2.data_ptr(), CF._ptr(d2),
+                                                    S2, C, CF._ptr(pairs[p0:p0 + n]), n, CF._ptr(out[p0:p0 + n]), CF._ptr(ws), ws_n,
+                                                    CF._stream()), "csn_ragged_retrieval_pairs_f32")
+    return out
+
+
+def _unscreenable(f: torch.Tensor, off: Sequence[int]) -> torch.Tensor:
+    """(S,) bool on the device: shapes holding a non-finite element or one beyond ``_SCREEN_SAFE_MAX``."""
+    bad = (~(f.abs().amax(dim=1) <= _SCREEN_SAFE_MAX)).to(torch.int64).cumsum(0)
+    bad = torch.cat([bad.new_zeros(1), bad])
+    o = torch.tensor(list(off), dtype=torch.int64, device=f.device)
+    return (bad[o[1:]] - bad[o[:-1]]) > 0
+
+
+def screen_shortlist(screen: torch.Tensor, k_top: int, eps: float, wild: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The selection rule on a (rows, S2) block of screen scores: keep a candidate iff its score is >= t - 2 eps, t = the k_top-th
+    largest score of its row.  Bool mask, same device.  With |screen - exact| <= eps a dropped candidate is strictly below k_top
+    others in exact arithmetic: it is in no top-k_top of the exact scores.  ``wild`` (S2,) bool marks the candidates the bound does
+    NOT cover: they are always kept and they take no part in t — the k_top scores that justify a drop must themselves be within
+    eps of their exact scores (a wild candidate's screen score can lie far above its exact one and would lift t).  A row with
+    fewer than k_top covered candidates, or with a non-finite score among them, keeps every candidate.
+    (Compared in fp64, where t - 2 eps is exact: an fp32 difference could round the threshold up.)"""
+    s = screen.double()
+    if wild is None:
+        wild = torch.zeros(screen.shape[1], dtype=torch.bool, device=screen.device)
+    s = s.masked_fill(wild[None, :], float("-inf"))
+    t = torch.topk(s, k_top, dim=1).values[:, -1:]              # -inf where fewer than k_top covered candidates: keeps the row
+    keep = (s >= t - 2.0 * float(eps)) | wild[None, :]
+    return keep | (~torch.isfinite(screen) & ~wild[None, :]).any(dim=1, keepdim=True)
+
+
+def topk_retrieval_ragged(f1: torch.Tensor, offsets1, f2: torch.Tensor, offsets2, K: int, is_same: bool,
+                          pair_budget: int = 2 ** 26) -> Tuple[List[Tuple[int, List[int]]], dict]:
+    """``topk_neighbors(retrieval_measure_ragged(f1, offsets1, f2, offsets2), K, is_same)`` — the same list of integers — without
+    the exact score of every pair.  Per chunk of query rows: the fp16 screen of the chunk; the shortlist of ``screen_shortlist``
+    with K' = K + 1 when ``is_same`` (the query itself may have to be dropped, csn_utils.py:91-96), else K; the exact fp32 score
+    of the shortlisted pairs (``retrieval_pairs_ragged``) scattered into a matrix of -inf; ``topk_neighbors`` on the result.
+    Selection stays on the device; one host read per chunk (the pair count).  A shape with a non-finite or huge (> 2^55) element
+    is outside the bound: as a query its row is scored in full, as a key it is always scored and takes no part in the row's
+    threshold.  A row with a non-finite screen score is scored in full; fewer than K' keys take the all-pairs path and raise
+    what it raises.  ``stats``: pairs screened, pairs re-scored exactly, the largest shortlist of a row."""
+    f1, o1, f2, o2 = _ragged_args(f1, offsets1, f2, offsets2)
+    S1, S2, C = len(o1) - 1, len(o2) - 1, f1.shape[1]
+    k_top = K + 1 if is_same else K
+    if S2 < k_top or K < 1:
+        sim = retrieval_measure_ragged(f1, o1, f2, o2, pair_budget)
+        return topk_neighbors(sim.cpu(), K, is_same), {"pairs_screened": 0, "pairs_rescored": S1 * S2, "max_shortlist": S2}
+    eps = screen_eps(C)
+    wild_q, wild_k = _unscreenable(f1, o1), _unscreenable(f2, o2)
+    lens1 = [b - a for a, b in zip(o1, o1[1:])]
+    blocks, rescored, longest = [], 0, torch.zeros((), dtype=torch.int64, device=f1.device)
+    for i, j, _ in _row_chunks(lens1, S2, pair_budget):
+        sub = [o - o1[i] for o in o1[i:j + 1]]
+        rows = f1[o1[i]:o1[j]]
+        screen = retrieval_screen_ragged(rows, sub, f2, o2, pair_budget)
+        keep = screen_shortlist(screen, k_top, eps, wild_k) | wild_q[i:j, None]
+        pairs = keep.nonzero()                                  # the chunk's one host read: the pair count
+        longest = torch.maximum(longest, keep.sum(dim=1).max())
+        rescored += pairs.shape[0]
+        full = torch.full((j - i, S2), float("-inf"), device=f1.device, dtype=torch.float32)
+        full[pairs[:, 0], pairs[:, 1]] = retrieval_pairs_ragged(rows, sub, f2, o2, pairs, pair_budget)
+        blocks.append(full.cpu())
+    stats = {"pairs_screened": S1 * S2, "pairs_rescored": rescored, "max_shortlist": int(longest)}
+    return topk_neighbors(torch.cat(blocks), K, is_same), stats
+
+
+SCREEN_MAX_POINTS = 61000                    # points per shape the fixed-length measure's fp32 mean stays inside screen_eps for
+
+
+def knn_graph_screened(f1: torch.Tensor, f2: torch.Tensor, K: int, pair_budget: int = 2 ** 26) -> Tuple[torch.Tensor, dict]:
+    """``csn_amd.functional.retrieval_measure(f1, f2).topk(K + 1, -1).indices`` for fixed-length point-major features (S1, N1, C),
+    (S2, N2, C) — MID-FC's get_knn_graph — behind the same screen: the features are a ragged set with uniform offsets, K' = K + 1,
+    and the shortlisted candidates of a query are scored by the fixed-length fp32 kernel itself (a pair's bits there depend on
+    the pair alone), so the (S1, K + 1) int64 tensor is the one the all-pairs path returns.  One host read per call."""
+    CF._need_cuda(f1, f2)
+    S1, N1, C = f1.shape
+    S2, N2, _ = f2.shape
+    if S2 < K + 1:
+        return CF.retrieval_measure(f1, f2).topk(K + 1, -1)[1], {"pairs_screened": 0, "pairs_rescored": S1 * S2, "max_shortlist": S2}
+    if N1 > SCREEN_MAX_POINTS:
+        raise _lib.CsnError(f"the retrieval screen's bound covers up to {SCREEN_MAX_POINTS} points per query shape (got {N1})")
+    f1, f2 = f1.contiguous(), f2.contiguous()
+    r1, r2 = f1.reshape(S1 * N1, C), f2.reshape(S2 * N2, C)
+    o1, o2 = [i * N1 for i in range(S1 + 1)], [i * N2 for i in range(S2 + 1)]
+    screen = retrieval_screen_ragged(r1, o1, r2, o2, pair_budget)
+    keep = screen_shortlist(screen, K + 1, screen_eps(C), _unscreenable(r2, o2)) | _unscreenable(r1, o1)[:, None]
+    full = torch.full((S1, S2), float("-inf"), device=f1.device, dtype=torch.float32)
+    pairs = keep.nonzero()                                      # the call's one host read (row-major: a query's candidates adjoin)
+    counts = torch.bincount(pairs[:, 0], minlength=S1).tolist()
+    at = 0
+    for q, n in enumerate(counts):
+        cols = pairs[at:at + n, 1]
+        full[q, cols] = CF.retrieval_measure(f1[q:q + 1], f2[cols])[0]
+        at += n
+    stats = {"pairs_screened": S1 * S2, "pairs_rescored": pairs.shape[0], "max_shortlist": max(counts)}
+    return full.topk(K + 1, -1)[1], stats
+
+
+# ------------------------------------------------------------------------------------------------------
 # the head's pool / compatibility / mix as one autograd node
 # ------------------------------------------------------------------------------------------------------
 class _RaggedHead(torch.autograd.Function):
@@ -470,12 +653,14 @@ def shape_ssa(head: SimCSNHead, shapes: Sequence[torch.Tensor], max_rows: int = 
 
 def construct_shape_graph(head: SimCSNHead, query_shapes: Sequence[torch.Tensor], key_shapes: Optional[Sequence[torch.Tensor]] = None,
                           K: int = 1, random_pairs: bool = False, rng: Optional[np.random.Generator] = None,
-                          max_rows: int = 1 << 15) -> List[Tuple[int, List[int]]]:
+                          max_rows: int = 1 << 15, screen: Optional[bool] = None) -> List[Tuple[int, List[int]]]:
     """csn_utils.py:11-111 on per-shape backbone features ``query_shapes[i]`` (n_i, d_model) (device tensors): the K
     neighbours of every query shape among ``key_shapes`` (None: among the queries themselves, never the query).  Returns
     ``[(q_idx, [neighbours])]``.  ``random_pairs``: the random branch (:31-43) drawn from ``rng`` (a numpy Generator).
     Similarity branch (:44-97): the SSA of every shape (chunked varlen calls, no grad, the head's current train / eval mode as
-    in the reference), the ragged retrieval measure of every (query, key) pair, and the top-K rule of :91-96."""
+    in the reference), the ragged retrieval measure of every (query, key) pair, and the top-K rule of :91-96.
+    ``screen``: True scores only the pairs an fp16 screen cannot rule out (``topk_retrieval_ragged``: the same neighbours, the
+    fp32 measure alone ranks), False every pair, None follows ``tuning.current().retrieval_screen`` (off by default)."""
     if K < 1:
         raise ValueError("K must be >= 1 (csn_utils.py:16)")
     is_same = key_shapes is None
@@ -487,5 +672,7 @@ def construct_shape_graph(head: SimCSNHead, query_shapes: Sequence[torch.Tensor]
     q_rows, q_off = shape_ssa(head, query_shapes, max_rows)
     k_rows, k_off = (q_rows, q_off) if is_same else shape_ssa(head, key_shapes, max_rows)
     with torch.no_grad():
+        if tuning.current().retrieval_screen if screen is None else screen:
+            return topk_retrieval_ragged(q_rows, q_off, k_rows, k_off, K, is_same)[0]
         sim = retrieval_measure_ragged(q_rows, q_off, k_rows, k_off)
     return topk_neighbors(sim.cpu(), K, is_same)

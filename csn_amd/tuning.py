@@ -86,6 +86,12 @@ class Tuning:
     # is added in an order of its own, so results differ from the two-launch path by fp32 rounding.  Training, grad-enabled and
     # fused=False calls never see it.  Off: opt-in (bytes and timing: DESIGN.md "Inference backbone", scripts/bench_hrnet.py)
     eval_epilogue: bool = False
+    # kNN shape graphs (construct_shape_graph with screen=None, CrossShapeAt.get_knn_graph / get_knn_graph_big): an fp16 pass over all
+    # pairs (csn_ragged_retrieval_screen_f16) names the candidates that provably cannot be among a row's top K — more than
+    # 2 * screen_eps below its K-th best screen score — and only the rest are scored by the exact fp32 kernels.  The SAME integers
+    # come out (tests/test_gpu_retrieval_screen.py); the fp32 measure alone ranks.  Off: opt-in — the share of pairs that survives the
+    # screen on real PartNet features is not measured (DESIGN.md "fp16 screen of the shape graph", scripts/bench_retrieval_screen.py)
+    retrieval_screen: bool = False
 
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))

@@ -56,8 +56,9 @@ CSN_API int csn_version(void);
  *   3 CSN_MATH_FP16    the same with fp16 operands — FORWARD entry points only (gradients of this path reach 1e-7 and
  *                      underflow fp16): the backward entry points return CSN_E_ARG in this mode; callers run them in mode 2
  *                      (csn_amd does: "fp16 forward / bf16 backward").
- * The retrieval measure (7) always runs in exact fp32 (bit-exact kNN indices).  The cross-length entry points (3b) have no
- * single-product kernels: in modes 2 / 3 they run as mode 1.
+ * The retrieval measure (7) always runs in exact fp32 (bit-exact kNN indices); the fp16 screen of (11b) never decides a rank: it
+ * only names candidates that provably cannot be ranked, and every candidate it keeps is scored in fp32.
+ * The cross-length entry points (3b) have no single-product kernels: in modes 2 / 3 they run as mode 1.
  * The row products of the MinkowskiNet side — (13) csn_rows_fc_*, (14) csn_sparse_conv_*, (15a) csn_sparse_conv_stats_fwd_f32 —
  * have single-product instances behind a per-thread, opt-in flag, csn_set_thread_rows16(on): on = 0 (THE DEFAULT) runs modes 2 / 3
  * as mode 1 there, as before the instances existed; on = 1 runs mode 2 in every forward and backward entry point of those sections
@@ -581,6 +582,38 @@ CSN_API int csn_ragged_mix_bwd_f32(const float* dout, long long ld_dout, const f
 CSN_API int csn_ragged_retrieval_f32(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
                              const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
                              long long ws_floats, void* stream);
+
+/* ---- (11b) fp16 screen and pair-list form of the ragged retrieval measure: top-K retrieval without every pair in fp32 ----
+ * Offsets as in (11).  Independent of the math mode.
+ * csn_ragged_retrieval_screen_f16  the arguments and the meaning of csn_ragged_retrieval_f32, out[i][j] within
+ *                          csn_retrieval_screen_eps(channels) of what that entry writes: every row normalised in fp32 (the
+ *                          same max(|x|, 1e-12) clamp, behind an exact power-of-two scaling by the row's largest element),
+ *                          times 2^7, rounded ONCE to fp16 (channels zero-padded to a multiple of 32), one
+ *                          v_mfma_f32_32x32x16_f16 per product, fp32 accumulation, the product scaled back by 2^-14 (exact).
+ *                          A work-group keeps its 128 query points in LDS and streams the candidate's points through a
+ *                          double-buffered image; partial sums per (pair, tile) are added in tile order in fp64: no atomics,
+ *                          two calls give the same bits.  channels % 4 == 0 and round-up-32(channels) <= 288 (CSN_E_DIM
+ *                          beyond: the three images no longer fit one CU's LDS).  ws >=
+ *                          csn_retrieval_screen_workspace_floats(N1, N2, s1, s2, max n1_i, channels) floats, 16-byte aligned.
+ * csn_retrieval_screen_eps  the bound: |screen - fp32 measure| <= eps for every pair whose rows the fp32 measure can normalise
+ *                          (a sum of squares inside the fp32 range; a caller keeps other rows out of the screen's decisions).
+ *                          DERIVED (DESIGN.md "fp16 screen of the shape graph"), a function of the channel count alone:
+ *                          about 2^-10 + (7 channels + 350) 2^-24 (1.10e-3 at 256 channels).  It holds whether the matrix
+ *                          unit flushes fp16 subnormal operands or not: after the 2^7 scaling an element in that range
+ *                          moves a cosine by < 2^-21.
+ * csn_ragged_retrieval_pairs_f32  out[p] = the fp32 measure of the pair (pairs[2p], pairs[2p+1]) for n_pairs listed pairs
+ *                          (DEVICE int32, any order, repeats allowed): the work-groups of csn_ragged_retrieval_f32 with the
+ *                          pair looked up — the same sums in the same order, the same bits.  An index outside
+ *                          [0, s1) x [0, s2) reads nothing and writes nan.
+ *                          ws >= N1 + N2 + n_pairs ceil(max n1_i / 128) floats. */
+CSN_API long long csn_retrieval_screen_workspace_floats(long long n1_rows, long long n2_rows, int s1, int s2, int max_n1, int channels);
+CSN_API float csn_retrieval_screen_eps(int channels);
+CSN_API int csn_ragged_retrieval_screen_f16(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                                    const int* offsets2_host, const int* offsets2, int s2, int channels, float* out, float* ws,
+                                    long long ws_floats, void* stream);
+CSN_API int csn_ragged_retrieval_pairs_f32(const float* f1, const int* offsets1_host, const int* offsets1, int s1, const float* f2,
+                                   const int* offsets2_host, const int* offsets2, int s2, int channels, const int* pairs,
+                                   long long n_pairs, float* out, float* ws, long long ws_floats, void* stream);
 
 /* ---- (12) loss, predictions and IoU counts of the MinkowskiNet head (MinkowskiNet/lib/trainer_csn.py:188-224, 400-500;
  *           lib/utils.py:64-176) -----------------------------------------------------------------------------------------------
