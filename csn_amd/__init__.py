@@ -40,3 +40,8 @@ from .minkowski_field import PointField, batch_points  # noqa: E402,F401
 # resident point collections: a category's points on the device, normalised once, augmented and collated per batch
 # (MinkowskiNet/lib/dataset.py:104-126, 221-252, lib/transforms.py:12-89, 195-225, lib/voxelizer.py:34-45)
 from .minkowski_points import AugmentParams, AugmentSpec, PointBatch, PointCollection  # noqa: E402,F401
+
+# the training procedure around them: optimizer, schedules, the patience-driven graph rebuilds, checkpoints and resume
+# (MinkowskiNet/lib/solvers.py, lib/trainer_csn.py:20-186, 262-395, lib/dataloader.py; the CLI is ``python -m csn_amd.train_csn``)
+from .minkowski_solvers import TrainConfig, initialize_optimizer, initialize_scheduler  # noqa: E402,F401
+from .minkowski_trainer import CSNTrainer, InfSampler, PatienceState  # noqa: E402,F401

@@ -1,0 +1,454 @@
+"""The MinkowskiNet CSN training procedure: epochs of ``train_iter``, validation, the patience-driven rebuilds of the shape graph,
+checkpoints and resume.
+
+Reference (marios2019/CSN):
+  * ``Trainer.__init__`` / ``train``: the epoch loop, patience, cooldown, graph rebuilds     MinkowskiNet/lib/trainer_csn.py:20-186
+  * ``_construct_shape_graph``                                                             MinkowskiNet/lib/trainer_csn.py:262-282
+  * ``_save_curr_checkpoint`` / ``_save_best_checkpoints`` / ``_resume``                    MinkowskiNet/lib/trainer_csn.py:315-387
+  * ``checkpoint`` (file names, dictionary keys, the ``weights.pth`` link)                  MinkowskiNet/lib/utils.py:11-61
+  * ``InfSampler``                                                                         MinkowskiNet/lib/dataloader.py:5-34
+
+Everything on the device is what exists already: a batch is ``PointCollection.batch`` / ``neighbor_batches`` /
+``PointBatch.field()``, an iteration is ``train_iter``, validation is ``evaluate``, the graph is ``construct_shape_graph``.  This
+module is the host side around them.  The loss and the score of an iteration stay device tensors and are added into a device
+accumulator; they are read at ``stat_freq`` and at the end of an epoch, never per iteration.  The reference empties torch's
+allocator cache after every iteration (:216); nothing here does.
+
+WHAT THE METHOD IS.  The shape graph starts from random pairs (:78-83).  After every epoch the validation Part IoU is compared
+with the best so far; while it does not improve, ``cooldown`` runs down first and ``patience`` after it, and at ``patience <= 0``
+the best-Part-IoU checkpoint is loaded again and both splits' neighbours are recomputed with its retrieval measure (:134-158) — at
+most ``MAX_GRAPH_CONSTRUCTION`` constructions, the first one included.  ``PatienceState`` is that state machine alone.
+
+CHECKPOINTS.  The reference's dictionary and file names (``checkpoint_<model><postfix>.pth``, ``weights.pth`` a link to the current
+one) plus one key, ``csn_amd``, with what an exact resume needs and the reference does not save: the scheduler's state, the
+``bit_generator.state`` of the augmentation, sampler and graph generators, the sampler's permutation and position, the iteration
+counter as it stands, and the state of torch's CPU generator — the head's dropout masks are counter-based and take their seeds from
+it (``csn_amd.functional.draw_seeds``).  A checkpoint without the key loads as the reference's does (``_resume``, :348-387): a
+fresh schedule at ``iteration + 1``, fresh generators — a valid continuation, not a bit-equal one.
+"""
+from __future__ import annotations
+
+import dataclasses
+import json
+import logging
+import math
+import os
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .minkowski_csn import construct_shape_graph, random_neighbors
+from .minkowski_points import AugmentSpec, PointCollection
+from .minkowski_solvers import TrainConfig, initialize_optimizer, initialize_scheduler
+from .minkowski_training import evaluate, train_iter
+
+log = logging.getLogger(__name__)
+
+MAX_PATIENCE, MAX_COOLDOWN, MAX_GRAPH_CONSTRUCTION = 10, 5, 3          # trainer_csn.py:36
+LR_FACTOR = 0.5                                                        # ReduceLROnPlateau's factor (:41)
+Neighbors = List[Tuple[int, List[int]]]
+
+
+class InfSampler:
+    """An endless permutation sampler (dataloader.py:5-34): ``next()`` walks a permutation of ``range(n)`` and draws a fresh one from
+    ``rng`` (the caller's ``numpy.random.Generator``) when it is used up; ``shuffle=False`` walks ``0 .. n-1`` over and over.
+    ``len()`` is n.  ``state_dict()`` holds the permutation, the position in it and the generator's state."""
+
+    def __init__(self, n: int, shuffle: bool = True, rng: Optional[np.random.Generator] = None):
+        if n < 1:
+            raise ValueError("InfSampler needs at least one item")
+        if shuffle and rng is None:
+            raise ValueError("a shuffling InfSampler needs an explicit numpy Generator (rng)")
+        self.n, self.shuffle, self.rng = int(n), bool(shuffle), rng
+        self._perm: List[int] = []
+        self._pos = 0
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> int:
+        if self._pos >= len(self._perm):
+            self._perm = [int(i) for i in (self.rng.permutation(self.n) if self.shuffle else range(self.n))]
+            self._pos = 0
+        self._pos += 1
+        return self._perm[self._pos - 1]
+
+    def state_dict(self) -> dict:
+        return {"n": self.n, "shuffle": self.shuffle, "perm": list(self._perm), "pos": self._pos,
+                "bit_generator": None if self.rng is None else self.rng.bit_generator.state}
+
+    def load_state_dict(self, state: dict) -> None:
+        if state["n"] != self.n or state["shuffle"] != self.shuffle:
+            raise ValueError(f"the saved sampler walks {state['n']} items (shuffle={state['shuffle']}), this one {self.n} "
+                             f"(shuffle={self.shuffle})")
+        self._perm, self._pos = [int(i) for i in state["perm"]], int(state["pos"])
+        if self.rng is not None and state["bit_generator"] is not None:
+            self.rng.bit_generator.state = state["bit_generator"]
+
+
+class PatienceState:
+    """The trainer's state machine (trainer_csn.py:36-52, 114-158), host numbers only.
+
+    ``observe(part_iou)`` is the end of an epoch BEFORE the best values move (:115-130): ``cooldown -= 1``; a Part IoU above the best
+    so far resets ``patience``; otherwise — only while ``k_neighbors > 0`` and fewer than ``MAX_GRAPH_CONSTRUCTION`` graphs were built
+    — a cooldown that reached zero is held there and ``patience`` falls by one.  ``record_best(...)`` then moves the four best values
+    (:330-346), each stamped with the iteration given, calling ``on_best(postfix)`` right after each one moved: a checkpoint written
+    there sees the values moved so far, as the reference's files do.  ``should_rebuild()``: ``k_neighbors > 0`` and ``patience <= 0``
+    (:134-136).  ``rebuilt()``: one more construction, patience and cooldown back at their maxima (:154-156); ``constructed()`` is
+    the first, random graph, which only counts (:82)."""
+
+    def __init__(self, k_neighbors: int):
+        self.k_neighbors = int(k_neighbors)
+        self.patience, self.cooldown = MAX_PATIENCE, MAX_COOLDOWN
+        self.n_graph_construction = 0
+        self.best_val_part_iou, self.best_val_part_iou_iter = 0, 0
+        self.best_val_shape_iou, self.best_val_shape_iou_iter = 0, 0
+        self.best_val_loss, self.best_val_loss_iter = float("inf"), 0
+        self.best_val_acc, self.best_val_acc_iter = 0, 0
+
+    def observe(self, val_part_iou: float) -> None:
+        self.cooldown -= 1
+        if val_part_iou > self.best_val_part_iou:
+            self.patience = MAX_PATIENCE
+        elif self.k_neighbors > 0 and self.n_graph_construction < MAX_GRAPH_CONSTRUCTION:
+            if self.cooldown <= 0:
+                self.cooldown = 0
+                self.patience -= 1
+
+    def record_best(self, val_loss: float, val_score: float, val_part_iou: float, val_shape_iou: float, curr_iter: int,
+                    on_best: Optional[Callable[[str], None]] = None) -> List[str]:
+        moved = []
+
+        def hit(postfix):
+            moved.append(postfix)
+            if on_best is not None:
+                on_best(postfix)
+        if val_part_iou > self.best_val_part_iou:
+            self.best_val_part_iou, self.best_val_part_iou_iter = val_part_iou, curr_iter
+            hit("best_part_iou")
+        if val_shape_iou > self.best_val_shape_iou:
+            self.best_val_shape_iou, self.best_val_shape_iou_iter = val_shape_iou, curr_iter
+            hit("best_shape_iou")
+        if val_loss < self.best_val_loss:
+            self.best_val_loss, self.best_val_loss_iter = val_loss, curr_iter
+            hit("best_loss")
+        if val_score > self.best_val_acc:
+            self.best_val_acc, self.best_val_acc_iter = val_score, curr_iter
+            hit("best_acc")
+        return moved
+
+    def should_rebuild(self) -> bool:
+        return self.k_neighbors > 0 and self.patience <= 0
+
+    def constructed(self) -> None:
+        self.n_graph_construction += 1
+
+    def rebuilt(self) -> None:
+        self.n_graph_construction += 1
+        self.patience, self.cooldown = MAX_PATIENCE, MAX_COOLDOWN
+
+    def best_values(self) -> Dict[str, float]:
+        return {k: getattr(self, k) for k in ("best_val_part_iou", "best_val_part_iou_iter", "best_val_shape_iou",
+                                              "best_val_shape_iou_iter", "best_val_loss", "best_val_loss_iter", "best_val_acc",
+                                              "best_val_acc_iter")}
+
+
+class _SubBatches:
+    """The ``iter_size`` sub-batches of one iteration, fetched one at a time as ``train_iter`` walks them (it asks for ``len()``
+    first): one sub-batch is resident at a time, as in trainer_csn.py:194-210."""
+
+    def __init__(self, trainer: "CSNTrainer"):
+        self.trainer = trainer
+        self.rows = 0
+
+    def __len__(self) -> int:
+        return self.trainer.cfg.iter_size
+
+    def __iter__(self):
+        t = self.trainer
+        for _ in range(t.cfg.iter_size):
+            batch, target = t.fetch([next(t.sampler) for _ in range(t.cfg.batch_size)])
+            self.rows = int(target.shape[0])
+            yield batch, target
+
+
+class CSNTrainer:
+    """``Trainer`` of trainer_csn.py for an ``HRNetSimCSN`` on two resident ``PointCollection``s (both normalised by the caller, both
+    with labels, on the model's device).  ``cfg`` is a ``TrainConfig``; ``spec`` the training augmentation (None:
+    ``AugmentSpec.distort_partnet()``); ``seed`` seeds the three generators the trainer owns — augmentation, sampler, random graph.
+    The dropout seeds come from torch's CPU generator: ``torch.manual_seed`` before the run fixes them.  Validation walks the
+    validation split in order, ``val_batch_size`` shapes at a time (config.py: 1), unaugmented, keys from the TRAINING split."""
+
+    def __init__(self, model, train_collection: PointCollection, val_collection: PointCollection, cfg: TrainConfig,
+                 spec: Optional[AugmentSpec] = None, seed: int = 0, val_batch_size: int = 1,
+                 quantization_mode: str = "random_subsample"):
+        if train_collection.labels is None or val_collection.labels is None:
+            raise ValueError("both collections need per-point labels")
+        if cfg.batch_size < 1 or cfg.iter_size < 1 or val_batch_size < 1:
+            raise ValueError("batch_size, iter_size and val_batch_size must be at least 1")
+        if cfg.k_neighbors < 0 or cfg.k_neighbors > train_collection.n_shapes - 1:
+            raise ValueError(f"k_neighbors must lie in [0, {train_collection.n_shapes - 1}] for {train_collection.n_shapes} training shapes")
+        if cfg.k_neighbors > 0 and model.head.k_neighbors == 0:
+            raise ValueError("the model's head was built with k_neighbors = 0: it takes no key batches")
+        self.model, self.train_collection, self.val_collection, self.cfg = model, train_collection, val_collection, cfg
+        self.spec = AugmentSpec.distort_partnet() if spec is None else spec
+        self.val_batch_size, self.quantization_mode = int(val_batch_size), quantization_mode
+        self.num_labels = int(model.head.output.out_features)
+        self.aug_rng, sampler_rng, self.graph_rng = (np.random.default_rng([int(seed), i]) for i in range(3))
+        self.sampler = InfSampler(train_collection.n_shapes, True, sampler_rng)
+        self.optimizer = initialize_optimizer(model.parameters(), cfg)
+        self.scheduler = initialize_scheduler(self.optimizer, cfg, factor=LR_FACTOR, patience=MAX_PATIENCE, cooldown=MAX_COOLDOWN * 2)
+        self.state = PatienceState(cfg.k_neighbors)
+        self.curr_iter, self.epoch = 1, 1                                         # trainer_csn.py:51
+        self.train_neighbors: Optional[Neighbors] = None
+        self.val_neighbors: Optional[Neighbors] = None
+
+    # ---- batches ----
+    def _forward(self, batch):
+        field, keys = batch
+        return field.interpolate(self.model(field.sparse(), [k.sparse() for k in keys] or None)), field.offsets
+
+    def _fields(self, queries_from: PointCollection, q_idx: Sequence[int], neighbors: Optional[Neighbors], augment: bool):
+        cfg, K, B = self.cfg, self.cfg.k_neighbors, len(q_idx)
+        if K > 0 and neighbors is None:
+            raise ValueError("no shape graph yet: call construct_graphs() or load a checkpoint that holds one")
+        p = self.spec.draw((K + 1) * B, self.aug_rng) if augment else None
+        queries = queries_from.batch(q_idx, None if p is None else p.slice(0, B), cfg.voxel_size, self.spec.shift)
+        keys = []
+        if K > 0:
+            keys = self.train_collection.neighbor_batches([neighbors[int(i)] for i in q_idx], K,
+                                                          None if p is None else p.slice(B, (K + 1) * B), cfg.voxel_size, self.spec.shift)
+        mode = self.quantization_mode
+        return (queries.field(mode), [k.field(mode) for k in keys]), queries.labels
+
+    def fetch(self, q_idx: Sequence[int]):
+        """``_fetch_data`` (:236-260) for the training shapes ``q_idx``: ``((queries_field, key_fields), target)`` — the queries and
+        the i-th neighbour of every query, each item augmented with numbers of its own from the augmentation generator."""
+        return self._fields(self.train_collection, q_idx, self.train_neighbors, True)
+
+    def _val_batches(self):
+        n = self.val_collection.n_shapes
+        for lo in range(0, n, self.val_batch_size):
+            yield self._fields(self.val_collection, list(range(lo, min(lo + self.val_batch_size, n))), self.val_neighbors, False)
+
+    # ---- the shape graph ----
+    def _backbone_shapes(self, col: PointCollection) -> List[torch.Tensor]:
+        """The backbone rows of every shape of ``col`` (unaugmented, no grad): what ``construct_shape_graph`` scores.  All of them
+        stay resident until the graph is built: voxels x backbone channels x 4 bytes per split."""
+        out = []
+        with torch.no_grad():
+            for lo in range(0, col.n_shapes, self.cfg.batch_size):
+                idx = list(range(lo, min(lo + self.cfg.batch_size, col.n_shapes)))
+                rows, off = self.model.backbone_rows(col.batch(idx, None, self.cfg.voxel_size).field(self.quantization_mode).sparse())
+                off = [int(v) for v in off.tolist()]
+                out += [rows[a:b] for a, b in zip(off, off[1:])]
+        return out
+
+    def construct_graphs(self, recalculate: bool = False) -> None:
+        """``_construct_shape_graph`` (:262-282) in eval mode (the mode it found is restored): the first construction pairs every
+        shape with random training shapes (``construct_shape_graph``'s random branch, from the graph generator), a recalculation
+        ranks the training shapes by the model's retrieval measure — for the training split among themselves, never a shape
+        itself, for the validation split against the training split."""
+        K = self.cfg.k_neighbors
+        if K < 1:
+            raise ValueError("k_neighbors = 0: there is no shape graph")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            log.info("===> %s shape graph for the training and validation splits", "Recalculate" if recalculate else "Construct")
+            if recalculate:
+                train_rows, val_rows = self._backbone_shapes(self.train_collection), self._backbone_shapes(self.val_collection)
+                self.train_neighbors = construct_shape_graph(self.model.head, train_rows, None, K)
+                self.val_neighbors = construct_shape_graph(self.model.head, val_rows, train_rows, K)
+            else:
+                n_train, n_val = self.train_collection.n_shapes, self.val_collection.n_shapes
+                self.train_neighbors = random_neighbors(n_train, n_train, K, True, self.graph_rng)
+                self.val_neighbors = random_neighbors(n_val, n_train, K, False, self.graph_rng)
+        finally:
+            self.model.train(was_training)
+
+    # ---- one epoch, one validation ----
+    @property
+    def iters_per_epoch(self) -> int:
+        return math.ceil(len(self.sampler) / self.cfg.batch_size / self.cfg.iter_size)
+
+    def _plateau(self) -> bool:
+        return self.cfg.scheduler == "ReduceLROnPlateau"
+
+    def train_epoch(self) -> Tuple[float, float]:
+        """``iters_per_epoch`` iterations of ``train_iter`` (:94-103), ``iter_size`` sub-batches each; the scheduler steps per
+        iteration unless it is ``ReduceLROnPlateau``.  Returns the epoch's (loss, score) averages, weighted as the reference's
+        meters are (:223-224: by the rows of the last sub-batch) — the epoch's one read besides those at ``stat_freq``."""
+        cfg = self.cfg
+        self.model.train()
+        acc, rows = None, 0
+        n_iter = self.iters_per_epoch
+        for _ in range(n_iter):
+            subs = _SubBatches(self)
+            loss, score = train_iter(self._forward, subs, self.optimizer, None if self._plateau() else self.scheduler, cfg.ignore_label)
+            term = torch.stack([loss.double(), score.double()]) * subs.rows
+            acc = term if acc is None else acc + term
+            rows += subs.rows
+            if self.curr_iter % cfg.stat_freq == 0 or self.curr_iter == 1:
+                l, s = (acc / rows).tolist()
+                log.info("===> Epoch[%d](%d/%d): Loss %.4f\tLR: %.3e\tScore %.3f", self.epoch, self.curr_iter, n_iter, l, self.lr, s)
+            self.curr_iter += 1
+        l, s = (acc / rows).tolist()
+        return l, s
+
+    @property
+    def lr(self) -> float:
+        return self.optimizer.param_groups[0]["lr"]
+
+    def validate(self) -> Tuple[float, float, float, float]:
+        """``_validate`` / ``Trainer.test`` (:226-234, 400-500) through ``evaluate``: (loss, precision, Part IoU, Shape IoU) of the
+        validation split in eval mode; the mode it found is restored."""
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return evaluate(self._forward, self._val_batches(), self.num_labels, self.cfg.ignore_label)
+        finally:
+            self.model.train(was_training)
+
+    # ---- the procedure ----
+    def train(self) -> None:
+        """``Trainer.train`` (:54-186)."""
+        cfg, st = self.cfg, self.state
+        self.model.train()
+        log.info("===> Start training")
+        if cfg.resume:
+            self.load_checkpoint(os.path.join(cfg.resume, "weights.pth"))
+            if st.should_rebuild():                                              # the run stopped between the verdict and the rebuild
+                self.construct_graphs(recalculate=True)
+                st.rebuilt()
+        elif cfg.k_neighbors > 0:
+            self.construct_graphs(recalculate=False)
+            st.constructed()
+        while True:
+            self.train_epoch()
+            if self.epoch >= cfg.max_epoch:
+                break
+            self._save_curr_checkpoint()                                         # before the validation, as the reference does
+            val = self.validate()
+            st.observe(val[2])
+            log.info("=====> (Iteration:%d) patience %d, cooldown %d", self.curr_iter, st.patience, st.cooldown)
+            self._record(val)
+            if st.should_rebuild():
+                self._reload_best()
+                self.construct_graphs(recalculate=True)
+                st.rebuilt()
+                self._save_curr_checkpoint()                                     # keeps the new graph
+            self.model.train()
+            if self._plateau():
+                self.scheduler.step(val[0])
+            self.epoch += 1
+        self._record(self.validate(), save_current=True)
+
+    def _record(self, val, save_current: bool = False) -> None:
+        loss, score, part_iou, shape_iou = val
+        if save_current:
+            self._save_curr_checkpoint()
+        self.state.record_best(loss, score, part_iou, shape_iou, self.curr_iter, on_best=self._save_curr_checkpoint)
+        st = self.state
+        log.info("Validation at iter %d: loss %.3f, score %.3f, Part IoU %.3f, Shape IoU %.3f", self.curr_iter, loss, score, part_iou, shape_iou)
+        log.info("Current best Part IoU: %.3f at iter %d", st.best_val_part_iou, st.best_val_part_iou_iter)
+        log.info("Current best Shape IoU: %.3f at iter %d", st.best_val_shape_iou, st.best_val_shape_iou_iter)
+        log.info("Current best Loss: %.3f at iter %d", st.best_val_loss, st.best_val_loss_iter)
+        log.info("Current best Score: %.3f at iter %d", st.best_val_acc, st.best_val_acc_iter)
+
+    def _reload_best(self) -> None:
+        """:136-148: back to the best-Part-IoU weights before the graph is recomputed; with ``resume_optimizer`` its optimizer too,
+        the rate back at ``cfg.lr`` and a fresh schedule that starts at the current iteration."""
+        path = self.checkpoint_path("best_part_iou")
+        log.info("=====> Loading checkpoint '%s'", path)
+        state = torch.load(path, map_location="cpu")
+        self._load_model_state(state["state_dict"])
+        log.info("=====> Checkpoint loaded from epoch %s (iter %s)", state["epoch"], state["iteration"])
+        if self.cfg.resume_optimizer:
+            self.optimizer.load_state_dict(state["optimizer"])
+            for group in self.optimizer.param_groups:
+                group["lr"] = group["initial_lr"] = self.cfg.lr
+            self.scheduler = initialize_scheduler(self.optimizer, self.cfg, last_step=self.curr_iter, factor=LR_FACTOR)
+
+    # ---- checkpoints ----
+    def checkpoint_path(self, postfix: Optional[str] = None) -> str:
+        return os.path.join(self.cfg.log_dir, f"checkpoint_{self.cfg.model}{postfix or ''}.pth")
+
+    def checkpoint_state(self) -> dict:
+        """The dictionary ``save_checkpoint`` writes: the reference's keys (utils.py:25-51, trainer_csn.py:315-328; ``csn_data`` only
+        with ``k_neighbors > 0``) and ``csn_amd``."""
+        st = self.state
+        state = {"iteration": self.curr_iter, "epoch": self.epoch + 1, "arch": self.cfg.model, "state_dict": self.model.state_dict(),
+                 "optimizer": self.optimizer.state_dict()}
+        if self.cfg.k_neighbors > 0:
+            state["csn_data"] = {"patience": st.patience, "cooldown": st.cooldown, "n_graph_construction": st.n_graph_construction,
+                                 "train_neighbors": self.train_neighbors, "val_neighbors": self.val_neighbors}
+        state.update(st.best_values())
+        state["csn_amd"] = {"version": 1, "curr_iter": self.curr_iter, "scheduler": self.scheduler.state_dict(),
+                            "augment_rng": self.aug_rng.bit_generator.state, "graph_rng": self.graph_rng.bit_generator.state,
+                            "sampler": self.sampler.state_dict(), "torch_rng_state": torch.get_rng_state()}
+        return state
+
+    def save_checkpoint(self, path: str) -> None:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save(self.checkpoint_state(), path)
+        log.info("Checkpoint saved to %s", path)
+
+    def _save_curr_checkpoint(self, postfix: Optional[str] = None) -> None:
+        path = self.checkpoint_path(postfix)
+        self.save_checkpoint(path)
+        if postfix is None:                                                      # utils.py:52-61: the settings, and weights.pth -> the file
+            with open(os.path.join(self.cfg.log_dir, "config.json"), "w") as fh:
+                json.dump(dataclasses.asdict(self.cfg), fh, indent=4)
+            link = os.path.join(self.cfg.log_dir, "weights.pth")
+            if os.path.lexists(link):
+                os.remove(link)
+            os.symlink(os.path.basename(path), link)
+
+    def _load_model_state(self, state_dict) -> None:
+        """This project's names (``backbone.*`` / ``head.*``) go through ``load_state_dict``; a dictionary without them is taken for
+        the reference's layout and goes through ``load_me_hrnet_state``."""
+        if any(k.startswith("backbone.") for k in state_dict):
+            self.model.load_state_dict(state_dict)
+        else:
+            from .minkowski_hrnet import load_me_hrnet_state
+            load_me_hrnet_state(self.model, state_dict)
+
+    def load_checkpoint(self, path: str) -> None:
+        """``_resume`` (:348-387).  With the ``csn_amd`` key the run continues bit for bit (given ``resume_optimizer``); without it,
+        as the reference resumes."""
+        if not os.path.isfile(path):
+            raise ValueError(f"no checkpoint found at '{path}'")
+        log.info("=> Loading checkpoint '%s'", path)
+        state = torch.load(path, map_location="cpu")
+        extra = state.get("csn_amd")
+        self.curr_iter = int(extra["curr_iter"]) if extra else int(state["iteration"]) + 1
+        self.epoch = int(state["epoch"])
+        self._load_model_state(state["state_dict"])
+        if self.cfg.resume_optimizer:
+            if extra:
+                self.optimizer.load_state_dict(state["optimizer"])
+                self.scheduler.load_state_dict(extra["scheduler"])
+            else:
+                self.scheduler = initialize_scheduler(self.optimizer, self.cfg, last_step=self.curr_iter, factor=LR_FACTOR)
+                self.optimizer.load_state_dict(state["optimizer"])
+        st = self.state
+        if "csn_data" in state:
+            data = state["csn_data"]
+            st.patience, st.cooldown, st.n_graph_construction = int(data["patience"]), int(data["cooldown"]), int(data["n_graph_construction"])
+            self.train_neighbors = [(int(q), [int(i) for i in nb]) for q, nb in data["train_neighbors"]]
+            self.val_neighbors = [(int(q), [int(i) for i in nb]) for q, nb in data["val_neighbors"]]
+            log.info("===> Patience=%d, Cooldown=%d, #Graph construction=%d", st.patience, st.cooldown, st.n_graph_construction)
+        for k in st.best_values():
+            if k in state:
+                setattr(st, k, state[k])
+        if extra:
+            self.aug_rng.bit_generator.state = extra["augment_rng"]
+            self.graph_rng.bit_generator.state = extra["graph_rng"]
+            self.sampler.load_state_dict(extra["sampler"])
+            torch.set_rng_state(extra["torch_rng_state"])
+        log.info("=> Loaded checkpoint '%s' (epoch %d)", path, self.epoch)
