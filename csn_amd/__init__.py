@@ -45,3 +45,7 @@ from .minkowski_points import AugmentParams, AugmentSpec, PointBatch, PointColle
 # (MinkowskiNet/lib/solvers.py, lib/trainer_csn.py:20-186, 262-395, lib/dataloader.py; the CLI is ``python -m csn_amd.train_csn``)
 from .minkowski_solvers import TrainConfig, initialize_optimizer, initialize_scheduler  # noqa: E402,F401
 from .minkowski_trainer import CSNTrainer, InfSampler, PatienceState  # noqa: E402,F401
+# the HRNetSeg baseline's procedure and test mode for both model families (lib/trainer_seg.py, tasks/main_csn.py:121-141,
+# tasks/main_seg.py:124-130; the CLIs are ``python -m csn_amd.train_seg`` and ``--is_train False`` of either, and
+# ``python -m csn_amd.collect_partnet_results`` gathers the result files)
+from .minkowski_trainer import BestValues, SegTrainer, checkpoint_num_labels, load_model_state, test_split  # noqa: E402,F401
