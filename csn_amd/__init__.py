@@ -29,6 +29,7 @@ from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseCo
 # 296-454)
 from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetSimCSN3S, HRNetSimCSN4S, VoxelPyramid,  # noqa: E402,F401
                               bn_act, build_pyramid, conv_stats, load_me_hrnet_state)
+from .minkowski_hrnet import GroupedPyramid, bn_act_groups, conv_stats_groups, group_pyramid, merge_batches  # noqa: E402,F401
 # the plain segmentation networks (hrnet.py:214-293) and the backbone's one-launch-per-convolution inference primitive
 from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
                               sparse_conv_bn_act)

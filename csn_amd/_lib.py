@@ -267,6 +267,15 @@ _SIGNATURES = {
     "csn_sparse_conv_bn_act_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_longlong, c_int, c_void_p,
                                                c_longlong, c_void_p]),
+    "csn_sparse_conv_stats_groups_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "csn_sparse_conv_stats_groups_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                                     c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                                     c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
+    "csn_rows_bn_act_groups_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "csn_rows_bn_act_groups_fwd_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_longlong, c_int, c_void_p,
+                                               c_longlong, c_void_p]),
+    "csn_rows_bn_act_groups_bwd_f32": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_void_p,
+                                               c_int, c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p]),
     "csn_voxel_mean_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "csn_point_interp_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong,
                                          c_void_p]),

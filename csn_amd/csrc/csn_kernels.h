@@ -363,6 +363,16 @@ int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C,
 long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms);
 int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, hipStream_t st);
 int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, hipStream_t st);
+// (20) the same over row groups: group g is the rows [group_rows[g], group_rows[g + 1]) (device, n_groups + 1 entries), mean /
+// scale of the terms are [n_groups][C]; training mode only
+int csn_launch_sparse_conv_stats_groups_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
+                                            float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st);
+int csn_launch_bn_stats_merge_groups(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, const float* z, int ld_z,
+                                     const int* group_rows, int n_groups, float* mean, float* invstd, float* running_mean,
+                                     float* running_var, hipStream_t st);
+long long csn_rows_bn_act_groups_ws_bytes(long long n_rows, int C, int n_terms, int n_groups);
+int csn_launch_rows_bn_act_groups_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
+int csn_launch_rows_bn_act_groups_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
 
 // ---- point fields: voxel means, trilinear interpolation onto points and its adjoint (point_field.hip) ----
 struct CsnPointFieldArgs {

@@ -292,6 +292,20 @@ int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, fl
   return csn_launch_bn_stats_merge(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, mean, invstd, running_mean, running_var, st);
 }
 
+// (20a) the same product and epilogue on a map whose rows are n_groups BatchNorm batches: the kernel above unchanged, then the
+// tiles merged per group (rows_bn_act.hip: the tiles a group boundary cuts are re-read from z)
+int csn_launch_sparse_conv_stats_groups_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
+                                            float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st) {
+  SconvGemmP p{};
+  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
+  p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = nullptr;
+  p.part = static_cast<float*>(a.ws);
+  if (const int e = launch_gemm<true>(p, mode, st)) return e;
+  const int n_tiles = (int)(((long long)a.n_out + 127) / 128) * 4;
+  return csn_launch_bn_stats_merge_groups(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, a.y, a.ld_y, group_rows, n_groups, mean,
+                                          invstd, running_mean, running_var, st);
+}
+
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {
   if (mode == 3) return -1;                                           // fp16 is forward only
   const WsLayout L = ws_layout(a.n_out, a.kv, a.c_in, a.c_out);

@@ -22,6 +22,11 @@ ONE launch of include/csn_hip.h section 19 (``sparse_conv_bn_act``: the BatchNor
 ReLU in the product's epilogue), a branch sum is a chain of such launches into one buffer, and the concatenated result is
 allocated once and written in place through the kernels' output pitch: no ``torch.cat``.  Off by default.
 
+Grouped passes (include/csn_hip.h section 20): the K + 1 batches of a CSN training step merged into ONE coordinate set with
+shifted batch indices (``merge_batches`` -> ``GroupedPyramid``).  The rows of a batch are then a contiguous range at every level, the
+convolutions run once on the merged maps, and ``conv_stats_groups`` / ``bn_act_groups`` take the BatchNorm statistics per row group.
+``tuning.override(grouped_passes=True)`` makes ``HRNetSimCSN.forward`` do so.  Off by default.
+
 ``VoxelPyramid`` holds the coordinate sets and kernel maps of one batch, built once (``build_pyramid``): level l's coordinates are
 ``down^l(coords)`` by the stride-2 rule of ``build_kernel_map``; per level the stride-1 kernel-3 map, at level 0 the stem's map,
 between neighbouring levels the stride-2 map whose ``transpose()`` serves the up direction.
@@ -128,6 +133,155 @@ def _build_pyramid_hip(coords: torch.Tensor, n_levels: int, stem_kernel: int) ->
     return VoxelPyramid([s.coords for s in sets], s1, stem, down, stem_kernel)
 
 
+MAX_GROUPS = 8                                        # the head's own limit: K + 1 <= 8
+
+
+class GroupedPyramid:
+    """The ``VoxelPyramid`` of G batches merged into one coordinate set (``merge_batches`` / ``group_pyramid``), and where every
+    batch's rows lie in it.  The batch index leads the sort, so group g's rows are one contiguous range at EVERY level: the same
+    rows in the same order as in that batch's own pyramid.
+
+    ``pyramid`` the ``VoxelPyramid``; ``group_rows[l]`` (G + 1,) int32 on the pyramid's device: the row offsets of the groups at
+    level l; ``group_rows_host[l]`` the same numbers as a list; ``n_shapes[g]`` the shapes of group g and ``shape_offsets`` (G + 1)
+    their running sum: group g's shapes carry the batch indices ``[shape_offsets[g], shape_offsets[g + 1])``; ``row_offsets``
+    (total shapes + 1, a host list) the level-0 row offset of every shape.  ``coords``, ``s1``, ``stem``, ``down``, ``up``,
+    ``n_levels`` and ``stem_kernel`` are the pyramid's."""
+
+    def __init__(self, pyramid: VoxelPyramid, group_rows: List[torch.Tensor], group_rows_host: List[List[int]], n_shapes: List[int],
+                 row_offsets: Optional[List[int]]):
+        self.pyramid, self.group_rows, self.group_rows_host, self.n_shapes = pyramid, group_rows, group_rows_host, list(n_shapes)
+        self.shape_offsets = [0]
+        for n in self.n_shapes:
+            self.shape_offsets.append(self.shape_offsets[-1] + n)
+        self._row_offsets = row_offsets
+
+    coords = property(lambda self: self.pyramid.coords)
+    s1 = property(lambda self: self.pyramid.s1)
+    stem = property(lambda self: self.pyramid.stem)
+    down = property(lambda self: self.pyramid.down)
+    stem_kernel = property(lambda self: self.pyramid.stem_kernel)
+    n_levels = property(lambda self: self.pyramid.n_levels)
+
+    def up(self, level: int) -> KernelMap:
+        return self.pyramid.up(level)
+
+    @property
+    def n_groups(self) -> int:
+        return len(self.n_shapes)
+
+    @property
+    def row_offsets(self) -> List[int]:
+        """Level-0 row offset of every shape (a host list).  Known from the construction's one host read when ``n_shapes`` was
+        given or the coordinates were host tensors; otherwise read here, once."""
+        if self._row_offsets is None:
+            self._row_offsets = [int(v) for v in offsets_from_batch_index(self.coords[0][:, 0], self.shape_offsets[-1]).tolist()]
+        return self._row_offsets
+
+    def group_offsets(self, g: int) -> List[int]:
+        """The (n_shapes[g] + 1) row offsets of group g's shapes inside the group's own level-0 rows: what the head takes."""
+        ro = self.row_offsets
+        a, b = self.shape_offsets[g], self.shape_offsets[g + 1]
+        return [v - ro[a] for v in ro[a:b + 1]]
+
+    def groups(self, level: int) -> Tuple[torch.Tensor, int]:
+        return self.group_rows[level], self.n_groups
+
+    def to(self, device) -> "GroupedPyramid":
+        return GroupedPyramid(self.pyramid.to(device), [t.to(device) for t in self.group_rows], self.group_rows_host, self.n_shapes,
+                              self._row_offsets)
+
+
+def group_pyramid(coords: torch.Tensor, n_shapes: Sequence[int], n_levels: int, stem_kernel: int = 5,
+                  backend: Optional[str] = None) -> GroupedPyramid:
+    """The ``GroupedPyramid`` of ``coords (n, 4)`` that ALREADY hold G batches one after the other with running batch indices
+    (group g's shapes are ``[sum n_shapes[:g], sum n_shapes[:g + 1])``; rows sorted by shape).  The pyramid is ``build_pyramid``'s;
+    on top of what that does, ONE host read: every level's group row offsets (and the level-0 row offset of every shape) in one
+    transfer.  It is checked there that the offsets start at 0, ascend and end at the level's row count — no kernel is launched on
+    offsets nobody looked at — and a group with exactly one row at any level raises ``ValueError``."""
+    n_shapes = [int(v) for v in n_shapes]
+    if not 1 <= len(n_shapes) <= MAX_GROUPS:
+        raise ValueError(f"1 to {MAX_GROUPS} groups (K + 1 <= {MAX_GROUPS}), not {len(n_shapes)}")
+    if min(n_shapes) < 1:
+        raise ValueError("every group needs at least one shape")
+    pyr = build_pyramid(coords, n_levels, stem_kernel, backend=backend)
+    dev = pyr.coords[0].device
+    total = sum(n_shapes)
+    bounds = torch.tensor([sum(n_shapes[:g]) for g in range(len(n_shapes) + 1)], dtype=torch.int64, device=dev)
+    found = [torch.searchsorted(c[:, 0].contiguous(), bounds) for c in pyr.coords]
+    b0 = pyr.coords[0][:, 0].contiguous()
+    found.append(torch.searchsorted(b0, torch.arange(total + 1, dtype=torch.int64, device=dev)))
+    found.append((b0[1:] < b0[:-1]).any().long().reshape(1))
+    host = torch.cat(found).tolist()                                        # the one host read
+    if host.pop():
+        raise ValueError("batch-index column is not non-decreasing: the rows are not sorted by shape")
+    G1 = len(n_shapes) + 1
+    rows_host = [host[l * G1:(l + 1) * G1] for l in range(n_levels)]
+    row_offsets = host[n_levels * G1:]
+    for l, off in enumerate(rows_host):
+        n_l = pyr.coords[l].shape[0]
+        if off[0] != 0 or off[-1] != n_l or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError(f"level {l}: the group row offsets {off} do not start at 0, ascend and end at the {n_l} rows: the batch "
+                             "indices are not sorted, or leave the groups' shapes")
+        if any(b == a for a, b in zip(off, off[1:])):
+            raise ValueError(f"level {l}: a group has no rows")
+        if any(b - a == 1 for a, b in zip(off, off[1:])):
+            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance): "
+                             f"a group has exactly one row at level {l}")
+    if any(b <= a for a, b in zip(row_offsets, row_offsets[1:])):
+        raise ValueError("every shape of the batch needs at least one row")
+    group_rows = [torch.tensor(off, dtype=torch.int32).to(dev) for off in rows_host]
+    return GroupedPyramid(pyr, group_rows, rows_host, n_shapes, row_offsets)
+
+
+def merge_batches(batches: Sequence, n_levels: int, stem_kernel: int = 5, n_shapes: Optional[Sequence[int]] = None,
+                  backend: Optional[str] = None) -> GroupedPyramid:
+    """G batches ``(coords (n_g, 4), feats)``, 1 <= G <= 8, as ONE coordinate set: group g's batch column is shifted by the number of
+    shapes in groups 0 .. g - 1 (``n_shapes[g]`` where given — a ``PointBatch`` knows it on the host —, else the group's largest batch
+    index + 1) and the coordinates are concatenated, which keeps them sorted.  The pyramid is ``build_pyramid``'s with either
+    backend; shifted batch indices that leave the range it accepts raise as it does.  Beyond ``build_pyramid``'s own, the
+    construction does one host read (``group_pyramid``); without ``n_shapes`` on device tensors the shape counts are that read
+    and the per-shape row offsets a second one, taken when ``row_offsets`` is first asked for.  The features are the caller's to
+    concatenate (``torch.cat([f for _, f in batches])``)."""
+    if not 1 <= len(batches) <= MAX_GROUPS:
+        raise ValueError(f"1 to {MAX_GROUPS} batches (K + 1 <= {MAX_GROUPS}), not {len(batches)}")
+    cs = [b[0] for b in batches]
+    for c in cs:
+        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 4 or c.shape[0] < 1:
+            raise ValueError("every batch needs (n, 4) coordinates [b, x, y, z] with n >= 1")
+    if n_shapes is not None:
+        n_shapes = [int(v) for v in n_shapes]
+        if len(n_shapes) != len(cs):
+            raise ValueError("n_shapes needs one entry per batch")
+    elif not cs[0].is_cuda:
+        n_shapes = [int(c[:, 0].max()) + 1 for c in cs]
+    if n_shapes is not None:
+        shifted = [c.long() if g == 0 else c.long() + c.new_tensor([sum(n_shapes[:g]), 0, 0, 0], dtype=torch.int64)
+                   for g, c in enumerate(cs)]
+        return group_pyramid(torch.cat(shifted), n_shapes, n_levels, stem_kernel, backend)
+    # device tensors, shape counts unknown: shift on the device, and learn the counts in the one read
+    counts = torch.stack([c[:, 0].max().long() + 1 for c in cs])
+    shifts = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+    e0 = torch.tensor([1, 0, 0, 0], dtype=torch.int64, device=cs[0].device)
+    merged = torch.cat([c.long() + shifts[g] * e0 for g, c in enumerate(cs)])
+    pyr = build_pyramid(merged, n_levels, stem_kernel, backend=backend)
+    found = [torch.searchsorted(c[:, 0].contiguous(), shifts) for c in pyr.coords]
+    b0 = pyr.coords[0][:, 0].contiguous()
+    host = torch.cat([counts] + found + [(b0[1:] < b0[:-1]).any().long().reshape(1)]).tolist()      # the one host read
+    if host.pop():
+        raise ValueError("batch-index column is not non-decreasing: the rows are not sorted by shape")
+    G = len(cs)
+    n_shapes, rows_host = host[:G], [host[G + l * (G + 1):G + (l + 1) * (G + 1)] for l in range(n_levels)]
+    for l, off in enumerate(rows_host):
+        n_l = pyr.coords[l].shape[0]
+        if off[0] != 0 or off[-1] != n_l or any(b <= a for a, b in zip(off, off[1:])):
+            raise ValueError(f"level {l}: the group row offsets {off} do not start at 0, ascend and end at the {n_l} rows")
+        if any(b - a == 1 for a, b in zip(off, off[1:])):
+            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance): "
+                             f"a group has exactly one row at level {l}")
+    dev = pyr.coords[0].device
+    return GroupedPyramid(pyr, [torch.tensor(off, dtype=torch.int32).to(dev) for off in rows_host], rows_host, n_shapes, None)
+
+
 # ------------------------------------------------------------------------------------------------------
 # autograd nodes on section 15
 # ------------------------------------------------------------------------------------------------------
@@ -164,25 +318,30 @@ class _ConvStats(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, _dmean, _dinvstd):
-        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
-            x, w = ctx.saved_tensors
-            kmap = ctx.kmap
-            L = _lib.lib()
-            KV, c_in, c_out = w.shape
-            n_in, n_out = kmap.n_in, kmap.n_out
-            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (need_x or need_w):
-                return (None,) * 7
-            dz = dz.contiguous()
-            dx = torch.empty_like(x) if need_x else None
-            dw = torch.empty_like(w) if need_w else None
-            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
-            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-            bwd = kmap.bwd_table if need_x else None
-            _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
-                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
-                                                 CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
-            return dx, dw, None, None, None, None, None
+        return _conv_stats_backward(ctx, dz) + (None,) * 5
+
+
+def _conv_stats_backward(ctx, dz):
+    """(dx, dw) of a convolution node that saved (x, w) and its map: ``csn_sparse_conv_bwd_f32``."""
+    with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
+        x, w = ctx.saved_tensors
+        kmap = ctx.kmap
+        L = _lib.lib()
+        KV, c_in, c_out = w.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_w):
+            return None, None
+        dz = dz.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(w) if need_w else None
+        ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+        ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+        bwd = kmap.bwd_table if need_x else None
+        _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
+                                             CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
+                                             CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+        return dx, dw
 
 
 def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_mean: Optional[torch.Tensor],
@@ -268,6 +427,142 @@ class _BnAct(torch.autograd.Function):
 
 
 Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
+
+
+# ------------------------------------------------------------------------------------------------------
+# autograd nodes on section 20: BatchNorm over row groups
+# ------------------------------------------------------------------------------------------------------
+def _check_groups(group_rows: torch.Tensor, like: torch.Tensor) -> int:
+    if not isinstance(group_rows, torch.Tensor) or group_rows.dtype != torch.int32 or group_rows.dim() != 1:
+        raise ValueError("group_rows must be a (G + 1,) int32 tensor of row offsets")
+    G = group_rows.numel() - 1
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError(f"1 to {MAX_GROUPS} groups, not {G}")
+    if not group_rows.is_cuda or group_rows.device != like.device:
+        raise _lib.CsnError(_NO_CPU)
+    return G
+
+
+class _ConvStatsGroups(torch.autograd.Function):
+    """``_ConvStats`` with the statistics per row group (``csn_sparse_conv_stats_groups_fwd_f32``): mean / invstd are (G, c_out),
+    the running statistics take G updates in group order.  The backward is ``csn_sparse_conv_bwd_f32`` on the merged map."""
+
+    @staticmethod
+    def forward(ctx, x, w, kmap, group_rows, running_mean, running_var, eps, momentum):
+        CF._need_cuda(x, w, kmap.fwd, running_mean, running_var)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        ctx.rows16 = tuning.current().rows_single_product
+        x = x.contiguous()
+        w_c = w.detach().contiguous()
+        group_rows = group_rows.contiguous()
+        G = group_rows.numel() - 1
+        KV, c_in, c_out = w_c.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        dev = x.device
+        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
+        mean = torch.empty((G, c_out), device=dev, dtype=torch.float32)
+        invstd = torch.empty((G, c_out), device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_sparse_conv_stats_groups_workspace_bytes(n_out, c_out, G))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        with CF.rows16(ctx.rows16):
+            _lib.check(L.csn_sparse_conv_stats_groups_fwd_f32(
+                CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean),
+                CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum), group_rows.data_ptr(), G,
+                CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_stats_groups_fwd_f32")
+        ctx.save_for_backward(x, w_c)
+        ctx.kmap = kmap
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dmean, _dinvstd):
+        return _conv_stats_backward(ctx, dz) + (None,) * 6
+
+
+def conv_stats_groups(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, group_rows: torch.Tensor,
+                      running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``conv_stats`` on a merged map whose output rows are G BatchNorm batches: ``group_rows (G + 1,)`` int32 on the device are the
+    row offsets of the groups (``GroupedPyramid.group_rows[level]``: start at 0, ascend, end at ``kmap.n_out``, every group two rows
+    or more — the CALLER has checked that, the kernels cannot).  Returns ``z (n_out, c_out)`` — the bits of ``conv_stats`` —,
+    ``mean (G, c_out)`` and ``invstd (G, c_out)``; the running statistics (either may be None) take G updates in group order."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
+        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out) for the map's KV and n_in")
+    c_in, c_out = weight.shape[1], weight.shape[2]
+    if c_out % 32 or not 32 <= c_out <= 256 or c_in > 256:
+        raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in at most 256")
+    G = _check_groups(group_rows, x)
+    if kmap.n_out < 2 * G:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    pad = -c_in % 32
+    if pad:
+        x = F.pad(x, (0, pad))
+        weight = F.pad(weight, (0, 0, 0, pad))
+    return _ConvStatsGroups.apply(x.float(), weight, kmap, group_rows, running_mean, running_var, eps, momentum)
+
+
+class _BnActGroups(torch.autograd.Function):
+    """``_BnAct`` in training mode with (G, C) statistics per term (``csn_rows_bn_act_groups_fwd_f32`` / ``_bwd_f32``).
+    Arguments after the fixed ones: (z, mean, scale, gamma, beta) per term."""
+
+    @staticmethod
+    def forward(ctx, relu, group_rows, r, *flat):
+        M = len(flat) // 5
+        CF._need_cuda(r, *flat)
+        L = _lib.lib()
+        group_rows = group_rows.contiguous()
+        G = group_rows.numel() - 1
+        zs = [flat[5 * m].contiguous() for m in range(M)]
+        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
+        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
+        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
+        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+        N, C = zs[0].shape
+        r_c = None if r is None else r.contiguous()
+        y = torch.empty((N, C), device=zs[0].device, dtype=torch.float32)
+        t = _lib.BnTerms()
+        for m in range(M):
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
+            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
+        _lib.check(L.csn_rows_bn_act_groups_fwd_f32(ctypes.addressof(t), M, N, C, group_rows.data_ptr(), G, CF._ptr(r_c), C, int(relu),
+                                                    CF._ptr(y), C, CF._stream()), "csn_rows_bn_act_groups_fwd_f32")
+        ctx.save_for_backward(y if relu else None, group_rows, *zs, *means, *scales, *gammas)
+        ctx.M, ctx.relu, ctx.has_r = M, bool(relu), r is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        M = ctx.M
+        saved = ctx.saved_tensors
+        y, group_rows = saved[0], saved[1]
+        zs, means, scales, gammas = (saved[2 + k * M:2 + (k + 1) * M] for k in range(4))
+        L = _lib.lib()
+        N, C = zs[0].shape
+        G = group_rows.numel() - 1
+        dev = dy.device
+        dy = dy.contiguous()
+        need = ctx.needs_input_grad
+        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[2]) else None
+        t = _lib.BnTerms()
+        outs = []
+        for m in range(M):
+            nz, ng, nb = need[3 + 5 * m], need[3 + 5 * m + 3], need[3 + 5 * m + 4]
+            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
+            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
+            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
+            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
+            outs += [dz, None, None, dg, db]
+        ws_n = int(L.csn_rows_bn_act_groups_workspace_bytes(N, C, M, G))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        _lib.check(L.csn_rows_bn_act_groups_bwd_f32(CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C, group_rows.data_ptr(), G,
+                                                    int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),
+                   "csn_rows_bn_act_groups_bwd_f32")
+        return (None, None, dr, *outs)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -371,12 +666,48 @@ def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu:
     return _BnAct.apply(bool(relu), bool(training), float(eps), residual, *flat)
 
 
+def bn_act_groups(terms: Sequence[Term], group_rows: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = True,
+                  eps: float = 1e-5) -> torch.Tensor:
+    """``bn_act`` in training mode on rows that are G BatchNorm batches: for row i of group g (``group_rows`` as in
+    ``conv_stats_groups``) ``y_i = act(sum_m (gamma_m (z_m,i - mean_m[g]) scale_m[g] + beta_m) + residual_i)`` for 1 to 3 terms
+    ``(z (N, C), mean (G, C), scale (G, C) = invstd of conv_stats_groups, gamma (C,), beta (C,))``.  ``eps`` is part of the
+    statistics already (kept for the signature of ``bn_act``).  The backward is the complete BatchNorm gradient per group."""
+    if not 1 <= len(terms) <= 3:
+        raise ValueError("bn_act_groups takes 1 to 3 terms")
+    flat = []
+    N, C = terms[0][0].shape
+    for z, *_ in terms:
+        if not z.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+    G = _check_groups(group_rows, terms[0][0])
+    for z, mean, scale, gamma, beta in terms:
+        if tuple(z.shape) != (N, C) or any(tuple(v.shape) != (G, C) for v in (mean, scale)) or any(v.numel() != C for v in (gamma, beta)):
+            raise ValueError("every term needs an (N, C) map, two (G, C) statistics and two (C,) vectors")
+        flat += [z.float(), mean, scale, gamma, beta]
+    if C % 32 or not 32 <= C <= 256:
+        raise ValueError(f"width {C} is not supported: a multiple of 32 in [32, 256]")
+    if residual is not None:
+        if not residual.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if tuple(residual.shape) != (N, C):
+            raise ValueError("the residual must be (N, C)")
+        residual = residual.float()
+    return _BnActGroups.apply(bool(relu), group_rows, residual, *flat)
+
+
 # ------------------------------------------------------------------------------------------------------
 # conv + norm as a term; combining terms
 # ------------------------------------------------------------------------------------------------------
-def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, fused: bool):
-    """fused: the term (z, mean, scale, gamma, beta) of ``bn_act``; else the normalised map through ATen."""
+def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, fused: bool, groups=None):
+    """fused: the term (z, mean, scale, gamma, beta) of ``bn_act``; else the normalised map through ATen.  ``groups`` (training,
+    fused): the (group_rows, G) of the map's output level — the term of ``bn_act_groups``, the norm sees G batches."""
     _fits(conv, kmap)
+    if groups is not None:
+        if not x.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        norm.num_batches_tracked += groups[1]
+        z, mean, invstd = conv_stats_groups(x, conv.kernel, kmap, groups[0], norm.running_mean, norm.running_var, norm.eps, norm.momentum)
+        return (z, mean, invstd, norm.weight, norm.bias)
     training = norm.training
     if not x.is_cuda:
         raise _lib.CsnError(_NO_CPU)
@@ -391,9 +722,9 @@ def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: Ke
     return (sparse_conv3d(x, conv.kernel, None, kmap), norm.running_mean, norm.running_var, norm.weight, norm.bias)
 
 
-def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5) -> torch.Tensor:
+def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5, groups=None) -> torch.Tensor:
     """relu(sum of ``parts``) where a part is a term / normalised map of ``_conv_bn`` or ("r", map) for a plain map.  The ATen path
-    adds in the order given (the reference's, hrnet.py:157-161)."""
+    adds in the order given (the reference's, hrnet.py:157-161).  ``groups``: as in ``_conv_bn``, for the level of the sum."""
     if fused:
         terms = [p for p in parts if not (isinstance(p, tuple) and p[0] == "r")]
         res = [p[1] for p in parts if isinstance(p, tuple) and p[0] == "r"]
@@ -401,6 +732,8 @@ def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5) ->
             # the finest branch after stage 0 has no incoming path: the reference's ReLU of a block's output, itself a ReLU
             # output — the same values, and the same gradient (the block's own mask zeroes the same elements): no launch
             return res[0]
+        if groups is not None:
+            return bn_act_groups(terms, groups[0], res[0] if res else None, True, eps)
         return bn_act(terms, res[0] if res else None, True, training, eps)
     maps = [p[1] if isinstance(p, tuple) else p for p in parts]
     buf = maps[0]
@@ -432,11 +765,18 @@ class HRBasicBlock(nn.Module):
         self.norm2 = nn.BatchNorm1d(planes, momentum=bn_momentum)
         self.fused = fused
 
-    def forward(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "") -> torch.Tensor:
+    def forward(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
+                group_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``group_rows`` (training, fused): the rows are G BatchNorm batches (``conv_stats_groups``)."""
         f, tr = self.fused, self.training
-        out = _keep(trace, prefix + "norm1", _combine([_conv_bn(self.conv1, self.norm1, x, kmap, f)], f, tr, self.norm1.eps))
-        t2 = _conv_bn(self.conv2, self.norm2, out, kmap, f)
-        return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps))
+        g = None
+        if group_rows is not None and tr:
+            if not f:
+                raise ValueError("row groups in training need fused=True: ATen has no grouped BatchNorm")
+            g = (group_rows, group_rows.numel() - 1)
+        out = _keep(trace, prefix + "norm1", _combine([_conv_bn(self.conv1, self.norm1, x, kmap, f, g)], f, tr, self.norm1.eps, g))
+        t2 = _conv_bn(self.conv2, self.norm2, out, kmap, f, g)
+        return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps, g))
 
     def infer(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -458,6 +798,10 @@ class HRNetBackbone(nn.Module):
     ``(N, init_dim + sum of the branch widths)`` rows [out_init | branch 0 | transition 1 | ...].  ``trace``: a dict that receives
     every ReLU's output, keyed ``bn0s1``, ``bn1s1``, ``stages.i.j.b.norm1`` / ``.norm2``, ``exchange_blocks.i.j.k.<norm index>``
     (the inner steps of a multi-step path), ``sum.i.k`` (the branch sums after stage i) and ``final_transitions.i.<norm index>``.
+
+    ``pyramid`` may be a ``GroupedPyramid`` (G batches merged, ``merge_batches``): in training every BatchNorm then takes its
+    statistics per group (``conv_stats_groups`` / ``bn_act_groups``; ``num_batches_tracked`` advances by G, the running statistics
+    see the groups in order; ``fused=False`` raises ``ValueError``), in eval mode the pass is the one below on the merged pyramid.
 
     Under ``tuning.override(eval_epilogue=True)`` a fused backbone in eval mode, called with autograd disabled, runs the inference
     graph (``_forward_infer``); in every other case the switch changes nothing."""
@@ -517,9 +861,17 @@ class HRNetBackbone(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
                 nn.init.constant_(m.bias, 0.0)
 
-    def forward(self, feats: torch.Tensor, pyramid: VoxelPyramid, trace: Optional[dict] = None) -> torch.Tensor:
+    def forward(self, feats: torch.Tensor, pyramid, trace: Optional[dict] = None) -> torch.Tensor:
         if not feats.is_cuda:
             raise _lib.CsnError(_NO_CPU)
+        grp = None                                                          # level -> (group_rows, G): training on a GroupedPyramid
+        if isinstance(pyramid, GroupedPyramid):
+            # eval: the running statistics do not depend on the group — the existing path on the merged pyramid
+            if self.training:
+                if not self.fused:
+                    raise ValueError("a GroupedPyramid in training needs fused=True: ATen has no grouped BatchNorm")
+                grp = pyramid.groups
+            pyramid = pyramid.pyramid
         if pyramid.n_levels < self.num_stages or pyramid.stem_kernel != self.conv1_kernel_size:
             raise ValueError(f"the pyramid needs {self.num_stages} levels and a kernel-{self.conv1_kernel_size} stem map")
         if feats.dim() != 2 or feats.shape[0] != pyramid.coords[0].shape[0]:
@@ -527,16 +879,17 @@ class HRNetBackbone(nn.Module):
         f, tr = self.fused, self.training
         if tuning.current().eval_epilogue and f and not tr and not torch.is_grad_enabled():
             return self._forward_infer(feats, pyramid, trace)
-        act1 = lambda name, t: _keep(trace, name, _combine([t], f, tr))
-        out_init = act1("bn0s1", _conv_bn(self.conv0s1, self.bn0s1, feats.float(), pyramid.stem, f))
-        out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f))
+        G = (lambda level: None) if grp is None else grp                    # the groups of a map on `level`
+        act1 = lambda name, t, level: _keep(trace, name, _combine([t], f, tr, groups=G(level)))
+        out_init = act1("bn0s1", _conv_bn(self.conv0s1, self.bn0s1, feats.float(), pyramid.stem, f, G(0)), 0)
+        out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f, G(0)), 0)
         stage_input = [out]
         for i in range(self.num_stages):
             stage_output = []
             for j in range(i + 1):
                 x = stage_input[j]
                 for b, blk in enumerate(self.stages[i][j]):
-                    x = blk(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.")
+                    x = blk(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", None if grp is None else grp(j)[0])
                 stage_output.append(x)
             if i == self.num_stages - 1:
                 break
@@ -552,17 +905,19 @@ class HRNetBackbone(nn.Module):
                     for s in range(steps):
                         level = j + s if k > j else j - s                  # the level the step starts from
                         kmap = pyramid.down[level] if k > j else pyramid.up(level - 1)
-                        t = _conv_bn(path[3 * s], path[3 * s + 1], x, kmap, f)
+                        to = level + 1 if k > j else level - 1             # the level the step ends on
+                        t = _conv_bn(path[3 * s], path[3 * s + 1], x, kmap, f, G(to))
                         if s + 1 < steps:
-                            x = act1(f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", t)
+                            x = act1(f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", t, to)
                         else:
                             parts.append(t)
-                stage_input.append(_keep(trace, f"sum.{i}.{k}", _combine(parts, f, tr)))
+                stage_input.append(_keep(trace, f"sum.{i}.{k}", _combine(parts, f, tr, groups=G(k))))
         outs = [out_init, stage_output[0]]
         for i in range(1, self.num_stages):
             x, block = stage_output[i], self.final_transitions[i - 1]
             for s in range(i):
-                x = act1(f"final_transitions.{i - 1}.{3 * s + 1}", _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f))
+                x = act1(f"final_transitions.{i - 1}.{3 * s + 1}",
+                         _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f, G(i - s - 1)), i - s - 1)
             outs.append(x)
         return torch.cat(outs, dim=1)
 
@@ -653,10 +1008,50 @@ class HRNetSimCSN(nn.Module):
             pyr = pyr.to(feats.device)
         return self.backbone(feats, pyr), offsets_from_batch_index(pyr.coords[0][:, 0])
 
+    def _merged(self, queries: Batch, keys: Optional[Sequence[Batch]]) -> Optional[Tuple[GroupedPyramid, torch.Tensor]]:
+        """The (GroupedPyramid, features) of a call that takes the grouped pass, or None for the separate passes: a
+        ``GroupedPyramid`` given as the queries' coordinates; or ``tuning.grouped_passes`` with key batches, none of them a
+        prebuilt ``VoxelPyramid`` (that cannot be merged after the fact), a backbone that can normalise groups (fused, or eval)
+        and merged maps inside the kernels' 2 GiB gather window."""
+        where, feats = queries
+        if isinstance(where, GroupedPyramid):
+            if keys:
+                raise ValueError("a GroupedPyramid holds the key batches already: pass keys=None")
+            return where, feats
+        batches = [queries] + list(keys or [])
+        if not (tuning.current().grouped_passes and keys) or len(batches) > MAX_GROUPS:
+            return None
+        if any(not isinstance(c, torch.Tensor) for c, _ in batches) or (self.training and not self.backbone.fused):
+            return None
+        if not all(f.is_cuda for _, f in batches):
+            raise _lib.CsnError(_NO_CPU)
+        # merged where the queries' coordinates live (host coordinates: the shape counts are free, the pyramid moves afterwards)
+        dev = where.device
+        gp = merge_batches([(c.to(dev), f) for c, f in batches], self.NUM_STAGES, self.backbone.conv1_kernel_size)
+        D = self.backbone.init_stage_dims
+        if any(gp.coords[l].shape[0] * D * 2 ** l * 4 > _WINDOW for l in range(self.NUM_STAGES)):
+            return None
+        return gp, torch.cat([f for _, f in batches])
+
     def forward(self, queries: Batch, keys: Optional[Sequence[Batch]] = None, return_ssa: bool = False):
-        q, qo = self.backbone_rows(queries)
-        ks = [self.backbone_rows(b) for b in (keys or [])]
-        return self.head(q, qo, keys=ks or None, return_ssa=return_ssa)
+        """With ``tuning.grouped_passes`` (or a ``GroupedPyramid`` and the concatenated features as ``queries``, ``keys=None``) the
+        K + 1 batches run through the backbone as ONE pass over row groups — group 0 the queries, group 1 + i key batch i —
+        and the head receives the groups' rows (one ``torch.split``) and offsets; ``fc_layer`` still runs once per group, in order."""
+        merged = self._merged(queries, keys)
+        if merged is None:
+            q, qo = self.backbone_rows(queries)
+            ks = [self.backbone_rows(b) for b in (keys or [])]
+            return self.head(q, qo, keys=ks or None, return_ssa=return_ssa)
+        gp, feats = merged
+        if not feats.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if gp.coords[0].device != feats.device:
+            gp = gp.to(feats.device)
+        rows = self.backbone(feats, gp)
+        host = gp.group_rows_host[0]
+        parts = torch.split(rows, [b - a for a, b in zip(host, host[1:])])
+        ks = [(parts[g], gp.group_offsets(g)) for g in range(1, gp.n_groups)]
+        return self.head(parts[0], gp.group_offsets(0), keys=ks or None, return_ssa=return_ssa)
 
 
 class HRNetSimCSN2S(HRNetSimCSN):

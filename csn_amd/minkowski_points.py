@@ -136,6 +136,7 @@ class PointBatch:
 
     def __init__(self, coords, feats, labels, keys, status, offsets):
         self.coords, self.feats, self.labels, self.keys, self.status, self.offsets = coords, feats, labels, keys, status, offsets
+        self.group_shapes = None           # PointCollection.merged_batch: the shapes of every group of a merged batch
 
     @property
     def n_points(self) -> int:
@@ -323,3 +324,26 @@ class PointCollection:
             self._indices([int(nbrs[i]) for _, nbrs in neighbors])
         return [self.batch([int(nbrs[i]) for _, nbrs in neighbors], None if params is None else params.slice(i * B, (i + 1) * B),
                            voxel_size, shift) for i in range(K)]
+
+    def merged_batch(self, indices, neighbors: Sequence[Tuple[int, Sequence[int]]], K: int, params: Optional[AugmentParams] = None,
+                     voxel_size: float = 0.05, shift: Tuple[float, float] = (0.01, 0.05)) -> PointBatch:
+        """The queries ``indices`` and their K neighbour batches as ONE batch of (K + 1) B items, in the per-item order of ``batch``
+        followed by ``neighbor_batches``: the B queries, then the rank-0 neighbour of every query in query order, then rank 1, ...
+        — item numbers (the batch column) run on, so its voxel coordinates are already the merged coordinate set of
+        ``csn_amd.minkowski_hrnet.group_pyramid`` with ``n_shapes = batch.group_shapes`` ( = [B] * (K + 1)): a grouped pass
+        (``HRNetSimCSN.forward((GroupedPyramid, feats))``) without K + 1 collations.  ``params`` covers all (K + 1) B items, the
+        queries' first.  Still two launches and no host read."""
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        idx = [int(i) for i in self._indices(indices)]
+        B = len(idx)
+        if len(neighbors) != B:
+            raise ValueError("neighbors must hold one entry per query")
+        for _, nbrs in neighbors:
+            if len(nbrs) < K:
+                raise ValueError(f"every query needs at least K = {K} neighbours")
+        if params is not None and len(params) != (K + 1) * B:
+            raise ValueError(f"params hold {len(params)} items, the K + 1 batches {(K + 1) * B}")
+        out = self.batch(idx + [int(nbrs[i]) for i in range(K) for _, nbrs in neighbors], params, voxel_size, shift)
+        out.group_shapes = [B] * (K + 1)
+        return out

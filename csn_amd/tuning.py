@@ -93,6 +93,14 @@ class Tuning:
     # screen on real PartNet features is not measured (DESIGN.md "fp16 screen of the shape graph", scripts/bench_retrieval_screen.py)
     retrieval_screen: bool = False
 
+    # HRNetSimCSN.forward(queries, keys) with key batches: the K + 1 batches are merged into one coordinate set
+    # (csn_amd.minkowski_hrnet.merge_batches), the backbone runs ONCE, and every BatchNorm takes its statistics per row group
+    # (include/csn_hip.h section 20) — each batch stays its own BatchNorm batch, the running statistics see the batches in the same
+    # order.  The weight gradients become one sum over all rows instead of K + 1 sums added by autograd: results differ from the
+    # separate passes by rounding.  Batches given as prebuilt VoxelPyramids, an unfused backbone in training and merged maps past
+    # the kernels' 2 GiB window keep the separate passes.  Off: opt-in (DESIGN.md "Grouped passes", scripts/bench_hrnet_groups.py)
+    grouped_passes: bool = False
+
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))
 

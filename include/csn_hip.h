@@ -923,6 +923,52 @@ CSN_API int csn_sparse_conv_bn_act_fwd_f32(const float* x, long long ld_x, int n
                                    const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
                                    long long ld_y, void* stream);
 
+/* ---- (20) BatchNorm over row groups: the K + 1 backbone passes of a CSN training step as one (MinkowskiNet/models/hrnet.py:425-454:
+ *           the query batch and every key batch is a BatchNorm batch of its own) -------------------------------------------------
+ * The rows of a coordinate set are sorted with the batch index leading, so the rows of n_groups batches merged into ONE coordinate
+ * set with shifted batch indices are n_groups CONTIGUOUS ranges at every level of the pyramid.  The convolution does not care
+ * which batch a row belongs to; only the statistics and the normalisation do.  Additive to ABI version 17.
+ *   group_rows[n_groups + 1] int32 on the DEVICE (4-byte aligned: CSN_E_PTR; NULL: CSN_E_ARG): group g is the rows
+ *   [group_rows[g], group_rows[g + 1]); n_groups in [1, 8] (< 1: CSN_E_ARG, > 8: CSN_E_DIM).  The offsets live on the device, so the
+ *   library cannot read them before the launch: they must start at 0, ascend, end at the row count and leave every group at
+ *   least two rows, and the CALLER checks that (csn_amd.minkowski_hrnet.merge_batches does, in its one host read).  Whatever they
+ *   hold, no row, tile or part index leaves its array; a row outside every group is neither normalised nor written, a group that
+ *   is empty or leaves [0, n_rows] is skipped.
+ *   mean / invstd of (20a) and mean[m] / scale[m] of (20b) are [n_groups][channels] fp32.
+ * Everything else — layouts, pitches, widths, alignment, math modes, error codes, NULL outputs — is (15)'s.  Training mode only:
+ * in eval mode the running statistics do not depend on the group, and (15b) / (19) on the merged rows are the merged pass.
+ * No floating-point atomics: every reduction has a fixed order, two identical calls give the same bits.  With n_groups == 1 every
+ * output is bit for bit that of (15a) / (15b).
+ *
+ * (20a) csn_sparse_conv_stats_groups_fwd_f32: z exactly as (15a) on the same map (the same kernel, the same bits); per group g the
+ *   mean[g][c] and invstd[g][c] of its rows; the running statistics (either may be NULL) take n_groups updates in group order 0 ..
+ *   n_groups - 1, each with that group's mean and its n / (n - 1) variance, as n_groups sequential calls of (15a) would.  Per group:
+ *   the whole 32-row tiles of the epilogue's (mean, M2) partials merged as in (15a) — segments of the group's tile list in tile
+ *   order, the segments pairwise in a fixed tree, Chan's formula in fp64 — and the <= 31 rows of a tile that a group boundary cuts
+ *   re-read from z: their (mean, M2) in fp64, merged after the whole tiles, the piece before them first.  n_out < 2 n_groups:
+ *   CSN_E_ARG.  ws: csn_sparse_conv_stats_groups_workspace_bytes(n_out, c_out, n_groups).  Its backward is csn_sparse_conv_bwd_f32.
+ * (20b) csn_rows_bn_act_groups_fwd_f32: for row i of group g
+ *     y_i = act( sum_{m < n_terms} (gamma_m (z_m,i - mean_m[g]) scale_m[g] + beta_m) + r_i ).
+ *   csn_rows_bn_act_groups_bwd_f32: g' = dy [y > 0] read once for all terms; dr = g'; dbeta[m] = sum over ALL rows of g';
+ *   dgamma[m] = sum over all rows of g' xhat_m, xhat from the row's own group's statistics;
+ *     dz_m,i = gamma_m scale_m[g] (g'_i - mean_g(g') - xhat_m,i mean_g(g' xhat_m)),  the means over group g's rows.
+ *   Thread layout as (15b): 64 rows per work-group, a thread owns 4 consecutive channels, 16-byte accesses; a work-group walks the
+ *   groups that meet its rows and loads a group's constants when it enters it.  The fp64 chunk sums are cut at the group
+ *   boundaries (at most chunks + n_groups - 1 parts), added per group in part order (segments, then the fixed tree), and the groups
+ *   in ascending order for dgamma / dbeta.
+ *   ws: csn_rows_bn_act_groups_workspace_bytes(n_rows, channels, n_terms, n_groups) bytes (backward only). */
+CSN_API long long csn_sparse_conv_stats_groups_workspace_bytes(int n_out, int c_out, int n_groups);
+CSN_API int csn_sparse_conv_stats_groups_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                         int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                         float* running_mean, float* running_var, float eps, float momentum, const int* group_rows,
+                                         int n_groups, void* ws, long long ws_bytes, void* stream);
+CSN_API long long csn_rows_bn_act_groups_workspace_bytes(int n_rows, int channels, int n_terms, int n_groups);
+CSN_API int csn_rows_bn_act_groups_fwd_f32(const CsnBnTerms* terms, int n_terms, int n_rows, int channels, const int* group_rows,
+                                   int n_groups, const float* r, long long ld_r, int relu, float* y, long long ld_y, void* stream);
+CSN_API int csn_rows_bn_act_groups_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* terms,
+                                   int n_terms, int n_rows, int channels, const int* group_rows, int n_groups, int relu, float* dr,
+                                   long long ld_dr, void* ws, long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
