@@ -39,7 +39,7 @@ int launch_gemm(const CsnGemmArgs& a, int b_is_nk, int batch, hipStream_t st) {
   if (mode() != 0) {
     if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
     if ((a.A.ld & 3) || (a.B.ld & 3) || (a.K & 3) || (a.k_chunk & 3)) return CSN_E_ALIGN;
-    if (!b_is_nk && (a.N & 3)) return CSN_E_ALIGN;
+    if (a.N & 3) return CSN_E_ALIGN;               // (k-contiguous B too: the 256 x 256 epilogues write 16-byte chunks of C)
     return csn_launch_gemm_bf16x3(a, b_is_nk, batch, mode(), st);
   }
   return csn_launch_gemm_f32(a, b_is_nk, batch, st);
@@ -986,7 +986,8 @@ int csn_project_wgrad_f32(const float* dout, long long dout_shape_stride, int ld
                           void* stream) {
   if (!dout || !x || !dw || !ws || rows <= 0 || channels <= 0 || n_shapes <= 0 || n_points <= 0) return CSN_E_ARG;
   if (n_points > ld_dout || n_points > ld_x) return CSN_E_ARG;
-  if ((ld_dout & 3) || (ld_x & 3) || (n_points & 3)) return CSN_E_ALIGN;
+  // channels: the N of the product and the row pitch of every slab, written in 16-byte chunks (rows are only guarded per row)
+  if ((ld_dout & 3) || (ld_x & 3) || (n_points & 3) || (channels & 3)) return CSN_E_ALIGN;
   if (mis16(dout) || mis16(x) || mis16(dw) || mis16(ws)) return CSN_E_PTR;
   if ((dout_shape_stride & 3) || (x_shape_stride & 3)) return CSN_E_STRIDE;
   const bool g16 = act16() && grad16();                               // dout: bf16 gradient maps

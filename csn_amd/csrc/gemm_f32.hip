@@ -210,8 +210,9 @@ __global__ __launch_bounds__(256) void csn_slab_reduce_kernel(const float* __res
     f32x4 s = ((s0 + s1) + (s2 + s3)) * alpha;
     if (accumulate) s += *reinterpret_cast<const f32x4*>(out + i);
     *reinterpret_cast<f32x4*>(out + i) = s;
-  } else {
-    for (long long j = i; j < n; ++j) {
+  } else {                                                             // n % 4 != 0: this thread's own (up to) four elements
+    const long long end = i + 4 < n ? i + 4 : n;
+    for (long long j = i; j < end; ++j) {
       float s = 0.f;
       for (int z = 0; z < n_slabs; ++z) s += slab[(long long)z * n + j];
       s *= alpha;
@@ -236,7 +237,7 @@ static int launch(const CsnGemmArgs& a, int batch, hipStream_t st) {
 int csn_launch_gemm_f32(const CsnGemmArgs& a, int b_is_nk, int batch, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
   if ((a.A.ld & 3) || (a.B.ld & 3) || (a.K & 3) || (a.k_chunk & 3)) return -2;   // 16-byte pieces: rows, K multiples of 4
-  if (!b_is_nk && (a.N & 3)) return -2;
+  if (a.N & 3) return -2;                                              // 16-byte chunks of C in the epilogue, whatever B's layout
   if ((reinterpret_cast<uintptr_t>(a.A.ptr) & 15) || (reinterpret_cast<uintptr_t>(a.B.ptr) & 15)) return -3;
   if ((a.A.s0 & 3) || (a.A.s1 & 3) || (a.A.s2 & 3) || (a.B.s0 & 3) || (a.B.s1 & 3) || (a.B.s2 & 3)) return -4;
   if (a.M <= 64) return b_is_nk ? launch<64, 128, true>(a, batch, st) : launch<64, 128, false>(a, batch, st);

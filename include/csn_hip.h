@@ -461,7 +461,9 @@ CSN_API int csn_outproj_lnb_f32(const float* dxhat, const float* xhat, const flo
                         float* rowdot, float* rowsum, float* red_ws, long long red_ws_floats, void* stream);
 
 /* ---- (6) projection weight gradient ----------------------------------------------------------------------
- * dw[r][c] (+)= scale * sum_{s,n} dout[s][r][n] * x[s][c][n]        (autograd of csa_models.py:103-105) */
+ * dw[r][c] (+)= scale * sum_{s,n} dout[s][r][n] * x[s][c][n]        (autograd of csa_models.py:103-105)
+ * channels, n_points and both row pitches are multiples of 4 (CSN_E_ALIGN), rows is free; accumulate: scale applies to the new
+ * term only. */
 CSN_API int csn_project_wgrad_f32(const float* dout, long long dout_shape_stride, int ld_dout, const float* x,
                           long long x_shape_stride, int ld_x, float* dw, int rows, int channels, int n_shapes,
                           int n_points, float scale, int accumulate, float* ws, long long ws_floats,

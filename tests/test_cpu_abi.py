@@ -51,6 +51,8 @@ def test_argument_validation_happens_on_the_host(L):
     assert lib.csn_project_f32(None, 0, 4, None, 1, 1, None, 0, 4, 1, 4, 0, 1.0, 0, 0, None) == -1
     assert lib.csn_block_attn_fwd_f32(None, None, None, 0, 0, None, None, 4, None, 0, None, None, 1, 1, 32, 4, 1, 32, 0.0, 0.0, 0, 0, 0, None) == -1
     assert lib.csn_retrieval_measure_f32(None, None, None, 1, 1, 1, 1, 4, None, 0, None) == -1
+    # a weight gradient's channels are the row pitch of its slabs: 6 is refused (the pointers are never followed)
+    assert lib.csn_project_wgrad_f32(16, 0, 4, 16, 0, 4, 16, 4, 6, 1, 4, 1.0, 0, 16, 64, None) == -2
     assert lib.csn_wgrad_workspace_floats(256, 256, 0, 10) == 0
     n = lib.csn_wgrad_workspace_floats(256, 256, 128, 10000)
     assert n % (256 * 256) == 0 and n // (256 * 256) >= 128

@@ -626,7 +626,7 @@ def test_abi_argument_validation_table(L):
         valid = dict(dout=dout.data_ptr(), ds=R * N, ldd=N, x=x.data_ptr(), xs=C * N, ldx=N, dw=dw.data_ptr(), rows=R, ch=C, ns=S,
                      np=N, scale=1.0, acc=0, ws=ws.data_ptr(), wsn=ws_n, st=_stream())
         cases = [("dout", None, ARG), ("x", None, ARG), ("dw", None, ARG), ("ldd", N + 1, ALIGN), ("np", N - 1, ALIGN), ("ldx", N - 4, ARG),
-                 ("ds", R * N + 1, STRIDE), ("ns", 0, ARG), ("rows", 0, ARG)]
+                 ("ds", R * N + 1, STRIDE), ("ns", 0, ARG), ("rows", 0, ARG), ("ch", C - 2, ALIGN)]
         if ws_n > 0:
             cases += [("wsn", ws_n - 1, WS), ("ws", None, None)]
         _mutations(lib.csn_project_wgrad_f32, names, valid, cases)
