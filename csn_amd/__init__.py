@@ -24,6 +24,9 @@ from .minkowski_training import (SegBatch, SegMeter, evaluate, load_me_head_stat
 # sparse 3D convolution on voxel rows: the primitive of the HRNet backbone (MinkowskiNet/models/hrnet.py:39-53, 89-111, 233-239)
 from .minkowski_conv import (KernelMap, SparseBasicBlock, SparseConv3d, SparseConvTranspose3d, build_kernel_map,  # noqa: E402,F401
                              sparse_conv3d)
+# the kernel-2 stride-2 convolution and its transposed form over an octant map (MinkowskiNet/models/res16unet.py: conv*s2, convtr*s2)
+from .minkowski_conv import (OctantMap, SparseConvDown2, SparseConvUp2, build_octant_map, cat_conv3d,  # noqa: E402,F401
+                             octant_conv_down, octant_conv_up)
 
 # the HRNet backbone and HRNetSimCSN on voxel rows, on the fused convolution + BatchNorm kernels (MinkowskiNet/models/hrnet.py:31-163,
 # 296-454)
@@ -33,6 +36,12 @@ from .minkowski_hrnet import GroupedPyramid, bn_act_groups, conv_stats_groups, g
 # the plain segmentation networks (hrnet.py:214-293) and the backbone's one-launch-per-convolution inference primitive
 from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
                               sparse_conv_bn_act)
+
+# the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks
+from .minkowski_unet import (Res16UNet14, Res16UNet14A, Res16UNet14A2, Res16UNet14B, Res16UNet14B2, Res16UNet14B3,  # noqa: E402,F401
+                             Res16UNet14C, Res16UNet14D, Res16UNet18, Res16UNet18A, Res16UNet18B, Res16UNet18D, Res16UNet34,
+                             Res16UNet34A, Res16UNet34B, Res16UNet34C, Res16UNet50, Res16UNet101, Res16UNetBase, UNetBasicBlock,
+                             UNetPyramid, build_unet_pyramid, load_me_unet_state)
 
 # point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
 # (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))

@@ -1557,6 +1557,89 @@ int csn_rows_bn_act_groups_bwd_f32(const float* dy, long long ld_dy, const float
   return csn_launch_rows_bn_act_groups_bwd(a, group_rows, n_groups, (hipStream_t)stream);
 }
 
+
+// ---- (21) kernel-2 stride-2 convolution and its transposed form over an octant map ----
+static int octant_dims(int n_fine, int n_coarse, int c_in, int c_out) {
+  if (n_fine <= 0 || n_coarse <= 0) return CSN_E_ARG;
+  if (c_in < 32 || c_in > 256 || (c_in & 31) || c_out < 32 || c_out > 256 || (c_out & 31)) return CSN_E_DIM;
+  return 0;
+}
+static bool off4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
+static int octant_mode() { return mode() != 0; }                 // no single-product instances: modes 2 / 3 run as bf16x3
+
+long long csn_octant_conv_workspace_bytes(int n_fine, int n_coarse, int c_in, int c_out, int up, int backward) {
+  if (octant_dims(n_fine, n_coarse, c_in, c_out)) return 0;
+  return csn_octant_conv_ws_bytes(n_fine, n_coarse, c_in, c_out, up != 0, backward != 0);
+}
+
+int csn_octant_down_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
+                            const float* w, const float* bias, float* y, long long ld_y, void* stream) {
+  if (!x || !children || !w || !y) return CSN_E_ARG;
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_fine)) return e;
+  if (const int e = sparse_conv_map(ld_y, c_out, n_coarse)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || off4(children)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
+  a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
+  return csn_launch_octant_down_fwd(a, octant_mode(), (hipStream_t)stream);
+}
+
+int csn_octant_up_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
+                          int n_fine, int c_in, int c_out, const float* w, const float* bias, float* y, long long ld_y,
+                          void* stream) {
+  if (!x || !parent || !order || !seg || !w || !y) return CSN_E_ARG;
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_coarse)) return e;
+  if (const int e = sparse_conv_map(ld_y, c_out, n_fine)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
+  a.order = order; a.seg = seg; a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
+  return csn_launch_octant_up_fwd(a, octant_mode(), (hipStream_t)stream);
+}
+
+// the checks the two backward entry points share: n_x / n_dy are the rows of x / dy, `one` says whether dx is the one-weight form
+static int octant_bwd_args(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_x, int n_dy, int n_fine, int n_coarse,
+                           int c_in, int c_out, const int* children, const int* parent, const int* order, const int* seg,
+                           const float* w, float* dx, long long ld_dx, float* dw, void* ws, long long ws_bytes, bool one, bool up) {
+  if (!dy || !ws) return CSN_E_ARG;
+  if (dx && (!w || (one ? (!parent || !order || !seg) : !children))) return CSN_E_ARG;
+  if (dw && (!x || !parent || !order || !seg)) return CSN_E_ARG;
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_dy, c_out, n_dy)) return e;
+  if (dw) if (const int e = sparse_conv_map(ld_x, c_in, n_x)) return e;
+  if (dx) if (const int e = sparse_conv_map(ld_dx, c_in, n_x)) return e;
+  if (mis16(dy) || mis16(ws) || (dx && (mis16(dx) || mis16(w))) || (dw && (mis16(dw) || mis16(x)))) return CSN_E_PTR;
+  if (off4(children) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  if (ws_bytes < csn_octant_conv_ws_bytes(n_fine, n_coarse, c_in, c_out, up, 1)) return CSN_E_WORKSPACE;
+  return 0;
+}
+
+int csn_octant_down_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
+                            int c_out, const int* parent, const int* order, const int* seg, const float* w, float* dx,
+                            long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
+  if (const int e = octant_bwd_args(dy, ld_dy, x, ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w,
+                                    dx, ld_dx, dw, ws, ws_bytes, true, false)) return e;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
+  a.order = order; a.seg = seg; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias;
+  a.ws = ws;
+  return csn_launch_octant_down_bwd(a, octant_mode(), (hipStream_t)stream);
+}
+
+int csn_octant_up_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
+                          int c_out, const int* children, const int* parent, const int* order, const int* seg, const float* w,
+                          float* dx, long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
+  if (const int e = octant_bwd_args(dy, ld_dy, x, ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, children, parent, order, seg, w,
+                                    dx, ld_dx, dw, ws, ws_bytes, false, true)) return e;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
+  a.parent = parent; a.order = order; a.seg = seg; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx;
+  a.dw = dw; a.dbias = dbias; a.ws = ws;
+  return csn_launch_octant_up_bwd(a, octant_mode(), (hipStream_t)stream);
+}
+
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
 static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 

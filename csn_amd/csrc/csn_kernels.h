@@ -342,6 +342,24 @@ struct CsnSconvBnArgs {
 int csn_launch_sparse_conv_bn_act_fwd(const CsnSparseConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule
 
+// ---- kernel-2 stride-2 convolution and its transposed form over an octant map (octant_conv.hip) ----
+struct CsnOctantConvArgs {
+  const float* x;  int ld_x;                                      // down: [n_fine][ld_x]; up: [n_coarse][ld_x]; c_in <= ld_x
+  int n_fine, n_coarse, c_in, c_out;
+  const int* children;                                            // [8][n_coarse] fine row or -1
+  const int* parent;  const int* order;  const int* seg;          // [n_fine], [n_fine], [9]
+  const float* w;  const float* bias;                             // [8][c_in][c_out]; bias optional
+  float* y;  int ld_y;                                            // forward: down [n_coarse][ld_y], up [n_fine][ld_y]
+  const float* dy;  int ld_dy;
+  float* dx;  int ld_dx;  float* dw;  float* dbias;               // each skipped when NULL
+  void* ws;
+};
+long long csn_octant_conv_ws_bytes(long long n_fine, long long n_coarse, int c_in, int c_out, int up, int backward);
+int csn_launch_octant_down_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
+int csn_launch_octant_down_bwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
+int csn_launch_octant_up_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
+int csn_launch_octant_up_bwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
+
 // ---- BatchNorm apply + branch sum + residual + ReLU on point-major rows, forward and backward (rows_bn_act.hip) ----
 struct CsnRowsBnActArgs {
   // the terms (include/csn_hip.h section 15: CsnBnTerms, copied by the C ABI)

@@ -24,6 +24,12 @@ and one lookup kernel per table of include/csn_hip.h section 17 around ``torch.s
 ``sparse_conv3d`` is one autograd node on ``csn_sparse_conv_fwd_f32`` / ``csn_sparse_conv_bwd_f32`` (include/csn_hip.h section
 14); ``SparseConv3d`` / ``SparseConvTranspose3d`` hold MinkowskiEngine's ``kernel`` parameter; ``SparseBasicBlock`` is the
 residual block with the reference's attribute names (its batch norms are ``nn.BatchNorm1d`` through ATen).
+
+The kernel-2 stride-2 convolution and its transposed form (MinkowskiNet/models/res16unet.py: ``conv*s2`` / ``convtr*s2``) stand
+beside that surface: kernel 2 at stride 2 partitions the fine voxels, so ``build_octant_map`` keeps one parent and one octant per
+fine row instead of a table, and ``octant_conv_down`` / ``octant_conv_up`` (``SparseConvDown2`` / ``SparseConvUp2``) are one
+autograd node each on ``csn_octant_*`` (include/csn_hip.h section 21).  ``cat_conv3d`` is a convolution on a concatenation that is
+never formed.
 """
 from __future__ import annotations
 
@@ -385,6 +391,181 @@ def sparse_conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return _SparseConv.apply(x.float(), weight, bias, kmap)
 
 
+def cat_conv3d(parts, weight: torch.Tensor, kmap: KernelMap) -> torch.Tensor:
+    """The convolution of ``torch.cat(parts, dim=1)`` as the sum of the convolutions of the parts: ``parts`` is a list of ``(n, c_p)``
+    maps and ``weight (KV, sum c_p, c_out)`` ONE kernel.  The concatenation is never formed and every part (<= 256 wide) is taken
+    by the existing kernels, so a decoder block may be wider than 256 at its input.  Autograd composes the gradient."""
+    if not parts:
+        raise ValueError("cat_conv3d needs at least one part")
+    if weight.dim() != 3 or sum(int(p.shape[1]) for p in parts) != weight.shape[1]:
+        raise ValueError("the parts' widths must add up to the weight's c_in")
+    y, c0 = None, 0
+    for part in parts:
+        c1 = c0 + int(part.shape[1])
+        t = sparse_conv3d(part, weight[:, c0:c1], None, kmap)
+        y = t if y is None else y + t
+        c0 = c1
+    return y
+
+
+# ------------------------------------------------------------------------------------------------------
+# kernel 2 at stride 2: the octant map and its two convolutions (include/csn_hip.h section 21)
+# ------------------------------------------------------------------------------------------------------
+class OctantMap:
+    """The partition of a fine coordinate set at ``ts`` by its coarse set at ``2 ts`` (all index tensors int32):
+
+    ``parent (n_fine,)`` the coarse row of every fine row; ``octant (n_fine,)`` = ox + 2 oy + 4 oz with o = (xyz - floor(xyz /
+    2ts) 2ts) / ts in {0, 1}^3 (x fastest, as in ``kidx``); ``children (8, n_coarse)`` the fine row in octant k of coarse row j, or
+    -1; ``order (n_fine,)`` the fine rows sorted by (octant, row) and ``seg (9,)`` its segment bounds, on the device like the
+    rest.  The octant numbering is this project's choice, like the offset numbering: parity unpinned against MinkowskiEngine's own
+    checkpoints."""
+
+    def __init__(self, in_coords, out_coords, in_tensor_stride, out_tensor_stride, parent, octant, children, order, seg):
+        self.in_coords, self.out_coords = in_coords, out_coords
+        self.in_tensor_stride, self.out_tensor_stride = in_tensor_stride, out_tensor_stride
+        self.parent, self.octant, self.children, self.order, self.seg = parent, octant, children, order, seg
+
+    @property
+    def n_fine(self) -> int:
+        return self.in_coords.shape[0]
+
+    @property
+    def n_coarse(self) -> int:
+        return self.out_coords.shape[0]
+
+    def to(self, device) -> "OctantMap":
+        mv = lambda t: t.to(device)
+        return OctantMap(mv(self.in_coords), mv(self.out_coords), self.in_tensor_stride, self.out_tensor_stride, mv(self.parent),
+                         mv(self.octant), mv(self.children), mv(self.order), mv(self.seg))
+
+
+def build_octant_map(coords: torch.Tensor, tensor_stride: int = 1, out_coords: Optional[torch.Tensor] = None) -> OctantMap:
+    """The octant map of ``coords (n_fine, 4) = [b, x, y, z]`` (unique rows in any order, multiples of ``tensor_stride``) onto the
+    coarse set ``build_kernel_map(..., stride=2)`` generates — ``unique([b, floor(xyz / 2ts) 2ts])`` sorted by (b, x, y, z) — or
+    onto ``out_coords`` when given (it must hold every parent: ``ValueError``).  Torch ops on the coordinates' device: one
+    ``searchsorted``, one stable sort, one scatter; nothing is read back beyond what ``torch.unique`` and the checks cost.  The
+    octant numbering is this project's choice, unpinned against MinkowskiEngine (``OctantMap``)."""
+    ts = int(tensor_stride)
+    if ts < 1:
+        raise ValueError(f"tensor_stride {tensor_stride} is not valid here")
+    out_ts = 2 * ts
+    c_in = _check_coords(coords, ts, "coords")
+    _Index(c_in, "coords")                                           # duplicates
+    down = c_in.clone()
+    down[:, 1:] = torch.div(c_in[:, 1:], out_ts, rounding_mode="floor") * out_ts          # floor, not truncation, for negatives
+    if out_coords is not None:
+        if out_coords.device != coords.device:
+            raise ValueError("coords and out_coords must be on one device")
+        c_out = _check_coords(out_coords, out_ts, "out_coords")
+        idx_out = _Index(c_out, "out_coords")
+    else:
+        c_out = _unpack(torch.unique(_pack(down), sorted=True))
+        idx_out = _Index(c_out, "out_coords")
+    parent = idx_out.rows(down)
+    if out_coords is not None and bool((parent < 0).any()):
+        raise ValueError("out_coords misses the parent of some row of coords")
+    o = (c_in[:, 1:] - down[:, 1:]) // ts
+    octant = (o[:, 0] + 2 * o[:, 1] + 4 * o[:, 2]).int()
+    n_fine, n_coarse = c_in.shape[0], c_out.shape[0]
+    rows = torch.arange(n_fine, device=coords.device, dtype=torch.int32)
+    children = torch.full((8 * n_coarse,), -1, dtype=torch.int32, device=coords.device)
+    children[octant.long() * n_coarse + parent.long()] = rows
+    order = torch.sort(octant, stable=True)[1].int()
+    seg = torch.zeros(9, dtype=torch.int32, device=coords.device)
+    seg[1:] = torch.cumsum(torch.bincount(octant, minlength=8), 0).int()
+    return OctantMap(c_in, c_out, ts, out_ts, parent, octant, children.view(8, n_coarse), order, seg)
+
+
+class _OctantConv(torch.autograd.Function):
+    """``up`` False: y[j] = sum_k x[children[k][j]] W[k] + b;  True: y[i] = x[parent[i]] W[octant[i]] + b — one node on
+    ``csn_octant_{down,up}_fwd_f32`` / ``_bwd_f32``."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, omap, up):
+        CF._need_cuda(x, w, b, omap.parent)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        x = x.contiguous()
+        w_c = w.detach().contiguous()
+        b_c = None if b is None else b.detach().reshape(-1).contiguous()
+        _, c_in, c_out = w_c.shape
+        n_fine, n_coarse = omap.n_fine, omap.n_coarse
+        y = torch.empty((n_fine if up else n_coarse, c_out), device=x.device, dtype=torch.float32)
+        if up:
+            _lib.check(L.csn_octant_up_fwd_f32(CF._ptr(x), c_in, n_coarse, CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg),
+                                               n_fine, c_in, c_out, CF._ptr(w_c), CF._ptr(b_c), CF._ptr(y), c_out, CF._stream()),
+                       "csn_octant_up_fwd_f32")
+        else:
+            _lib.check(L.csn_octant_down_fwd_f32(CF._ptr(x), c_in, n_fine, CF._ptr(omap.children), n_coarse, c_in, c_out, CF._ptr(w_c),
+                                                 CF._ptr(b_c), CF._ptr(y), c_out, CF._stream()), "csn_octant_down_fwd_f32")
+        ctx.save_for_backward(x, w_c)
+        ctx.omap, ctx.up = omap, up
+        ctx.b_shape = None if b is None else b.shape
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        with CF.math_mode(CF.backward_mode(ctx.mode)):
+            x, w = ctx.saved_tensors
+            omap, up = ctx.omap, ctx.up
+            L = _lib.lib()
+            _, c_in, c_out = w.shape
+            n_fine, n_coarse = omap.n_fine, omap.n_coarse
+            dy = dy.contiguous()
+            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            need_b = ctx.b_shape is not None and ctx.needs_input_grad[2]
+            if not (need_x or need_w or need_b):
+                return None, None, None, None, None
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            db = torch.empty((c_out,), device=x.device, dtype=torch.float32) if need_b else None
+            ws_n = int(L.csn_octant_conv_workspace_bytes(n_fine, n_coarse, c_in, c_out, int(up), 1))
+            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+            if up:
+                _lib.check(L.csn_octant_up_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
+                                                   CF._ptr(omap.children), CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg),
+                                                   CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db), CF._ptr(ws), ws_n,
+                                                   CF._stream()), "csn_octant_up_bwd_f32")
+            else:
+                _lib.check(L.csn_octant_down_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
+                                                     CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg), CF._ptr(w),
+                                                     CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db), CF._ptr(ws), ws_n, CF._stream()),
+                           "csn_octant_down_bwd_f32")
+            return dx, dw, None if db is None else db.reshape(ctx.b_shape), None, None
+
+
+def _octant_conv(x, weight, bias, omap, up):
+    if not (x.is_cuda and weight.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1]:
+        raise ValueError("x must be (n_in, c_in) and weight (8, c_in, c_out)")
+    if weight.shape[0] != 8:
+        raise ValueError(f"the weight holds {weight.shape[0]} offsets, the octant map 8")
+    n_in = omap.n_coarse if up else omap.n_fine
+    if x.shape[0] != n_in:
+        raise ValueError(f"x has {x.shape[0]} rows, the map's input set {n_in}")
+    c_in, c_out = weight.shape[1], weight.shape[2]
+    for name, c in (("c_in", c_in), ("c_out", c_out)):
+        if c % 32 or not 32 <= c <= 256:
+            raise ValueError(f"{name} {c} is not supported: a multiple of 32 in [32, 256]")
+    if bias is not None and bias.numel() != c_out:
+        raise ValueError(f"bias must hold {c_out} values")
+    return _OctantConv.apply(x.float(), weight, bias, omap, up)
+
+
+def octant_conv_down(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], omap: OctantMap) -> torch.Tensor:
+    """The kernel-2 stride-2 convolution: ``x (n_fine, c_in)`` -> ``(n_coarse, c_out)``, ``y[j] = sum_k x[children[k][j]] W[k] + b``;
+    ``weight (8, c_in, c_out)``, widths multiples of 32 in [32, 256]."""
+    return _octant_conv(x, weight, bias, omap, False)
+
+
+def octant_conv_up(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], omap: OctantMap) -> torch.Tensor:
+    """Its transposed form, back onto the map's fine set: ``x (n_coarse, c_in)`` -> ``(n_fine, c_out)``,
+    ``y[i] = x[parent[i]] W[octant[i]] + b`` — one weight per row."""
+    return _octant_conv(x, weight, bias, omap, True)
+
+
 # ------------------------------------------------------------------------------------------------------
 # modules
 # ------------------------------------------------------------------------------------------------------
@@ -426,6 +607,41 @@ class SparseConvTranspose3d(SparseConv3d):
 
     def __init__(self, c_in: int, c_out: int, bias: bool = False):
         super().__init__(c_in, c_out, kernel_size=3, stride=2, bias=bias)
+
+
+class SparseConvDown2(nn.Module):
+    """``ME.MinkowskiConvolution(c_in, c_out, kernel_size=2, stride=2, dimension=3)`` on rows and an octant map: parameter
+    ``kernel (8, c_in, c_out)`` and, when asked, ``bias (1, c_out)``."""
+
+    up = False
+
+    def __init__(self, c_in: int, c_out: int, bias: bool = False):
+        super().__init__()
+        if c_in % 32 or c_out % 32 or not 32 <= c_in <= 256 or not 32 <= c_out <= 256:
+            raise ValueError("widths: c_in and c_out multiples of 32 in [32, 256]")
+        self.c_in, self.c_out = c_in, c_out
+        self.kernel = nn.Parameter(torch.empty(8, c_in, c_out))
+        self.bias = nn.Parameter(torch.zeros(1, c_out)) if bias else None
+        nn.init.normal_(self.kernel, std=(8 * c_in) ** -0.5)              # unit-variance outputs for unit-variance rows
+
+    def forward(self, x: torch.Tensor, omap: OctantMap) -> torch.Tensor:
+        if not isinstance(omap, OctantMap):
+            raise ValueError(f"this layer (kernel 2, stride 2) takes an OctantMap, not {type(omap).__name__}")
+        n_in = omap.n_coarse if self.up else omap.n_fine
+        if x.shape[0] != n_in:
+            raise ValueError(f"the map ({omap.n_fine} fine rows, {omap.n_coarse} coarse rows) does not fit the {x.shape[0]} rows "
+                             f"given to this layer ({'transposed' if self.up else 'down'})")
+        return _octant_conv(x, self.kernel, self.bias, omap, self.up)
+
+    def extra_repr(self) -> str:
+        return f"{self.c_in}, {self.c_out}, kernel_size=2, stride=2, bias={self.bias is not None}"
+
+
+class SparseConvUp2(SparseConvDown2):
+    """``ME.MinkowskiConvolutionTranspose(c_in, c_out, kernel_size=2, stride=2, dimension=3)`` back onto the fine set of the octant
+    map that took the features down."""
+
+    up = True
 
 
 class SparseBasicBlock(nn.Module):

@@ -46,6 +46,7 @@ import torch
 
 from .minkowski_csn import construct_shape_graph, random_neighbors
 from .minkowski_hrnet import HRNetSimCSN, load_me_hrnet_state, load_me_seg_state
+from .minkowski_unet import Res16UNetBase, load_me_unet_state
 from .minkowski_points import AugmentSpec, PointCollection
 from .minkowski_solvers import TrainConfig, initialize_optimizer, initialize_scheduler
 from .minkowski_training import evaluate, train_iter
@@ -176,28 +177,35 @@ class PatienceState(BestValues):
 # what the two trainers and test mode share
 # ------------------------------------------------------------------------------------------------------
 def load_model_state(model, state_dict) -> None:
-    """A checkpoint's ``state_dict`` in either layout: this project's names (``backbone.*`` with ``head.*`` / ``final.*``) go through
-    ``load_state_dict``; a dictionary without a ``backbone.`` key is taken for the reference's layout and goes through
-    ``load_me_hrnet_state`` (an ``HRNetSimCSN``) or ``load_me_seg_state`` (an ``HRNetSeg``)."""
-    if any(k.startswith("backbone.") for k in state_dict):
+    """A checkpoint's ``state_dict`` in either layout: this project's names (``backbone.*`` with ``head.*`` / ``final.*``; a
+    ``Res16UNet``'s ``final.weight``) go through ``load_state_dict``; any other dictionary is taken for the reference's layout and
+    goes through ``load_me_hrnet_state`` (an ``HRNetSimCSN``), ``load_me_unet_state`` (a ``Res16UNet``) or ``load_me_seg_state`` (an
+    ``HRNetSeg``)."""
+    if any(k.startswith("backbone.") for k in state_dict) or (isinstance(model, Res16UNetBase) and "final.weight" in state_dict):
         model.load_state_dict(state_dict)
     elif isinstance(model, HRNetSimCSN):
         load_me_hrnet_state(model, state_dict)
+    elif isinstance(model, Res16UNetBase):
+        load_me_unet_state(model, state_dict)
     else:
         load_me_seg_state(model, state_dict)
 
 
 def checkpoint_num_labels(state_dict) -> int:
-    """The rows of a checkpoint's output layer: ``head.output.weight`` / ``final.3.weight`` (out, in) here, the last axis of
-    ``output.kernel`` / ``final.3.kernel`` ((1,) in, out) in the reference's layout."""
-    for name, axis in (("head.output.weight", 0), ("final.3.weight", 0), ("output.kernel", -1), ("final.3.kernel", -1)):
+    """The rows of a checkpoint's output layer: ``head.output.weight`` / ``final.3.weight`` / ``final.weight`` (out, in) here, the
+    last axis of ``output.kernel`` / ``final.3.kernel`` / ``final.kernel`` ((1,) in, out) in the reference's layout."""
+    for name, axis in (("head.output.weight", 0), ("final.3.weight", 0), ("output.kernel", -1), ("final.3.kernel", -1),
+                       ("final.weight", 0), ("final.kernel", -1)):
         if name in state_dict:
             return int(state_dict[name].shape[axis])
-    raise ValueError("the checkpoint has no output layer: none of head.output.weight, final.3.weight, output.kernel, final.3.kernel")
+    raise ValueError("the checkpoint has no output layer: none of head.output.weight, final.3.weight, output.kernel, final.3.kernel, "
+                     "final.weight, final.kernel")
 
 
 def _model_num_labels(model) -> int:
-    return int((model.head.output if isinstance(model, HRNetSimCSN) else model.final[3]).out_features)
+    if isinstance(model, HRNetSimCSN):
+        return int(model.head.output.out_features)
+    return int((model.final if isinstance(model, Res16UNetBase) else model.final[3]).out_features)
 
 
 def _forward(model, batch):

@@ -1,0 +1,350 @@
+"""MinkowskiNet's Res16UNet family on voxel rows, on the MI355X kernels.
+
+Reference (marios2019/CSN):
+  * ``Res16UNetBase`` and its classes                                  MinkowskiNet/models/res16unet.py:11-330
+  * ``_make_layer`` (the blocks' ``downsample``)                        MinkowskiNet/models/resnet.py:86-127
+  * ``BasicBlock``                                                      MinkowskiNet/models/modules/resnet_block.py:22-57
+
+An encoder of four kernel-2 stride-2 convolutions, a decoder of four transposed ones, a list of ``BasicBlock`` after each and the
+encoder's maps concatenated to the decoder's (``me.cat``).  The two resolution changes run on ``SparseConvDown2`` / ``SparseConvUp2``
+over an ``OctantMap`` (include/csn_hip.h section 21), their BatchNorm through ATen.  The blocks run on the fused nodes of
+minkowski_hrnet.py (``conv_stats`` + ``bn_act``, section 15): a block whose width changes has a ``downsample`` (kernel-1 convolution
++ BatchNorm) and sums TWO terms, ``norm2(conv2)`` and ``norm(downsample)``, in one ``bn_act`` launch.  A decoder block's input is
+``[up | skip]``: up to 256 columns it is formed with ``torch.cat`` and takes the fused path; beyond, ``conv1`` and the ``downsample``
+convolution go through ``cat_conv3d`` (the concatenation is never formed) with an ATen BatchNorm, and the rest of the block stays
+fused.  ``fused=False`` runs everything on ``sparse_conv3d`` / the octant nodes + ATen: the timing baseline and the tests' yardstick.
+
+``UNetPyramid`` holds what one batch needs, built once (``build_unet_pyramid``): five levels at tensor strides 1 .. 16 — the
+coordinate sets ``build_pyramid`` gives —, per level the kernel-3 and the kernel-1 map, at level 0 the stem's map, between
+neighbouring levels the octant map.
+
+Offset and octant numbering and the sorted order of the coarse levels are this project's choice (minkowski_conv.py): parity unpinned
+against MinkowskiEngine's own checkpoints.  The switches ``grouped_passes``, ``eval_epilogue`` and ``rows_single_product`` of
+``tuning`` leave these networks as they are (``rows_single_product`` reaches the kernel-3 / kernel-1 convolutions as everywhere).
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .minkowski_conv import (KernelMap, OctantMap, SparseConv3d, SparseConvDown2, SparseConvUp2, build_kernel_map, build_octant_map,
+                             cat_conv3d)
+from .minkowski_hrnet import HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _keep
+
+_NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
+N_LEVELS = 5
+
+
+class UNetPyramid:
+    """Coordinates and maps of one batch for a Res16UNet: ``coords[l]`` (n_l, 4) at tensor stride 2^l for l = 0 .. 4; ``s1[l]`` the
+    kernel-3 stride-1 map of level l; ``one[l]`` its kernel-1 map (the blocks' ``downsample``); ``stem`` the kernel-``stem_kernel``
+    map of level 0; ``oct[l]`` the octant map from level l onto level l + 1 (both directions)."""
+
+    def __init__(self, coords: List[torch.Tensor], s1: List[KernelMap], one: List[KernelMap], stem: KernelMap, oct: List[OctantMap],
+                 stem_kernel: int):
+        self.coords, self.s1, self.one, self.stem, self.oct, self.stem_kernel = coords, s1, one, stem, oct, stem_kernel
+
+    def to(self, device) -> "UNetPyramid":
+        return UNetPyramid([c.to(device) for c in self.coords], [m.to(device) for m in self.s1], [m.to(device) for m in self.one],
+                           self.stem.to(device), [m.to(device) for m in self.oct], self.stem_kernel)
+
+
+def build_unet_pyramid(coords: torch.Tensor, stem_kernel: int = 5, backend: Optional[str] = None) -> UNetPyramid:
+    """The pyramid of ``coords`` (n, 4) = [b, x, y, z] at tensor stride 1 (device or CPU tensor; the maps live where it does).
+    ``backend`` as in ``build_kernel_map``, for the kernel maps; the octant maps are torch ops either way."""
+    levels, s1, one, octs = [coords.long()], [], [], []
+    for l in range(N_LEVELS):
+        ts = 1 << l
+        s1.append(build_kernel_map(levels[l], kernel_size=3, stride=1, tensor_stride=ts, backend=backend))
+        one.append(build_kernel_map(levels[l], kernel_size=1, stride=1, tensor_stride=ts, backend=backend))
+        if l + 1 < N_LEVELS:
+            octs.append(build_octant_map(levels[l], tensor_stride=ts))
+            levels.append(octs[-1].out_coords)
+    stem = s1[0] if stem_kernel == 3 else build_kernel_map(levels[0], kernel_size=stem_kernel, stride=1, tensor_stride=1,
+                                                           backend=backend)
+    return UNetPyramid(levels, s1, one, stem, octs, stem_kernel)
+
+
+class CatConv3d(nn.Module):
+    """A stride-1 convolution whose input is a concatenation wider than 256 columns: it holds MinkowskiEngine's ``kernel (KV,
+    c_in, c_out)`` and runs ``cat_conv3d`` on the parts."""
+
+    stride, transposed = 1, False
+
+    def __init__(self, c_in: int, c_out: int, kernel_size: int = 3):
+        super().__init__()
+        if kernel_size not in (1, 3, 5):
+            raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 or 5")
+        if c_out % 32 or not 32 <= c_out <= 256 or c_in < 1:
+            raise ValueError("widths: c_out a multiple of 32 in [32, 256]")
+        self.c_in, self.c_out, self.kernel_size = c_in, c_out, kernel_size
+        KV = kernel_size ** 3
+        self.kernel = nn.Parameter(torch.empty(KV, c_in, c_out))
+        nn.init.normal_(self.kernel, std=(KV * c_in) ** -0.5)
+
+    def forward(self, parts: Sequence[torch.Tensor], kmap: KernelMap) -> torch.Tensor:
+        if kmap.kernel_size != self.kernel_size or kmap.stride != 1 or kmap.transposed:
+            raise ValueError(f"the map (kernel {kmap.kernel_size}, stride {kmap.stride}, transposed {kmap.transposed}) does not fit "
+                             f"this layer (kernel {self.kernel_size}, stride 1, transposed False)")
+        return cat_conv3d(parts, self.kernel, kmap)
+
+    def extra_repr(self) -> str:
+        return f"{self.c_in}, {self.c_out}, kernel_size={self.kernel_size}, stride=1, bias=False"
+
+
+class UNetBasicBlock(nn.Module):
+    """``BasicBlock`` of resnet_block.py:22-57 with the ``downsample`` of resnet.py:96-107 (``downsample.0`` the kernel-1
+    convolution, ``downsample.1`` its BatchNorm): conv1 - norm1 - relu - conv2 - norm2, plus norm(downsample(x)), relu.  ``forward``
+    takes the input as a list of parts ``[up, skip]`` (or ``[x]``) with the level's kernel-3 and kernel-1 maps; ``trace`` (a dict)
+    receives the two ReLU outputs under ``prefix + "norm1"`` / ``prefix + "norm2"``, as in ``HRBasicBlock``."""
+
+    expansion = 1
+
+    def __init__(self, inplanes: int, planes: int, bn_momentum: float = 0.02, fused: bool = True):
+        super().__init__()
+        conv = SparseConv3d if inplanes <= 256 else CatConv3d
+        self.conv1 = conv(inplanes, planes, kernel_size=3)
+        self.norm1 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.conv2 = SparseConv3d(planes, planes, kernel_size=3)
+        self.norm2 = nn.BatchNorm1d(planes, momentum=bn_momentum)
+        self.downsample = nn.Sequential(conv(inplanes, planes, kernel_size=1), nn.BatchNorm1d(planes, momentum=bn_momentum))
+        self.inplanes, self.fused = inplanes, fused
+
+    def forward(self, parts: Sequence[torch.Tensor], s1: KernelMap, one: KernelMap, trace: Optional[dict] = None,
+                prefix: str = "") -> torch.Tensor:
+        f, tr = self.fused, self.training
+        if sum(int(p.shape[1]) for p in parts) != self.inplanes:
+            raise ValueError(f"the parts are {[int(p.shape[1]) for p in parts]} wide; this block takes {self.inplanes} columns")
+        if not all(p.is_cuda for p in parts):
+            raise _lib.CsnError(_NO_CPU)
+        ds_conv, ds_norm = self.downsample[0], self.downsample[1]
+        if self.inplanes <= 256:
+            x = parts[0] if len(parts) == 1 else torch.cat(list(parts), dim=1)
+            out = _combine([_conv_bn(self.conv1, self.norm1, x, s1, f)], f, tr, self.norm1.eps)
+            res = _conv_bn(ds_conv, ds_norm, x, one, f)
+        else:
+            # the split path: the two convolutions that read the concatenation are sums over its parts; their norms are ATen's
+            out = F.relu(self.norm1(self.conv1(parts, s1)))
+            res = ("r", ds_norm(ds_conv(parts, one)))
+        _keep(trace, prefix + "norm1", out)
+        return _keep(trace, prefix + "norm2", _combine([_conv_bn(self.conv2, self.norm2, out, s1, f), res], f, tr, self.norm2.eps))
+
+
+class Res16UNetBase(nn.Module):
+    """``Res16UNetBase`` (res16unet.py:11-229) with the reference's attribute names: ``conv0p1s1`` / ``bn0``, ``conv{1..4}p{1,2,4,
+    8}s2`` / ``bn{1..4}``, ``block1`` .. ``block8`` (``nn.Sequential`` of blocks: ``blockN.i.conv1.kernel``, ``.norm1.*``,
+    ``.downsample.0.kernel``, ``.downsample.1.*``), ``convtr{4..7}p{16,8,4,2}s2`` / ``bntr{4..7}``, ``final`` (the kernel-1 output
+    convolution as an ``nn.Linear`` with bias).
+
+    ``forward((coords, feats))``: ``coords (N, 4)`` rows [b, x, y, z] (or a ``UNetPyramid`` built for them, or a ``VoxelPyramid``,
+    whose level-0 coordinates are taken), ``feats (N, in_channels)``; returns the (N, out_channels) logits, in training and eval.
+    ``trace``: a dict that receives every ReLU's output, keyed ``bn0`` .. ``bn4``, ``bntr4`` .. ``bntr7`` and
+    ``blockN.i.norm1`` / ``.norm2``."""
+
+    PLANES = (32, 64, 128, 256, 256, 256, 256, 256)
+    LAYERS = (2, 2, 2, 2, 2, 2, 2, 2)
+    INIT_DIM = 32
+    BLOCK = "BasicBlock"
+    NORM_TYPE = "BATCH_NORM"
+
+    def __init__(self, in_channels: int, out_channels: int, bn_momentum: float = 0.02, conv1_kernel_size: int = 5, fused: bool = True):
+        super().__init__()
+        name = type(self).__name__
+        if self.BLOCK != "BasicBlock":
+            raise NotImplementedError(f"{name} is built from Bottleneck blocks, whose inner widths (planes // 4 = 8, 16, 24, ...) are no "
+                                      "multiples of 32; the kernels take widths that are")
+        if self.NORM_TYPE != "BATCH_NORM":
+            raise NotImplementedError(f"{name}: norm type {self.NORM_TYPE} is not supported: BatchNorm only")
+        if max(self.PLANES) > 256:
+            raise NotImplementedError(f"{name} needs {max(self.PLANES)}-wide convolutions; the kernels (include/csn_hip.h sections 14 "
+                                      "and 21) take widths up to 256")
+        P, self.fused, self.conv1_kernel_size = self.PLANES, fused, conv1_kernel_size
+        mom = bn_momentum
+        bn = lambda c: nn.BatchNorm1d(c, momentum=mom)
+        self.inplanes = self.INIT_DIM
+        self.conv0p1s1 = SparseConv3d(in_channels, self.inplanes, kernel_size=conv1_kernel_size)
+        self.bn0 = bn(self.inplanes)
+        for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
+            setattr(self, f"conv{n}p{ts}s2", SparseConvDown2(self.inplanes, self.inplanes))
+            setattr(self, f"bn{n}", bn(self.inplanes))
+            setattr(self, f"block{n}", self._make_layer(P[n - 1], self.LAYERS[n - 1], mom))
+        skips = (P[2], P[1], P[0], self.INIT_DIM)
+        for n, ts in ((4, 16), (5, 8), (6, 4), (7, 2)):
+            setattr(self, f"convtr{n}p{ts}s2", SparseConvUp2(self.inplanes, P[n]))
+            setattr(self, f"bntr{n}", bn(P[n]))
+            self.inplanes = P[n] + skips[n - 4]
+            setattr(self, f"block{n + 1}", self._make_layer(P[n], self.LAYERS[n], mom))
+        self.final = nn.Linear(P[7], out_channels, bias=True)
+
+    def _make_layer(self, planes: int, blocks: int, mom: float) -> nn.Sequential:
+        """resnet.py:86-127: the first block changes the width (with a ``downsample`` when it does), the others keep it."""
+        first = (UNetBasicBlock(self.inplanes, planes, mom, self.fused) if self.inplanes != planes
+                 else HRBasicBlock(planes, planes, mom, self.fused))
+        self.inplanes = planes
+        return nn.Sequential(first, *[HRBasicBlock(planes, planes, mom, self.fused) for _ in range(1, blocks)])
+
+    @staticmethod
+    def _blocks(seq: nn.Sequential, parts, s1: KernelMap, one: KernelMap, trace: Optional[dict], name: str) -> torch.Tensor:
+        first = seq[0]
+        if isinstance(first, UNetBasicBlock):
+            x = first(parts, s1, one, trace, f"{name}.0.")
+        else:
+            x = first(parts[0] if len(parts) == 1 else torch.cat(list(parts), dim=1), s1, trace, f"{name}.0.")
+        for i, blk in enumerate(list(seq)[1:], 1):
+            x = blk(x, s1, trace, f"{name}.{i}.")
+        return x
+
+    def _pyramid(self, where) -> UNetPyramid:
+        if isinstance(where, UNetPyramid):
+            return where
+        if isinstance(where, VoxelPyramid):
+            where = where.coords[0]
+        return build_unet_pyramid(where, self.conv1_kernel_size)
+
+    def forward(self, batch, trace: Optional[dict] = None) -> torch.Tensor:
+        where, feats = batch
+        pyr = self._pyramid(where)
+        if not feats.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if pyr.coords[0].device != feats.device:
+            pyr = pyr.to(feats.device)
+        f, tr = self.fused, self.training
+        out_p1 = _keep(trace, "bn0", _combine([_conv_bn(self.conv0p1s1, self.bn0, feats, pyr.stem, f)], f, tr, self.bn0.eps))
+        skips, out = [out_p1], out_p1
+        for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
+            out = _keep(trace, f"bn{n}", F.relu(getattr(self, f"bn{n}")(getattr(self, f"conv{n}p{ts}s2")(out, pyr.oct[n - 1]))))
+            out = self._blocks(getattr(self, f"block{n}"), [out], pyr.s1[n], pyr.one[n], trace, f"block{n}")
+            skips.append(out)
+        skips.pop()                                                    # block4's output goes up, not across
+        for n, ts in ((4, 16), (5, 8), (6, 4), (7, 2)):
+            level = 7 - n
+            out = _keep(trace, f"bntr{n}", F.relu(getattr(self, f"bntr{n}")(getattr(self, f"convtr{n}p{ts}s2")(out, pyr.oct[level]))))
+            out = self._blocks(getattr(self, f"block{n + 1}"), [out, skips.pop()], pyr.s1[level], pyr.one[level], trace,
+                               f"block{n + 1}")
+        return self.final(out)
+
+
+class Res16UNet14(Res16UNetBase):
+    LAYERS = (1, 1, 1, 1, 1, 1, 1, 1)
+
+
+class Res16UNet18(Res16UNetBase):
+    LAYERS = (2, 2, 2, 2, 2, 2, 2, 2)
+
+
+class Res16UNet34(Res16UNetBase):
+    LAYERS = (2, 3, 4, 6, 2, 2, 2, 2)
+
+
+class Res16UNet50(Res16UNetBase):
+    BLOCK = "Bottleneck"
+    LAYERS = (2, 3, 4, 6, 2, 2, 2, 2)
+
+
+class Res16UNet101(Res16UNetBase):
+    BLOCK = "Bottleneck"
+    LAYERS = (2, 3, 4, 23, 2, 2, 2, 2)
+
+
+class Res16UNet14A(Res16UNet14):
+    PLANES = (32, 64, 128, 256, 128, 128, 96, 96)
+
+
+class Res16UNet14A2(Res16UNet14A):
+    LAYERS = (1, 1, 1, 1, 2, 2, 2, 2)
+
+
+class Res16UNet14B(Res16UNet14):
+    PLANES = (32, 64, 128, 256, 128, 128, 128, 128)
+
+
+class Res16UNet14B2(Res16UNet14B):
+    LAYERS = (1, 1, 1, 1, 2, 2, 2, 2)
+
+
+class Res16UNet14B3(Res16UNet14B):
+    LAYERS = (2, 2, 2, 2, 1, 1, 1, 1)
+
+
+class Res16UNet14C(Res16UNet14):
+    PLANES = (32, 64, 128, 256, 192, 192, 128, 128)
+
+
+class Res16UNet14D(Res16UNet14):
+    PLANES = (32, 64, 128, 256, 384, 384, 384, 384)
+
+
+class Res16UNet18A(Res16UNet18):
+    PLANES = (32, 64, 128, 256, 128, 128, 96, 96)
+
+
+class Res16UNet18B(Res16UNet18):
+    PLANES = (32, 64, 128, 256, 128, 128, 128, 128)
+
+
+class Res16UNet18D(Res16UNet18):
+    PLANES = (32, 64, 128, 256, 384, 384, 384, 384)
+
+
+class Res16UNet34A(Res16UNet34):
+    PLANES = (32, 64, 128, 256, 256, 128, 64, 64)
+
+
+class Res16UNet34B(Res16UNet34):
+    PLANES = (32, 64, 128, 256, 256, 128, 64, 32)
+
+
+class Res16UNet34C(Res16UNet34):
+    PLANES = (32, 64, 128, 256, 256, 128, 96, 96)
+
+
+SUPPORTED = ("Res16UNet14", "Res16UNet14A", "Res16UNet14A2", "Res16UNet14B", "Res16UNet14B2", "Res16UNet14B3", "Res16UNet14C",
+             "Res16UNet18", "Res16UNet18A", "Res16UNet18B", "Res16UNet34", "Res16UNet34A", "Res16UNet34B", "Res16UNet34C")
+REFUSED = ("Res16UNet14D", "Res16UNet18D", "Res16UNet50", "Res16UNet101")
+
+
+def load_me_unet_state(model: Res16UNetBase, state_dict) -> Res16UNetBase:
+    """Copy a ``Res16UNet`` checkpoint of the reference into ``model``.  The modules keep the reference's names; a
+    ``MinkowskiBatchNorm`` wraps its norm, so ``<name>.bn.weight`` etc. map to ``<name>.weight`` (``bnX.bn.*``,
+    ``blockN.i.norm1.bn.*``, ``blockN.i.downsample.1.bn.*``); a convolution's ``<name>.kernel`` is (KV, c_in, c_out) on both sides;
+    ``final.kernel`` — (c_in, c_out) or (1, c_in, c_out) — is transposed into the ``nn.Linear`` weight and ``final.bias`` — (c_out,)
+    or (1, c_out) — flattened.  A missing key or a wrong shape raises ``ValueError`` before the model is touched.  The order of the KV
+    axis (the offset and octant numbering of minkowski_conv.py) is this project's choice: parity unpinned against MinkowskiEngine."""
+    new = {}
+    c_out, c_in = model.final.weight.shape
+    for need in ("final.kernel", "final.bias"):
+        if need not in state_dict:
+            raise ValueError(f"checkpoint has no {need}")
+    kernel, bias = state_dict["final.kernel"], state_dict["final.bias"]
+    if tuple(kernel.shape) == (1, c_in, c_out):
+        kernel = kernel[0]
+    if tuple(kernel.shape) != (c_in, c_out):
+        raise ValueError(f"final.kernel is {tuple(kernel.shape)}; expected ({c_in}, {c_out}) or (1, {c_in}, {c_out})")
+    if tuple(bias.shape) == (1, c_out):
+        bias = bias[0]
+    if tuple(bias.shape) != (c_out,):
+        raise ValueError(f"final.bias is {tuple(bias.shape)}; expected ({c_out},) or (1, {c_out})")
+    new["final.weight"], new["final.bias"] = kernel.t(), bias
+    for name, mod in model.named_modules():
+        if isinstance(mod, (SparseConv3d, SparseConvDown2, CatConv3d)):
+            pairs = [(f"{name}.kernel", f"{name}.kernel", mod.kernel)]
+        elif isinstance(mod, nn.BatchNorm1d):
+            pairs = [(f"{name}.{p}", f"{name}.bn.{p}", getattr(mod, p))
+                     for p in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+        else:
+            continue
+        for own, ref, cur in pairs:
+            if ref not in state_dict:
+                raise ValueError(f"checkpoint has no {ref}")
+            v = state_dict[ref]
+            if v.dim() == 2 and cur.dim() == 3 and cur.shape[0] == 1:      # a kernel-1 convolution kept as (c_in, c_out)
+                v = v[None]
+            if tuple(v.shape) != tuple(cur.shape):
+                raise ValueError(f"{ref} is {tuple(v.shape)}; expected {tuple(cur.shape)}")
+            new[own] = v
+    model.load_state_dict(new, strict=True)
+    return model

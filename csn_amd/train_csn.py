@@ -129,7 +129,7 @@ def run(cfg: TrainConfig, args, csn: bool) -> int:
                         handlers=[logging.StreamHandler(sys.stdout)])
     import torch
 
-    from . import minkowski_hrnet
+    from . import minkowski_hrnet, minkowski_unet
     from .minkowski_points import AugmentSpec, PointCollection
     from .minkowski_trainer import CSNTrainer, SegTrainer, checkpoint_num_labels, load_model_state, test_split
 
@@ -160,7 +160,7 @@ def run(cfg: TrainConfig, args, csn: bool) -> int:
         num_labels = checkpoint_num_labels(state["state_dict"])
     else:
         num_labels = SYNTHETIC_LABELS if args.synthetic else int(splits["train"].labels.max()) + 1
-    net = getattr(minkowski_hrnet, cfg.model)
+    net = getattr(minkowski_hrnet, cfg.model, None) or getattr(minkowski_unet, cfg.model)
     model = net(3, num_labels, d_model=args.d_model, n_head=args.n_head, k_neighbors=K) if csn else net(3, num_labels)
     model = model.to("cuda")
     if state is not None:

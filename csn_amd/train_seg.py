@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Train an ``HRNetSeg``, the baseline cross-shape attention is measured against, or test one: what MinkowskiNet/tasks/main_seg.py
+"""Train an ``HRNetSeg``, the baseline cross-shape attention is measured against (or a ``Res16UNet``: ``--model Res16UNet34C``), or test one: what MinkowskiNet/tasks/main_seg.py
 does, on ``csn_amd.minkowski_trainer.SegTrainer`` and ``test_split``.
 
     python -m csn_amd.train_seg --log_dir <out> --model HRNetSeg3S --lr 0.05 --optimizer SGD --batch_size 8
@@ -16,7 +16,9 @@ import sys
 
 from . import train_csn
 
-MODELS = ("HRNetSeg2S", "HRNetSeg3S")
+# (the parser's default is the last name)
+MODELS = ("Res16UNet14", "Res16UNet14A", "Res16UNet14A2", "Res16UNet14B", "Res16UNet14B2", "Res16UNet14B3", "Res16UNet14C", "Res16UNet18",
+          "Res16UNet18A", "Res16UNet18B", "Res16UNet34", "Res16UNet34A", "Res16UNet34B", "Res16UNet34C", "HRNetSeg2S", "HRNetSeg3S")
 
 
 def build_parser():

@@ -971,6 +971,45 @@ CSN_API int csn_rows_bn_act_groups_bwd_f32(const float* dy, long long ld_dy, con
                                    int n_terms, int n_rows, int channels, const int* group_rows, int n_groups, int relu, float* dr,
                                    long long ld_dr, void* ws, long long ws_bytes, void* stream);
 
+/* ---- (21) kernel-2 stride-2 convolution and its transposed form (MinkowskiNet/models/res16unet.py: conv1p1s2 .. conv4p8s2,
+ *           convtr4p16s2 .. convtr7p2s2) ---------------------------------------------------------------------------------------
+ * Kernel 2 at stride 2 partitions the fine voxels: every fine row has exactly one parent among the coarse rows and sits in exactly
+ * one of its 8 octants.  The caller builds the OCTANT MAP (csn_amd.minkowski_conv.build_octant_map), all int32 on the device:
+ *   parent[n_fine]        the coarse row of fine row i
+ *   children[8][n_coarse] the fine row in octant k of coarse row j, or -1
+ *   order[n_fine]         the fine rows sorted by (octant, row);  seg[9]: octant k is order[seg[k] .. seg[k + 1])
+ * DOWN (x[n_fine][c_in] -> y[n_coarse][c_out]):  y[j] = sum_k x[children[k][j]] W[k] + bias
+ * UP   (x[n_coarse][c_in] -> y[n_fine][c_out]):  y[i] = x[parent[i]] W[octant[i]] + bias     (one weight per row)
+ * Everything is POINT-MAJOR fp32 with pitches as in (14): w[8][c_in][c_out] contiguous (MinkowskiEngine's `kernel`), bias[c_out]
+ * may be NULL; columns of a row beyond its width are neither read as data nor written.  A negative index reads as "no voxel"; an
+ * index past its array is the caller's error and is never dereferenced (dropped, or caught by the buffer range check); seg is
+ * read as a monotone sequence inside [0, n_fine] whatever it holds.
+ * Geometry: n_fine, n_coarse >= 1 (CSN_E_ARG); c_in % 32 == 0 and c_out % 32 == 0, both in [32, 256] (CSN_E_DIM); every pitch
+ * % 4 == 0 (CSN_E_ALIGN), >= its width (CSN_E_ARG), <= 2^20 and rows * pitch * 4 < 2 GiB (CSN_E_DIM); maps, w, dw and ws 16-byte
+ * aligned, the index arrays 4-byte (CSN_E_PTR).  All of this is checked on the host before any launch.  ws (backward only):
+ * csn_octant_conv_workspace_bytes(..., up, backward = 1) bytes (CSN_E_WORKSPACE); the forward takes none (backward = 0 returns 0).
+ * The gather form (down forward, up dx) is the gather-GEMM of (14) over 8 offsets.  The one-weight form (up forward, down dx) walks
+ * `order`: a work-group's tile of <= 128 entries lies inside one segment, the grid is ceil(n_fine / 128) + 7 row groups sized from
+ * n_fine alone, every output row is written exactly once and an empty octant costs nothing.
+ *   dw[k] = sum_{i : octant[i] = k} in_row(i)^T dy_row(i)   split-K over chunks of `order` cut at the segment bounds, slabs added in
+ *                                                           chunk order: work proportional to n_fine; an empty octant's dw is 0
+ *   dbias = sum of dy's rows                                fp64 partials of 64-row chunks added in chunk order
+ * Each backward output is skipped when its pointer is NULL (its own inputs may then be NULL too).  No floating-point atomics: two
+ * identical calls give the same bits.  Math mode 0 runs the products on the exact fp32 matrix instruction, every other mode as
+ * bf16x3 whatever csn_set_thread_rows16 says (there are no single-product instances).  Additive to ABI version 17. */
+CSN_API long long csn_octant_conv_workspace_bytes(int n_fine, int n_coarse, int c_in, int c_out, int up, int backward);
+CSN_API int csn_octant_down_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
+                            const float* w, const float* bias, float* y, long long ld_y, void* stream);
+CSN_API int csn_octant_down_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
+                            int c_out, const int* parent, const int* order, const int* seg, const float* w, float* dx,
+                            long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
+CSN_API int csn_octant_up_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
+                          int n_fine, int c_in, int c_out, const float* w, const float* bias, float* y, long long ld_y,
+                          void* stream);
+CSN_API int csn_octant_up_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
+                          int c_out, const int* children, const int* parent, const int* order, const int* seg, const float* w,
+                          float* dx, long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
