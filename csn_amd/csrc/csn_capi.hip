@@ -1381,21 +1381,39 @@ long long csn_sparse_conv_stats_workspace_bytes(int n_out, int c_out) {
   return csn_sparse_conv_stats_ws_bytes(n_out, c_out);
 }
 
-int csn_sparse_conv_stats_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
-                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
-                                  float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
-                                  void* stream) {
+// (15) the whole map is one BatchNorm batch, (20) the batch per row group: one implementation each, `grouped` is the entry point
+static int groups_args(const int* group_rows, int n_groups) {
+  if (!group_rows || n_groups < 1) return CSN_E_ARG;
+  if (n_groups > 8) return CSN_E_DIM;
+  if (reinterpret_cast<uintptr_t>(group_rows) & 3) return CSN_E_PTR;
+  return 0;
+}
+
+static int sparse_conv_stats_fwd_impl(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
+                                      const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
+                                      float* running_var, float eps, float momentum, bool grouped, const int* group_rows, int n_groups,
+                                      void* ws, long long ws_bytes, void* stream) {
   if (!x || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
+  if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
   if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
   if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
   if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
-  if (n_out == 1) return CSN_E_ARG;                               // a one-row batch has no variance
+  if (n_out < 2 * (grouped ? n_groups : 1)) return CSN_E_ARG;    // every batch needs two rows: a one-row batch has no variance
   if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
-  return csn_launch_sparse_conv_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, rows_mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_stats_fwd(a, grouped ? group_rows : nullptr, n_groups, mean, invstd, running_mean, running_var, eps,
+                                          momentum, rows_mode(), (hipStream_t)stream);
+}
+
+int csn_sparse_conv_stats_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                  float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
+                                  void* stream) {
+  return sparse_conv_stats_fwd_impl(x, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
+                                    eps, momentum, false, nullptr, 0, ws, ws_bytes, stream);
 }
 
 static int bn_act_dims(int n_terms, int n_rows, int channels) {
@@ -1406,12 +1424,14 @@ static int bn_act_dims(int n_terms, int n_rows, int channels) {
 
 long long csn_rows_bn_act_workspace_bytes(int n_rows, int channels, int n_terms) {
   if (bn_act_dims(n_terms, n_rows, channels)) return 0;
-  return csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms);
+  return csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, 1);
 }
 
-int csn_rows_bn_act_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, const float* r,
-                            long long ld_r, int relu, float* y, long long ld_y, void* stream) {
+static int rows_bn_act_fwd_impl(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, bool grouped,
+                                const int* group_rows, int n_groups, const float* r, long long ld_r, int relu, float* y, long long ld_y,
+                                void* stream) {
   if (!t || !y) return CSN_E_ARG;
+  if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
   CsnRowsBnActArgs a{};
   for (int m = 0; m < n_terms; ++m) {
@@ -1426,13 +1446,19 @@ int csn_rows_bn_act_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int ch
   if (mis16(y) || (r && mis16(r))) return CSN_E_PTR;
   a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
   a.r = r; a.ld_r = (int)ld_r; a.y = y; a.ld_y = (int)ld_y;
-  return csn_launch_rows_bn_act_fwd(a, (hipStream_t)stream);
+  return csn_launch_rows_bn_act_fwd(a, grouped ? group_rows : nullptr, n_groups, (hipStream_t)stream);
 }
 
-int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
-                            int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr, void* ws,
-                            long long ws_bytes, void* stream) {
+int csn_rows_bn_act_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, const float* r,
+                            long long ld_r, int relu, float* y, long long ld_y, void* stream) {
+  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, r, ld_r, relu, y, ld_y, stream);
+}
+
+static int rows_bn_act_bwd_impl(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
+                                int n_rows, int channels, int training, float eps, bool grouped, const int* group_rows, int n_groups,
+                                int relu, float* dr, long long ld_dr, void* ws, long long ws_bytes, void* stream) {
   if (!dy || !t || !ws || (relu && !y)) return CSN_E_ARG;
+  if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
   CsnRowsBnActArgs a{};
   for (int m = 0; m < n_terms; ++m) {
@@ -1447,10 +1473,17 @@ int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, lo
   if (relu) if (const int e = sparse_conv_map(ld_y, channels, n_rows)) return e;
   if (dr) if (const int e = sparse_conv_map(ld_dr, channels, n_rows)) return e;
   if (mis16(dy) || mis16(ws) || (relu && mis16(y)) || (dr && mis16(dr))) return CSN_E_PTR;
-  if (ws_bytes < csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms)) return CSN_E_WORKSPACE;
+  if (ws_bytes < csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, grouped ? n_groups : 1)) return CSN_E_WORKSPACE;
   a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
   a.y = const_cast<float*>(y); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr; a.ws = ws;
-  return csn_launch_rows_bn_act_bwd(a, (hipStream_t)stream);
+  return csn_launch_rows_bn_act_bwd(a, grouped ? group_rows : nullptr, n_groups, (hipStream_t)stream);
+}
+
+int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
+                            int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr, void* ws,
+                            long long ws_bytes, void* stream) {
+  return rows_bn_act_bwd_impl(dy, ld_dy, y, ld_y, t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, relu, dr, ld_dr, ws,
+                              ws_bytes, stream);
 }
 
 // ---- (19) the gather-GEMM with a BatchNorm + residual + ReLU epilogue (inference) ----
@@ -1474,14 +1507,7 @@ int csn_sparse_conv_bn_act_fwd_f32(const float* x, long long ld_x, int n_in, con
   return csn_launch_sparse_conv_bn_act_fwd(a, n, rows_mode(), (hipStream_t)stream);
 }
 
-// ---- (20) BatchNorm over row groups ----
-static int groups_args(const int* group_rows, int n_groups) {
-  if (!group_rows || n_groups < 1) return CSN_E_ARG;
-  if (n_groups > 8) return CSN_E_DIM;
-  if (reinterpret_cast<uintptr_t>(group_rows) & 3) return CSN_E_PTR;
-  return 0;
-}
-
+// ---- (20) BatchNorm over row groups: the implementations of (15) with the batch per group, training mode ----
 long long csn_sparse_conv_stats_groups_workspace_bytes(int n_out, int c_out, int n_groups) {
   if (n_groups < 1 || n_groups > 8) return 0;
   return csn_sparse_conv_stats_workspace_bytes(n_out, c_out);
@@ -1491,72 +1517,26 @@ int csn_sparse_conv_stats_groups_fwd_f32(const float* x, long long ld_x, int n_i
                                          int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
                                          float* running_mean, float* running_var, float eps, float momentum, const int* group_rows,
                                          int n_groups, void* ws, long long ws_bytes, void* stream) {
-  if (!x || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
-  if (const int e = groups_args(group_rows, n_groups)) return e;
-  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
-  if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
-  if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
-  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
-  if (n_out < 2 * n_groups) return CSN_E_ARG;                     // every group needs two rows: a one-row batch has no variance
-  if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
-  CsnSparseConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
-  a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
-  return csn_launch_sparse_conv_stats_groups_fwd(a, group_rows, n_groups, mean, invstd, running_mean, running_var, eps, momentum,
-                                                 rows_mode(), (hipStream_t)stream);
+  return sparse_conv_stats_fwd_impl(x, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
+                                    eps, momentum, true, group_rows, n_groups, ws, ws_bytes, stream);
 }
 
 long long csn_rows_bn_act_groups_workspace_bytes(int n_rows, int channels, int n_terms, int n_groups) {
   if (bn_act_dims(n_terms, n_rows, channels) || n_groups < 1 || n_groups > 8) return 0;
-  return csn_rows_bn_act_groups_ws_bytes(n_rows, channels, n_terms, n_groups);
+  return csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, n_groups);
 }
 
 int csn_rows_bn_act_groups_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int channels, const int* group_rows, int n_groups,
                                    const float* r, long long ld_r, int relu, float* y, long long ld_y, void* stream) {
-  if (!t || !y) return CSN_E_ARG;
-  if (const int e = groups_args(group_rows, n_groups)) return e;
-  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
-  CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m] || !t->beta[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (mis16(t->z[m])) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.beta[m] = t->beta[m];
-  }
-  if (const int e = sparse_conv_map(ld_y, channels, n_rows)) return e;
-  if (r) if (const int e = sparse_conv_map(ld_r, channels, n_rows)) return e;
-  if (mis16(y) || (r && mis16(r))) return CSN_E_PTR;
-  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = 1; a.relu = relu != 0;
-  a.r = r; a.ld_r = (int)ld_r; a.y = y; a.ld_y = (int)ld_y;
-  return csn_launch_rows_bn_act_groups_fwd(a, group_rows, n_groups, (hipStream_t)stream);
+  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, r, ld_r, relu, y, ld_y, stream);
 }
 
 int csn_rows_bn_act_groups_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
                                    int n_rows, int channels, const int* group_rows, int n_groups, int relu, float* dr, long long ld_dr,
                                    void* ws, long long ws_bytes, void* stream) {
-  if (!dy || !t || !ws || (relu && !y)) return CSN_E_ARG;
-  if (const int e = groups_args(group_rows, n_groups)) return e;
-  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
-  CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (t->dz[m]) if (const int e = sparse_conv_map(t->ld_dz[m], channels, n_rows)) return e;
-    if (mis16(t->z[m]) || (t->dz[m] && mis16(t->dz[m]))) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.dz[m] = t->dz[m]; a.ld_dz[m] = (int)t->ld_dz[m]; a.dgamma[m] = t->dgamma[m]; a.dbeta[m] = t->dbeta[m];
-  }
-  if (const int e = sparse_conv_map(ld_dy, channels, n_rows)) return e;
-  if (relu) if (const int e = sparse_conv_map(ld_y, channels, n_rows)) return e;
-  if (dr) if (const int e = sparse_conv_map(ld_dr, channels, n_rows)) return e;
-  if (mis16(dy) || mis16(ws) || (relu && mis16(y)) || (dr && mis16(dr))) return CSN_E_PTR;
-  if (ws_bytes < csn_rows_bn_act_groups_ws_bytes(n_rows, channels, n_terms, n_groups)) return CSN_E_WORKSPACE;
-  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = 1; a.relu = relu != 0;
-  a.y = const_cast<float*>(y); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr; a.ws = ws;
-  return csn_launch_rows_bn_act_groups_bwd(a, group_rows, n_groups, (hipStream_t)stream);
+  return rows_bn_act_bwd_impl(dy, ld_dy, y, ld_y, t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, relu, dr, ld_dr, ws,
+                              ws_bytes, stream);
 }
-
 
 // ---- (21) kernel-2 stride-2 convolution and its transposed form over an octant map ----
 static int octant_dims(int n_fine, int n_coarse, int c_in, int c_out) {

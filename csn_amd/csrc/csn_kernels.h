@@ -329,10 +329,11 @@ struct CsnSparseConvArgs {
 long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward);
 int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
-// forward with the BatchNorm statistics epilogue (no bias): a.y = z, a.ws = csn_sparse_conv_stats_ws_bytes(n_out, c_out) bytes
+// forward with the BatchNorm statistics epilogue (no bias): a.y = z, a.ws = csn_sparse_conv_stats_ws_bytes(n_out, c_out) bytes.
+// group_rows (NULL, 0: the whole map is one batch): as for csn_launch_rows_bn_act_fwd below, mean / invstd [n_groups][c_out]
 long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out);
-int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
-                                     float eps, float momentum, int mode, hipStream_t st);
+int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
+                                     float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st);
 // forward with the inference epilogue (no bias): a.y = act(z s + t + r), s = gamma / sqrt(running_var + eps), t = beta -
 // running_mean s; r optional, may be a.y itself with ld_r == a.ld_y.  One launch, no workspace
 struct CsnSconvBnArgs {
@@ -374,23 +375,16 @@ struct CsnRowsBnActArgs {
   float* dr;  int ld_dr;
   void* ws;
 };
+// group_rows (device, n_groups + 1 entries; NULL, 0: the whole map is one BatchNorm batch): group g is the rows [group_rows[g],
+// group_rows[g + 1]) and a batch of its own, mean / scale of the terms are [n_groups][C]; training mode only.
 // the Chan merge of [tile][2][C] (mean, M2) partials of 32-row tiles (the statistics epilogue of sparse_conv.hip): mean, invstd,
-// running statistics (either may be NULL)
-int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, float* mean, float* invstd,
-                              float* running_mean, float* running_var, hipStream_t st);
-long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms);
-int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, hipStream_t st);
-int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, hipStream_t st);
-// (20) the same over row groups: group g is the rows [group_rows[g], group_rows[g + 1]) (device, n_groups + 1 entries), mean /
-// scale of the terms are [n_groups][C]; training mode only
-int csn_launch_sparse_conv_stats_groups_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
-                                            float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st);
-int csn_launch_bn_stats_merge_groups(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, const float* z, int ld_z,
-                                     const int* group_rows, int n_groups, float* mean, float* invstd, float* running_mean,
-                                     float* running_var, hipStream_t st);
-long long csn_rows_bn_act_groups_ws_bytes(long long n_rows, int C, int n_terms, int n_groups);
-int csn_launch_rows_bn_act_groups_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
-int csn_launch_rows_bn_act_groups_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
+// running statistics (either may be NULL); z, ld_z: the map itself, read only where a group boundary cuts a tile
+int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, const float* z, int ld_z,
+                              const int* group_rows, int n_groups, float* mean, float* invstd, float* running_mean, float* running_var,
+                              hipStream_t st);
+long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms, int n_groups);      // n_groups 1: the whole map
+int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
+int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
 
 // ---- point fields: voxel means, trilinear interpolation onto points and its adjoint (point_field.hip) ----
 struct CsnPointFieldArgs {

@@ -14,14 +14,19 @@
 //   bn_stats_merge      (15a) the (mean, M2) pairs that the convolution's epilogue leaves per 32-row tile, merged by Chan's formula in
 //                       fp64 in a fixed order: mean, invstd, running statistics (the merge, the tile walk and the finish are
 //                       rows_mma.h's, shared with rows_fc_stats; the segment count and the tree are this kernel's).
-//   *_groups           (20) the same passes with the BatchNorm batch taken per contiguous ROW GROUP: group g is the rows
-//                       [group_rows[g], group_rows[g + 1]) and has its own (mu, s).  A work-group walks the groups that meet its 64
-//                       rows one after the other and loads a group's per-column constants when it enters it; the backward's chunk
-//                       sums are cut at the group boundaries (at most chunks + G - 1 parts), added per group and the groups in
-//                       ascending order.  bn_stats_merge_groups: the whole 32-row tiles of a group from the epilogue's partials as
-//                       above, the <= 31 rows of a tile that a boundary cuts re-read from z.  With one group every sum is the sum
-//                       of the ungrouped kernel in the same order: the same bits.  A row outside every group is not touched, and
-//                       no row or part index leaves its array whatever group_rows holds.
+//
+// The backward's passes, its sums and the tile merge are stated ONCE, each as a __device__ body over a span of rows (of parts, of
+// tiles) and an offset into the statistics, for the two forms of the BatchNorm batch.  (15) the whole map: the body once, on the
+// work-group's whole chunk (the whole part / tile list) at offset 0; no group offsets are read, and the eval path (running
+// statistics and eps) is kept.  (20, training only) per contiguous ROW GROUP: group g is the rows [group_rows[g], group_rows[g + 1])
+// and has its own (mu, s) at offset g * C.  A work-group walks the groups that meet its 64 rows one after the other and calls the
+// body per span, which loads that group's per-column constants; the backward's chunk sums are cut at the group boundaries (at most
+// chunks + G - 1 parts), added per group and the groups in ascending order; the merge takes the whole 32-row tiles of a group
+// from the epilogue's partials and re-reads the <= 31 rows of a tile that a boundary cuts from z.  rows_bn_act_bwd and
+// rows_bn_act_sums are templates on GROUPED; bn_stats_merge / bn_stats_merge_groups are two kernels on the one merge_tiles, and
+// the forward has two kernels of its own, rows_bn_act_fwd / rows_bn_act_groups_fwd (see there for why).  With one group every sum
+// is the whole-map sum in the same order: the same bits.  A row outside every group is not touched, and no row or part index
+// leaves its array whatever group_rows holds.
 // No floating-point atomics anywhere: every reduction has a fixed order, two calls give the same bits.
 #include "rows_mma.h"
 
@@ -32,7 +37,7 @@ constexpr int MAXT = 3;
 
 struct BnActP {
   const float* z[MAXT]; int ld_z[MAXT];
-  const float* mean[MAXT]; const float* scale[MAXT]; const float* gamma[MAXT]; const float* beta[MAXT];
+  const float* mean[MAXT]; const float* scale[MAXT]; const float* gamma[MAXT]; const float* beta[MAXT];   // mean / scale: [G][C]
   float* dz[MAXT]; int ld_dz[MAXT];
   int M;
   long long n_rows; int C;
@@ -41,12 +46,14 @@ struct BnActP {
   float* y; int ld_y;                          // forward: written; backward: read
   const float* dy; int ld_dy;
   float* dr; int ld_dr;
-  const float* coef;                           // pass 2, training: [1 + M][C] mean g', mean g' xhat_m
-  double* part;                                // pass 1: [chunk][1 + M][C]
+  const float* coef;                           // pass 2, training: [G][1 + M][C] mean g', mean g' xhat_m
+  double* part;                                // pass 1: [part][1 + M][C]; a part is a chunk, or what a chunk and a group share
+  const int* grp; int G;                       // GROUPED only: [G + 1] row offsets of the groups
+  int n_parts;                                 // GROUPED only: chunks + G - 1, the bound of the part index
 };
 
-__device__ __forceinline__ float inv_std(const BnActP& p, int m, int c) {
-  return p.eval ? 1.f / sqrtf(p.scale[m][c] + p.eps) : p.scale[m][c];
+__device__ __forceinline__ float inv_std(const BnActP& p, int m, int c, bool eval) {
+  return eval ? 1.f / sqrtf(p.scale[m][c] + p.eps) : p.scale[m][c];
 }
 
 // Thread layout of the three row kernels: 64 rows per work-group; a thread owns 4 consecutive channels (16-byte accesses on every
@@ -58,6 +65,27 @@ __device__ __forceinline__ Lane lane_of(int C) {
   return Lane{rl, ((int)threadIdx.x - rl * c4) * 4, RL, rl < RL};
 }
 
+// the rows [lo, hi) of the work-group's chunk (rows from r0) that belong to group g; false: none
+__device__ __forceinline__ bool group_span(const BnActP& p, int g, long long r0, int rows, int& lo, int& hi) {
+  const long long a = (long long)p.grp[g], b = (long long)p.grp[g + 1];
+  lo = (int)(a > r0 ? (a < r0 + rows ? a - r0 : rows) : 0);
+  hi = (int)(b < r0 + rows ? (b > r0 ? b - r0 : 0) : rows);
+  return lo < hi;
+}
+// a row lane's first row at or after lo
+__device__ __forceinline__ int first_row(const Lane& t, int lo) { return t.rl >= lo ? t.rl : t.rl + (lo - t.rl + t.RL - 1) / t.RL * t.RL; }
+
+// number of the part that chunk `chunk` and group g share: one more per chunk and per group, less the boundaries that fall on a
+// chunk edge (there the chunk and the group change together)
+__device__ __forceinline__ int part_index(const int* grp, int g, long long chunk) {
+  int on_edge = 0;
+  for (int j = 1; j <= g; ++j) on_edge += (grp[j] & 63) == 0;
+  return (int)chunk + g - on_edge;
+}
+
+// The forward keeps a kernel of its own for the whole map and for row groups: on one shared row loop the whole-map kernel measured
+// slower than as written here (profiles/rows_bn_act_ab_time.txt), and with the group's constants loaded the way the whole-map
+// kernel loads them the row-group kernel loses a wave per SIMD.
 __global__ __launch_bounds__(256) void rows_bn_act_fwd_kernel(const BnActP p) {
   const Lane t = lane_of(p.C);
   if (!t.on) return;
@@ -70,7 +98,7 @@ __global__ __launch_bounds__(256) void rows_bn_act_fwd_kernel(const BnActP p) {
     for (int e = 0; e < 4; ++e) {
       const bool in = m < p.M;
       mu[m][e] = in ? p.mean[m][t.c + e] : 0.f;
-      is[m][e] = in ? inv_std(p, m, t.c + e) : 0.f;
+      is[m][e] = in ? inv_std(p, m, t.c + e, p.eval) : 0.f;
       ga[m][e] = in ? p.gamma[m][t.c + e] : 0.f;
       be[m][e] = in ? p.beta[m][t.c + e] : 0.f;
     }
@@ -94,165 +122,8 @@ __global__ __launch_bounds__(256) void rows_bn_act_fwd_kernel(const BnActP p) {
   }
 }
 
-// PASS 1: dr = g' and the chunk's fp64 column sums of g' and g' xhat_m: a thread adds its rows in row order, the row lanes are added
-// in lane order through LDS.  PASS 2: dz_m.
-template <int PASS>
-__global__ __launch_bounds__(256) void rows_bn_act_bwd_kernel(const BnActP p) {
-  __shared__ double sh[PASS == 1 ? (1 + MAXT) * 1024 : 1];                  // [q][row lane][C]: row lanes * C <= 1024
-  const Lane t = lane_of(p.C);
-  const long long r0 = (long long)blockIdx.x * 64;
-  const int rows = (int)(p.n_rows - r0 < 64 ? p.n_rows - r0 : 64);
-  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[MAXT][4];
-#pragma unroll
-  for (int m = 0; m < MAXT; ++m)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s1[m][e] = 0.0;
-  if (t.on) {
-    float mu[MAXT][4], is[MAXT][4], gi[MAXT][4], cm[MAXT][4], c0[4];
-    const bool coef = PASS == 2 && !p.eval;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c0[e] = coef ? p.coef[t.c + e] : 0.f;
-#pragma unroll
-    for (int m = 0; m < MAXT; ++m)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool in = m < p.M;
-        mu[m][e] = in ? p.mean[m][t.c + e] : 0.f;
-        is[m][e] = in ? inv_std(p, m, t.c + e) : 0.f;
-        gi[m][e] = in ? p.gamma[m][t.c + e] * is[m][e] : 0.f;
-        cm[m][e] = (in && coef) ? p.coef[(1 + m) * p.C + t.c + e] : 0.f;
-      }
-#pragma unroll 2
-    for (int rr = t.rl; rr < rows; rr += t.RL) {
-      const long long row = r0 + rr;
-      f32x4 g = *reinterpret_cast<const f32x4*>(p.dy + row * p.ld_dy + t.c);
-      if (p.relu) {
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(p.y + row * p.ld_y + t.c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = yv[e] > 0.f ? g[e] : 0.f;
-      }
-      if constexpr (PASS == 1) {
-        if (p.dr) *reinterpret_cast<f32x4*>(p.dr + row * p.ld_dr + t.c) = g;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s0[e] += (double)g[e];
-      }
-#pragma unroll
-      for (int m = 0; m < MAXT; ++m) {
-        if (m >= p.M) continue;
-        if (PASS == 2 && !p.dz[m]) continue;
-        if (PASS == 2 && p.eval) {
-          f32x4 d;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] = g[e] * gi[m][e];
-          *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
-          continue;
-        }
-        const f32x4 zv = *reinterpret_cast<const f32x4*>(p.z[m] + row * p.ld_z[m] + t.c);
-        f32x4 d;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xh = (zv[e] - mu[m][e]) * is[m][e];
-          if constexpr (PASS == 1) s1[m][e] += (double)g[e] * (double)xh;
-          else d[e] = gi[m][e] * (g[e] - c0[e] - xh * cm[m][e]);
-        }
-        if constexpr (PASS == 2) *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
-      }
-    }
-  }
-  if constexpr (PASS == 1) {
-    if (t.on) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sh[t.rl * p.C + t.c + e] = s0[e];
-#pragma unroll
-        for (int m = 0; m < MAXT; ++m)
-          if (m < p.M) sh[((1 + m) * t.RL + t.rl) * p.C + t.c + e] = s1[m][e];
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < (1 + p.M) * p.C; i += 256) {
-      const int q = i / p.C, col = i - q * p.C;
-      double s = 0.0;
-      for (int k = 0; k < t.RL; ++k) s += sh[(q * t.RL + k) * p.C + col];
-      p.part[((long long)blockIdx.x * (1 + p.M) + q) * p.C + col] = s;
-    }
-  }
-}
-
-// The tiles' (mean, M2) of a convolution's statistics epilogue -> mean, invstd, running statistics: 16 columns x 64 segments of the
-// tile list per work-group; a thread merges its segment's tiles in tile order, the segments are merged pairwise in a fixed tree
-// (neighbours first, the lower tiles on the left).
-constexpr int SCOLS = 16, SSEG = 64;
-__global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_kernel(const float* __restrict__ part, int n_tiles, int n_rows, int C,
-                                                                       float eps, float momentum, float* __restrict__ mean,
-                                                                       float* __restrict__ invstd, float* __restrict__ rmean,
-                                                                       float* __restrict__ rvar) {
-  __shared__ double sh[3][SSEG][SCOLS];
-  const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
-  const int per = (n_tiles + SSEG - 1) / SSEG;
-  const int t0 = seg * per, t1 = min(n_tiles, t0 + per);
-  double n = 0.0, mu = 0.0, m2 = 0.0;
-  chan_walk(n, mu, m2, part, t0, t1, n_rows, C, col);
-  for (int stride = 1; stride < SSEG; stride <<= 1) {
-    sh[0][seg][lc] = n; sh[1][seg][lc] = mu; sh[2][seg][lc] = m2;
-    __syncthreads();
-    if (seg % (2 * stride) == 0) chan_merge(n, mu, m2, sh[0][seg + stride][lc], sh[1][seg + stride][lc], sh[2][seg + stride][lc]);
-    __syncthreads();
-  }
-  if (seg == 0) bn_finish(n, mu, m2, col, eps, momentum, mean, invstd, rmean, rvar);
-}
-
-struct BnSumsP {
-  const double* part; int n_chunks, M, C; long long n_rows;
-  float* dgamma[MAXT]; float* dbeta[MAXT];
-  float* coef;                                 // [1 + M][C], may be NULL
-};
-
-// sums of the chunks' partials in a fixed order: one quantity q (blockIdx.y: 0 = sum g', 1 + m = sum g' xhat_m) of 16 columns per
-// work-group; a thread adds its segment of the chunk list in chunk order, the 64 segments are added pairwise in a fixed tree
-__global__ __launch_bounds__(SCOLS * SSEG) void rows_bn_act_sums_kernel(const BnSumsP p) {
-  __shared__ double sh[SSEG][SCOLS];
-  const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
-  const int q = blockIdx.y, nq = 1 + p.M;
-  const int per = (p.n_chunks + SSEG - 1) / SSEG;
-  const int t0 = seg * per, t1 = min(p.n_chunks, t0 + per);
-  double s = 0.0;
-  for (int t = t0; t < t1; ++t) s += p.part[((long long)t * nq + q) * p.C + col];
-  for (int stride = 1; stride < SSEG; stride <<= 1) {
-    sh[seg][lc] = s;
-    __syncthreads();
-    if (seg % (2 * stride) == 0) s += sh[seg + stride][lc];
-    __syncthreads();
-  }
-  if (seg != 0) return;
-  if (p.coef) p.coef[q * p.C + col] = (float)(s / (double)p.n_rows);
-#pragma unroll
-  for (int m = 0; m < MAXT; ++m) {
-    if (m >= p.M) continue;
-    if (q == 0 && p.dbeta[m]) p.dbeta[m][col] = (float)s;
-    if (q == 1 + m && p.dgamma[m]) p.dgamma[m][col] = (float)s;
-  }
-}
-
-// ---- (20) BatchNorm over row groups ----------------------------------------------------------------------------------------
-struct BnActGP {
-  BnActP b;                                    // mean / scale: [G][C]; coef: [G][1 + M][C]; part: [part][1 + M][C]
-  const int* grp; int G;                       // [G + 1] row offsets of the groups
-  int n_parts;                                 // chunks + G - 1: the bound of the part index
-};
-
-// the rows [lo, hi) of the work-group's chunk (rows from r0) that belong to group g; false: none
-__device__ __forceinline__ bool group_span(const BnActGP& p, int g, long long r0, int rows, int& lo, int& hi) {
-  const long long a = (long long)p.grp[g], b = (long long)p.grp[g + 1];
-  lo = (int)(a > r0 ? (a < r0 + rows ? a - r0 : rows) : 0);
-  hi = (int)(b < r0 + rows ? (b > r0 ? b - r0 : 0) : rows);
-  return lo < hi;
-}
-// a row lane's first row at or after lo
-__device__ __forceinline__ int first_row(const Lane& t, int lo) { return t.rl >= lo ? t.rl : t.rl + (lo - t.rl + t.RL - 1) / t.RL * t.RL; }
-
-__global__ __launch_bounds__(256) void rows_bn_act_groups_fwd_kernel(const BnActGP q) {
-  const BnActP& p = q.b;
+// the same per group span of the chunk: gamma / beta once, a group's (mu, s) when the work-group enters it
+__global__ __launch_bounds__(256) void rows_bn_act_groups_fwd_kernel(const BnActP p) {
   const Lane t = lane_of(p.C);
   if (!t.on) return;
   const long long r0 = (long long)blockIdx.x * 64;
@@ -266,9 +137,9 @@ __global__ __launch_bounds__(256) void rows_bn_act_groups_fwd_kernel(const BnAct
       ga[m][e] = in ? p.gamma[m][t.c + e] : 0.f;
       be[m][e] = in ? p.beta[m][t.c + e] : 0.f;
     }
-  for (int g = 0; g < q.G; ++g) {
+  for (int g = 0; g < p.G; ++g) {
     int lo, hi;
-    if (!group_span(q, g, r0, rows, lo, hi)) continue;
+    if (!group_span(p, g, r0, rows, lo, hi)) continue;
 #pragma unroll
     for (int m = 0; m < MAXT; ++m)
 #pragma unroll
@@ -298,147 +169,153 @@ __global__ __launch_bounds__(256) void rows_bn_act_groups_fwd_kernel(const BnAct
   }
 }
 
-// number of the part that chunk `chunk` and group g share: one more per chunk and per group, less the boundaries that fall on a
-// chunk edge (there the chunk and the group change together)
-__device__ __forceinline__ int part_index(const int* grp, int g, long long chunk) {
-  int on_edge = 0;
-  for (int j = 1; j <= g; ++j) on_edge += (grp[j] & 63) == 0;
-  return (int)chunk + g - on_edge;
-}
-
-// PASS 1 / PASS 2 of rows_bn_act_bwd_kernel (training) per group span of the chunk
+// PASS 1: dr = g' and the span's fp64 column sums of g' and g' xhat_m, a thread's rows added in row order and left in LDS per row
+// lane (store_part adds them).  PASS 2: dz_m.  The span: this thread's rows first, first + RL, ... < hi of the chunk at r0, the
+// statistics at column offset so; the whole work-group calls.
 template <int PASS>
-__global__ __launch_bounds__(256) void rows_bn_act_groups_bwd_kernel(const BnActGP q) {
-  __shared__ double sh[PASS == 1 ? (1 + MAXT) * 1024 : 1];                  // [q][row lane][C]: row lanes * C <= 1024
-  const BnActP& p = q.b;
-  const Lane t = lane_of(p.C);
-  const long long r0 = (long long)blockIdx.x * 64;
-  const int rows = (int)(p.n_rows - r0 < 64 ? p.n_rows - r0 : 64);
-  for (int g = 0; g < q.G; ++g) {
-    int lo, hi;
-    if (!group_span(q, g, r0, rows, lo, hi)) continue;                      // uniform over the work-group
-    double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[MAXT][4];
+__device__ __forceinline__ void bwd_span(const BnActP& p, const Lane& t, long long r0, int first, int hi, int so, bool eval, double* sh) {
+  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[MAXT][4];
+#pragma unroll
+  for (int m = 0; m < MAXT; ++m)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s1[m][e] = 0.0;
+  if (t.on) {
+    float mu[MAXT][4], is[MAXT][4], gi[MAXT][4], cm[MAXT][4], c0[4];
+    const bool use_coef = PASS == 2 && !eval;
+    const float* coef = p.coef + (long long)so * (1 + p.M);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) c0[e] = use_coef ? coef[t.c + e] : 0.f;
 #pragma unroll
     for (int m = 0; m < MAXT; ++m)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s1[m][e] = 0.0;
-    if (t.on) {
-      float mu[MAXT][4], is[MAXT][4], gi[MAXT][4], cm[MAXT][4], c0[4];
-      const float* coef = p.coef + (long long)g * (1 + p.M) * p.C;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) c0[e] = PASS == 2 ? coef[t.c + e] : 0.f;
-#pragma unroll
-      for (int m = 0; m < MAXT; ++m)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool in = m < p.M;
-          mu[m][e] = in ? p.mean[m][g * p.C + t.c + e] : 0.f;
-          is[m][e] = in ? p.scale[m][g * p.C + t.c + e] : 0.f;
-          gi[m][e] = in ? p.gamma[m][t.c + e] * is[m][e] : 0.f;
-          cm[m][e] = (in && PASS == 2) ? coef[(1 + m) * p.C + t.c + e] : 0.f;
-        }
+      for (int e = 0; e < 4; ++e) {
+        const bool in = m < p.M;
+        mu[m][e] = in ? p.mean[m][so + t.c + e] : 0.f;
+        is[m][e] = in ? inv_std(p, m, so + t.c + e, eval) : 0.f;
+        gi[m][e] = in ? p.gamma[m][t.c + e] * is[m][e] : 0.f;
+        cm[m][e] = (in && use_coef) ? coef[(1 + m) * p.C + t.c + e] : 0.f;
+      }
 #pragma unroll 2
-      for (int rr = first_row(t, lo); rr < hi; rr += t.RL) {
-        const long long row = r0 + rr;
-        f32x4 g4 = *reinterpret_cast<const f32x4*>(p.dy + row * p.ld_dy + t.c);
-        if (p.relu) {
-          const f32x4 yv = *reinterpret_cast<const f32x4*>(p.y + row * p.ld_y + t.c);
+    for (int rr = first; rr < hi; rr += t.RL) {
+      const long long row = r0 + rr;
+      f32x4 g = *reinterpret_cast<const f32x4*>(p.dy + row * p.ld_dy + t.c);
+      if (p.relu) {
+        const f32x4 yv = *reinterpret_cast<const f32x4*>(p.y + row * p.ld_y + t.c);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) g4[e] = yv[e] > 0.f ? g4[e] : 0.f;
-        }
-        if constexpr (PASS == 1) {
-          if (p.dr) *reinterpret_cast<f32x4*>(p.dr + row * p.ld_dr + t.c) = g4;
+        for (int e = 0; e < 4; ++e) g[e] = yv[e] > 0.f ? g[e] : 0.f;
+      }
+      if constexpr (PASS == 1) {
+        if (p.dr) *reinterpret_cast<f32x4*>(p.dr + row * p.ld_dr + t.c) = g;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) s0[e] += (double)g4[e];
-        }
+        for (int e = 0; e < 4; ++e) s0[e] += (double)g[e];
+      }
 #pragma unroll
-        for (int m = 0; m < MAXT; ++m) {
-          if (m >= p.M) continue;
-          if (PASS == 2 && !p.dz[m]) continue;
-          const f32x4 zv = *reinterpret_cast<const f32x4*>(p.z[m] + row * p.ld_z[m] + t.c);
+      for (int m = 0; m < MAXT; ++m) {
+        if (m >= p.M) continue;
+        if (PASS == 2 && !p.dz[m]) continue;
+        if (PASS == 2 && eval) {
           f32x4 d;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float xh = (zv[e] - mu[m][e]) * is[m][e];
-            if constexpr (PASS == 1) s1[m][e] += (double)g4[e] * (double)xh;
-            else d[e] = gi[m][e] * (g4[e] - c0[e] - xh * cm[m][e]);
-          }
-          if constexpr (PASS == 2) *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
+          for (int e = 0; e < 4; ++e) d[e] = g[e] * gi[m][e];
+          *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
+          continue;
         }
-      }
-    }
-    if constexpr (PASS == 1) {
-      if (t.on) {
+        const f32x4 zv = *reinterpret_cast<const f32x4*>(p.z[m] + row * p.ld_z[m] + t.c);
+        f32x4 d;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          sh[t.rl * p.C + t.c + e] = s0[e];
-#pragma unroll
-          for (int m = 0; m < MAXT; ++m)
-            if (m < p.M) sh[((1 + m) * t.RL + t.rl) * p.C + t.c + e] = s1[m][e];
+          const float xh = (zv[e] - mu[m][e]) * is[m][e];
+          if constexpr (PASS == 1) s1[m][e] += (double)g[e] * (double)xh;
+          else d[e] = gi[m][e] * (g[e] - c0[e] - xh * cm[m][e]);
         }
+        if constexpr (PASS == 2) *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
       }
-      __syncthreads();
-      const int pi = part_index(q.grp, g, blockIdx.x);
-      if (pi >= 0 && pi < q.n_parts) {
-        for (int i = threadIdx.x; i < (1 + p.M) * p.C; i += 256) {
-          const int qq = i / p.C, col = i - qq * p.C;
-          double s = 0.0;
-          for (int k = 0; k < t.RL; ++k) s += sh[(qq * t.RL + k) * p.C + col];
-          p.part[((long long)pi * (1 + p.M) + qq) * p.C + col] = s;
-        }
-      }
-      __syncthreads();                                                      // sh is the next group's
     }
+  }
+  if constexpr (PASS == 1) {
+    if (t.on) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sh[t.rl * p.C + t.c + e] = s0[e];
+#pragma unroll
+        for (int m = 0; m < MAXT; ++m)
+          if (m < p.M) sh[((1 + m) * t.RL + t.rl) * p.C + t.c + e] = s1[m][e];
+      }
+    }
+    __syncthreads();
   }
 }
 
-struct BnSumsGP {
-  BnSumsP s;                                   // coef: [G][1 + M][C]; n_chunks: the bound of the part index
-  const int* grp; int G;
-};
-
-// rows_bn_act_sums per group: the parts of group g are consecutive; their sum in rows_bn_act_sums' order gives the group's
-// means (coef), and the groups' sums are added in ascending order for dgamma / dbeta
-__global__ __launch_bounds__(SCOLS * SSEG) void rows_bn_act_groups_sums_kernel(const BnSumsGP gp) {
-  __shared__ double sh[SSEG][SCOLS];
-  const BnSumsP& p = gp.s;
-  const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
-  const int q = blockIdx.y, nq = 1 + p.M;
-  double tot = 0.0;
-  for (int g = 0; g < gp.G; ++g) {
-    const long long a = (long long)gp.grp[g], b = (long long)gp.grp[g + 1];
-    if (a < 0 || b <= a || b > p.n_rows) continue;                          // uniform
-    int p0 = part_index(gp.grp, g, a >> 6), p1 = part_index(gp.grp, g, (b - 1) >> 6) + 1;
-    p0 = max(p0, 0); p1 = min(p1, p.n_chunks);
-    const int n = max(p1 - p0, 0), per = (n + SSEG - 1) / SSEG;
-    const int t0 = p0 + seg * per, t1 = min(p1, t0 + per);
+// the row lanes' sums of bwd_span<1>, added in lane order, as part `part_i`
+__device__ __forceinline__ void store_part(const BnActP& p, const Lane& t, long long part_i, const double* sh) {
+  for (int i = threadIdx.x; i < (1 + p.M) * p.C; i += 256) {
+    const int q = i / p.C, col = i - q * p.C;
     double s = 0.0;
-    for (int t = t0; t < t1; ++t) s += p.part[((long long)t * nq + q) * p.C + col];
-    for (int stride = 1; stride < SSEG; stride <<= 1) {
-      sh[seg][lc] = s;
-      __syncthreads();
-      if (seg % (2 * stride) == 0) s += sh[seg + stride][lc];
-      __syncthreads();
-    }
-    if (seg == 0) {
-      if (p.coef) p.coef[((long long)g * nq + q) * p.C + col] = (float)(s / (double)(b - a));
-      tot += s;
-    }
-  }
-  if (seg != 0) return;
-#pragma unroll
-  for (int m = 0; m < MAXT; ++m) {
-    if (m >= p.M) continue;
-    if (q == 0 && p.dbeta[m]) p.dbeta[m][col] = (float)tot;
-    if (q == 1 + m && p.dgamma[m]) p.dgamma[m][col] = (float)tot;
+    for (int k = 0; k < t.RL; ++k) s += sh[(q * t.RL + k) * p.C + col];
+    p.part[(part_i * (1 + p.M) + q) * p.C + col] = s;
   }
 }
 
-// bn_stats_merge per group, the groups one after the other (the running statistics take G updates in group order).  A group's
-// whole 32-row tiles come from the epilogue's partials, merged as bn_stats_merge does; a tile that a group boundary cuts gives the
-// group its rows on this side of the boundary, re-read from z: (mean, M2) of the <= 31 rows in fp64, one row per segment through
-// LDS — the head piece before the first whole tile, the tail piece after the last.  The last group owns the map's short last tile
-// as a whole tile when it begins on or before that tile's first row.
+template <int PASS, bool GROUPED>
+__global__ __launch_bounds__(256) void rows_bn_act_bwd_kernel(const BnActP p) {
+  __shared__ double sh[PASS == 1 ? (1 + MAXT) * 1024 : 1];                  // [q][row lane][C]: row lanes * C <= 1024
+  const Lane t = lane_of(p.C);
+  const long long r0 = (long long)blockIdx.x * 64;
+  const int rows = (int)(p.n_rows - r0 < 64 ? p.n_rows - r0 : 64);
+  if constexpr (!GROUPED) {
+    bwd_span<PASS>(p, t, r0, t.rl, rows, 0, p.eval, sh);
+    if constexpr (PASS == 1) store_part(p, t, blockIdx.x, sh);
+  } else {
+    for (int g = 0; g < p.G; ++g) {
+      int lo, hi;
+      if (!group_span(p, g, r0, rows, lo, hi)) continue;                    // uniform over the work-group
+      bwd_span<PASS>(p, t, r0, first_row(t, lo), hi, g * p.C, false, sh);
+      if constexpr (PASS == 1) {
+        // the part index AFTER the row loop: formed before it, the offsets' scalar loads hold back the first row loads
+        const int pi = part_index(p.grp, g, blockIdx.x);
+        if (pi >= 0 && pi < p.n_parts) store_part(p, t, pi, sh);
+        __syncthreads();                                                    // sh is the next group's
+      }
+    }
+  }
+}
+
+constexpr int SCOLS = 16, SSEG = 64;
+
+// (n, mean, M2) of the tiles [ta, tb) of a convolution's statistics epilogue, for 16 columns x 64 segments of that tile list per
+// work-group: a thread merges its segment's tiles in tile order, the segments are merged pairwise in a fixed tree (neighbours
+// first, the lower tiles on the left).  The result is segment 0's.
+__device__ __forceinline__ void merge_tiles(double& n, double& mu, double& m2, const float* __restrict__ part, int ta, int tb, int n_rows,
+                                            int C, int col, int seg, int lc, double (*sh)[SSEG][SCOLS]) {
+  const int per = (tb - ta + SSEG - 1) / SSEG;
+  const int t0 = ta + seg * per, t1 = min(tb, t0 + per);
+  chan_walk(n, mu, m2, part, t0, t1, n_rows, C, col);
+  for (int stride = 1; stride < SSEG; stride <<= 1) {
+    sh[0][seg][lc] = n; sh[1][seg][lc] = mu; sh[2][seg][lc] = m2;
+    __syncthreads();
+    if (seg % (2 * stride) == 0) chan_merge(n, mu, m2, sh[0][seg + stride][lc], sh[1][seg + stride][lc], sh[2][seg + stride][lc]);
+    __syncthreads();
+  }
+}
+
+// The tiles' (mean, M2) -> mean, invstd, running statistics of the whole map.  (Two kernels on the one merge_tiles: the whole-map
+// kernel keeps the arguments it had; as an instance that also takes z and the offsets it measured 0.4 % slower.)
+__global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_kernel(const float* __restrict__ part, int n_tiles, int n_rows, int C,
+                                                                       float eps, float momentum, float* __restrict__ mean,
+                                                                       float* __restrict__ invstd, float* __restrict__ rmean,
+                                                                       float* __restrict__ rvar) {
+  __shared__ double sh[3][SSEG][SCOLS];
+  const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
+  double n = 0.0, mu = 0.0, m2 = 0.0;
+  merge_tiles(n, mu, m2, part, 0, n_tiles, n_rows, C, col, seg, lc, sh);
+  if (seg == 0) bn_finish(n, mu, m2, col, eps, momentum, mean, invstd, rmean, rvar);
+}
+
+// The same per group, the groups one after the other (the running statistics take G updates in group order).  A group's whole
+// 32-row tiles come from the epilogue's partials; a tile that a group boundary cuts gives the group its rows on this side of the
+// boundary, re-read from z: (mean, M2) of the <= 31 rows in fp64, one row per segment through LDS — the head piece before the
+// first whole tile, the tail piece after the last.  The last group owns the map's short last tile as a whole tile when it begins
+// on or before that tile's first row.
 __global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_groups_kernel(const float* __restrict__ part, int n_tiles, int n_rows, int C,
                                                                               float eps, float momentum, const float* __restrict__ z,
                                                                               int ld_z, const int* __restrict__ grp, int G,
@@ -449,27 +326,19 @@ __global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_groups_kernel(con
   const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
   for (int g = 0; g < G; ++g) {
     const int r0 = grp[g], r1 = grp[g + 1];
-    if (r0 < 0 || r1 <= r0 || r1 > n_rows) continue;                        // uniform
+    if (r0 < 0 || r1 <= r0 || r1 > n_rows) continue;                      // uniform
     const int ta = (r0 + 31) >> 5;
     int tb = r1 == n_rows ? n_tiles : r1 >> 5;
     if (tb < ta) tb = ta;
-    const int head0 = r0, head1 = (r0 & 31) ? min(r1, ta * 32) : r0;         // [head0, head1): before the first whole tile
+    const int head0 = r0, head1 = (r0 & 31) ? min(r1, ta * 32) : r0;       // [head0, head1): before the first whole tile
     const int tail0 = (r1 != n_rows && (r1 & 31) && (r1 >> 5) >= ta) ? (r1 >> 5) * 32 : r1, tail1 = r1;
     {
       const int row = seg < 32 ? head0 + seg : tail0 + (seg - 32);
       const bool in = seg < 32 ? row < head1 : row < tail1;
       zs[seg][lc] = in ? z[(long long)row * ld_z + col] : 0.f;
     }
-    const int per = (tb - ta + SSEG - 1) / SSEG;
-    const int t0 = ta + seg * per, t1 = min(tb, t0 + per);
     double n = 0.0, mu = 0.0, m2 = 0.0;
-    chan_walk(n, mu, m2, part, t0, t1, n_rows, C, col);
-    for (int stride = 1; stride < SSEG; stride <<= 1) {
-      sh[0][seg][lc] = n; sh[1][seg][lc] = mu; sh[2][seg][lc] = m2;
-      __syncthreads();
-      if (seg % (2 * stride) == 0) chan_merge(n, mu, m2, sh[0][seg + stride][lc], sh[1][seg + stride][lc], sh[2][seg + stride][lc]);
-      __syncthreads();
-    }
+    merge_tiles(n, mu, m2, part, ta, tb, n_rows, C, col, seg, lc, sh);
     if (seg == 0) {
       for (int piece = 0; piece < 2; ++piece) {
         const int cnt = piece ? tail1 - tail0 : head1 - head0, base = piece * 32;
@@ -482,84 +351,68 @@ __global__ __launch_bounds__(SCOLS * SSEG) void bn_stats_merge_groups_kernel(con
       }
       bn_finish(n, mu, m2, col, eps, momentum, mean + g * C, invstd + g * C, rmean, rvar);
     }
-    __syncthreads();                                                        // segment 0 has read zs: the next group may write it
+    __syncthreads();                                                      // segment 0 has read zs: the next group may write it
+  }
+}
+
+struct BnSumsP {
+  const double* part; int n_parts, M, C; long long n_rows;
+  float* dgamma[MAXT]; float* dbeta[MAXT];
+  float* coef;                                 // [G][1 + M][C], may be NULL
+  const int* grp; int G;                       // GROUPED only
+};
+
+// sum of the parts [p0, p1) of quantity q (0 = sum g', 1 + m = sum g' xhat_m) for 16 columns: a thread adds its segment of that
+// part list in part order, the 64 segments are added pairwise in a fixed tree.  Segment 0 has the sum: it writes its mean over
+// the `count` rows as the coefficients of group g and adds it to tot (a sum that begins at +0.0 is never -0.0: 0.0 + s is s).
+__device__ __forceinline__ void sums_span(const BnSumsP& p, int p0, int p1, long long count, int g, int q, int nq, int col, int seg,
+                                          int lc, double (*sh)[SCOLS], double& tot) {
+  const int per = (max(p1 - p0, 0) + SSEG - 1) / SSEG;
+  const int t0 = p0 + seg * per, t1 = min(p1, t0 + per);
+  double s = 0.0;
+  for (int t = t0; t < t1; ++t) s += p.part[((long long)t * nq + q) * p.C + col];
+  for (int stride = 1; stride < SSEG; stride <<= 1) {
+    sh[seg][lc] = s;
+    __syncthreads();
+    if (seg % (2 * stride) == 0) s += sh[seg + stride][lc];
+    __syncthreads();
+  }
+  // the total is added inside this branch and nq comes from the kernel: otherwise the kernel reads M again at its end
+  if (seg == 0) {
+    if (p.coef) p.coef[((long long)g * nq + q) * p.C + col] = (float)(s / (double)count);
+    tot += s;
+  }
+}
+
+// one quantity q (blockIdx.y) of 16 columns per work-group.  GROUPED: the parts of group g are consecutive; their sum gives the
+// group's means (coef), and the groups' sums are added in ascending order for dgamma / dbeta
+template <bool GROUPED>
+__global__ __launch_bounds__(SCOLS * SSEG) void rows_bn_act_sums_kernel(const BnSumsP p) {
+  __shared__ double sh[SSEG][SCOLS];
+  const int lc = threadIdx.x % SCOLS, seg = threadIdx.x / SCOLS, col = blockIdx.x * SCOLS + lc;
+  const int q = blockIdx.y, nq = 1 + p.M;
+  double tot = 0.0;
+  if constexpr (!GROUPED) {
+    sums_span(p, 0, p.n_parts, p.n_rows, 0, q, nq, col, seg, lc, sh, tot);
+  } else {
+    for (int g = 0; g < p.G; ++g) {
+      const long long a = (long long)p.grp[g], b = (long long)p.grp[g + 1];
+      if (a < 0 || b <= a || b > p.n_rows) continue;                        // uniform
+      const int p0 = max(part_index(p.grp, g, a >> 6), 0), p1 = min(part_index(p.grp, g, (b - 1) >> 6) + 1, p.n_parts);
+      sums_span(p, p0, p1, b - a, g, q, nq, col, seg, lc, sh, tot);
+    }
+  }
+  if (seg != 0) return;
+#pragma unroll
+  for (int m = 0; m < MAXT; ++m) {
+    if (1 + m >= nq) continue;
+    if (q == 0 && p.dbeta[m]) p.dbeta[m][col] = (float)tot;
+    if (q == 1 + m && p.dgamma[m]) p.dgamma[m][col] = (float)tot;
   }
 }
 
 struct WsLayout { long long part, coef, total; };
-WsLayout ws_layout(long long n_rows, int C, int M) {
-  WsLayout L{};
-  long long o = 0;
-  L.part = o; o += up256(((n_rows + 63) / 64) * (1 + M) * C * (long long)sizeof(double));
-  L.coef = o; o += up256((long long)(1 + M) * C * (long long)sizeof(float));
-  L.total = o;
-  return L;
-}
-
-BnActP make_p(const CsnRowsBnActArgs& a) {
-  BnActP p{};
-  for (int m = 0; m < a.n_terms; ++m) {
-    p.z[m] = a.z[m]; p.ld_z[m] = a.ld_z[m]; p.mean[m] = a.mean[m]; p.scale[m] = a.scale[m]; p.gamma[m] = a.gamma[m];
-    p.beta[m] = a.beta[m]; p.dz[m] = a.dz[m]; p.ld_dz[m] = a.ld_dz[m];
-  }
-  p.M = a.n_terms; p.n_rows = a.n_rows; p.C = a.C; p.eval = !a.training; p.relu = a.relu; p.eps = a.eps;
-  p.r = a.r; p.ld_r = a.ld_r; p.y = a.y; p.ld_y = a.ld_y; p.dy = a.dy; p.ld_dy = a.ld_dy; p.dr = a.dr; p.ld_dr = a.ld_dr;
-  return p;
-}
-
-}  // namespace
-
-long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms) { return ws_layout(n_rows, C, n_terms).total; }
-
-int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, float* mean, float* invstd,
-                              float* running_mean, float* running_var, hipStream_t st) {
-  hipLaunchKernelGGL(bn_stats_merge_kernel, dim3(C / SCOLS), dim3(SCOLS * SSEG), 0, st, part, n_tiles, n_rows, C, eps, momentum, mean,
-                     invstd, running_mean, running_var);
-  return (int)hipGetLastError();
-}
-
-int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, hipStream_t st) {
-  const BnActP p = make_p(a);
-  const unsigned n_chunks = (unsigned)(((long long)a.n_rows + 63) / 64);
-  hipLaunchKernelGGL(rows_bn_act_fwd_kernel, dim3(n_chunks), dim3(256), 0, st, p);
-  return (int)hipGetLastError();
-}
-
-int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, hipStream_t st) {
-  const WsLayout L = ws_layout(a.n_rows, a.C, a.n_terms);
-  char* ws = static_cast<char*>(a.ws);
-  BnActP p = make_p(a);
-  p.part = reinterpret_cast<double*>(ws + L.part);
-  float* coef = reinterpret_cast<float*>(ws + L.coef);
-  p.coef = coef;
-  const int n_chunks = (int)(((long long)a.n_rows + 63) / 64);
-  bool any_dz = false, any_sum = false;
-  for (int m = 0; m < a.n_terms; ++m) {
-    any_dz |= a.dz[m] != nullptr;
-    any_sum |= a.dgamma[m] != nullptr || a.dbeta[m] != nullptr;
-  }
-  const bool need_coef = any_dz && a.training;
-  if (a.dr || any_sum || need_coef) {
-    hipLaunchKernelGGL(rows_bn_act_bwd_kernel<1>, dim3(n_chunks), dim3(256), 0, st, p);
-    if (const int e = (int)hipGetLastError()) return e;
-  }
-  if (any_sum || need_coef) {
-    BnSumsP s{};
-    s.part = p.part; s.n_chunks = n_chunks; s.M = a.n_terms; s.C = a.C; s.n_rows = a.n_rows; s.coef = need_coef ? coef : nullptr;
-    for (int m = 0; m < a.n_terms; ++m) { s.dgamma[m] = a.dgamma[m]; s.dbeta[m] = a.dbeta[m]; }
-    hipLaunchKernelGGL(rows_bn_act_sums_kernel, dim3(a.C / SCOLS, 1 + a.n_terms), dim3(SCOLS * SSEG), 0, st, s);
-    if (const int e = (int)hipGetLastError()) return e;
-  }
-  if (any_dz) {
-    hipLaunchKernelGGL(rows_bn_act_bwd_kernel<2>, dim3(n_chunks), dim3(256), 0, st, p);
-    if (const int e = (int)hipGetLastError()) return e;
-  }
-  return 0;
-}
-
-// ---- (20) BatchNorm over row groups ----
-namespace {
-WsLayout ws_layout_groups(long long n_rows, int C, int M, int G) {
+WsLayout ws_layout(long long n_rows, int C, int M, int G) {
   WsLayout L{};
   long long o = 0;
   L.part = o; o += up256(((n_rows + 63) / 64 + G - 1) * (1 + M) * C * (long long)sizeof(double));
@@ -567,57 +420,75 @@ WsLayout ws_layout_groups(long long n_rows, int C, int M, int G) {
   L.total = o;
   return L;
 }
+
+BnActP make_p(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups) {
+  BnActP p{};
+  for (int m = 0; m < a.n_terms; ++m) {
+    p.z[m] = a.z[m]; p.ld_z[m] = a.ld_z[m]; p.mean[m] = a.mean[m]; p.scale[m] = a.scale[m]; p.gamma[m] = a.gamma[m];
+    p.beta[m] = a.beta[m]; p.dz[m] = a.dz[m]; p.ld_dz[m] = a.ld_dz[m];
+  }
+  p.M = a.n_terms; p.n_rows = a.n_rows; p.C = a.C; p.eval = !a.training && !group_rows; p.relu = a.relu; p.eps = a.eps;
+  p.r = a.r; p.ld_r = a.ld_r; p.y = a.y; p.ld_y = a.ld_y; p.dy = a.dy; p.ld_dy = a.ld_dy; p.dr = a.dr; p.ld_dr = a.ld_dr;
+  p.grp = group_rows; p.G = group_rows ? n_groups : 1;
+  return p;
+}
+
 }  // namespace
 
-long long csn_rows_bn_act_groups_ws_bytes(long long n_rows, int C, int n_terms, int n_groups) {
-  return ws_layout_groups(n_rows, C, n_terms, n_groups).total;
+long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms, int n_groups) {
+  return ws_layout(n_rows, C, n_terms, n_groups).total;
 }
 
-int csn_launch_bn_stats_merge_groups(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, const float* z, int ld_z,
-                                     const int* group_rows, int n_groups, float* mean, float* invstd, float* running_mean,
-                                     float* running_var, hipStream_t st) {
-  hipLaunchKernelGGL(bn_stats_merge_groups_kernel, dim3(C / SCOLS), dim3(SCOLS * SSEG), 0, st, part, n_tiles, n_rows, C, eps, momentum, z,
-                     ld_z, group_rows, n_groups, mean, invstd, running_mean, running_var);
+int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C, float eps, float momentum, const float* z, int ld_z,
+                              const int* group_rows, int n_groups, float* mean, float* invstd, float* running_mean, float* running_var,
+                              hipStream_t st) {
+  if (group_rows)
+    hipLaunchKernelGGL(bn_stats_merge_groups_kernel, dim3(C / SCOLS), dim3(SCOLS * SSEG), 0, st, part, n_tiles, n_rows, C, eps, momentum, z,
+                       ld_z, group_rows, n_groups, mean, invstd, running_mean, running_var);
+  else
+    hipLaunchKernelGGL(bn_stats_merge_kernel, dim3(C / SCOLS), dim3(SCOLS * SSEG), 0, st, part, n_tiles, n_rows, C, eps, momentum, mean,
+                       invstd, running_mean, running_var);
   return (int)hipGetLastError();
 }
 
-int csn_launch_rows_bn_act_groups_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st) {
-  BnActGP q{};
-  q.b = make_p(a); q.grp = group_rows; q.G = n_groups;
+int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st) {
+  const BnActP p = make_p(a, group_rows, n_groups);
   const unsigned n_chunks = (unsigned)(((long long)a.n_rows + 63) / 64);
-  hipLaunchKernelGGL(rows_bn_act_groups_fwd_kernel, dim3(n_chunks), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(group_rows ? rows_bn_act_groups_fwd_kernel : rows_bn_act_fwd_kernel, dim3(n_chunks), dim3(256), 0, st, p);
   return (int)hipGetLastError();
 }
 
-int csn_launch_rows_bn_act_groups_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st) {
-  const WsLayout L = ws_layout_groups(a.n_rows, a.C, a.n_terms, n_groups);
+int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st) {
+  BnActP p = make_p(a, group_rows, n_groups);
+  const bool grouped = group_rows != nullptr;
+  const WsLayout L = ws_layout(a.n_rows, a.C, a.n_terms, p.G);
   char* ws = static_cast<char*>(a.ws);
-  BnActGP q{};
-  q.b = make_p(a); q.grp = group_rows; q.G = n_groups;
-  q.b.part = reinterpret_cast<double*>(ws + L.part);
+  p.part = reinterpret_cast<double*>(ws + L.part);
   float* coef = reinterpret_cast<float*>(ws + L.coef);
-  q.b.coef = coef;
+  p.coef = coef;
   const int n_chunks = (int)(((long long)a.n_rows + 63) / 64);
-  q.n_parts = n_chunks + n_groups - 1;
+  p.n_parts = n_chunks + p.G - 1;
   bool any_dz = false, any_sum = false;
   for (int m = 0; m < a.n_terms; ++m) {
     any_dz |= a.dz[m] != nullptr;
     any_sum |= a.dgamma[m] != nullptr || a.dbeta[m] != nullptr;
   }
-  if (a.dr || any_sum || any_dz) {
-    hipLaunchKernelGGL(rows_bn_act_groups_bwd_kernel<1>, dim3(n_chunks), dim3(256), 0, st, q);
+  const bool need_coef = any_dz && (a.training || grouped);                  // the grouped passes are training passes
+  if (a.dr || any_sum || need_coef) {
+    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<1, true> : rows_bn_act_bwd_kernel<1, false>), dim3(n_chunks), dim3(256), 0, st, p);
     if (const int e = (int)hipGetLastError()) return e;
   }
-  if (any_sum || any_dz) {
-    BnSumsGP s{};
-    s.s.part = q.b.part; s.s.n_chunks = q.n_parts; s.s.M = a.n_terms; s.s.C = a.C; s.s.n_rows = a.n_rows; s.s.coef = any_dz ? coef : nullptr;
-    for (int m = 0; m < a.n_terms; ++m) { s.s.dgamma[m] = a.dgamma[m]; s.s.dbeta[m] = a.dbeta[m]; }
-    s.grp = group_rows; s.G = n_groups;
-    hipLaunchKernelGGL(rows_bn_act_groups_sums_kernel, dim3(a.C / SCOLS, 1 + a.n_terms), dim3(SCOLS * SSEG), 0, st, s);
+  if (any_sum || need_coef) {
+    BnSumsP s{};
+    s.part = p.part; s.n_parts = p.n_parts; s.M = a.n_terms; s.C = a.C; s.n_rows = a.n_rows; s.coef = need_coef ? coef : nullptr;
+    for (int m = 0; m < a.n_terms; ++m) { s.dgamma[m] = a.dgamma[m]; s.dbeta[m] = a.dbeta[m]; }
+    s.grp = group_rows; s.G = p.G;
+    hipLaunchKernelGGL(grouped ? rows_bn_act_sums_kernel<true> : rows_bn_act_sums_kernel<false>, dim3(a.C / SCOLS, 1 + a.n_terms),
+                       dim3(SCOLS * SSEG), 0, st, s);
     if (const int e = (int)hipGetLastError()) return e;
   }
   if (any_dz) {
-    hipLaunchKernelGGL(rows_bn_act_groups_bwd_kernel<2>, dim3(n_chunks), dim3(256), 0, st, q);
+    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<2, true> : rows_bn_act_bwd_kernel<2, false>), dim3(n_chunks), dim3(256), 0, st, p);
     if (const int e = (int)hipGetLastError()) return e;
   }
   return 0;

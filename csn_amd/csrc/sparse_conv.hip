@@ -280,30 +280,18 @@ long long csn_sparse_conv_stats_ws_bytes(long long n_out, int c_out) {
   return up256(((n_out + 127) / 128) * 4 * 2 * c_out * (long long)sizeof(float));
 }
 
-// the forward product with the statistics epilogue, then the tiles' (mean, M2) merged in fp64 in a fixed order (rows_bn_act.hip)
-int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
-                                     float eps, float momentum, int mode, hipStream_t st) {
+// the forward product with the statistics epilogue, then the tiles' (mean, M2) merged in fp64 in a fixed order (rows_bn_act.hip).
+// (20a) group_rows: the map's rows are n_groups BatchNorm batches — the same product and epilogue, the tiles merged per group
+int csn_launch_sparse_conv_stats_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
+                                     float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st) {
   SconvGemmP p{};
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = nullptr;
   p.part = static_cast<float*>(a.ws);
   if (const int e = launch_gemm<true>(p, mode, st)) return e;
   const int n_tiles = (int)(((long long)a.n_out + 127) / 128) * 4;
-  return csn_launch_bn_stats_merge(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, mean, invstd, running_mean, running_var, st);
-}
-
-// (20a) the same product and epilogue on a map whose rows are n_groups BatchNorm batches: the kernel above unchanged, then the
-// tiles merged per group (rows_bn_act.hip: the tiles a group boundary cuts are re-read from z)
-int csn_launch_sparse_conv_stats_groups_fwd(const CsnSparseConvArgs& a, const int* group_rows, int n_groups, float* mean, float* invstd,
-                                            float* running_mean, float* running_var, float eps, float momentum, int mode, hipStream_t st) {
-  SconvGemmP p{};
-  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
-  p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = nullptr;
-  p.part = static_cast<float*>(a.ws);
-  if (const int e = launch_gemm<true>(p, mode, st)) return e;
-  const int n_tiles = (int)(((long long)a.n_out + 127) / 128) * 4;
-  return csn_launch_bn_stats_merge_groups(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, a.y, a.ld_y, group_rows, n_groups, mean,
-                                          invstd, running_mean, running_var, st);
+  return csn_launch_bn_stats_merge(p.part, n_tiles, a.n_out, a.c_out, eps, momentum, a.y, a.ld_y, group_rows, n_groups, mean, invstd,
+                                   running_mean, running_var, st);
 }
 
 int csn_launch_sparse_conv_bwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {

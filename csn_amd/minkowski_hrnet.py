@@ -217,20 +217,28 @@ def group_pyramid(coords: torch.Tensor, n_shapes: Sequence[int], n_levels: int, 
     G1 = len(n_shapes) + 1
     rows_host = [host[l * G1:(l + 1) * G1] for l in range(n_levels)]
     row_offsets = host[n_levels * G1:]
-    for l, off in enumerate(rows_host):
-        n_l = pyr.coords[l].shape[0]
-        if off[0] != 0 or off[-1] != n_l or any(b < a for a, b in zip(off, off[1:])):
-            raise ValueError(f"level {l}: the group row offsets {off} do not start at 0, ascend and end at the {n_l} rows: the batch "
-                             "indices are not sorted, or leave the groups' shapes")
-        if any(b == a for a, b in zip(off, off[1:])):
-            raise ValueError(f"level {l}: a group has no rows")
-        if any(b - a == 1 for a, b in zip(off, off[1:])):
-            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance): "
-                             f"a group has exactly one row at level {l}")
+    group_rows = _level_rows(pyr, rows_host, True)
     if any(b <= a for a, b in zip(row_offsets, row_offsets[1:])):
         raise ValueError("every shape of the batch needs at least one row")
-    group_rows = [torch.tensor(off, dtype=torch.int32).to(dev) for off in rows_host]
     return GroupedPyramid(pyr, group_rows, rows_host, n_shapes, row_offsets)
+
+
+def _level_rows(pyr: VoxelPyramid, rows_host: List[List[int]], given: bool) -> List[torch.Tensor]:
+    """Checks every level's group row offsets as the host read them (they start at 0, ascend, end at the level's row count; no group
+    has one row or none) and returns them as int32 tensors on the pyramid's device.  ``given``: the caller stated the groups' shape
+    counts, so offsets out of order mean batch indices that do not fit them, and an empty group is told apart."""
+    for l, off in enumerate(rows_host):
+        n_l, steps = pyr.coords[l].shape[0], list(zip(off, off[1:]))
+        if off[0] != 0 or off[-1] != n_l or any(b < a or (b == a and not given) for a, b in steps):
+            raise ValueError(f"level {l}: the group row offsets {off} do not start at 0, ascend and end at the {n_l} rows"
+                             + (": the batch indices are not sorted, or leave the groups' shapes" if given else ""))
+        if any(b == a for a, b in steps):
+            raise ValueError(f"level {l}: a group has no rows")
+        if any(b - a == 1 for a, b in steps):
+            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance): "
+                             f"a group has exactly one row at level {l}")
+    dev = pyr.coords[0].device
+    return [torch.tensor(off, dtype=torch.int32).to(dev) for off in rows_host]
 
 
 def merge_batches(batches: Sequence, n_levels: int, stem_kernel: int = 5, n_shapes: Optional[Sequence[int]] = None,
@@ -271,26 +279,30 @@ def merge_batches(batches: Sequence, n_levels: int, stem_kernel: int = 5, n_shap
         raise ValueError("batch-index column is not non-decreasing: the rows are not sorted by shape")
     G = len(cs)
     n_shapes, rows_host = host[:G], [host[G + l * (G + 1):G + (l + 1) * (G + 1)] for l in range(n_levels)]
-    for l, off in enumerate(rows_host):
-        n_l = pyr.coords[l].shape[0]
-        if off[0] != 0 or off[-1] != n_l or any(b <= a for a, b in zip(off, off[1:])):
-            raise ValueError(f"level {l}: the group row offsets {off} do not start at 0, ascend and end at the {n_l} rows")
-        if any(b - a == 1 for a, b in zip(off, off[1:])):
-            raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance): "
-                             f"a group has exactly one row at level {l}")
-    dev = pyr.coords[0].device
-    return GroupedPyramid(pyr, [torch.tensor(off, dtype=torch.int32).to(dev) for off in rows_host], rows_host, n_shapes, None)
+    return GroupedPyramid(pyr, _level_rows(pyr, rows_host, False), rows_host, n_shapes, None)
 
 
 # ------------------------------------------------------------------------------------------------------
-# autograd nodes on section 15
+# autograd nodes on sections 15 (the whole map is one BatchNorm batch) and 20 (``group_rows``: a batch per row group)
 # ------------------------------------------------------------------------------------------------------
+def _check_groups(group_rows: torch.Tensor, like: torch.Tensor) -> int:
+    if not isinstance(group_rows, torch.Tensor) or group_rows.dtype != torch.int32 or group_rows.dim() != 1:
+        raise ValueError("group_rows must be a (G + 1,) int32 tensor of row offsets")
+    G = group_rows.numel() - 1
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError(f"1 to {MAX_GROUPS} groups, not {G}")
+    if not group_rows.is_cuda or group_rows.device != like.device:
+        raise _lib.CsnError(_NO_CPU)
+    return G
+
+
 class _ConvStats(torch.autograd.Function):
-    """(z, mean, invstd) = ``csn_sparse_conv_stats_fwd_f32``; updates the running statistics in place.  mean / invstd are constants
-    of the graph; the backward is ``csn_sparse_conv_bwd_f32``."""
+    """(z, mean, invstd) = ``csn_sparse_conv_stats_fwd_f32``, or with ``group_rows`` ``csn_sparse_conv_stats_groups_fwd_f32``: mean /
+    invstd are then (G, c_out) and the running statistics take G updates in group order; updates the running statistics in place.
+    mean / invstd are constants of the graph; the backward is ``csn_sparse_conv_bwd_f32`` (on the merged map)."""
 
     @staticmethod
-    def forward(ctx, x, w, kmap, running_mean, running_var, eps, momentum):
+    def forward(ctx, x, w, kmap, group_rows, running_mean, running_var, eps, momentum):
         CF._need_cuda(x, w, kmap.fwd, running_mean, running_var)
         L = _lib.lib()
         ctx.mode = CF.current_mode()
@@ -300,16 +312,25 @@ class _ConvStats(torch.autograd.Function):
         KV, c_in, c_out = w_c.shape
         n_in, n_out = kmap.n_in, kmap.n_out
         dev = x.device
+        stats = (c_out,)
+        if group_rows is not None:
+            group_rows = group_rows.contiguous()
+            G = group_rows.numel() - 1
+            stats = (G, c_out)
         z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
-        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
-        ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out))
+        mean = torch.empty(stats, device=dev, dtype=torch.float32)
+        invstd = torch.empty(stats, device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out) if group_rows is None else
+                   L.csn_sparse_conv_stats_groups_workspace_bytes(n_out, c_out, G))
         ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        head = (CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean),
+                CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum))
         with CF.rows16(ctx.rows16):
-            _lib.check(L.csn_sparse_conv_stats_fwd_f32(CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
-                                                       CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
-                                                       CF._ptr(running_var), float(eps), float(momentum), CF._ptr(ws), ws_n,
-                                                       CF._stream()), "csn_sparse_conv_stats_fwd_f32")
+            if group_rows is None:
+                _lib.check(L.csn_sparse_conv_stats_fwd_f32(*head, CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_stats_fwd_f32")
+            else:
+                _lib.check(L.csn_sparse_conv_stats_groups_fwd_f32(*head, group_rows.data_ptr(), G, CF._ptr(ws), ws_n, CF._stream()),
+                           "csn_sparse_conv_stats_groups_fwd_f32")
         ctx.save_for_backward(x, w_c)
         ctx.kmap = kmap
         ctx.mark_non_differentiable(mean, invstd)
@@ -318,7 +339,7 @@ class _ConvStats(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, _dmean, _dinvstd):
-        return _conv_stats_backward(ctx, dz) + (None,) * 5
+        return _conv_stats_backward(ctx, dz) + (None,) * 6
 
 
 def _conv_stats_backward(ctx, dz):
@@ -344,11 +365,7 @@ def _conv_stats_backward(ctx, dz):
         return dx, dw
 
 
-def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_mean: Optional[torch.Tensor],
-               running_var: Optional[torch.Tensor], eps: float, momentum: float):
-    """``z (n_out, c_out)``, ``mean``, ``invstd`` of the convolution ``kmap`` describes and of its output's BatchNorm batch; the
-    running statistics (either may be None) are updated in place.  An input width that is no multiple of 32 is zero-padded as in
-    ``sparse_conv3d``.  A one-row output raises ``ValueError`` (no variance), as torch does."""
+def _conv_stats(x, weight, kmap, grouped: bool, group_rows, running_mean, running_var, eps, momentum):
     if not (x.is_cuda and weight.is_cuda):
         raise _lib.CsnError(_NO_CPU)
     if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
@@ -356,21 +373,40 @@ def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_m
     c_in, c_out = weight.shape[1], weight.shape[2]
     if c_out % 32 or not 32 <= c_out <= 256 or c_in > 256:
         raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in at most 256")
-    if kmap.n_out == 1:
+    G = _check_groups(group_rows, x) if grouped else None
+    if kmap.n_out == 1 if G is None else kmap.n_out < 2 * G:
         raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
     pad = -c_in % 32
     if pad:
         x = F.pad(x, (0, pad))
         weight = F.pad(weight, (0, 0, 0, pad))
-    return _ConvStats.apply(x.float(), weight, kmap, running_mean, running_var, eps, momentum)
+    return _ConvStats.apply(x.float(), weight, kmap, group_rows if grouped else None, running_mean, running_var, eps, momentum)
+
+
+def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_mean: Optional[torch.Tensor],
+               running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``z (n_out, c_out)``, ``mean``, ``invstd`` of the convolution ``kmap`` describes and of its output's BatchNorm batch; the
+    running statistics (either may be None) are updated in place.  An input width that is no multiple of 32 is zero-padded as in
+    ``sparse_conv3d``.  A one-row output raises ``ValueError`` (no variance), as torch does."""
+    return _conv_stats(x, weight, kmap, False, None, running_mean, running_var, eps, momentum)
+
+
+def conv_stats_groups(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, group_rows: torch.Tensor,
+                      running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``conv_stats`` on a merged map whose output rows are G BatchNorm batches: ``group_rows (G + 1,)`` int32 on the device are the
+    row offsets of the groups (``GroupedPyramid.group_rows[level]``: start at 0, ascend, end at ``kmap.n_out``, every group two rows
+    or more — the CALLER has checked that, the kernels cannot).  Returns ``z (n_out, c_out)`` — the bits of ``conv_stats`` —,
+    ``mean (G, c_out)`` and ``invstd (G, c_out)``; the running statistics (either may be None) take G updates in group order."""
+    return _conv_stats(x, weight, kmap, True, group_rows, running_mean, running_var, eps, momentum)
 
 
 class _BnAct(torch.autograd.Function):
-    """y = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + r) through ``csn_rows_bn_act_fwd_f32`` / ``_bwd_f32``.
+    """y = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + r) through ``csn_rows_bn_act_fwd_f32`` / ``_bwd_f32``, or with
+    ``group_rows`` (training mode, (G, C) statistics per term) through ``csn_rows_bn_act_groups_fwd_f32`` / ``_bwd_f32``.
     Arguments after the fixed ones: (z, mean, scale, gamma, beta) per term."""
 
     @staticmethod
-    def forward(ctx, relu, training, eps, r, *flat):
+    def forward(ctx, relu, training, eps, group_rows, r, *flat):
         M = len(flat) // 5
         CF._need_cuda(r, *flat)
         L = _lib.lib()
@@ -389,148 +425,15 @@ class _BnAct(torch.autograd.Function):
         for m in range(M):
             t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
             t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
-        _lib.check(L.csn_rows_bn_act_fwd_f32(ctypes.addressof(t), M, N, C, int(training), float(eps), CF._ptr(r_c), C, int(relu),
-                                             CF._ptr(y), C, CF._stream()), "csn_rows_bn_act_fwd_f32")
-        ctx.save_for_backward(y if relu else None, *zs, *means, *scales, *gammas)
-        ctx.M, ctx.relu, ctx.training, ctx.eps, ctx.has_r = M, bool(relu), bool(training), float(eps), r is not None
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        M = ctx.M
-        saved = ctx.saved_tensors
-        y = saved[0]
-        zs, means, scales, gammas = (saved[1 + k * M:1 + (k + 1) * M] for k in range(4))
-        L = _lib.lib()
-        N, C = zs[0].shape
-        dev = dy.device
-        dy = dy.contiguous()
-        need = ctx.needs_input_grad
-        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[3]) else None
-        t = _lib.BnTerms()
-        outs = []
-        for m in range(M):
-            nz, ng, nb = need[4 + 5 * m], need[4 + 5 * m + 3], need[4 + 5 * m + 4]
-            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
-            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
-            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
-            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
-            outs += [dz, None, None, dg, db]
-        ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
-        _lib.check(L.csn_rows_bn_act_bwd_f32(CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C, int(ctx.training), ctx.eps,
-                                             int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),
-                   "csn_rows_bn_act_bwd_f32")
-        return (None, None, None, dr, *outs)
-
-
-Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
-
-
-# ------------------------------------------------------------------------------------------------------
-# autograd nodes on section 20: BatchNorm over row groups
-# ------------------------------------------------------------------------------------------------------
-def _check_groups(group_rows: torch.Tensor, like: torch.Tensor) -> int:
-    if not isinstance(group_rows, torch.Tensor) or group_rows.dtype != torch.int32 or group_rows.dim() != 1:
-        raise ValueError("group_rows must be a (G + 1,) int32 tensor of row offsets")
-    G = group_rows.numel() - 1
-    if not 1 <= G <= MAX_GROUPS:
-        raise ValueError(f"1 to {MAX_GROUPS} groups, not {G}")
-    if not group_rows.is_cuda or group_rows.device != like.device:
-        raise _lib.CsnError(_NO_CPU)
-    return G
-
-
-class _ConvStatsGroups(torch.autograd.Function):
-    """``_ConvStats`` with the statistics per row group (``csn_sparse_conv_stats_groups_fwd_f32``): mean / invstd are (G, c_out),
-    the running statistics take G updates in group order.  The backward is ``csn_sparse_conv_bwd_f32`` on the merged map."""
-
-    @staticmethod
-    def forward(ctx, x, w, kmap, group_rows, running_mean, running_var, eps, momentum):
-        CF._need_cuda(x, w, kmap.fwd, running_mean, running_var)
-        L = _lib.lib()
-        ctx.mode = CF.current_mode()
-        ctx.rows16 = tuning.current().rows_single_product
-        x = x.contiguous()
-        w_c = w.detach().contiguous()
-        group_rows = group_rows.contiguous()
-        G = group_rows.numel() - 1
-        KV, c_in, c_out = w_c.shape
-        n_in, n_out = kmap.n_in, kmap.n_out
-        dev = x.device
-        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty((G, c_out), device=dev, dtype=torch.float32)
-        invstd = torch.empty((G, c_out), device=dev, dtype=torch.float32)
-        ws_n = int(L.csn_sparse_conv_stats_groups_workspace_bytes(n_out, c_out, G))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
-        with CF.rows16(ctx.rows16):
-            _lib.check(L.csn_sparse_conv_stats_groups_fwd_f32(
-                CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean),
-                CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum), group_rows.data_ptr(), G,
-                CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_stats_groups_fwd_f32")
-        ctx.save_for_backward(x, w_c)
-        ctx.kmap = kmap
-        ctx.mark_non_differentiable(mean, invstd)
-        return z, mean, invstd
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dz, _dmean, _dinvstd):
-        return _conv_stats_backward(ctx, dz) + (None,) * 6
-
-
-def conv_stats_groups(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, group_rows: torch.Tensor,
-                      running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], eps: float, momentum: float):
-    """``conv_stats`` on a merged map whose output rows are G BatchNorm batches: ``group_rows (G + 1,)`` int32 on the device are the
-    row offsets of the groups (``GroupedPyramid.group_rows[level]``: start at 0, ascend, end at ``kmap.n_out``, every group two rows
-    or more — the CALLER has checked that, the kernels cannot).  Returns ``z (n_out, c_out)`` — the bits of ``conv_stats`` —,
-    ``mean (G, c_out)`` and ``invstd (G, c_out)``; the running statistics (either may be None) take G updates in group order."""
-    if not (x.is_cuda and weight.is_cuda):
-        raise _lib.CsnError(_NO_CPU)
-    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
-        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out) for the map's KV and n_in")
-    c_in, c_out = weight.shape[1], weight.shape[2]
-    if c_out % 32 or not 32 <= c_out <= 256 or c_in > 256:
-        raise ValueError("widths: c_out a multiple of 32 in [32, 256], c_in at most 256")
-    G = _check_groups(group_rows, x)
-    if kmap.n_out < 2 * G:
-        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
-    pad = -c_in % 32
-    if pad:
-        x = F.pad(x, (0, pad))
-        weight = F.pad(weight, (0, 0, 0, pad))
-    return _ConvStatsGroups.apply(x.float(), weight, kmap, group_rows, running_mean, running_var, eps, momentum)
-
-
-class _BnActGroups(torch.autograd.Function):
-    """``_BnAct`` in training mode with (G, C) statistics per term (``csn_rows_bn_act_groups_fwd_f32`` / ``_bwd_f32``).
-    Arguments after the fixed ones: (z, mean, scale, gamma, beta) per term."""
-
-    @staticmethod
-    def forward(ctx, relu, group_rows, r, *flat):
-        M = len(flat) // 5
-        CF._need_cuda(r, *flat)
-        L = _lib.lib()
-        group_rows = group_rows.contiguous()
-        G = group_rows.numel() - 1
-        zs = [flat[5 * m].contiguous() for m in range(M)]
-        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
-        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
-        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
-        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
-        N, C = zs[0].shape
-        r_c = None if r is None else r.contiguous()
-        y = torch.empty((N, C), device=zs[0].device, dtype=torch.float32)
-        t = _lib.BnTerms()
-        for m in range(M):
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
-            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
-        _lib.check(L.csn_rows_bn_act_groups_fwd_f32(ctypes.addressof(t), M, N, C, group_rows.data_ptr(), G, CF._ptr(r_c), C, int(relu),
-                                                    CF._ptr(y), C, CF._stream()), "csn_rows_bn_act_groups_fwd_f32")
+        tail = (CF._ptr(r_c), C, int(relu), CF._ptr(y), C, CF._stream())
+        if group_rows is None:
+            _lib.check(L.csn_rows_bn_act_fwd_f32(ctypes.addressof(t), M, N, C, int(training), float(eps), *tail), "csn_rows_bn_act_fwd_f32")
+        else:
+            group_rows = group_rows.contiguous()
+            _lib.check(L.csn_rows_bn_act_groups_fwd_f32(ctypes.addressof(t), M, N, C, group_rows.data_ptr(), group_rows.numel() - 1, *tail),
+                       "csn_rows_bn_act_groups_fwd_f32")
         ctx.save_for_backward(y if relu else None, group_rows, *zs, *means, *scales, *gammas)
-        ctx.M, ctx.relu, ctx.has_r = M, bool(relu), r is not None
+        ctx.M, ctx.relu, ctx.training, ctx.eps, ctx.has_r = M, bool(relu), bool(training), float(eps), r is not None
         return y
 
     @staticmethod
@@ -542,27 +445,36 @@ class _BnActGroups(torch.autograd.Function):
         zs, means, scales, gammas = (saved[2 + k * M:2 + (k + 1) * M] for k in range(4))
         L = _lib.lib()
         N, C = zs[0].shape
-        G = group_rows.numel() - 1
         dev = dy.device
         dy = dy.contiguous()
         need = ctx.needs_input_grad
-        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[2]) else None
+        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[4]) else None
         t = _lib.BnTerms()
         outs = []
         for m in range(M):
-            nz, ng, nb = need[3 + 5 * m], need[3 + 5 * m + 3], need[3 + 5 * m + 4]
+            nz, ng, nb = need[5 + 5 * m], need[5 + 5 * m + 3], need[5 + 5 * m + 4]
             dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
             dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
             db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
             t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
             t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
             outs += [dz, None, None, dg, db]
-        ws_n = int(L.csn_rows_bn_act_groups_workspace_bytes(N, C, M, G))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
-        _lib.check(L.csn_rows_bn_act_groups_bwd_f32(CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C, group_rows.data_ptr(), G,
-                                                    int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),
-                   "csn_rows_bn_act_groups_bwd_f32")
-        return (None, None, dr, *outs)
+        head = (CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C)
+        if group_rows is None:
+            ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
+            ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+            _lib.check(L.csn_rows_bn_act_bwd_f32(*head, int(ctx.training), ctx.eps, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n,
+                                                 CF._stream()), "csn_rows_bn_act_bwd_f32")
+        else:
+            G = group_rows.numel() - 1
+            ws_n = int(L.csn_rows_bn_act_groups_workspace_bytes(N, C, M, G))
+            ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+            _lib.check(L.csn_rows_bn_act_groups_bwd_f32(*head, group_rows.data_ptr(), G, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n,
+                                                        CF._stream()), "csn_rows_bn_act_groups_bwd_f32")
+        return (None, None, None, None, dr, *outs)
+
+
+Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -641,19 +553,24 @@ def _conv_bn_act(conv: SparseConv3d, norm: nn.BatchNorm1d, x, kmap: KernelMap, r
     return sparse_conv_bn_act(x, conv.kernel, kmap, norm, residual, relu, out)
 
 
-def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu: bool = True, training: bool = True,
-           eps: float = 1e-5) -> torch.Tensor:
-    """``y (N, C) = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + residual)`` for 1 to 3 terms ``(z, mean, scale, gamma, beta)``:
-    training takes ``scale = invstd`` (of ``conv_stats``), eval the running mean / variance and ``eps``."""
+def _bn_act(terms: Sequence[Term], grouped: bool, group_rows, residual, relu, training, eps) -> torch.Tensor:
     if not 1 <= len(terms) <= 3:
-        raise ValueError("bn_act takes 1 to 3 terms")
+        raise ValueError(("bn_act_groups" if grouped else "bn_act") + " takes 1 to 3 terms")
     flat = []
     N, C = terms[0][0].shape
+    G = None
+    if grouped:                                       # every map's device before the offsets' own checks
+        for z, *_ in terms:
+            if not z.is_cuda:
+                raise _lib.CsnError(_NO_CPU)
+        G = _check_groups(group_rows, terms[0][0])
     for z, mean, scale, gamma, beta in terms:
-        if not z.is_cuda:
+        if not grouped and not z.is_cuda:             # a term's device before its shapes
             raise _lib.CsnError(_NO_CPU)
-        if tuple(z.shape) != (N, C) or any(v.numel() != C for v in (mean, scale, gamma, beta)):
-            raise ValueError("every term needs an (N, C) map and four (C,) vectors")
+        if tuple(z.shape) != (N, C) or any(v.numel() != C for v in (gamma, beta)) or any(
+                v.numel() != C if G is None else tuple(v.shape) != (G, C) for v in (mean, scale)):
+            raise ValueError("every term needs an (N, C) map and four (C,) vectors" if G is None else
+                             "every term needs an (N, C) map, two (G, C) statistics and two (C,) vectors")
         flat += [z.float(), mean, scale, gamma, beta]
     if C % 32 or not 32 <= C <= 256:
         raise ValueError(f"width {C} is not supported: a multiple of 32 in [32, 256]")
@@ -663,7 +580,14 @@ def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu:
         if tuple(residual.shape) != (N, C):
             raise ValueError("the residual must be (N, C)")
         residual = residual.float()
-    return _BnAct.apply(bool(relu), bool(training), float(eps), residual, *flat)
+    return _BnAct.apply(bool(relu), bool(training), float(eps), group_rows if grouped else None, residual, *flat)
+
+
+def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu: bool = True, training: bool = True,
+           eps: float = 1e-5) -> torch.Tensor:
+    """``y (N, C) = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + residual)`` for 1 to 3 terms ``(z, mean, scale, gamma, beta)``:
+    training takes ``scale = invstd`` (of ``conv_stats``), eval the running mean / variance and ``eps``."""
+    return _bn_act(terms, False, None, residual, relu, training, eps)
 
 
 def bn_act_groups(terms: Sequence[Term], group_rows: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = True,
@@ -672,27 +596,7 @@ def bn_act_groups(terms: Sequence[Term], group_rows: torch.Tensor, residual: Opt
     ``conv_stats_groups``) ``y_i = act(sum_m (gamma_m (z_m,i - mean_m[g]) scale_m[g] + beta_m) + residual_i)`` for 1 to 3 terms
     ``(z (N, C), mean (G, C), scale (G, C) = invstd of conv_stats_groups, gamma (C,), beta (C,))``.  ``eps`` is part of the
     statistics already (kept for the signature of ``bn_act``).  The backward is the complete BatchNorm gradient per group."""
-    if not 1 <= len(terms) <= 3:
-        raise ValueError("bn_act_groups takes 1 to 3 terms")
-    flat = []
-    N, C = terms[0][0].shape
-    for z, *_ in terms:
-        if not z.is_cuda:
-            raise _lib.CsnError(_NO_CPU)
-    G = _check_groups(group_rows, terms[0][0])
-    for z, mean, scale, gamma, beta in terms:
-        if tuple(z.shape) != (N, C) or any(tuple(v.shape) != (G, C) for v in (mean, scale)) or any(v.numel() != C for v in (gamma, beta)):
-            raise ValueError("every term needs an (N, C) map, two (G, C) statistics and two (C,) vectors")
-        flat += [z.float(), mean, scale, gamma, beta]
-    if C % 32 or not 32 <= C <= 256:
-        raise ValueError(f"width {C} is not supported: a multiple of 32 in [32, 256]")
-    if residual is not None:
-        if not residual.is_cuda:
-            raise _lib.CsnError(_NO_CPU)
-        if tuple(residual.shape) != (N, C):
-            raise ValueError("the residual must be (N, C)")
-        residual = residual.float()
-    return _BnActGroups.apply(bool(relu), group_rows, residual, *flat)
+    return _bn_act(terms, True, group_rows, residual, relu, True, eps)
 
 
 # ------------------------------------------------------------------------------------------------------
