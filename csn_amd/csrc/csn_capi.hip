@@ -1692,6 +1692,33 @@ int csn_kernel_map_i32(const long long* set_keys, const int* set_rows, int n_set
   return csn_launch_kernel_map(a, (hipStream_t)stream);
 }
 
+// ---- (22) octant maps: the partition of a fine set by its coarse set, the rows sorted by octant ----
+int csn_octant_partition_i32(const long long* fine_keys, const long long* fine_sorted, int n_fine, int tensor_stride,
+                             const long long* coarse_keys, const int* coarse_rows, int n_coarse, int* parent, int* octant, int* children,
+                             int* status, void* stream) {
+  if (!fine_keys || !coarse_keys || !parent || !octant || !children || !status) return CSN_E_ARG;
+  if (n_fine < 1 || n_coarse < 1 || tensor_stride < 1) return CSN_E_ARG;
+  if (mis8(fine_keys) || mis8(coarse_keys) || (fine_sorted && mis8(fine_sorted)) || (coarse_rows && mis4(coarse_rows))) return CSN_E_PTR;
+  if (mis4(parent) || mis4(octant) || mis4(children) || mis4(status)) return CSN_E_PTR;
+  CsnOctantMapArgs a{};
+  a.fine_keys = fine_keys; a.fine_sorted = fine_sorted; a.n_fine = n_fine; a.tensor_stride = tensor_stride; a.coarse_keys = coarse_keys;
+  a.coarse_rows = coarse_rows; a.n_coarse = n_coarse; a.parent = parent; a.octant = octant; a.children = children; a.status = status;
+  return csn_launch_octant_partition(a, (hipStream_t)stream);
+}
+
+long long csn_octant_order_workspace_bytes(int n) {
+  if (n < 1) return 0;
+  return 8 * csn_octant_order_tiles(n) * (long long)sizeof(int);
+}
+
+int csn_octant_order_i32(const int* octant, int n, int* order, int* seg, void* ws, long long ws_bytes, int* status, void* stream) {
+  if (!octant || !order || !seg || !ws || !status) return CSN_E_ARG;
+  if (n < 1) return CSN_E_ARG;
+  if (mis4(octant) || mis4(order) || mis4(seg) || mis4(ws) || mis4(status)) return CSN_E_PTR;
+  if (ws_bytes < csn_octant_order_workspace_bytes(n)) return CSN_E_WORKSPACE;
+  return csn_launch_octant_order(octant, n, order, seg, static_cast<int*>(ws), status, (hipStream_t)stream);
+}
+
 // ---- (18) resident point collections: normalise, bound, augment + collate + key; a PointField's index arrays ----
 static int points_collection(const float* points, const long long* offsets, int n_shapes, long long n_total, const int* status) {
   if (!points || !offsets || !status) return CSN_E_ARG;

@@ -415,6 +415,23 @@ int csn_launch_coord_keys(const long long* coords, int n, int tensor_stride, lon
 int csn_launch_coord_down(const long long* keys, int n, int out_tensor_stride, long long* down_keys, hipStream_t st);
 int csn_launch_kernel_map(const CsnKernelMapArgs& a, hipStream_t st);
 
+// ---- octant maps: parent, octant and children of a fine set by one search per row; the rows sorted by octant (octant_map.hip) ----
+struct CsnOctantMapArgs {
+  const long long* fine_keys;                                     // [n_fine] packed keys of the fine rows, in row order
+  const long long* fine_sorted;                                   // [n_fine] the same keys ascending, or NULL: their neighbours are not checked
+  const long long* coarse_keys;                                   // [n_coarse] ascending packed keys of the coarse set
+  const int* coarse_rows;                                         // [n_coarse] the row of every sorted key, or NULL: the position itself
+  int n_fine, n_coarse, tensor_stride;                            // tensor_stride: the fine set's
+  int* parent;  int* octant;                                      // [n_fine], written
+  int* children;                                                  // [8][n_coarse], filled with -1 and written
+  int* status;                                                    // one word, or-ed into (8: a set is not strictly ascending, 16: no parent)
+};
+constexpr int CSN_OCTANT_ORDER_TILE = 256;                        // rows per work-group of the count and scatter launches
+constexpr int CSN_OCTANT_ORDER_SCAN = 256;                        // tiles per pass of the scan's one work-group
+int csn_launch_octant_partition(const CsnOctantMapArgs& a, hipStream_t st);
+long long csn_octant_order_tiles(int n);
+int csn_launch_octant_order(const int* octant, int n, int* order, int* seg, int* counts, int* status, hipStream_t st);  // counts: [8][tiles]
+
 // ---- resident point collections: normalise, bound, augment + collate + key, and a PointField's index arrays (points.hip) ----
 constexpr int CSN_POINTS_NPARAM = 9;                              // per item: cos, sin, shift_z[3], jitter[3], scale
 struct CsnPointsArgs {

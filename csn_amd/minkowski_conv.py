@@ -28,8 +28,9 @@ residual block with the reference's attribute names (its batch norms are ``nn.Ba
 The kernel-2 stride-2 convolution and its transposed form (MinkowskiNet/models/res16unet.py: ``conv*s2`` / ``convtr*s2``) stand
 beside that surface: kernel 2 at stride 2 partitions the fine voxels, so ``build_octant_map`` keeps one parent and one octant per
 fine row instead of a table, and ``octant_conv_down`` / ``octant_conv_up`` (``SparseConvDown2`` / ``SparseConvUp2``) are one
-autograd node each on ``csn_octant_*`` (include/csn_hip.h section 21).  ``cat_conv3d`` is a convolution on a concatenation that is
-never formed.
+autograd node each on ``csn_octant_*`` (include/csn_hip.h section 21).  ``build_octant_map`` has the two backends of
+``build_kernel_map``: torch ops, or the partition and the stable counting sort of section 22 around ``torch.sort`` /
+``torch.unique``.  ``cat_conv3d`` is a convolution on a concatenation that is never formed.
 """
 from __future__ import annotations
 
@@ -439,16 +440,69 @@ class OctantMap:
                          mv(self.octant), mv(self.children), mv(self.order), mv(self.seg))
 
 
-def build_octant_map(coords: torch.Tensor, tensor_stride: int = 1, out_coords: Optional[torch.Tensor] = None) -> OctantMap:
+OCTANT_ORDER_TILE, OCTANT_ORDER_SCAN = 256, 256     # csrc/csn_kernels.h: rows per tile of (22b), tiles per pass of its scan
+_NO_PARENT = "out_coords misses the parent of some row of coords"
+
+
+def _octant_map(fine: _KeySet, coarse: _KeySet, ts: int, status: torch.Tensor, check_fine: bool) -> OctantMap:
+    """(22a) and (22b): the octant map of ``fine`` at ``ts`` onto ``coarse``.  ``check_fine`` hands the sorted fine keys in for the
+    duplicate check; a caller whose (17c) lookup on ``fine`` has made it passes False."""
+    L = _lib.lib()
+    dev = fine.keys.device
+    n_fine, n_coarse = fine.keys.numel(), coarse.sorted.numel()
+    parent = torch.empty(n_fine, dtype=torch.int32, device=dev)
+    octant = torch.empty(n_fine, dtype=torch.int32, device=dev)
+    children = torch.empty((8, n_coarse), dtype=torch.int32, device=dev)
+    _lib.check(L.csn_octant_partition_i32(CF._ptr(fine.keys), CF._ptr(fine.sorted) if check_fine else None, n_fine, ts,
+                                          CF._ptr(coarse.sorted), CF._ptr(coarse.rows), n_coarse, CF._ptr(parent), CF._ptr(octant),
+                                          CF._ptr(children), CF._ptr(status), CF._stream()), "csn_octant_partition_i32")
+    order = torch.empty(n_fine, dtype=torch.int32, device=dev)
+    seg = torch.empty(9, dtype=torch.int32, device=dev)
+    ws_n = int(L.csn_octant_order_workspace_bytes(n_fine))
+    ws = torch.empty(ws_n // 4, dtype=torch.int32, device=dev)
+    _lib.check(L.csn_octant_order_i32(CF._ptr(octant), n_fine, CF._ptr(order), CF._ptr(seg), CF._ptr(ws), ws_n, CF._ptr(status),
+                                      CF._stream()), "csn_octant_order_i32")
+    return OctantMap(fine.coords, coarse.coords, ts, 2 * ts, parent, octant, children, order, seg)
+
+
+def _build_octant_map_hip(coords, ts, out_coords) -> OctantMap:
+    status = _new_status(coords.device)
+    s_in = _key_set(coords, ts, "coords", status)
+    sets = [(coords, ts, "coords")]
+    if out_coords is not None:
+        s_out = _key_set(out_coords, 2 * ts, "out_coords", status)
+        sets.append((out_coords, 2 * ts, "out_coords"))
+    else:
+        s_out = _coarse_set(s_in, 2 * ts)
+    omap = _octant_map(s_in, s_out, ts, status, True)
+    word = _read_status(status)
+    if word & 16:                                                    # the sets' own failures first, in the torch backend's order
+        _raise_for_status(word & ~16, sets)
+        raise ValueError(_NO_PARENT)
+    _raise_for_status(word, sets)
+    return omap
+
+
+def build_octant_map(coords: torch.Tensor, tensor_stride: int = 1, out_coords: Optional[torch.Tensor] = None,
+                     backend: Optional[str] = None) -> OctantMap:
     """The octant map of ``coords (n_fine, 4) = [b, x, y, z]`` (unique rows in any order, multiples of ``tensor_stride``) onto the
     coarse set ``build_kernel_map(..., stride=2)`` generates — ``unique([b, floor(xyz / 2ts) 2ts])`` sorted by (b, x, y, z) — or
-    onto ``out_coords`` when given (it must hold every parent: ``ValueError``).  Torch ops on the coordinates' device: one
-    ``searchsorted``, one stable sort, one scatter; nothing is read back beyond what ``torch.unique`` and the checks cost.  The
-    octant numbering is this project's choice, unpinned against MinkowskiEngine (``OctantMap``)."""
+    onto ``out_coords`` when given (it must hold every parent: ``ValueError``).  The octant numbering is this project's choice,
+    unpinned against MinkowskiEngine (``OctantMap``).
+
+    ``backend`` as in ``build_kernel_map``.  ``"torch"``: torch ops on the coordinates' device (one ``searchsorted``, one stable
+    sort, one scatter), with a host read per check.  ``"hip"``: the kernels of include/csn_hip.h section 22 around ``torch.sort`` /
+    ``torch.unique`` — device tensors only (``CsnError`` otherwise), the same attributes, dtypes and integers, the same
+    ``ValueError`` messages (raised after the launches: one status word is read back per call).  None takes ``"hip"`` for device
+    tensors when ``tuning.current().native_kernel_maps`` is set and ``"torch"`` otherwise."""
     ts = int(tensor_stride)
     if ts < 1:
         raise ValueError(f"tensor_stride {tensor_stride} is not valid here")
     out_ts = 2 * ts
+    if resolve_backend(backend, coords, out_coords) == "hip":
+        if out_coords is not None and out_coords.device != coords.device:
+            raise ValueError("coords and out_coords must be on one device")
+        return _build_octant_map_hip(coords, ts, out_coords)
     c_in = _check_coords(coords, ts, "coords")
     _Index(c_in, "coords")                                           # duplicates
     down = c_in.clone()
@@ -463,7 +517,7 @@ def build_octant_map(coords: torch.Tensor, tensor_stride: int = 1, out_coords: O
         idx_out = _Index(c_out, "out_coords")
     parent = idx_out.rows(down)
     if out_coords is not None and bool((parent < 0).any()):
-        raise ValueError("out_coords misses the parent of some row of coords")
+        raise ValueError(_NO_PARENT)
     o = (c_in[:, 1:] - down[:, 1:]) // ts
     octant = (o[:, 0] + 2 * o[:, 1] + 4 * o[:, 2]).int()
     n_fine, n_coarse = c_in.shape[0], c_out.shape[0]

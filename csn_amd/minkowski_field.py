@@ -49,6 +49,7 @@ from . import functional as CF
 from .minkowski_conv import _B_BITS, _C_BIAS, _pack, _unpack, build_kernel_map
 from .minkowski_csn import offsets_from_batch_index
 from .minkowski_hrnet import VoxelPyramid, build_pyramid
+from .minkowski_unet import UNetPyramid, build_unet_pyramid
 
 _NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
 QUANTIZATION_MODES = ("random_subsample", "unweighted_average")
@@ -181,6 +182,7 @@ class PointField:
         self.voxel_offsets = offsets_from_batch_index(self.voxel_coords[:, 0])
         self._voxel_feats: Optional[torch.Tensor] = None
         self._pyramid: Optional[VoxelPyramid] = None
+        self._unet_pyramid: Optional[UNetPyramid] = None
         self._table: Optional[torch.Tensor] = None
 
     @classmethod
@@ -236,7 +238,7 @@ class PointField:
         f.voxel_coords = _unpack(uniq)
         f.offsets = off
         f.voxel_offsets = torch.tensor(word[2:] + [n_vox], dtype=torch.int64)
-        f._voxel_feats = f._pyramid = f._table = None
+        f._voxel_feats = f._pyramid = f._unet_pyramid = f._table = None
         return f
 
     # ---- sizes ----
@@ -279,6 +281,17 @@ class PointField:
             self._table = p.s1[0].fwd
         return p
 
+    def unet_pyramid(self, stem_kernel: int = 5, backend: Optional[str] = None) -> UNetPyramid:
+        """The ``UNetPyramid`` of ``voxel_coords`` for a ``Res16UNet*`` — ``model((field.unet_pyramid(), field.voxel_feats))`` —, built
+        once and kept like ``pyramid()`` (a different stem kernel rebuilds it).  ``backend`` as in ``build_unet_pyramid`` (both give
+        the same pyramid, so it is no part of the request).  Its level-0 kernel-3 map serves ``corner_table`` where none is there."""
+        p = self._unet_pyramid
+        if p is None or p.stem_kernel != stem_kernel:
+            self._unet_pyramid = p = build_unet_pyramid(self.voxel_coords, stem_kernel, backend=backend)
+            if self._table is None:
+                self._table = p.s1[0].fwd
+        return p
+
     def sparse(self) -> Tuple[object, torch.Tensor]:
         """``field.sparse()``: ``(pyramid or voxel_coords, voxel_feats)`` — a batch that ``HRNetSimCSN.forward`` / ``backbone_rows``
         take as it stands (the pyramid once ``pyramid()`` was called, the coordinates otherwise)."""
@@ -315,6 +328,7 @@ class PointField:
         f.offsets, f.voxel_offsets = self.offsets, self.voxel_offsets
         f._voxel_feats = None if self._voxel_feats is None else self._voxel_feats.to(device)
         f._pyramid = None if self._pyramid is None else self._pyramid.to(device)
+        f._unet_pyramid = None if self._unet_pyramid is None else self._unet_pyramid.to(device)
         f._table = f._pyramid.s1[0].fwd if f._pyramid is not None else (None if self._table is None else self._table.to(device))
         return f
 

@@ -31,6 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import minkowski_conv as _mc
 from .minkowski_conv import (KernelMap, OctantMap, SparseConv3d, SparseConvDown2, SparseConvUp2, build_kernel_map, build_octant_map,
                              cat_conv3d)
 from .minkowski_hrnet import HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _keep
@@ -55,18 +56,54 @@ class UNetPyramid:
 
 def build_unet_pyramid(coords: torch.Tensor, stem_kernel: int = 5, backend: Optional[str] = None) -> UNetPyramid:
     """The pyramid of ``coords`` (n, 4) = [b, x, y, z] at tensor stride 1 (device or CPU tensor; the maps live where it does).
-    ``backend`` as in ``build_kernel_map``, for the kernel maps; the octant maps are torch ops either way."""
+    ``backend`` as in ``build_kernel_map``: ``"torch"``, ``"hip"`` (device tensors only) or None for the tuning switch
+    ``native_kernel_maps``; both give the same pyramid, kernel maps and octant maps alike."""
+    backend = _mc.resolve_backend(backend, coords)
+    if backend == "hip":
+        return _build_unet_pyramid_hip(coords, stem_kernel)
     levels, s1, one, octs = [coords.long()], [], [], []
     for l in range(N_LEVELS):
         ts = 1 << l
         s1.append(build_kernel_map(levels[l], kernel_size=3, stride=1, tensor_stride=ts, backend=backend))
         one.append(build_kernel_map(levels[l], kernel_size=1, stride=1, tensor_stride=ts, backend=backend))
         if l + 1 < N_LEVELS:
-            octs.append(build_octant_map(levels[l], tensor_stride=ts))
+            octs.append(build_octant_map(levels[l], tensor_stride=ts, backend=backend))
             levels.append(octs[-1].out_coords)
     stem = s1[0] if stem_kernel == 3 else build_kernel_map(levels[0], kernel_size=stem_kernel, stride=1, tensor_stride=1,
                                                            backend=backend)
     return UNetPyramid(levels, s1, one, stem, octs, stem_kernel)
+
+
+def _build_unet_pyramid_hip(coords: torch.Tensor, stem_kernel: int) -> UNetPyramid:
+    """The same pyramid on include/csn_hip.h sections 17 and 22, in the manner of ``minkowski_hrnet._build_pyramid_hip``.  Level l's
+    keys and their sort are formed once and serve ``s1[l]``, ``one[l]``, the stem and ``oct[l]``; a coarser level leaves
+    ``torch.unique`` sorted, so it is never sorted again.  Level 0 takes one key launch; a coarser level one launch for the floored
+    keys and one key launch on its unpacked coordinates (the level's range and tensor-stride check, as in the HRNet's pyramid); one
+    lookup launch per table — five kernel-3, five kernel-1, the stem's —; per octant map one partition call and one order call.  The
+    kernel-3 lookup of a level has checked its sorted keys' neighbours, so the partition is not handed them again.  One status word
+    for the whole pyramid, read once at the end: 5 + 4 + 11 + 4 + 4 = 28 library calls (27 with a kernel-3 stem) and one host read."""
+    if stem_kernel < 1 or stem_kernel % 2 == 0:
+        raise ValueError(f"kernel_size {stem_kernel} is not supported: odd sizes only")
+    if stem_kernel not in (1, 3, 5):
+        raise ValueError(f"kernel_size {stem_kernel} is not supported: the kernels take 1, 3 and 5")
+    status = _mc._new_status(coords.device)
+    sets, s1, one, octs = [_mc._key_set(coords, 1, "coords", status)], [], [], []
+    for l in range(N_LEVELS):
+        ts, here = 1 << l, sets[l]
+        s1.append(KernelMap(here.coords, here.coords, 3, 1, ts, ts, False, _mc._lookup(here, here, 3, ts, status), None))
+        one.append(KernelMap(here.coords, here.coords, 1, 1, ts, ts, False, _mc._lookup(here, here, 1, ts, status), None))
+        if l + 1 < N_LEVELS:
+            up = _mc._coarse_set(here, 2 * ts)
+            up.keys = _mc._coord_keys(up.coords, 2 * ts, status)
+            sets.append(up)
+            octs.append(_mc._octant_map(here, up, ts, status, False))
+    if stem_kernel == 3:
+        stem = s1[0]
+    else:
+        stem = KernelMap(sets[0].coords, sets[0].coords, stem_kernel, 1, 1, 1, False,
+                         _mc._lookup(sets[0], sets[0], stem_kernel, 1, status), None)
+    _mc._raise_for_status(_mc._read_status(status), [(coords, 1, "coords")])
+    return UNetPyramid([s.coords for s in sets], s1, one, stem, octs, stem_kernel)
 
 
 class CatConv3d(nn.Module):

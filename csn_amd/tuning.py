@@ -70,9 +70,11 @@ class Tuning:
     cross_score_budget: Optional[int] = None
     # kernel maps and voxel pyramids of DEVICE tensors (csn_amd.minkowski_conv.build_kernel_map, csn_amd.minkowski_hrnet.build_pyramid
     # with backend=None, hence PointField.pyramid and HRNetSimCSN.forward on bare coordinates) through the kernels of include/csn_hip.h
-    # section 17 instead of one searchsorted per offset in torch ops.  The same integers (tests/test_gpu_kernel_map.py), so every launch
-    # downstream is the same launch.  CPU tensors keep the torch backend whatever this says.  Off: opt-in until the default is flipped
-    # on its own (timing: DESIGN.md "Kernel maps", scripts/bench_kernel_map.py)
+    # section 17 instead of one searchsorted per offset in torch ops; likewise the octant maps and the U-Net's pyramid
+    # (build_octant_map, csn_amd.minkowski_unet.build_unet_pyramid, hence PointField.unet_pyramid and Res16UNet*.forward on bare
+    # coordinates) through sections 17 and 22.  The same integers (tests/test_gpu_kernel_map.py, tests/test_gpu_octant_map.py), so every
+    # launch downstream is the same launch.  CPU tensors keep the torch backend whatever this says.  Off: opt-in until the default is
+    # flipped on its own (timing: DESIGN.md "Kernel maps" and "Native octant maps", scripts/bench_kernel_map.py, bench_unet_pyramid.py)
     native_kernel_maps: bool = False
     # math modes "bf16" / "fp16" on the MinkowskiNet side: fc_layer, the sparse convolutions and their statistics form (_RowsFC,
     # _SparseConv, _ConvStats) run ONE 16-bit product per operand pair (csn_set_thread_rows16; an fp16 forward runs its backward in

@@ -1010,6 +1010,41 @@ CSN_API int csn_octant_up_bwd_f32(const float* dy, long long ld_dy, const float*
                           int c_out, const int* children, const int* parent, const int* order, const int* seg, const float* w,
                           float* dx, long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
 
+/* ---- (22) octant maps: the coordinate manager of (21) — parent, octant and children by one search per fine row, the rows sorted
+ *           by octant ----------------------------------------------------------------------------------------------------------
+ * csn_amd.minkowski_conv.build_octant_map(backend="hip") and csn_amd.minkowski_unet.build_unet_pyramid(backend="hip") build the
+ * octant map of (21) here, on the PACKED KEY and the STATUS WORD of (17); the sort and the unique of the keys stay the caller's.
+ * Additive to ABI version 17.  Two more flags of the status word:
+ *   16 a fine row whose parent [b, floor(xyz / 2ts) 2ts] is not in the coarse set (or whose floor leaves [-2^15, 2^15));
+ *   32 an entry of `octant` outside [0, 8) handed to (22b).
+ * Nothing is dereferenced through a bad value, and no write leaves its array: a flagged call's outputs are merely not meaningful.
+ * Host-side checks before any launch: a NULL pointer (fine_sorted and coarse_rows may be NULL), n_fine, n_coarse or n < 1,
+ * tensor_stride < 1: CSN_E_ARG; a key array off 8 bytes, an int32 array, the workspace or the status word off 4 bytes: CSN_E_PTR;
+ * ws_bytes < csn_octant_order_workspace_bytes(n): CSN_E_WORKSPACE.
+ * (22a) csn_octant_partition_i32: fine_keys[n_fine] in row order at tensor_stride ts; coarse_keys[n_coarse] ascending, coarse_rows
+ *   [n_coarse] the row number of every sorted key (NULL: its position), as in (17c).  For every fine row i
+ *     parent[i] = the coarse row of [b, floor(xyz / 2ts) 2ts], or -1 (flag 16; no children entry is written for it);
+ *     octant[i] = ox + 2 oy + 4 oz, o = (xyz - floor(xyz / 2ts) 2ts) / ts   (always in [0, 8));
+ *     children[octant[i]][parent[i]] = i;   every other entry of children[8][n_coarse] is -1: the entry point fills the array.
+ *   Floor, not truncation (-1 -> -2 at ts = 1), per field after unpacking; the batch field is never touched.  One lower-bound search
+ *   per fine row; offsets into children are 64-bit.  A row number outside [0, n_coarse) in coarse_rows reads as "no parent".  With
+ *   unique fine rows every (octant, parent) slot has one writer at most: no atomics on data, the same integers on every call.
+ *   Duplicate fine rows are the caller's to exclude: fine_sorted[n_fine], the fine keys ascending, has its neighbours checked in the
+ *   same launch (flag 8, like those of coarse_keys); NULL where a (17c) call on that set has checked them already.
+ * (22b) csn_octant_order_i32: order[n] = the rows sorted by (octant, row), seg[9] with octant k at order[seg[k] .. seg[k + 1]): the
+ *   integers of a stable sort of octant[n] and of the running sum of its histogram.  A stable counting sort in three launches over
+ *   tiles of 256 rows: counts per tile and octant from wave ballots; one work-group scans the counts octant by octant, 256 tiles
+ *   per pass, and writes seg; a scatter in which a row's rank inside its tile is the population count of its octant's ballot below
+ *   its lane plus the counts of the waves before its own.  No position comes from an atomic counter.  An entry outside [0, 8)
+ *   (which (22a) never writes) is dropped and flagged 32: seg[8] is then the number of rows kept and order[seg[8] .. n) is left as
+ *   it was.  ws: csn_octant_order_workspace_bytes(n) = 8 ceil(n / 256) int32 (0 for n < 1). */
+CSN_API int csn_octant_partition_i32(const long long* fine_keys, const long long* fine_sorted, int n_fine, int tensor_stride,
+                             const long long* coarse_keys, const int* coarse_rows, int n_coarse, int* parent, int* octant,
+                             int* children, int* status, void* stream);
+CSN_API long long csn_octant_order_workspace_bytes(int n);
+CSN_API int csn_octant_order_i32(const int* octant, int n, int* order, int* seg, void* ws, long long ws_bytes, int* status,
+                         void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
