@@ -5,8 +5,11 @@
 // gamma / beta is applied here, never materialised per evaluation).  Evaluation e has counts[e] real points; the varlen
 // attention ran it with round-up-4(counts[e]) queries, so the points [counts[e], round-up-4) hold REAL, non-zero values
 // (attention of a zero query is the mean of V).  Every kernel here uses the exact count: those points enter no sum and
-// their gradient is written as zero.
-//   pool      pooled[e][c] = gamma[c] mean_{n < counts[e]} xhat[e][c][n] + beta[c]                      (hrnet.py:380-381, 388-389)
+// their gradient is written as zero.  Every point of xhat up to ld must be FINITE all the same: the mix backward forms
+// 0 * xhat for the points between a shape's count and the end of its last 64-point tile (an inf or nan there would reach
+// rowdot).  The attention keeps that promise: the context of a padding query is zero, and fc + LayerNorm of a zero row is a
+// finite row (minkowski_attention.py, _CrossMHA.forward).
+//   pool     pooled[e][c] = gamma[c] mean_{n < counts[e]} xhat[e][c][n] + beta[c]                      (hrnet.py:380-381, 388-389)
 //   mix fwd   out[off[b] + n][c] = sum_j comp[b][j] (gamma[c] xhat[ev(b,j)][c][n] + beta[c])            (hrnet.py:397-411)
 //             written POINT-MAJOR into the caller's row (the csa half of the output layer's input: the concatenation of
 //             hrnet.py:423 costs nothing)

@@ -549,7 +549,9 @@ CSN_API int csn_masked_ce_bwd_f32(const float* logits, long long shape_stride, i
  * the kernels read.  Maps xhat / dxhat are the varlen attention's channel-major, pre-affine LayerNorm outputs
  * [n_evals][channels][ld] at eval_stride floats per evaluation (ld, eval_stride % 4, 16-byte aligned); evaluation e has
  * counts[e] real points — the points [counts[e], ld) enter no sum and are written as zero in every gradient map (the varlen
- * attention runs round-up-4(counts[e]) queries: the points up to that bound hold real, non-zero values).
+ * attention runs round-up-4(counts[e]) queries: the points up to that bound hold real, non-zero values).  The points
+ * [counts[e], ld) of xhat must still be FINITE: csn_ragged_mix_bwd_f32 forms 0 * xhat for the points between a shape's count
+ * and the end of its last 64-point tile, so an inf or nan there reaches rowdot (the varlen attention leaves finite values).
  * Evaluation order of the mix: ev(b, 0) = b (SSA of query shape b), ev(b, j >= 1) = cross_first + (j-1) n_shapes + b
  * (MHA(q_b, k_{j,b}, k_{j,b})); k1 = K + 1 <= 8.  All sums accumulate in fp64 in a fixed order (bitwise reproducible).
  * csn_ragged_pool_f32      pooled[e][c] = gamma[c] mean_{n < counts[e]} xhat[e][c][n] + beta[c]  (hrnet.py:380-381, 388-389:

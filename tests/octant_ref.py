@@ -8,7 +8,8 @@ coordinate dictionary — no searchsorted, no tables:
   up          y[i] = x[parent[i]] W[octant[i]]  (+ bias)
 
 ``down`` / ``up`` and their gradients walk the fine rows one by one.  The point sets are those of tests/sparse_conv_ref.py, plus one
-whose y are all even (the octants with oy = 1 are empty)."""
+whose y are all even (the octants with oy = 1 are empty), two dense boxes whose octant segments fill the 128-row tile exactly or miss it
+by one row, and the cases that take the weight gradient past one 16-row step per wave."""
 import functools
 
 import torch
@@ -19,6 +20,27 @@ from tests import sparse_conv_ref as R
 def even_y(n=200, ts=1):
     """``random_set`` with every y doubled: four empty octants."""
     return [[b, x, 2 * y, z] for b, x, y, z in R.random_set(n, ts=ts)]
+
+
+def box128():
+    """A dense 16 x 16 x 4 block of one shape on even corners: 1024 fine rows, 128 coarse rows, eight segments of exactly 128 rows
+    (every 128-row tile exactly full, the slot behind it empty)."""
+    return [[0, x, y, z] for z in range(4) for y in range(16) for x in range(16)]
+
+
+def box127_129():
+    """``box128`` without its last voxel (octant 7) plus one far-away voxel on an even corner (octant 0): segments
+    [129, 128, 128, 128, 128, 128, 128, 127]."""
+    return box128()[:-1] + [[0, 1000, 1000, 1000]]
+
+
+# (point set, c_in, c_out, split-K chunk of the weight gradient by the launch rule of csn_amd/csrc/octant_conv.hip): a wave contracts
+# a quarter of the chunk in 16-row steps, so chunk 128 is two steps, 192 three (a segment of rand2100 is 192 + about 70 rows: in the
+# short chunk waves 0 and 1 work, wave 1 ends inside its second step, waves 2 and 3 have nothing), 256 four; 160 and 224 rows of dw
+# take one row block per work-group (5 and 7 of them), 256 take four.  tests/test_cpu_ragged_head.py pins the chunks.
+WGRAD_CASES = [("rand1031", 160, 256, 128), ("rand1031", 224, 256, 128), ("rand2100", 160, 256, 192), ("rand2100", 224, 256, 256),
+               ("rand2100", 256, 256, 128)]
+WGRAD_SETS = {"rand1031": lambda: R.random_set(1031), "rand2100": lambda: R.random_set(2100)}
 
 
 def level(pts, ts, times):

@@ -5,7 +5,10 @@ everywhere), random occupancy trimmed to 33 / 129 / 1031 rows (octant segments o
 128-row tile), two clusters and a line (one segment of 180 rows, seven of 9-27), their level 3 (four EMPTY octants) and a set whose
 y are all even (four empty octants) — at four width pairs, at natural and padded pitches; every kernel instance (the column blocks a
 wave owns pinned by ``CSN_DEV_SCONV_NB``); NULL outputs; determinism; the two autograd nodes and their composition on one map;
-``cat_conv3d`` against the convolution of the concatenation.
+``cat_conv3d`` against the convolution of the concatenation.  The weight gradient past one 16-row step per wave: widths (160, 256),
+(224, 256) and (256, 256) on 1031 and 2100 rows, whose split-K chunks are 128, 192 and 256 rows (every other case here has chunk 64: one
+step, the prefetch of the next never runs), with two calls of the chunk-192 case compared bit for bit; and two sets whose segments fill
+the 128-row tile exactly (eight of 128 rows) or straddle it by one row (129, six of 128, 127).
 
 Bounds (the project's contract, as tests/test_gpu_sparse_conv.py states it): weights of variance 1 / (8 c_in), outputs within 1e-4
 absolute, each gradient within 1e-4 of its tensor's max.  The contraction is 8 x 256 terms at most — shorter than the 27 x 256 that
@@ -15,7 +18,10 @@ Measured on MI355X, maxima over the cases (fp32 / bf16x3).  Raw ABI, all point s
 8.8e-6, dw 1.8e-7 / 1.4e-5, dbias 5.4e-8; up: y 1.2e-6 / 1.3e-5, dx 1.6e-6 / 1.0e-5, dw 1.6e-7 / 1.0e-5, dbias 4.3e-8.  Padded pitches:
 y 2.7e-6 / 1.5e-5, gradients <= 1.0e-6 / 1.0e-5.  Column blocks per wave pinned to 2 / 3 / 4 on 1031 rows: y 4.1e-6 / 1.5e-5, dx 1.1e-6 /
 6.5e-6, dw 1.5e-7 / 5.9e-6.  Autograd nodes: y 1.5e-6 / 1.1e-5, gradients <= 6.4e-7 / 6.5e-6.  Down + up on one map: y 3.8e-7 / 6.5e-6,
-gradients <= 2.9e-7 / 7.0e-6.  ``cat_conv3d``: y 2.3e-6 / 7.7e-6, dx 1.1e-6 / 5.0e-6, dw 1.5e-7 / 5.2e-6."""
+gradients <= 2.9e-7 / 7.0e-6.  ``cat_conv3d``: y 2.3e-6 / 7.7e-6, dx 1.1e-6 / 5.0e-6, dw 1.5e-7 / 5.2e-6.  Chunks of 128 / 192 / 256 rows, down:
+y 2.6e-6 / 1.2e-5, dx 8.8e-7 / 5.4e-6, dw 2.6e-7 / 5.3e-6, dbias 4.1e-8; up: y 1.2e-6 / 9.8e-6, dx 1.2e-6 / 5.2e-6, dw 2.0e-7 / 5.5e-6, dbias
+3.3e-8.  Exactly full tiles, down: y 6.8e-6 / 2.0e-5, dx 6.4e-7 / 7.4e-6, dw 1.4e-7 / 5.4e-6; up: y 1.2e-6 / 9.3e-6, dx 2.1e-6 / 4.6e-6, dw 1.3e-7 /
+5.5e-6."""
 import functools
 
 import pytest
@@ -30,6 +36,9 @@ CANARY = -777.25
 SETS = {"single": (R.single_voxel, 1), "dense4": (R.dense_block, 1), "rand33": (lambda: R.random_set(33), 1),
         "rand129": (lambda: R.random_set(129), 1), "rand1031": (lambda: R.random_set(1031), 1), "clusters": (R.two_clusters, 1),
         "clusters_l3": (lambda: O.level(R.two_clusters(), 1, 3)[0], 8), "even_y": (O.even_y, 1)}
+# beyond the sets every test walks: segments of exactly 128 rows, 129 / 127 rows side by side, and one large enough for weight-gradient
+# chunks of 192 and 256 rows (the cases of O.WGRAD_CASES)
+MORE_SETS = {"box128": (O.box128, 1), "box127_129": (O.box127_129, 1), "rand2100": (O.WGRAD_SETS["rand2100"], 1)}
 WIDTHS = [(32, 32), (96, 64), (64, 96), (256, 256)]
 NB_CASES = [(64, 64, 2), (96, 96, 3), (128, 128, 4), (256, 256, 4), (256, 96, 3), (96, 256, 2)]
 
@@ -53,7 +62,7 @@ def math_mode(request, L):
 def _geometry(name):
     """Dictionary partition and the octant map built on CPU tensors of one point set (shared, never modified)."""
     from csn_amd.minkowski_conv import build_octant_map
-    make, ts = SETS[name]
+    make, ts = (SETS.get(name) or MORE_SETS[name])
     pts = make()
     return O.Partition(pts, ts), build_octant_map(torch.tensor(pts), tensor_stride=ts)
 
@@ -184,6 +193,47 @@ def test_the_sets_have_the_segments_the_kernels_are_tested_on():
     assert seg("clusters")[-1] == 180 and seg("clusters")[-2] <= 27
     assert seg("clusters_l3").count(0) == 4 and seg("even_y").count(0) == 4
     assert seg("dense4") == [8] * 8
+    assert _geometry("box128")[0].segments() == [128] * 8                      # every tile exactly full, the next slot empty
+    assert (_geometry("box128")[0].n_fine, _geometry("box128")[0].n_coarse) == (1024, 128)
+    assert _geometry("box127_129")[0].segments() == [129, 128, 128, 128, 128, 128, 128, 127]
+    assert seg("rand2100")[0] >= 243 and seg("rand2100")[-1] <= 283            # a chunk of 192 or 256 rows and a short one
+    assert O.WGRAD_SETS["rand1031"]() == SETS["rand1031"][0]()
+
+
+WGRAD_IDS = [f"{n}-{a}to{b}-chunk{c}" for n, a, b, c in O.WGRAD_CASES]
+
+
+@DIRS
+@pytest.mark.parametrize("name,c_in,c_out,chunk", O.WGRAD_CASES, ids=WGRAD_IDS)
+def test_weight_gradient_past_one_step_per_wave_against_float64(L, math_mode, name, c_in, c_out, chunk, up):
+    """The split-K chunk of every case above is 64 rows: a wave contracts 16 rows, one step, and the prefetch of the next step never
+    runs.  These widths and sets give chunks of 128, 192 and 256 rows (pinned on the CPU by tests/test_cpu_ragged_head.py): two to
+    four steps per wave, a wave that ends inside a later step, waves with nothing, and 5, 7 and 2 row blocks of dw."""
+    p, m, t, f, b = _case(up, name, c_in, c_out)
+    run = Run(L, up, m, t).backward(t["dy"])
+    _check(f"mode {math_mode} {'up' if up else 'down'} {name} {c_in}->{c_out} chunk {chunk}", run, f, b)
+    for key in ("y", "dx", "dw", "dbias"):
+        assert not bool((getattr(run, key) == CANARY).any()), key
+    if chunk == 192:
+        again = Run(L, up, m, t).backward(t["dy"])
+        for key in ("y", "dx", "dw", "dbias"):
+            assert torch.equal(getattr(run, key), getattr(again, key)), key     # two calls give the same bits
+
+
+@DIRS
+@pytest.mark.parametrize("c_in,c_out", [(96, 64), (256, 256)], ids=["96to64", "256to256"])
+@pytest.mark.parametrize("name", ["box128", "box127_129"])
+def test_exactly_full_tiles_write_every_row_once(L, math_mode, name, c_in, c_out, up):
+    """Segments of exactly 128 rows (a tile exactly full, the slot behind it empty) and of 129 and 127 rows side by side: every output
+    row of the one-weight row product is written (no canary left) with the right values, dw[k] of every octant is right."""
+    p, m, t, f, b = _case(up, name, c_in, c_out)
+    run = Run(L, up, m, t).backward(t["dy"])
+    _check(f"mode {math_mode} {'up' if up else 'down'} {name} n {p.n_fine}/{p.n_coarse} {c_in}->{c_out}", run, f, b)
+    for key in ("y", "dx", "dw", "dbias"):
+        assert not bool((getattr(run, key) == CANARY).any()), key
+    for k in range(8):
+        scale = max(b["dw"][k].abs().max().item(), 1e-30)
+        assert _err(run.dw[k], b["dw"][k]) < 1e-4 * scale, k                     # each octant against its own maximum
 
 
 @DIRS
