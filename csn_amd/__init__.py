@@ -41,7 +41,7 @@ from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load
 from .minkowski_unet import (Res16UNet14, Res16UNet14A, Res16UNet14A2, Res16UNet14B, Res16UNet14B2, Res16UNet14B3,  # noqa: E402,F401
                              Res16UNet14C, Res16UNet14D, Res16UNet18, Res16UNet18A, Res16UNet18B, Res16UNet18D, Res16UNet34,
                              Res16UNet34A, Res16UNet34B, Res16UNet34C, Res16UNet50, Res16UNet101, Res16UNetBase, UNetBasicBlock,
-                             UNetPyramid, build_unet_pyramid, load_me_unet_state)
+                             UNetPyramid, build_unet_pyramid, load_me_unet_state, octant_conv_bn_act)
 
 # point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
 # (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))

@@ -1620,6 +1620,50 @@ int csn_octant_up_bwd_f32(const float* dy, long long ld_dy, const float* x, long
   return csn_launch_octant_up_bwd(a, octant_mode(), (hipStream_t)stream);
 }
 
+// ---- (23) the octant convolutions with a BatchNorm + residual + ReLU epilogue (inference) ----
+// (21)'s checks on the maps, (19)'s on the residual; n_y: the rows of y and r
+static int octant_bn_args(long long ld_x, int n_x, int n_y, int n_fine, int n_coarse, int c_in, int c_out, const float* r,
+                          long long ld_r, const float* y, long long ld_y) {
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_x)) return e;
+  if (const int e = sparse_conv_map(ld_y, c_out, n_y)) return e;
+  if (r) if (const int e = sparse_conv_map(ld_r, c_out, n_y)) return e;
+  if (r == y && ld_r != ld_y) return CSN_E_ARG;                   // y as its own residual: element for element, or not at all
+  return 0;
+}
+
+int csn_octant_down_bn_act_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
+                                   const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
+                                   long long ld_y, void* stream) {
+  if (!x || !children || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (const int e = octant_bn_args(ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, r, ld_r, y, ld_y)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(children)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
+  a.w = w; a.y = y; a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
+  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
+  return csn_launch_octant_down_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
+}
+
+int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
+                                 int n_fine, int c_in, int c_out, const float* w, const float* gamma, const float* beta,
+                                 const float* running_mean, const float* running_var, float eps, const float* r, long long ld_r,
+                                 int relu, float* y, long long ld_y, void* stream) {
+  if (!x || !parent || !order || !seg || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (const int e = octant_bn_args(ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, r, ld_r, y, ld_y)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
+  a.order = order; a.seg = seg; a.w = w; a.y = y; a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
+  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
+  return csn_launch_octant_up_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
+}
+
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
 static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 

@@ -360,6 +360,9 @@ int csn_launch_octant_down_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t
 int csn_launch_octant_down_bwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
 int csn_launch_octant_up_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
 int csn_launch_octant_up_bwd(const CsnOctantConvArgs& a, int mode, hipStream_t st);
+// the two forwards with the inference epilogue of CsnSconvBnArgs (no bias): a.y = act(z s + t + r), one launch, no workspace
+int csn_launch_octant_down_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
+int csn_launch_octant_up_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 
 // ---- BatchNorm apply + branch sum + residual + ReLU on point-major rows, forward and backward (rows_bn_act.hip) ----
 struct CsnRowsBnActArgs {

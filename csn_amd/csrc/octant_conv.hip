@@ -57,62 +57,37 @@ struct OctRowsP {
   const float* bias;
 };
 
+// the inference epilogue's arguments on top of the product's (bias stays unused): c[order[r]] = act(acc * s + t + r[order[r]]),
+// s = gamma / sqrt(rvar + eps), t = beta - rmean * s
+struct OctRowsBnP : OctRowsP {
+  const float* gamma; const float* beta; const float* rmean; const float* rvar; float eps;
+  const float* r; int ldr;              // residual [M][ldr], optional; may be c itself with ldr == ldc
+  int relu;
+};
+// The epilogue's own arguments, read from the kernel-argument segment after the loop and not at kernel entry (bn_args_late of
+// sparse_conv.hip: read at entry they would sit in scalar registers across the contraction loop).
+typedef const OctRowsBnP __attribute__((address_space(4)))* OctRowsBnLateP;
+__device__ __forceinline__ OctRowsBnLateP oct_bn_args_late() {
+  OctRowsBnLateP k = (OctRowsBnLateP)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
 // C[order[r]] = A[parent[order[r]]] * B[k] (+ bias) for the entries r of one tile of segment k.  B_KN: B[k] = W[k] ([K][J]), else
 // W[k]^T (the same memory read [J][K]).  grid: column groups of NB * 32 fastest, then ceil(M / 128) + 7 row groups
+// (BN is stated in terms of NB so that the body's choice between the two epilogues is made per instance, as in sparse_conv.hip)
 template <int NB, int MODE, bool B_KN>
 __global__ __launch_bounds__(256) void octant_rows_kernel(const OctRowsP p) {
-  __shared__ __attribute__((aligned(16))) float Bs[NB * 32 * BS_PITCH];
-  __shared__ int s_dst[128];
-  const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
-  const int ncg = (p.J + NB * 32 - 1) / (NB * 32);
-  const int cg = blockIdx.x % ncg, rg = blockIdx.x / ncg;
-  const int j0 = cg * NB * 32;
-  int k, lo, hi;
-  if (!octant_span(p.seg, p.M, rg, 128, k, lo, hi)) return;           // uniform over the work-group
-  const int r = lo + wave * 32 + li;                                  // the lane's entry of `order`
-  int dst = r < hi ? p.order[r] : -1;
-  if (dst >= p.M) dst = -1;
-  int src = dst >= 0 ? p.parent[dst] : -1;
-  if (src >= p.n_src) src = -1;
-  if (h == 0) s_dst[wave * 32 + li] = dst;
-  const csn_rsrc_t ar = csn_make_rsrc(p.a, ((long long)(p.n_src - 1) * p.lda + p.K) * 4LL);
-  const unsigned a_row = src < 0 ? CSN_OOB : (unsigned)src * (unsigned)p.lda * 4u + (unsigned)((MODE == 0 ? 4 : 8) * h * 4);
-  const float* bk = p.b + (long long)k * p.c_in * p.c_out;
-  const int S = p.K >> 5;                                             // 32-channel steps
+  constexpr bool BN = NB < 0;
+#include "octant_rows_body.inc"
+}
 
-  f32x16 acc[NB] = {};
-  f32x4 an[4], bn[NB];
-  auto load = [&](int s) {
-    const unsigned off = src < 0 ? CSN_OOB : a_row + (unsigned)(s * 128);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) an[g] = csn_bload4(ar, off + (unsigned)(a_kofs<MODE>(g) * 4));
-    load_b<NB, B_KN>(bn, bk, p.c_out, s * 32, j0, p.J, tid);
-  };
-  load(0);
-  for (int s = 0; s < S; ++s) {
-    __syncthreads();                                                  // the previous step's reads of Bs are done
-    store_b<NB, B_KN, MODE>(Bs, bn, tid);
-    f32x4 af[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) af[g] = an[g];
-    __syncthreads();
-    if (s + 1 < S) load(s + 1);
-    mma_step<NB, MODE>(acc, af, Bs, li, h);
-  }
-
-  // the wave's 32 rows leave for their own places: accumulator row rr of the lane goes to row s_dst[rr], 32 lanes one 128-byte run
-  const csn_rsrc_t cr = csn_make_rsrc(p.c, ((long long)(p.M - 1) * p.ldc + p.J) * 4LL);
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    if (j0 + nb * 32 >= p.J) continue;                                // wave-uniform: J % 32 == 0
-    const int col = j0 + nb * 32 + li;
-    const float bv = p.bias ? p.bias[col] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int d = s_dst[wave * 32 + csn_acc_row(q, h)];
-      csn_bstore(acc[nb][q] + bv, cr, d < 0 ? CSN_OOB : ((unsigned)d * (unsigned)p.ldc + (unsigned)col) * 4u);
-    }
-  }
+// the up convolution's forward with the inference epilogue: the same body, kernels of their own (the instances above keep their
+// names, arguments and code)
+template <int NB, int MODE>
+__global__ __launch_bounds__(256) void octant_rows_bn_kernel(const OctRowsBnP p) {
+  constexpr bool B_KN = true, BN = NB > 0;
+#include "octant_rows_body.inc"
 }
 
 struct OctWgradP {
@@ -229,9 +204,20 @@ int launch_rows_nb(const OctRowsP& p, int mode, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// the instances with the inference epilogue (the up convolution's forward only)
+template <int NB, bool B_KN>
+int launch_rows_nb(const OctRowsBnP& p, int mode, hipStream_t st) {
+  static_assert(B_KN, "the inference epilogue belongs to the forward product");
+  const long long groups = (long long)((p.J + NB * 32 - 1) / (NB * 32)) * (((long long)p.M + 127) / 128 + 7);
+  if (groups > 0x7fffffffLL) return -5;
+  auto* const k = mode == 0 ? octant_rows_bn_kernel<NB, 0> : octant_rows_bn_kernel<NB, 1>;
+  hipLaunchKernelGGL(k, dim3((unsigned)groups), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
 // the column blocks a wave owns: the rule of sparse_conv.hip's launch_gemm (CSN_DEV_SCONV_NB pins them here too)
-template <bool B_KN>
-int launch_rows(const OctRowsP& p, int mode, hipStream_t st) {
+template <bool B_KN, typename P>
+int launch_rows(const P& p, int mode, hipStream_t st) {
   const int t = p.J / 32;
   int nb = t <= 4 ? t : (t + 1) / 2;
   const long long row_groups = ((long long)p.M + 127) / 128;
@@ -310,6 +296,23 @@ int csn_launch_octant_up_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t s
   OctRowsP p{};
   p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_coarse; p.parent = a.parent; p.order = a.order; p.seg = a.seg; p.b = a.w;
   p.c_in = a.c_in; p.c_out = a.c_out; p.c = a.y; p.ldc = a.ld_y; p.M = a.n_fine; p.K = a.c_in; p.J = a.c_out; p.bias = a.bias;
+  return launch_rows<true>(p, mode != 0, st);
+}
+
+// the two forwards with the inference epilogue (include/csn_hip.h section 23): one launch each, no workspace.  Down is the
+// gather-GEMM's BN instances over children[8][n_coarse]; a coarse row without children has acc = 0 and gives act(t + r)
+int csn_launch_octant_down_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st) {
+  CsnSparseConvArgs g = gather_args(a);
+  g.x = a.x; g.ld_x = a.ld_x; g.n_in = a.n_fine; g.fwd_table = a.children; g.n_out = a.n_coarse; g.y = a.y; g.ld_y = a.ld_y;
+  return csn_launch_sparse_conv_bn_act_fwd(g, n, mode != 0, st);
+}
+
+int csn_launch_octant_up_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st) {
+  OctRowsBnP p{};
+  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_coarse; p.parent = a.parent; p.order = a.order; p.seg = a.seg; p.b = a.w;
+  p.c_in = a.c_in; p.c_out = a.c_out; p.c = a.y; p.ldc = a.ld_y; p.M = a.n_fine; p.K = a.c_in; p.J = a.c_out;
+  p.gamma = n.gamma; p.beta = n.beta; p.rmean = n.running_mean; p.rvar = n.running_var; p.eps = n.eps;
+  p.r = n.r; p.ldr = n.ld_r; p.relu = n.relu;
   return launch_rows<true>(p, mode != 0, st);
 }
 

@@ -495,8 +495,20 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t if _pitched(t) else t.contiguous()
 
 
+_ZEROS: Dict[Tuple[torch.device, int], torch.Tensor] = {}
+
+
+def _zero_vec(device: torch.device, c: int) -> torch.Tensor:
+    """``c`` fp32 zeros on ``device``, made once (never written)."""
+    key = (device, c)
+    if key not in _ZEROS:
+        _ZEROS[key] = torch.zeros(c, device=device, dtype=torch.float32)
+    return _ZEROS[key]
+
+
 def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, norm: nn.BatchNorm1d,
-                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None, *,
+                       shift: bool = True) -> torch.Tensor:
     """``y (n_out, c_out) = act(conv(x) s + t + residual)`` in one launch (``csn_sparse_conv_bn_act_fwd_f32``): ``conv`` the
     convolution ``kmap`` describes without a bias, ``s = gamma / sqrt(running_var + eps)``, ``t = beta - running_mean s`` from
     ``norm``'s running statistics, ``act`` the ReLU or the identity.  Inference only: no autograd node, the result has no ``grad_fn``.
@@ -505,7 +517,8 @@ def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, n
     16-byte aligned data pointer); ``x`` and ``residual`` are made contiguous otherwise, ``out`` raises ``ValueError``.  With
     ``out`` the result is written there (a column block of a wider buffer keeps its other columns) and ``out`` is returned;
     ``residual`` may be ``out`` itself — a sum that accumulates in place — and must not overlap it in any other way.  An input width
-    that is no multiple of 32 is zero-padded as in ``sparse_conv3d``."""
+    that is no multiple of 32 is zero-padded as in ``sparse_conv3d``.  ``shift=False`` hands the launch zero ``beta`` and
+    ``running_mean`` vectors (``t = 0``): the later launches of a chain that adds the products of an input's column blocks in place."""
     if not (x.is_cuda and weight.is_cuda) or (residual is not None and not residual.is_cuda) or (out is not None and not out.is_cuda):
         raise _lib.CsnError(_NO_CPU)
     if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
@@ -535,6 +548,8 @@ def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, n
             raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer")
     r = None if residual is None else (y if same else _rows(residual))
     vec = [v.detach().float().contiguous() for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+    if not shift:
+        vec[1] = vec[2] = _zero_vec(x.device, c_out)
     with CF.rows16(tuning.current().rows_single_product):
         _lib.check(_lib.lib().csn_sparse_conv_bn_act_fwd_f32(
             CF._ptr(x), x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w), *(CF._ptr(v) for v in vec),

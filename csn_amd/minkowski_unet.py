@@ -18,9 +18,16 @@ fused.  ``fused=False`` runs everything on ``sparse_conv3d`` / the octant nodes 
 coordinate sets ``build_pyramid`` gives —, per level the kernel-3 and the kernel-1 map, at level 0 the stem's map, between
 neighbouring levels the octant map.
 
+Inference (``tuning.override(eval_epilogue=True)``, a fused network in eval mode with autograd disabled): every convolution + norm
+is ONE library call (``Res16UNetBase._forward_infer``) — ``sparse_conv_bn_act`` (section 19) for the kernel-3 / kernel-1
+convolutions, ``octant_conv_bn_act`` (section 23) for the eight resolution changes.  A decoder level's ``[up | skip]`` input is one
+buffer that the transposed convolution and the launch that produces the skip map write their column blocks of; a block that reads
+more than 256 columns runs ``conv1`` and the ``downsample`` convolution as a chain of two launches over the two column blocks.
+
 Offset and octant numbering and the sorted order of the coarse levels are this project's choice (minkowski_conv.py): parity unpinned
-against MinkowskiEngine's own checkpoints.  The switches ``grouped_passes``, ``eval_epilogue`` and ``rows_single_product`` of
-``tuning`` leave these networks as they are (``rows_single_product`` reaches the kernel-3 / kernel-1 convolutions as everywhere).
+against MinkowskiEngine's own checkpoints.  The switch ``grouped_passes`` of ``tuning`` leaves these networks as they are;
+``rows_single_product`` reaches the kernel-3 / kernel-1 convolutions as everywhere, in training and on the inference graph, and
+never the octant products (sections 21 and 23 have no single-product instances).
 """
 from __future__ import annotations
 
@@ -31,10 +38,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import functional as CF
 from . import minkowski_conv as _mc
+from . import minkowski_hrnet as _mh
+from . import tuning
 from .minkowski_conv import (KernelMap, OctantMap, SparseConv3d, SparseConvDown2, SparseConvUp2, build_kernel_map, build_octant_map,
                              cat_conv3d)
-from .minkowski_hrnet import HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _keep
+from .minkowski_hrnet import (HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _conv_bn_act, _keep, _pitched, _rows,
+                              sparse_conv_bn_act)
 
 _NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
 N_LEVELS = 5
@@ -106,6 +117,70 @@ def _build_unet_pyramid_hip(coords: torch.Tensor, stem_kernel: int) -> UNetPyram
     return UNetPyramid([s.coords for s in sets], s1, one, stem, octs, stem_kernel)
 
 
+# ------------------------------------------------------------------------------------------------------
+# inference: an octant convolution + BatchNorm + residual + ReLU as one launch (section 23)
+# ------------------------------------------------------------------------------------------------------
+def octant_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, norm: nn.BatchNorm1d, up: bool,
+                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = act(conv(x) s + t + residual)`` in one launch, the counterpart of ``sparse_conv_bn_act`` for the kernel-2 stride-2
+    convolution (``up`` False: ``x (n_fine, c_in)`` -> ``(n_coarse, c_out)``, ``csn_octant_down_bn_act_fwd_f32``) and its transposed
+    form (``up`` True: ``x (n_coarse, c_in)`` -> ``(n_fine, c_out)``, ``csn_octant_up_bn_act_fwd_f32``), both without a bias:
+    ``weight (8, c_in, c_out)``, ``s = gamma / sqrt(running_var + eps)``, ``t = beta - running_mean s`` from ``norm``'s running
+    statistics, ``act`` the ReLU or the identity.  Inference only: no autograd node, the result has no ``grad_fn``.
+
+    ``x``, ``residual`` and ``out`` may be row-pitched views of a wider buffer (``stride(1) == 1``, ``stride(0) % 4 == 0``, a
+    16-byte aligned data pointer); ``x`` and ``residual`` are made contiguous otherwise, ``out`` raises ``ValueError``.  With
+    ``out`` the result is written there and ``out`` is returned; ``residual`` may be ``out`` itself and must not overlap it in any
+    other way.  The products run in fp32 (math mode 0) or as bf16x3 (every other mode), whatever ``rows_single_product`` says."""
+    if not (x.is_cuda and weight.is_cuda) or (residual is not None and not residual.is_cuda) or (out is not None and not out.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if not isinstance(omap, OctantMap):
+        raise ValueError(f"a kernel-2 stride-2 convolution takes an OctantMap, not {type(omap).__name__}")
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != 8:
+        raise ValueError("x must be (n_in, c_in) and weight (8, c_in, c_out)")
+    n_fine, n_coarse = omap.n_fine, omap.n_coarse
+    n_in, n_out = (n_coarse, n_fine) if up else (n_fine, n_coarse)
+    if x.shape[0] != n_in:
+        raise ValueError(f"x has {x.shape[0]} rows, the map's input set {n_in}")
+    _, c_in, c_out = weight.shape
+    for name, c in (("c_in", c_in), ("c_out", c_out)):
+        if c % 32 or not 32 <= c <= 256:
+            raise ValueError(f"{name} {c} is not supported: a multiple of 32 in [32, 256]")
+    if not isinstance(norm, nn.BatchNorm1d) or norm.num_features != c_out or norm.running_mean is None or norm.weight is None:
+        raise ValueError(f"norm must be an affine nn.BatchNorm1d({c_out}) that tracks running statistics")
+    for name, t in (("residual", residual), ("out", out)):
+        if t is not None and tuple(t.shape) != (n_out, c_out):
+            raise ValueError(f"{name} must be ({n_out}, {c_out})")
+    CF._need_cuda(omap.parent, norm.weight, norm.bias, norm.running_mean, norm.running_var)
+    same = residual is not None and out is not None and residual.data_ptr() == out.data_ptr() and residual.stride() == out.stride()
+    w = weight.detach().float().contiguous()
+    x = _rows(x)
+    if out is None:
+        y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
+    else:
+        y = out.detach()
+        if not _pitched(y):
+            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer")
+    r = None if residual is None else (y if same else _rows(residual))
+    vec = [CF._ptr(v.detach().float().contiguous()) for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+    tail = (float(norm.eps), CF._ptr(r), 0 if r is None else r.stride(0), int(bool(relu)), CF._ptr(y), y.stride(0), CF._stream())
+    L = _lib.lib()
+    if up:
+        _lib.check(L.csn_octant_up_bn_act_fwd_f32(CF._ptr(x), x.stride(0), n_coarse, CF._ptr(omap.parent), CF._ptr(omap.order),
+                                                  CF._ptr(omap.seg), n_fine, c_in, c_out, CF._ptr(w), *vec, *tail),
+                   "csn_octant_up_bn_act_fwd_f32")
+    else:
+        _lib.check(L.csn_octant_down_bn_act_fwd_f32(CF._ptr(x), x.stride(0), n_fine, CF._ptr(omap.children), n_coarse, c_in, c_out,
+                                                    CF._ptr(w), *vec, *tail), "csn_octant_down_bn_act_fwd_f32")
+    return y if out is None else out
+
+
+def _octant_bn_act(conv: SparseConvDown2, norm: nn.BatchNorm1d, x, omap: OctantMap, residual=None, relu=True, out=None) -> torch.Tensor:
+    if conv.bias is not None:
+        raise ValueError("the inference launch of an octant convolution takes no bias (the Res16UNets have none)")
+    return octant_conv_bn_act(x, conv.kernel, omap, norm, conv.up, residual, relu, out)
+
+
 class CatConv3d(nn.Module):
     """A stride-1 convolution whose input is a concatenation wider than 256 columns: it holds MinkowskiEngine's ``kernel (KV,
     c_in, c_out)`` and runs ``cat_conv3d`` on the parts."""
@@ -169,6 +244,47 @@ class UNetBasicBlock(nn.Module):
             res = ("r", ds_norm(ds_conv(parts, one)))
         _keep(trace, prefix + "norm1", out)
         return _keep(trace, prefix + "norm2", _combine([_conv_bn(self.conv2, self.norm2, out, s1, f), res], f, tr, self.norm2.eps))
+
+    def _column_kernels(self, conv, widths: Sequence[int]) -> List[torch.Tensor]:
+        """``conv.kernel`` cut along c_in into contiguous (KV, w, c_out) pieces, made once per state of the parameter."""
+        key = (conv.kernel.data_ptr(), conv.kernel._version, tuple(widths))
+        cache = self.__dict__.setdefault("_cut", {})
+        if cache.get(id(conv), (None,))[0] != key:
+            cache[id(conv)] = (key, [k.contiguous() for k in conv.kernel.detach().float().split(list(widths), dim=1)])
+        return cache[id(conv)][1]
+
+    def _infer_conv(self, conv, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, widths: Sequence[int], relu: bool) -> torch.Tensor:
+        """One convolution + norm that reads the block's input: one launch up to 256 columns; beyond, a chain over the input's
+        column blocks ``widths`` (each a multiple of 32, at most 256): the first launch writes ``z0 s + t`` without a ReLU, each
+        further one adds its ``z_i s`` to that map in place (zero shift) and the last applies the activation."""
+        if isinstance(conv, SparseConv3d):
+            return _conv_bn_act(conv, norm, x, kmap, relu=relu)
+        if kmap.kernel_size != conv.kernel_size or kmap.stride != 1 or kmap.transposed:
+            raise ValueError("the map does not fit this layer")
+        if sum(widths) != self.inplanes or any(w % 32 or not 32 <= w <= 256 for w in widths):
+            raise ValueError(f"column blocks {list(widths)} do not cut {self.inplanes} columns into multiples of 32 up to 256")
+        y, c0 = None, 0
+        for i, (w, k) in enumerate(zip(widths, self._column_kernels(conv, widths))):
+            y = sparse_conv_bn_act(x[:, c0:c0 + w], k, kmap, norm, residual=y, relu=relu and i == len(widths) - 1, out=y, shift=i == 0)
+            c0 += w
+        return y
+
+    def infer(self, x: torch.Tensor, s1: KernelMap, one: KernelMap, trace: Optional[dict] = None, prefix: str = "",
+              out: Optional[torch.Tensor] = None, widths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The block on the inference launches, ``x (n, inplanes)`` a map or the level's ``[up | skip]`` buffer: ``conv1`` + ``norm1``
+        + ReLU, the ``downsample`` convolution + its norm without a ReLU, ``conv2`` + ``norm2`` with that result as its residual,
+        then the ReLU (written to ``out`` when given, else in place over the residual).  ``widths``: the column blocks of a wider
+        input (default: 256 and the rest); the two convolutions that read it are then chains, ``(z0 s + t) + z1 s`` — a summation
+        order of its own, neither ``cat_conv3d``'s ``z0 + z1`` nor the one launch's."""
+        if not x.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+        if x.dim() != 2 or x.shape[1] != self.inplanes:
+            raise ValueError(f"x is {tuple(x.shape)}; this block takes {self.inplanes} columns")
+        if widths is None:
+            widths = [self.inplanes] if self.inplanes <= 256 else [256, self.inplanes - 256]
+        h = _keep(trace, prefix + "norm1", self._infer_conv(self.conv1, self.norm1, x, s1, widths, True))
+        res = self._infer_conv(self.downsample[0], self.downsample[1], x, one, widths, False)
+        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, s1, residual=res, out=res if out is None else out))
 
 
 class Res16UNetBase(nn.Module):
@@ -250,6 +366,8 @@ class Res16UNetBase(nn.Module):
         if pyr.coords[0].device != feats.device:
             pyr = pyr.to(feats.device)
         f, tr = self.fused, self.training
+        if tuning.current().eval_epilogue and f and not tr and not torch.is_grad_enabled():
+            return self._forward_infer(feats, pyr, trace)
         out_p1 = _keep(trace, "bn0", _combine([_conv_bn(self.conv0p1s1, self.bn0, feats, pyr.stem, f)], f, tr, self.bn0.eps))
         skips, out = [out_p1], out_p1
         for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
@@ -262,6 +380,54 @@ class Res16UNetBase(nn.Module):
             out = _keep(trace, f"bntr{n}", F.relu(getattr(self, f"bntr{n}")(getattr(self, f"convtr{n}p{ts}s2")(out, pyr.oct[level]))))
             out = self._blocks(getattr(self, f"block{n + 1}"), [out, skips.pop()], pyr.s1[level], pyr.one[level], trace,
                                f"block{n + 1}")
+        return self.final(out)
+
+    @staticmethod
+    def _blocks_infer(seq: nn.Sequential, x: torch.Tensor, widths, s1: KernelMap, one: KernelMap, trace: Optional[dict], name: str,
+                      out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``_blocks`` on the inference launches; the list's last launch writes ``out`` when given."""
+        blocks = list(seq)
+        for i, blk in enumerate(blocks):
+            to = out if i == len(blocks) - 1 else None
+            if isinstance(blk, UNetBasicBlock):
+                x = blk.infer(x, s1, one, trace, f"{name}.{i}.", out=to, widths=widths)
+            else:
+                x = blk.infer(x, s1, trace, f"{name}.{i}.", out=to)
+        return x
+
+    def _forward_infer(self, feats: torch.Tensor, pyr: UNetPyramid, trace: Optional[dict]) -> torch.Tensor:
+        """The same network with one library call per convolution + norm: ``sparse_conv_bn_act`` for the stem and the blocks
+        (``HRBasicBlock.infer`` / ``UNetBasicBlock.infer``), ``octant_conv_bn_act`` for the eight resolution changes.  Every ReLU
+        output is a stored map.  Decoder level l's ``[up | skip]`` input is ONE (n_l, P[n] + skip) buffer, allocated before the
+        encoder runs: the launch that produces the skip map (``bn0``; the last launch of ``block1`` .. ``block3``) writes its
+        columns [P[n], P[n] + skip), the transposed convolution its columns [0, P[n]) and the decoder block reads the buffer through
+        its row pitch — no concatenation is ever copied.  Where the buffer would pass the kernels' 2 GiB window the two maps stay
+        separate and are joined with ``torch.cat``.  A block that reads more than 256 columns runs ``conv1`` and the
+        ``downsample`` convolution as two launches over the buffer's two column blocks, ``(z_up s + t) + z_skip s``: a summation
+        order of its own (``UNetBasicBlock.infer``).  ``final`` stays the ``nn.Linear``."""
+        P, dev = self.PLANES, feats.device
+        skip_w = (self.INIT_DIM, P[0], P[1], P[2])                     # the skip map's width at level 0 .. 3
+        up_w = (P[7], P[6], P[5], P[4])                                # the transposed convolution's at level 0 .. 3
+        cat = []
+        for l in range(4):
+            n_l, w = pyr.coords[l].shape[0], up_w[l] + skip_w[l]
+            cat.append(torch.empty((n_l, w), device=dev, dtype=torch.float32) if n_l * w * 4 <= _mh._WINDOW else None)
+        skip_to = lambda l: None if l > 3 or cat[l] is None else cat[l][:, up_w[l]:]
+        out = _keep(trace, "bn0", _conv_bn_act(self.conv0p1s1, self.bn0, feats, pyr.stem, out=skip_to(0)))
+        skips = [out]
+        for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
+            out = _keep(trace, f"bn{n}", _octant_bn_act(getattr(self, f"conv{n}p{ts}s2"), getattr(self, f"bn{n}"), out, pyr.oct[n - 1]))
+            out = self._blocks_infer(getattr(self, f"block{n}"), out, None, pyr.s1[n], pyr.one[n], trace, f"block{n}", skip_to(n))
+            skips.append(out)
+        skips.pop()                                                    # block4's output goes up, not across
+        for n, ts in ((4, 16), (5, 8), (6, 4), (7, 2)):
+            l = 7 - n
+            up = _keep(trace, f"bntr{n}", _octant_bn_act(getattr(self, f"convtr{n}p{ts}s2"), getattr(self, f"bntr{n}"), out, pyr.oct[l],
+                                                         out=None if cat[l] is None else cat[l][:, :up_w[l]]))
+            skip = skips.pop()
+            x = cat[l] if cat[l] is not None else torch.cat([up, skip], dim=1)
+            out = self._blocks_infer(getattr(self, f"block{n + 1}"), x, (up_w[l], skip_w[l]), pyr.s1[l], pyr.one[l], trace,
+                                     f"block{n + 1}", None)
         return self.final(out)
 
 

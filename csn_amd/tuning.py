@@ -86,7 +86,10 @@ class Tuning:
     # every convolution + BatchNorm (+ residual, + ReLU) is ONE launch of include/csn_hip.h section 19 instead of sparse_conv3d +
     # bn_act, a branch sum accumulates in one buffer, and the concatenated result is written in place (no torch.cat).  A branch sum
     # is added in an order of its own, so results differ from the two-launch path by fp32 rounding.  Training, grad-enabled and
-    # fused=False calls never see it.  Off: opt-in (bytes and timing: DESIGN.md "Inference backbone", scripts/bench_hrnet.py)
+    # fused=False calls never see it.  Off: opt-in (bytes and timing: DESIGN.md "Inference backbone", scripts/bench_hrnet.py).
+    # The Res16UNets under the same conditions (Res16UNetBase._forward_infer): section 19 for the stem and the blocks, section 23
+    # for the eight resolution changes, a decoder level's [up | skip] input written in place, a convolution over more than 256
+    # columns as a chain of two launches — again a summation order of its own (DESIGN.md "Inference U-Net", scripts/bench_unet.py)
     eval_epilogue: bool = False
     # kNN shape graphs (construct_shape_graph with screen=None, CrossShapeAt.get_knn_graph / get_knn_graph_big): an fp16 pass over all
     # pairs (csn_ragged_retrieval_screen_f16) names the candidates that provably cannot be among a row's top K — more than

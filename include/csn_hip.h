@@ -1047,6 +1047,40 @@ CSN_API long long csn_octant_order_workspace_bytes(int n);
 CSN_API int csn_octant_order_i32(const int* octant, int n, int* order, int* seg, void* ws, long long ws_bytes, int* status,
                          void* stream);
 
+/* ---- (23) inference: the octant convolutions of (21) with the BatchNorm + residual + ReLU epilogue of (19) (MinkowskiNet/models/
+ *           res16unet.py: conv{n}p{ts}s2 + bn{n} + relu, convtr{n}p{ts}s2 + bntr{n} + relu) ------------------------------------------
+ * In eval mode a Res16UNet's eight resolution changes need no round trip of z through memory either: ONE launch forms the product
+ * of (21) and applies the BatchNorm on its running statistics, an optional residual and the activation to the accumulators.
+ * Additive to ABI version 17.  The map arguments are (21)'s without bias, the tail is (19)'s:
+ *   DOWN  acc[j] = sum_k x[children[k][j]] W[k]      y[n_coarse][ld_y], r[n_coarse][ld_r]
+ *   UP    acc[i] = x[parent[i]] W[octant[i]]         y[n_fine][ld_y],   r[n_fine][ld_r]
+ *   s[c] = gamma[c] / sqrt(running_var[c] + eps),  t[c] = beta[c] - running_mean[c] s[c]                      (fp32)
+ *   y[.][c] = act(acc s + t + r[.][c])               act = ReLU (relu != 0) or the identity; acc s + t is one fused multiply-add
+ * acc is exactly the sum of csn_octant_down_fwd_f32 / csn_octant_up_fwd_f32 with bias = NULL in the same math mode: the same
+ * contraction loop text, the same order.  s and t are formed per column block in the epilogue from the four vectors: no
+ * preparation launch, no workspace, no atomics; two identical calls give the same bits.  Nothing but y is written; x, r and y may
+ * be column blocks of wider buffers (independent pitches).  DOWN is (19)'s kernel over a table of 8 offsets: a coarse row without
+ * children has acc = 0 and gives act(t + r).  UP are kernels of their own around (21)'s one-weight loop; its index rules hold: a
+ * destination order[r] outside [0, n_fine) is dropped, a parent past n_coarse reads as no voxel (acc = 0), seg is read as a
+ * monotone sequence inside [0, n_fine], y and r go through buffer descriptors with the range check, every output row is written
+ * exactly once.
+ * ALIASING as in (19): r may be y itself (the same pointer AND ld_r == ld_y), every element read and then written by the same lane;
+ * r == y with ld_r != ld_y returns CSN_E_ARG; any other overlap is the caller's error.
+ * Host-side checks before any launch — exactly (21)'s codes, with r (when given; NULL: ld_r ignored) checked like y as in (19):
+ * x, an index array, w, a vector or y NULL, n_fine or n_coarse < 1: CSN_E_ARG; c_in % 32 == 0 and c_out % 32 == 0, both in [32, 256]
+ * (CSN_E_DIM); every pitch % 4 == 0 (CSN_E_ALIGN), >= its width (CSN_E_ARG), <= 2^20 and rows * pitch * 4 < 2 GiB (CSN_E_DIM); x, w,
+ * y, r 16-byte aligned, the index arrays 4-byte (CSN_E_PTR).
+ * Math modes as in (21): mode 0 the exact fp32 matrix instruction, every other mode bf16x3 whatever csn_set_thread_rows16 says.
+ * The launch rule for the column blocks a wave owns and CSN_DEV_SCONV_NB apply as in (21). */
+CSN_API int csn_octant_down_bn_act_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in,
+                                   int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
+                                   long long ld_y, void* stream);
+CSN_API int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order,
+                                 const int* seg, int n_fine, int c_in, int c_out, const float* w, const float* gamma,
+                                 const float* beta, const float* running_mean, const float* running_var, float eps, const float* r,
+                                 long long ld_r, int relu, float* y, long long ld_y, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

@@ -16,6 +16,15 @@ process: the figure is the median over the rounds of each round's median, ``spre
 (scripts/bench_hrnet.py).  Prints one JSON line.
 
     python scripts/bench_unet.py --out profiles/unet_bench.json
+
+``--infer`` times the eval variants instead and nothing else: the forward of ``Res16UNet34C`` and of ``Res16UNet14`` (every decoder
+block wider than 256 columns) in eval mode under ``torch.no_grad()`` with ``tuning.eval_epilogue`` off (``training_graph``: what
+the networks ran before the switch reached them) against on (``one_launch``: ``Res16UNetBase._forward_infer``), in math modes fp32
+and bf16x3, the same rounds in one process.  ``counted_bytes`` is the traffic of the maps between a convolution's accumulators and
+the next gather (``infer_bytes``; the gathers and the weights are the same reads in both graphs), ``library_calls`` the C-ABI calls
+of one forward.
+
+    python scripts/bench_unet.py --infer --rounds 5 --out profiles/unet_infer_bench.json
 """
 import argparse
 import json
@@ -52,6 +61,96 @@ def eager_octant(omap):
     return down, up
 
 
+def infer_bytes(net, rows):
+    """Bytes of the maps written and read back between a convolution's accumulators and the next convolution's gather, per forward
+    of ``net`` on levels of ``rows`` voxels: (training_graph, one_launch), counted as ``scripts/bench_hrnet.infer_bytes`` does.  With
+    e = 4 n c for an (n, c) map — training graph in eval mode: a fused convolution writes z (e) and ``bn_act`` reads every z of its
+    sum and the residual and writes y; an octant convolution writes z, ATen's BatchNorm reads and writes it, ``F.relu`` again (5 e); a
+    block that reads more than 256 columns forms each of its two sums with ``cat_conv3d`` (two z written, both read, one written: 5
+    e), ATen's BatchNorm (2 e) and, for ``conv1``, ``F.relu`` (2 e); a narrower decoder block's ``torch.cat`` reads and writes its
+    input once.  One launch: every launch writes y and reads its residual; the second launch of a chain reads and writes the sum."""
+    from csn_amd.minkowski_unet import UNetBasicBlock
+    two = one = 0
+    P = net.PLANES
+    e = lambda level, c: 4 * rows[level] * c
+
+    def blocks(seq, level):
+        nonlocal two, one
+        for blk in seq:
+            c = blk.norm2.num_features
+            if isinstance(blk, UNetBasicBlock):
+                if blk.inplanes > 256:
+                    two += (5 + 2 + 2) * e(level, c) + (5 + 2) * e(level, c)    # conv1: cat_conv3d, norm, relu; downsample: cat_conv3d, norm
+                    one += 2 * 3 * e(level, c)                                  # two chains: y written, read and written again
+                else:
+                    two += 3 * e(level, c) + e(level, c)                        # conv1: z w, z r, y w; downsample: z w
+                    one += 2 * e(level, c)                                      # two launches: y written
+                two += (2 + 2) * e(level, c)                                    # conv2: z w; bn_act: two z (or z and the map) r, y w
+                one += 2 * e(level, c)                                          # the residual read, y written
+            else:
+                two += 3 * e(level, c) + 4 * e(level, c)                        # conv1: z w, z r, y w; conv2: z w, z r, x r, y w
+                one += e(level, c) + 2 * e(level, c)
+    two += 3 * e(0, net.INIT_DIM)
+    one += e(0, net.INIT_DIM)
+    c = net.INIT_DIM
+    for n in (1, 2, 3, 4):
+        two += 5 * e(n, c)
+        one += e(n, c)
+        blocks(getattr(net, f"block{n}"), n)
+        c = P[n - 1]
+    skips = (P[2], P[1], P[0], net.INIT_DIM)
+    for n in (4, 5, 6, 7):
+        level = 7 - n
+        two += 5 * e(level, P[n])
+        one += e(level, P[n])
+        if P[n] + skips[n - 4] <= 256:
+            two += 2 * e(level, P[n] + skips[n - 4])                            # torch.cat: read + write
+        blocks(getattr(net, f"block{n + 1}"), level)
+    return two, one
+
+
+def infer(a):
+    import csn_amd
+    csn_amd.build()
+    from csn_amd import _lib, build_unet_pyramid, tuning
+    from csn_amd import functional as CF
+    torch.manual_seed(0)
+    coords = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
+    pyr = build_unet_pyramid(coords)
+    n = coords.shape[0]
+    rows = [int(c.shape[0]) for c in pyr.coords]
+    res = {"voxels": int(n), "level_rows": rows, "shapes": a.shapes, "warmup": a.warmup, "iters": a.iters, "rounds": a.rounds,
+           "device": torch.cuda.get_device_name(0), "what": "Res16UNet forward, eval, no_grad: eval_epilogue off against on"}
+    feats = torch.randn(n, 3, device="cuda")
+    for name in ("Res16UNet34C", "Res16UNet14"):
+        net = getattr(csn_amd, name)(3, 16).cuda().eval()
+
+        def step_of(mode, on):
+            def step():
+                with torch.no_grad(), CF.math_mode(CF.mode_id(mode)), tuning.override(eval_epilogue=on):
+                    net((pyr, feats))
+            return step
+        two, one = infer_bytes(net, rows)
+        calls = {}
+        for v, on in (("training_graph", False), ("one_launch", True)):
+            count = [0]
+            _lib.set_call_hook(lambda _name, phase: count.__setitem__(0, count[0] + (phase == "begin")))
+            try:
+                step_of("bf16x3", on)()
+            finally:
+                _lib.set_call_hook(None)
+            calls[v] = count[0]
+        res[name] = {"counted_bytes": {"training_graph": two, "one_launch": one}, "library_calls": calls}
+        for mode in ("fp32", "bf16x3"):
+            r = compare({"training_graph": step_of(mode, False), "one_launch": step_of(mode, True)}, a.warmup, a.iters, a.rounds)
+            gap = r["training_graph_ms"] - r["one_launch_ms"]
+            noise = max(r[f"{v}_spread_ms"][1] - r[f"{v}_spread_ms"][0] for v in ("training_graph", "one_launch"))
+            r["speedup"] = r["training_graph_ms"] / r["one_launch_ms"]
+            r["one_launch_is_faster"] = bool(gap > noise and r["one_launch_spread_ms"][1] < r["training_graph_spread_ms"][0])
+            res[name][f"eval_fwd_{mode}"] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--voxels", type=int, default=32768)
@@ -62,7 +161,15 @@ def main():
     ap.add_argument("--mode", default="bf16x3", help="math mode: fp32 or bf16x3 (the library's default)")
     ap.add_argument("--skip-network", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--infer", action="store_true", help="time the eval variants (eval_epilogue off against on, fp32 and bf16x3) instead")
     a = ap.parse_args()
+    if a.infer:
+        line = json.dumps(infer(a))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     import csn_amd
     csn_amd.build()
     from csn_amd import Res16UNet34C, build_octant_map, build_unet_pyramid, octant_conv_down, octant_conv_up
