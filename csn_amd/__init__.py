@@ -33,9 +33,10 @@ from .minkowski_conv import (OctantMap, SparseConvDown2, SparseConvUp2, build_oc
 from .minkowski_hrnet import (HRBasicBlock, HRNetBackbone, HRNetSimCSN2S, HRNetSimCSN3S, HRNetSimCSN4S, VoxelPyramid,  # noqa: E402,F401
                               bn_act, build_pyramid, conv_stats, load_me_hrnet_state)
 from .minkowski_hrnet import GroupedPyramid, bn_act_groups, conv_stats_groups, group_pyramid, merge_batches  # noqa: E402,F401
-# the plain segmentation networks (hrnet.py:214-293) and the backbone's one-launch-per-convolution inference primitive
+# the plain segmentation networks (hrnet.py:214-293) and the backbone's one-launch-per-convolution inference primitive, on fp32
+# or (maps16_dtype: math mode "bf16" / "fp16" with rows_single_product) 16-bit maps
 from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
-                              sparse_conv_bn_act)
+                              maps16_dtype, sparse_conv_bn_act)
 
 # the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks
 from .minkowski_unet import (Res16UNet14, Res16UNet14A, Res16UNet14A2, Res16UNet14B, Res16UNet14B2, Res16UNet14B3,  # noqa: E402,F401

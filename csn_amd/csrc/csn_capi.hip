@@ -1664,6 +1664,38 @@ int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_coarse, c
   return csn_launch_octant_up_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
 }
 
+// ---- (24) the launch of (19) on 16-bit maps: x, r and y each fp32 rows or rows of the math mode's 16-bit type ----
+// a 16-bit row-major map of n rows: pitch % 8, >= its width, and the whole map inside one 2 GiB buffer window
+static int sparse_conv_map16(long long ld, int width, int n) {
+  if (ld < width) return CSN_E_ARG;
+  if (ld & 7) return CSN_E_ALIGN;
+  if (ld > (1 << 20) || (long long)n * ld * 2 > 0x7fffffffLL) return CSN_E_DIM;
+  return 0;
+}
+
+int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                   int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const void* r, int r16, long long ld_r, int relu, void* y,
+                                   int y16, long long ld_y, void* stream) {
+  if (!x || !table || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if ((x16 | r16 | y16) & ~1) return CSN_E_ARG;
+  if (mode() < 2 || !t_rows16) return CSN_E_ARG;                  // single-product instances only: 16-bit maps under bf16x3 / fp32
+                                                                  // would throw away what they pay for
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  const auto map = [](int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); };
+  if (const int e = map(x16, ld_x, c_in, n_in)) return e;
+  if (const int e = map(y16, ld_y, c_out, n_out)) return e;
+  if (r) if (const int e = map(r16, ld_r, c_out, n_out)) return e;
+  if (r == y && (r16 != y16 || ld_r != ld_y)) return CSN_E_ARG;   // y as its own residual: element for element, or not at all
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  CsnSparseConvM16Args a{};
+  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_in = n_in; a.table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
+  a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16; a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
+  return csn_launch_sparse_conv_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+}
+
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
 static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 

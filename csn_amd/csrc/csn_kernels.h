@@ -342,6 +342,19 @@ struct CsnSconvBnArgs {
 };
 int csn_launch_sparse_conv_bn_act_fwd(const CsnSparseConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule
+// the 32-column blocks a wave owns in a gather-GEMM of J columns over M rows: sparse_conv.hip's launch rule, csn_dev_sconv_nb included
+int csn_sconv_column_blocks(int J, long long M);
+// the same forward with the inference epilogue on 16-bit maps (sparse_conv_maps16.hip; math modes 2 / 3, single product): x, r and
+// y are each fp32 rows (flag 0) or rows of the mode's 16-bit type (flag 1), pitches in elements of the map's own type; the vectors,
+// eps and relu come from CsnSconvBnArgs (its r / ld_r are not read)
+struct CsnSparseConvM16Args {
+  const void* x;  int x16;  int ld_x;  int n_in;
+  const int* table;  int n_out, kv, c_in, c_out;
+  const float* w;
+  const void* r;  int r16;  int ld_r;                             // optional; may be y itself with the same type and pitch
+  void* y;  int y16;  int ld_y;
+};
+int csn_launch_sparse_conv_bn_act_fwd_m16(const CsnSparseConvM16Args& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 
 // ---- kernel-2 stride-2 convolution and its transposed form over an octant map (octant_conv.hip) ----
 struct CsnOctantConvArgs {

@@ -233,12 +233,7 @@ int launch_gemm_nb(const SconvBnP& p, int mode, hipStream_t st) {
 // csn_dev_set(CSN_DEV_SCONV_NB, 1..4) pins the column blocks per wave instead (tests reach every instance at small sizes).
 template <bool B_KN, typename P>
 int launch_gemm(const P& p, int mode, hipStream_t st) {
-  const int t = p.J / 32;
-  int nb = t <= 4 ? t : (t + 1) / 2;
-  const long long row_groups = ((long long)p.M + 127) / 128;
-  while (nb > 1 && row_groups * ((t + nb - 1) / nb) < TARGET_GROUPS) nb = (nb + 1) / 2;
-  if (csn_dev_sconv_nb > 0) nb = csn_dev_sconv_nb < t ? csn_dev_sconv_nb : t;
-  return dispatch4(nb, [&](auto n) { return launch_gemm_nb<n(), B_KN>(p, mode, st); });
+  return dispatch4(csn_sconv_column_blocks(p.J, p.M), [&](auto n) { return launch_gemm_nb<n(), B_KN>(p, mode, st); });
 }
 
 template <int TA>
@@ -252,6 +247,16 @@ int launch_wgrad_ta(const CsnSparseConvArgs& a, float* out, int splits, int chun
 }  // namespace
 
 int csn_dev_sconv_nb = 0;
+
+// launch_gemm's rule, stated once for every file that launches this product (sparse_conv_maps16.hip)
+int csn_sconv_column_blocks(int J, long long M) {
+  const int t = J / 32;
+  int nb = t <= 4 ? t : (t + 1) / 2;
+  const long long row_groups = (M + 127) / 128;
+  while (nb > 1 && row_groups * ((t + nb - 1) / nb) < TARGET_GROUPS) nb = (nb + 1) / 2;
+  if (csn_dev_sconv_nb > 0) nb = csn_dev_sconv_nb < t ? csn_dev_sconv_nb : t;
+  return nb;
+}
 
 long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward) {
   (void)n_in;

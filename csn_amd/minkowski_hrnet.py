@@ -21,6 +21,8 @@ Inference (``tuning.override(eval_epilogue=True)``, a fused backbone in eval mod
 ONE launch of include/csn_hip.h section 19 (``sparse_conv_bn_act``: the BatchNorm on its running statistics, the residual and the
 ReLU in the product's epilogue), a branch sum is a chain of such launches into one buffer, and the concatenated result is
 allocated once and written in place through the kernels' output pitch: no ``torch.cat``.  Off by default.
+With ``infer_maps16`` on top, in math mode "bf16" / "fp16" with ``rows_single_product``, the maps between those launches are bf16 /
+fp16 rows (section 24, ``sparse_conv_bn_act`` on 16-bit tensors); the stem's input and the result stay fp32.  Off by default.
 
 Grouped passes (include/csn_hip.h section 20): the K + 1 batches of a CSN training step merged into ONE coordinate set with
 shifted batch indices (``merge_batches`` -> ``GroupedPyramid``).  The rows of a batch are then a contiguous range at every level, the
@@ -490,9 +492,55 @@ def _pitched(t: torch.Tensor) -> bool:
             and t.data_ptr() % 16 == 0)
 
 
+_DTYPES16 = (torch.bfloat16, torch.float16)
+_MODE_DTYPE16 = {2: torch.bfloat16, 3: torch.float16}  # the 16-bit map type of a math mode (CSN_MATH_BF16 / CSN_MATH_FP16)
+
+
+def _pitched16(t: torch.Tensor) -> bool:
+    """``_pitched`` for bf16 / fp16 rows: a row pitch that is a multiple of 8 elements (16 bytes) and at least the width, a 16-byte
+    aligned first element."""
+    return (t.dtype in _DTYPES16 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]
+            and t.data_ptr() % 16 == 0)
+
+
 def _rows(t: torch.Tensor) -> torch.Tensor:
     t = t.detach().float()
     return t if _pitched(t) else t.contiguous()
+
+
+def _rows_any(t: torch.Tensor) -> torch.Tensor:
+    """``_rows`` that leaves 16-bit rows in their type."""
+    if t.dtype not in _DTYPES16:
+        return _rows(t)
+    t = t.detach()
+    return t if _pitched16(t) else t.contiguous()
+
+
+def maps16_dtype() -> Optional[torch.dtype]:
+    """The dtype 16-bit maps have right now — ``bfloat16`` in math mode "bf16", ``float16`` in "fp16", each with
+    ``tuning.rows_single_product`` — or None where section 24 has no instance (every other mode, or the switch off)."""
+    if not tuning.current().rows_single_product:
+        return None
+    return _MODE_DTYPE16.get(CF.current_mode())
+
+
+def _maps16_route(x, residual, out, out_dtype) -> Optional[torch.dtype]:
+    """None: an all-fp32 call (section 19).  Otherwise the 16-bit dtype of a section-24 call, checked against the math mode."""
+    given = [t.dtype for t in (x, residual, out) if t is not None] + ([] if out_dtype is None else [out_dtype])
+    if out_dtype is None and not any(d in _DTYPES16 for d in given):
+        return None
+    if out_dtype is not None and out_dtype not in (torch.float32,) + _DTYPES16:
+        raise ValueError("out_dtype must be torch.float32, torch.bfloat16 or torch.float16")
+    if out is not None and out_dtype is not None and out.dtype != out_dtype:
+        raise ValueError("out_dtype differs from out's dtype")
+    want = maps16_dtype()
+    if want is None:
+        raise ValueError('16-bit maps (a bfloat16 / float16 tensor, or out_dtype) need math mode "bf16" or "fp16" together with '
+                         "tuning.override(rows_single_product=True)")
+    other = [d for d in given if d in _DTYPES16 and d != want]
+    if other:
+        raise ValueError(f"the 16-bit maps of this math mode are {want}: got {other[0]}")
+    return want
 
 
 _ZEROS: Dict[Tuple[torch.device, int], torch.Tensor] = {}
@@ -508,7 +556,7 @@ def _zero_vec(device: torch.device, c: int) -> torch.Tensor:
 
 def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, norm: nn.BatchNorm1d,
                        residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None, *,
-                       shift: bool = True) -> torch.Tensor:
+                       shift: bool = True, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """``y (n_out, c_out) = act(conv(x) s + t + residual)`` in one launch (``csn_sparse_conv_bn_act_fwd_f32``): ``conv`` the
     convolution ``kmap`` describes without a bias, ``s = gamma / sqrt(running_var + eps)``, ``t = beta - running_mean s`` from
     ``norm``'s running statistics, ``act`` the ReLU or the identity.  Inference only: no autograd node, the result has no ``grad_fn``.
@@ -518,7 +566,16 @@ def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, n
     ``out`` the result is written there (a column block of a wider buffer keeps its other columns) and ``out`` is returned;
     ``residual`` may be ``out`` itself — a sum that accumulates in place — and must not overlap it in any other way.  An input width
     that is no multiple of 32 is zero-padded as in ``sparse_conv3d``.  ``shift=False`` hands the launch zero ``beta`` and
-    ``running_mean`` vectors (``t = 0``): the later launches of a chain that adds the products of an input's column blocks in place."""
+    ``running_mean`` vectors (``t = 0``): the later launches of a chain that adds the products of an input's column blocks in place.
+
+    16-bit maps (``csn_sparse_conv_bn_act_fwd_m16``, section 24).  In math mode "bf16" / "fp16" with ``tuning.rows_single_product``,
+    ``x``, ``residual`` and ``out`` may each be fp32 or that mode's 16-bit dtype (``bfloat16`` / ``float16``; 16-bit views need
+    ``stride(0) % 8 == 0``), and ``out_dtype`` names the type of a result allocated here.  Any 16-bit tensor, or an ``out_dtype``
+    (``torch.float32`` included: all-fp32 maps on section 24's instances, the bits of section 19), takes that route; without the
+    mode and the switch, or with a tensor of the other 16-bit type, it raises ``ValueError``.  The launch is bit-identical to the
+    fp32 one on the same values, its result rounded once (nearest even) where the output is 16-bit.  Calls on fp32 tensors without
+    ``out_dtype`` are section 19 as ever."""
+    dt16 = _maps16_route(x, residual, out, out_dtype)
     if not (x.is_cuda and weight.is_cuda) or (residual is not None and not residual.is_cuda) or (out is not None and not out.is_cuda):
         raise _lib.CsnError(_NO_CPU)
     if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
@@ -535,21 +592,30 @@ def sparse_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, n
     CF._need_cuda(kmap.fwd, norm.weight, norm.bias, norm.running_mean, norm.running_var)
     same = residual is not None and out is not None and residual.data_ptr() == out.data_ptr() and residual.stride() == out.stride()
     w = weight.detach().float()
-    x = x.detach().float()
+    x = x.detach() if x.dtype in _DTYPES16 else x.detach().float()
     pad = -c_in % 32
     if pad:
         x, w, c_in = F.pad(x, (0, pad)), F.pad(w, (0, 0, 0, pad)), c_in + pad
-    x, w = _rows(x), w.contiguous()
+    x, w = _rows_any(x), w.contiguous()
     if out is None:
-        y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
+        y = torch.empty((n_out, c_out), device=x.device, dtype=out_dtype or torch.float32)
     else:
         y = out.detach()
-        if not _pitched(y):
-            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer")
-    r = None if residual is None else (y if same else _rows(residual))
+        if not (_pitched(y) or (dt16 is not None and _pitched16(y))):
+            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer"
+                             + ("" if dt16 is None else f", or {dt16} rows with stride(0) % 8 == 0"))
+    r = None if residual is None else (y if same else _rows_any(residual))
     vec = [v.detach().float().contiguous() for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
     if not shift:
         vec[1] = vec[2] = _zero_vec(x.device, c_out)
+    if dt16 is not None:
+        is16 = lambda t: int(t is not None and t.dtype == dt16)
+        with CF.rows16(True):
+            _lib.check(_lib.lib().csn_sparse_conv_bn_act_fwd_m16(
+                CF._ptr(x), is16(x), x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w), *(CF._ptr(v) for v in vec),
+                float(norm.eps), CF._ptr(r), is16(r), 0 if r is None else r.stride(0), int(bool(relu)), CF._ptr(y), is16(y), y.stride(0),
+                CF._stream()), "csn_sparse_conv_bn_act_fwd_m16")
+        return y if out is None else out
     with CF.rows16(tuning.current().rows_single_product):
         _lib.check(_lib.lib().csn_sparse_conv_bn_act_fwd_f32(
             CF._ptr(x), x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w), *(CF._ptr(v) for v in vec),
@@ -563,9 +629,10 @@ def _fits(layer: SparseConv3d, kmap: KernelMap) -> None:
         raise ValueError("the map does not fit this layer")
 
 
-def _conv_bn_act(conv: SparseConv3d, norm: nn.BatchNorm1d, x, kmap: KernelMap, residual=None, relu=True, out=None) -> torch.Tensor:
+def _conv_bn_act(conv: SparseConv3d, norm: nn.BatchNorm1d, x, kmap: KernelMap, residual=None, relu=True, out=None,
+                 out_dtype=None) -> torch.Tensor:
     _fits(conv, kmap)
-    return sparse_conv_bn_act(x, conv.kernel, kmap, norm, residual, relu, out)
+    return sparse_conv_bn_act(x, conv.kernel, kmap, norm, residual, relu, out, out_dtype=out_dtype)
 
 
 def _bn_act(terms: Sequence[Term], grouped: bool, group_rows, residual, relu, training, eps) -> torch.Tensor:
@@ -698,10 +765,13 @@ class HRBasicBlock(nn.Module):
         return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps, g))
 
     def infer(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The block on the inference launches: two, the second with ``x`` as its residual (written to ``out`` when given)."""
-        h = _keep(trace, prefix + "norm1", _conv_bn_act(self.conv1, self.norm1, x, kmap))
-        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, kmap, residual=x, out=out))
+              out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None,
+              out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """The block on the inference launches: two, the second with ``x`` as its residual (written to ``out`` when given).
+        ``dtype`` (16-bit inference maps, ``tuning.infer_maps16``): the type of the inner map; ``out_dtype``: that of the block's
+        result (``out``'s own when given)."""
+        h = _keep(trace, prefix + "norm1", _conv_bn_act(self.conv1, self.norm1, x, kmap, out_dtype=dtype))
+        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, kmap, residual=x, out=out, out_dtype=out_dtype))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -847,21 +917,30 @@ class HRNetBackbone(nn.Module):
         to that buffer in place, the last applies the ReLU — ((own + p_0) + p_1) + ..., a summation order of its own.  The
         (N, out_channels) result is allocated once; ``bn0s1``, branch 0's last block and the last step of every final transition
         write their column blocks of it, and ``conv1s1`` reads ``out_init`` from there through the row pitch.  Where that pitch
-        would take the result past the kernels' 2 GiB window, the maps stay separate and are joined with ``torch.cat``."""
+        would take the result past the kernels' 2 GiB window, the maps stay separate and are joined with ``torch.cat``.
+
+        Under ``tuning.infer_maps16`` in math mode "bf16" / "fp16" with ``rows_single_product`` (``maps16_dtype``), every map that
+        is not a column block of the result is allocated, written and gathered in the mode's 16-bit dtype (section 24; every launch
+        is ``csn_sparse_conv_bn_act_fwd_m16``): the same products, each stored map rounded once after the launch that writes it, a
+        branch sum rounded per launch in its 16-bit buffer.  The stem's input, the result and the launches that write its column
+        blocks stay fp32 (so does ``torch.cat``'s input past the window); ``trace`` receives the maps as stored."""
+        m16 = maps16_dtype() if tuning.current().infer_maps16 else None     # the stored maps' dtype, or None: fp32 on section 19
+        f32 = None if m16 is None else torch.float32                        # a result column's out_dtype under the switch
         n, D, S = feats.shape[0], self.init_stage_dims, self.num_stages
         widths = [self.init_dim] + [D * 2 ** s for s in range(S)]
         wide = torch.empty((n, self.out_channels), device=feats.device, dtype=torch.float32) \
             if n * self.out_channels * 4 <= _WINDOW else None
         col = lambda m: None if wide is None else wide[:, sum(widths[:m]):sum(widths[:m + 1])]
-        out_init = _keep(trace, "bn0s1", _conv_bn_act(self.conv0s1, self.bn0s1, feats, pyramid.stem, out=col(0)))
-        stage_input = [_keep(trace, "bn1s1", _conv_bn_act(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0]))]
+        out_init = _keep(trace, "bn0s1", _conv_bn_act(self.conv0s1, self.bn0s1, feats, pyramid.stem, out=col(0), out_dtype=f32))
+        stage_input = [_keep(trace, "bn1s1", _conv_bn_act(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], out_dtype=m16))]
         for i in range(S):
             stage_output = []
             for j in range(i + 1):
                 x, blocks = stage_input[j], self.stages[i][j]
                 for b, blk in enumerate(blocks):
                     last = i == S - 1 and j == 0 and b == len(blocks) - 1
-                    x = blk.infer(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", out=col(1) if last else None)
+                    x = blk.infer(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", out=col(1) if last else None, dtype=m16,
+                                  out_dtype=f32 if last else m16)
                 stage_output.append(x)
             if i == S - 1:
                 break
@@ -876,10 +955,11 @@ class HRNetBackbone(nn.Module):
                         level = j + s if k > j else j - s                  # the level the step starts from
                         kmap = pyramid.down[level] if k > j else pyramid.up(level - 1)
                         if s + 1 < steps:
-                            x = _keep(trace, f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", _conv_bn_act(path[3 * s], path[3 * s + 1], x, kmap))
+                            x = _keep(trace, f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}",
+                                      _conv_bn_act(path[3 * s], path[3 * s + 1], x, kmap, out_dtype=m16))
                         else:
                             buf = _conv_bn_act(path[3 * s], path[3 * s + 1], x, kmap, residual=buf, relu=j == sources[-1],
-                                               out=None if j == sources[0] else buf)
+                                               out=None if j == sources[0] else buf, out_dtype=m16)
                 # (no incoming path — the finest branch after stage 0 — is the block's own ReLU output: no launch, as in _combine)
                 stage_input.append(_keep(trace, f"sum.{i}.{k}", buf))
         outs = [out_init, stage_output[0]]
@@ -887,7 +967,8 @@ class HRNetBackbone(nn.Module):
             x, block = stage_output[i], self.final_transitions[i - 1]
             for s in range(i):
                 x = _keep(trace, f"final_transitions.{i - 1}.{3 * s + 1}",
-                          _conv_bn_act(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), out=col(i + 1) if s == i - 1 else None))
+                          _conv_bn_act(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), out=col(i + 1) if s == i - 1 else None,
+                                       out_dtype=f32 if s == i - 1 else m16))
             outs.append(x)
         return torch.cat(outs, dim=1) if wide is None else wide
 

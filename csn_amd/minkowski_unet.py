@@ -27,7 +27,9 @@ more than 256 columns runs ``conv1`` and the ``downsample`` convolution as a cha
 Offset and octant numbering and the sorted order of the coarse levels are this project's choice (minkowski_conv.py): parity unpinned
 against MinkowskiEngine's own checkpoints.  The switch ``grouped_passes`` of ``tuning`` leaves these networks as they are;
 ``rows_single_product`` reaches the kernel-3 / kernel-1 convolutions as everywhere, in training and on the inference graph, and
-never the octant products (sections 21 and 23 have no single-product instances).
+never the octant products (sections 21 and 23 have no single-product instances).  For the same reason ``infer_maps16`` (16-bit maps
+between the launches of ``HRNetBackbone``'s inference graph, section 24) is ignored here: ``UNetBasicBlock._infer_conv`` and
+``Res16UNetBase._forward_infer`` hand fp32 tensors everywhere and never name an ``out_dtype``, so every launch stays section 19 / 23.
 """
 from __future__ import annotations
 

@@ -91,6 +91,17 @@ class Tuning:
     # for the eight resolution changes, a decoder level's [up | skip] input written in place, a convolution over more than 256
     # columns as a chain of two launches — again a summation order of its own (DESIGN.md "Inference U-Net", scripts/bench_unet.py)
     eval_epilogue: bool = False
+    # HRNetBackbone's inference graph (where eval_epilogue already applies, and ONLY there) in math mode "bf16" / "fp16" with
+    # rows_single_product: the maps between the launches are stored as bf16 / fp16 rows (include/csn_hip.h section 24) instead of
+    # fp32 rows that their consumer's first instruction rounds to 16 bits anyway — gather bytes, map writes and residual reads halve.
+    # The stem's input, the (N, out_channels) result and the launches that write its column blocks stay fp32.  Every product is the
+    # same; a stored map (and a branch sum, per launch) is rounded once more, so results stay in the class those modes already have
+    # (tests/test_gpu_maps16.py holds the graph bit for bit to the fp32-map graph with every stored map rounded once).  In every
+    # other combination — modes fp32 / bf16x3, rows_single_product off, eval_epilogue off, training, grad enabled, fused=False — it
+    # changes nothing: the same launches, the same bits.  The Res16UNets ignore it: their octant launches (sections 21 / 23) have no
+    # single-product instances, so their inference graph keeps fp32 maps throughout.  Off: opt-in (bytes and timing: DESIGN.md
+    # "16-bit inference maps", scripts/bench_hrnet_maps16.py)
+    infer_maps16: bool = False
     # kNN shape graphs (construct_shape_graph with screen=None, CrossShapeAt.get_knn_graph / get_knn_graph_big): an fp16 pass over all
     # pairs (csn_ragged_retrieval_screen_f16) names the candidates that provably cannot be among a row's top K — more than
     # 2 * screen_eps below its K-th best screen score — and only the rest are scored by the exact fp32 kernels.  The SAME integers

@@ -1081,6 +1081,35 @@ CSN_API int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_c
                                  const float* beta, const float* running_mean, const float* running_var, float eps, const float* r,
                                  long long ld_r, int relu, float* y, long long ld_y, void* stream);
 
+/* ---- (24) inference: the launch of (19) on 16-bit maps (the maps between the launches of HRNetBackbone's inference graph) ---------
+ * Under csn_set_thread_rows16(1) in math mode 2 / 3, (19) rounds every gathered value to bf16 / fp16 as the first thing it does with
+ * it, yet the map it gathers from was written and is read as fp32.  Here x, r and y may each be rows of the mode's OWN 16-bit type
+ * (mode 2: bf16, mode 3: fp16): gather bytes, map writes and residual reads halve, the conversions of x leave the contraction loop.
+ * Additive to ABI version 17.  The arguments are (19)'s with a type flag beside each map:
+ *   x16 / r16 / y16   0: fp32 rows, 1: 16-bit rows.  Any other value: CSN_E_ARG.  ld_x / ld_r / ld_y count ELEMENTS of the map's own
+ *                     type.  table, w and the four vectors are as in (19) (w is fp32 and rounded when it is staged, as there).
+ *   acc, s, t         as in (19); y[j][c] = act(acc s + t + r[j][c]), stored as fp32 (y16 == 0) or rounded ONCE to the 16-bit type
+ *                     (nearest even, as a CPU cast).  An fp16 store that overflows is a plain conversion (inf), not a clamp.
+ * EXACTNESS: a 16-bit map changes where a value is rounded, not which product is formed.  Given the same representable inputs the
+ * call is bit-identical to csn_sparse_conv_bn_act_fwd_f32 under csn_set_thread_rows16(1) in the same math mode, its fp32 output
+ * rounded once when y16 == 1: a 16-bit x holds exactly what (19) would have rounded its fp32 value to, a 16-bit r converts to fp32
+ * exactly, w is rounded when staged as there, and the contraction walks the same (offset, 32-channel step) sequence under the same
+ * launch rule for the column blocks (CSN_DEV_SCONV_NB included) — the accumulators are the same bits.  All three flags 0 is allowed
+ * and gives the bits of (19).  No workspace, no atomics; two identical calls give the same bits.  Nothing but y is written; x, r and
+ * y may be column blocks of wider buffers of their own type.
+ * Requires math mode 2 or 3 AND csn_get_thread_rows16() == 1, otherwise CSN_E_ARG: there are no bf16x3 / fp32 instances (16-bit maps
+ * under those modes would throw away what they pay for).
+ * ALIASING: r may be y itself — the same pointer AND r16 == y16 AND ld_r == ld_y — every element read and then written by the same
+ * lane; r == y with another type or pitch returns CSN_E_ARG.  Any other overlap is the caller's error, as in (19).
+ * Host-side checks before any launch: (19)'s for NULLs, n_in, n_out, kv in {1, 27, 125} and the widths, and for every fp32 map
+ * (pitch % 4 CSN_E_ALIGN, >= width CSN_E_ARG, <= 2^20 and rows * pitch * 4 < 2 GiB CSN_E_DIM).  A 16-bit map needs pitch % 8 == 0
+ * (CSN_E_ALIGN), pitch >= width (CSN_E_ARG), pitch <= 2^20 and rows * pitch * 2 < 2 GiB (CSN_E_DIM).  x, w, y, r 16-byte aligned
+ * whatever their type, the table 4-byte (CSN_E_PTR). */
+CSN_API int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv,
+                                   int c_in, int c_out, const float* w, const float* gamma, const float* beta,
+                                   const float* running_mean, const float* running_var, float eps, const void* r, int r16,
+                                   long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
