@@ -284,22 +284,28 @@ __global__ __launch_bounds__(256, 2) void csn_outproj_ln_fwd_bf16x3_kernel(CsnOu
       sum += acc[c][r];
     }
   sum += csn_xhalf(sum);
-  const float mean = sum * (1.f / C);
+  // Every fused multiply-add of the statistics is SPELLED OUT (and no product is left next to a sum that could take it): left to
+  // the compiler, z - sum / C was one fma for some channels and a rounded mean subtracted for the others, differently in every
+  // instance of this template — and the 16-bit-map instances (A16) owe the bits of the fp32-map ones (include/csn_hip.h, 16-BIT
+  // ACTIVATION MAPS; tests/test_gpu_act16_edges.py)
   float sq = 0.f;
 #pragma unroll
   for (int c = 0; c < CT; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float dlt = acc[c][r] - mean;
-      sq += dlt * dlt;
+      acc[c][r] = fmaf(sum, -(1.f / C), acc[c][r]);                      // z - mean, one rounding
+      sq = fmaf(acc[c][r], acc[c][r], sq);
     }
   sq += csn_xhalf(sq);
-  const float rstd = 1.f / sqrtf(sq * (1.f / C) + p.eps);
+  const float rstd = 1.f / sqrtf(fmaf(sq, 1.f / C, p.eps));
 #pragma unroll
   for (int c = 0; c < CT; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float xh = (acc[c][r] - mean) * rstd;
+      float xh = acc[c][r] * rstd;
+      // (an opaque fp32 value: the fp16 map holds fp16(the fp32 map's xhat), as on the 256 x 256 tiles — the product and the
+      //  conversion would otherwise become one v_fma_mixlo_f16, whose single rounding is another value in ~1e-3 of the elements)
+      if constexpr (A16) asm volatile("" : "+v"(xh));
       if constexpr (A16) csn_bstore16(to16<true>(xh), Hr, n_ok ? n_off >> 1 : CSN_OOB, (unsigned)(c * 32 + csn_acc_row(r, 0)) * (unsigned)ld * 2u);
       else csn_bstore(xh, Hr, n_off, (unsigned)(c * 32 + csn_acc_row(r, 0)) * (unsigned)ld * 4u);
     }

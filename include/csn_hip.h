@@ -105,7 +105,8 @@ CSN_API int csn_version(void);
  * leading dimension of such a map counts 16-bit ELEMENTS (same numbers as for the fp32 map).  Everything else keeps its type:
  * the input maps x, the residual, dxhat / dfeats, lse / delta / rstd, every gradient map dQ / dK / dV / dz_res, weights and
  * weight gradients, the K / V tile planes (already 16-bit).  Products are bit-identical to the fp32 exchange wherever a map is
- * only a matrix operand (it was rounded to the same 16 bits at staging); delta = sum dO * O, the LayerNorm backward and the mix
+ * only a matrix operand (it was rounded to the same 16 bits at staging) and a 16-bit output map holds the fp32 map's values
+ * rounded once — both held bit for bit by tests/test_gpu_act16_edges.py; delta = sum dO * O, the LayerNorm backward and the mix
  * see the rounded maps (|xhat| error <= 2^-11 relative).  Requirements: math mode 2 / 3 with K / V tile planes, block mode (no
  * cross-length entry points), no split tensors, a mix backward without gradient maps (the linked form), evaluation outputs
  * written once (no accumulate into a 16-bit map).  A forward entry point returns CSN_E_ARG when fmt does not name its mode's
