@@ -38,7 +38,9 @@ from .minkowski_hrnet import GroupedPyramid, bn_act_groups, conv_stats_groups, g
 from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
                               maps16_dtype, sparse_conv_bn_act)
 
-# the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks
+# the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks; octant_conv_bn_act is the
+# inference primitive of its resolution changes, on fp32 maps or (single_product / 16-bit tensors, where maps16_dtype() names a
+# type) as one 16-bit product on fp32 or 16-bit maps
 from .minkowski_unet import (Res16UNet14, Res16UNet14A, Res16UNet14A2, Res16UNet14B, Res16UNet14B2, Res16UNet14B3,  # noqa: E402,F401
                              Res16UNet14C, Res16UNet14D, Res16UNet18, Res16UNet18A, Res16UNet18B, Res16UNet18D, Res16UNet34,
                              Res16UNet34A, Res16UNet34B, Res16UNet34C, Res16UNet50, Res16UNet101, Res16UNetBase, UNetBasicBlock,

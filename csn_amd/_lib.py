@@ -16,7 +16,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libcsn_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "octant_conv.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "octant_conv.hip", "octant_conv_maps16.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
 HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", "octant_rows_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
 ARCH = "gfx950"
 BUILD_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"]
@@ -295,6 +295,12 @@ _SIGNATURES = {
     "csn_sparse_conv_bn_act_fwd_m16": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_longlong, c_int,
                                                c_void_p, c_int, c_longlong, c_void_p]),
+    "csn_octant_down_bn_act_fwd_m16": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_longlong, c_int, c_void_p,
+                                               c_int, c_longlong, c_void_p]),
+    "csn_octant_up_bn_act_fwd_m16": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_longlong,
+                                             c_int, c_void_p, c_int, c_longlong, c_void_p]),
     "csn_voxel_mean_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "csn_point_interp_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong,
                                          c_void_p]),

@@ -1696,6 +1696,52 @@ int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n
   return csn_launch_sparse_conv_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
 }
 
+// ---- (25) the launches of (23) as one 16-bit product on maps that are each fp32 rows or rows of the mode's 16-bit type ----
+// (24)'s mode and flag checks, (21)'s on the sizes, each map by its own type's rule; n_x: the rows of x, n_y: those of y and r
+static int octant_m16_args(int x16, long long ld_x, int n_x, int n_y, int n_fine, int n_coarse, int c_in, int c_out, const void* r,
+                           int r16, long long ld_r, const void* y, int y16, long long ld_y) {
+  if ((x16 | r16 | y16) & ~1) return CSN_E_ARG;
+  if (mode() < 2 || !t_rows16) return CSN_E_ARG;                  // single-product instances only, as in (24)
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  const auto map = [](int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); };
+  if (const int e = map(x16, ld_x, c_in, n_x)) return e;
+  if (const int e = map(y16, ld_y, c_out, n_y)) return e;
+  if (r) if (const int e = map(r16, ld_r, c_out, n_y)) return e;
+  if (r == y && (r16 != y16 || ld_r != ld_y)) return CSN_E_ARG;   // y as its own residual: element for element, or not at all
+  return 0;
+}
+
+int csn_octant_down_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in,
+                                   int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, const void* r, int r16, long long ld_r, int relu, void* y,
+                                   int y16, long long ld_y, void* stream) {
+  if (!x || !children || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (const int e = octant_m16_args(x16, ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, r, r16, ld_r, y, y16, ld_y)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(children)) return CSN_E_PTR;
+  CsnOctantM16Args a{};
+  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
+  a.children = children; a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16; a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
+  return csn_launch_octant_down_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+}
+
+int csn_octant_up_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_coarse, const int* parent, const int* order,
+                                 const int* seg, int n_fine, int c_in, int c_out, const float* w, const float* gamma,
+                                 const float* beta, const float* running_mean, const float* running_var, float eps, const void* r,
+                                 int r16, long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream) {
+  if (!x || !parent || !order || !seg || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (const int e = octant_m16_args(x16, ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, r, r16, ld_r, y, y16, ld_y)) return e;
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  CsnOctantM16Args a{};
+  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
+  a.parent = parent; a.order = order; a.seg = seg; a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16;
+  a.ld_y = (int)ld_y;
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
+  return csn_launch_octant_up_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+}
+
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----
 static bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 

@@ -81,6 +81,9 @@ CSN_DEVINL u32x2 csn_bload2(csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
 CSN_DEVINL void csn_bstore_bf16(__bf16 v, csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
   __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v), r, voff, soff, 0);
 }
+CSN_DEVINL short csn_bload16(csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
+  return (short)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
+}
 CSN_DEVINL void csn_bstore16(short v, csn_rsrc_t r, unsigned voff, unsigned soff = 0) {
   __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, r, voff, soff, 0);
 }

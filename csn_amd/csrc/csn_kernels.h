@@ -376,6 +376,22 @@ int csn_launch_octant_up_bwd(const CsnOctantConvArgs& a, int mode, hipStream_t s
 // the two forwards with the inference epilogue of CsnSconvBnArgs (no bias): a.y = act(z s + t + r), one launch, no workspace
 int csn_launch_octant_down_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 int csn_launch_octant_up_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
+// the 32-column blocks a wave owns in a one-weight product of J columns over M rows: octant_conv.hip's launch rule
+int csn_octant_column_blocks(int J, long long M);
+// the same two forwards as ONE 16-bit product (math modes 2 / 3) on maps that are each fp32 or 16-bit rows
+// (octant_conv_maps16.hip): down is csn_launch_sparse_conv_bn_act_fwd_m16 over children as a table of 8 offsets, up kernels of
+// their own; the vectors, eps and relu come from CsnSconvBnArgs (its r / ld_r are not read)
+struct CsnOctantM16Args {
+  const void* x;  int x16;  int ld_x;
+  int n_fine, n_coarse, c_in, c_out;
+  const int* children;                                            // down
+  const int* parent;  const int* order;  const int* seg;          // up
+  const float* w;
+  const void* r;  int r16;  int ld_r;                             // optional; may be y itself with the same type and pitch
+  void* y;  int y16;  int ld_y;
+};
+int csn_launch_octant_down_bn_act_fwd_m16(const CsnOctantM16Args& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
+int csn_launch_octant_up_bn_act_fwd_m16(const CsnOctantM16Args& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 
 // ---- BatchNorm apply + branch sum + residual + ReLU on point-major rows, forward and backward (rows_bn_act.hip) ----
 struct CsnRowsBnActArgs {

@@ -28,23 +28,6 @@ using namespace rows_mma;
 
 constexpr int TARGET_GROUPS = 256;      // as in sparse_conv.hip: work-groups a launch should offer before it is split finer
 
-// The span of `order` that slot t owns when every segment is cut into spans of `span` entries: its octant k and [lo, hi).
-// false: the slot has none.  Wave-uniform (9 scalar reads).
-__device__ __forceinline__ bool octant_span(const int* __restrict__ seg, int n, int t, int span, int& k, int& lo, int& hi) {
-  int s0 = min(max(seg[0], 0), n);
-  for (int kk = 0; kk < 8; ++kk) {
-    const int s1 = min(max(seg[kk + 1], s0), n);
-    const int cnt = (s1 - s0 + span - 1) / span;
-    if (t < cnt) {
-      k = kk; lo = s0 + t * span; hi = min(lo + span, s1);
-      return true;
-    }
-    t -= cnt;
-    s0 = s1;
-  }
-  return false;
-}
-
 struct OctRowsP {
   const float* a; int lda; int n_src;   // A[n_src][lda]: the gathered (coarse) map
   const int* parent;                    // [M]
@@ -215,15 +198,10 @@ int launch_rows_nb(const OctRowsBnP& p, int mode, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// the column blocks a wave owns: the rule of sparse_conv.hip's launch_gemm (CSN_DEV_SCONV_NB pins them here too)
+// the column blocks a wave owns (csn_octant_column_blocks below)
 template <bool B_KN, typename P>
 int launch_rows(const P& p, int mode, hipStream_t st) {
-  const int t = p.J / 32;
-  int nb = t <= 4 ? t : (t + 1) / 2;
-  const long long row_groups = ((long long)p.M + 127) / 128;
-  while (nb > 1 && row_groups * ((t + nb - 1) / nb) < TARGET_GROUPS) nb = (nb + 1) / 2;
-  if (csn_dev_sconv_nb > 0) nb = csn_dev_sconv_nb < t ? csn_dev_sconv_nb : t;
-  return dispatch4(nb, [&](auto n) { return launch_rows_nb<n(), B_KN>(p, mode, st); });
+  return dispatch4(csn_octant_column_blocks(p.J, p.M), [&](auto n) { return launch_rows_nb<n(), B_KN>(p, mode, st); });
 }
 
 template <int TA>
@@ -270,11 +248,22 @@ CsnSparseConvArgs gather_args(const CsnOctantConvArgs& a) {
 
 }  // namespace
 
+// the column blocks a wave owns in a one-weight product of J columns over M rows: the rule of sparse_conv.hip's launch_gemm
+// (CSN_DEV_SCONV_NB pins them here too); octant_conv_maps16.hip launches by it as well
+int csn_octant_column_blocks(int J, long long M) {
+  const int t = J / 32;
+  int nb = t <= 4 ? t : (t + 1) / 2;
+  const long long row_groups = (M + 127) / 128;
+  while (nb > 1 && row_groups * ((t + nb - 1) / nb) < TARGET_GROUPS) nb = (nb + 1) / 2;
+  if (csn_dev_sconv_nb > 0) nb = csn_dev_sconv_nb < t ? csn_dev_sconv_nb : t;
+  return nb;
+}
+
 long long csn_octant_conv_ws_bytes(long long n_fine, long long n_coarse, int c_in, int c_out, int up, int backward) {
   return backward ? ws_layout(n_fine, up ? n_fine : n_coarse, c_in, c_out).total : 0;
 }
 
-// mode: 0 fp32, anything else bf16x3 (there are no single-product instances)
+// mode: 0 fp32, anything else bf16x3 (the single-product forwards of section 25 are octant_conv_maps16.hip)
 int csn_launch_octant_down_fwd(const CsnOctantConvArgs& a, int mode, hipStream_t st) {
   CsnSparseConvArgs g = gather_args(a);
   g.x = a.x; g.ld_x = a.ld_x; g.n_in = a.n_fine; g.fwd_table = a.children; g.n_out = a.n_coarse; g.bias = a.bias; g.y = a.y; g.ld_y = a.ld_y;

@@ -7,6 +7,10 @@
 //                    32-k step (a_kofs); B — [J][K] or [K][J] (B_KN) — is staged through LDS once per work-group (load_b,
 //                    store_b); mma_step contracts one step; store_tile adds the bias, stores the wave's rows and forms their
 //                    (mean, M2) from the accumulators; store_tile_bn stores act(acc * s + t + r) instead (inference).
+//                    mma_step_a16 is the single-product step on A fragments that ARE 16-bit (the 16-bit maps of
+//                    sparse_conv_maps16.hip and octant_conv_maps16.hip: two 16-byte loads per step, no conversion).
+//   octant tiles     octant_span: the (octant, range) of `order` a work-group or a chunk owns (octant_conv.hip,
+//                    octant_conv_maps16.hip).
 //   weight gradient  both operands are k-major (the contraction runs over the rows): a lane holds 8 rows of one column per 16-row
 //                    step (wgrad_row) and splits them in registers (wgrad_step); the four waves of a work-group contract a
 //                    quarter of its row chunk each and are added through LDS in wave order (wgrad_reduce_store).
@@ -120,6 +124,18 @@ __device__ __forceinline__ void mma_step(f32x16 (&acc)[NB], const f32x4 (&af)[4]
   }
 }
 
+// one 32-k step on 16-bit A: the lane's two fragments against the staged tile, in mma_step's order (half step, column block)
+template <int NB, bool H16>
+__device__ __forceinline__ void mma_step_a16(f32x16 (&acc)[NB], const f32x4 (&af)[2], const short* Bs, int li, int h) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    const s16x8 a = __builtin_bit_cast(s16x8, af[s2]);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+      acc[nb] = mfma32<H16>(a, *reinterpret_cast<const s16x8*>(&Bs[(nb * 32 + li) * BS16_PITCH + 16 * s2 + 8 * h]), acc[nb]);
+  }
+}
+
 // One 32 x 32 accumulator block of a wave (column `col` of rows row_w .. row_w + 31, of which the first cnt exist): z = acc + bv
 // is stored to c; with `stats` the (mean, M2) of the cnt rows go to part[tile][2][J] — two passes over the registers (no
 // cancellation); the stored values are the same bits either way.  A store's address is a wave-uniform row address (scalar
@@ -170,6 +186,24 @@ __device__ __forceinline__ void store_tile_bn(const f32x16& acc, float s, float 
     if (rw) v += (rw + csn_acc_row(q, 0) * ldr)[lane_r];
     (cw + csn_acc_row(q, 0) * ldc)[lane] = relu ? fmaxf(0.f, v) : v;
   }
+}
+
+// ---- octant tiles (octant_conv.hip, octant_conv_maps16.hip) ---------------------------------------------------------------
+// The span of `order` that slot t owns when every segment is cut into spans of `span` entries: its octant k and [lo, hi).
+// false: the slot has none.  Wave-uniform (9 scalar reads).
+__device__ __forceinline__ bool octant_span(const int* __restrict__ seg, int n, int t, int span, int& k, int& lo, int& hi) {
+  int s0 = min(max(seg[0], 0), n);
+  for (int kk = 0; kk < 8; ++kk) {
+    const int s1 = min(max(seg[kk + 1], s0), n);
+    const int cnt = (s1 - s0 + span - 1) / span;
+    if (t < cnt) {
+      k = kk; lo = s0 + t * span; hi = min(lo + span, s1);
+      return true;
+    }
+    t -= cnt;
+    s0 = s1;
+  }
+  return false;
 }
 
 // ---- weight gradient ---------------------------------------------------------------------------------------------------

@@ -44,18 +44,6 @@ __device__ __forceinline__ SconvM16LateP m16_args_late() {
   return k;
 }
 
-// one 32-k step on 16-bit A: the lane's two fragments against the staged tile, in mma_step's order (half step, column block)
-template <int NB, bool H16>
-__device__ __forceinline__ void mma_step_a16(f32x16 (&acc)[NB], const f32x4 (&af)[2], const short* Bs, int li, int h) {
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    const s16x8 a = __builtin_bit_cast(s16x8, af[s2]);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-      acc[nb] = mfma32<H16>(a, *reinterpret_cast<const s16x8*>(&Bs[(nb * 32 + li) * BS16_PITCH + 16 * s2 + 8 * h]), acc[nb]);
-  }
-}
-
 // store_tile_bn with the residual and the output in either type (wave-uniform flags): the same wave-uniform row address + lane
 // offset form, in bytes of the map's own element
 template <bool H16>

@@ -27,9 +27,14 @@ more than 256 columns runs ``conv1`` and the ``downsample`` convolution as a cha
 Offset and octant numbering and the sorted order of the coarse levels are this project's choice (minkowski_conv.py): parity unpinned
 against MinkowskiEngine's own checkpoints.  The switch ``grouped_passes`` of ``tuning`` leaves these networks as they are;
 ``rows_single_product`` reaches the kernel-3 / kernel-1 convolutions as everywhere, in training and on the inference graph, and
-never the octant products (sections 21 and 23 have no single-product instances).  For the same reason ``infer_maps16`` (16-bit maps
-between the launches of ``HRNetBackbone``'s inference graph, section 24) is ignored here: ``UNetBasicBlock._infer_conv`` and
-``Res16UNetBase._forward_infer`` hand fp32 tensors everywhere and never name an ``out_dtype``, so every launch stays section 19 / 23.
+by itself never the octant products (sections 21 and 23 have no single-product instances).  ``infer_maps16`` (16-bit maps between
+the launches of ``HRNetBackbone``'s inference graph) is ignored here.  The inference graph has two switches of its own, which act
+where ``eval_epilogue`` acts on these networks AND ``maps16_dtype()`` is not None (math mode "bf16" / "fp16" with
+``rows_single_product``) and change nothing anywhere else: ``octant_single_product`` runs the eight resolution changes as ONE 16-bit
+product (section 25) on fp32 maps; ``unet_maps16`` implies that and stores every map between the launches as a bf16 / fp16 tensor
+(sections 24 and 25) — the ``[up | skip]`` buffers included, written in place by their two producers as before.  The stem's input, a
+chain's running sum (an fp32 scratch map: the sum is rounded once, like every other stored map) and the last block's output, which
+``final`` reads, stay fp32.
 """
 from __future__ import annotations
 
@@ -46,8 +51,8 @@ from . import minkowski_hrnet as _mh
 from . import tuning
 from .minkowski_conv import (KernelMap, OctantMap, SparseConv3d, SparseConvDown2, SparseConvUp2, build_kernel_map, build_octant_map,
                              cat_conv3d)
-from .minkowski_hrnet import (HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _conv_bn_act, _keep, _pitched, _rows,
-                              sparse_conv_bn_act)
+from .minkowski_hrnet import (HRBasicBlock, VoxelPyramid, _combine, _conv_bn, _conv_bn_act, _keep, _pitched, _pitched16, _rows_any,
+                              maps16_dtype, sparse_conv_bn_act)
 
 _NO_CPU = "csn_amd ops need tensors on the MI355X (cuda) device; there is no CPU path"
 N_LEVELS = 5
@@ -120,10 +125,11 @@ def _build_unet_pyramid_hip(coords: torch.Tensor, stem_kernel: int) -> UNetPyram
 
 
 # ------------------------------------------------------------------------------------------------------
-# inference: an octant convolution + BatchNorm + residual + ReLU as one launch (section 23)
+# inference: an octant convolution + BatchNorm + residual + ReLU as one launch (sections 23 and 25)
 # ------------------------------------------------------------------------------------------------------
 def octant_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, norm: nn.BatchNorm1d, up: bool,
-                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       residual: Optional[torch.Tensor] = None, relu: bool = True, out: Optional[torch.Tensor] = None, *,
+                       out_dtype: Optional[torch.dtype] = None, single_product: bool = False) -> torch.Tensor:
     """``y = act(conv(x) s + t + residual)`` in one launch, the counterpart of ``sparse_conv_bn_act`` for the kernel-2 stride-2
     convolution (``up`` False: ``x (n_fine, c_in)`` -> ``(n_coarse, c_out)``, ``csn_octant_down_bn_act_fwd_f32``) and its transposed
     form (``up`` True: ``x (n_coarse, c_in)`` -> ``(n_fine, c_out)``, ``csn_octant_up_bn_act_fwd_f32``), both without a bias:
@@ -133,7 +139,17 @@ def octant_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, n
     ``x``, ``residual`` and ``out`` may be row-pitched views of a wider buffer (``stride(1) == 1``, ``stride(0) % 4 == 0``, a
     16-byte aligned data pointer); ``x`` and ``residual`` are made contiguous otherwise, ``out`` raises ``ValueError``.  With
     ``out`` the result is written there and ``out`` is returned; ``residual`` may be ``out`` itself and must not overlap it in any
-    other way.  The products run in fp32 (math mode 0) or as bf16x3 (every other mode), whatever ``rows_single_product`` says."""
+    other way.  The products run in fp32 (math mode 0) or as bf16x3 (every other mode), whatever ``rows_single_product`` says.
+
+    Single product and 16-bit maps (``csn_octant_down_bn_act_fwd_m16`` / ``csn_octant_up_bn_act_fwd_m16``, section 25).  In math
+    mode "bf16" / "fp16" with ``tuning.rows_single_product``, ``single_product=True`` runs ONE 16-bit product per operand pair, and
+    ``x``, ``residual`` and ``out`` may each be fp32 or that mode's 16-bit dtype (16-bit views need ``stride(0) % 8 == 0``);
+    ``out_dtype`` names the type of a result allocated here.  Any of these takes that route; without the mode and the switch, or
+    with a tensor of the other 16-bit type, it raises ``ValueError``.  A launch on 16-bit maps is bit-identical to the
+    ``single_product=True`` launch on the same values in fp32 maps, its result rounded once (nearest even) where the output is
+    16-bit.  Calls on fp32 tensors without ``out_dtype`` and ``single_product`` are section 23 as ever."""
+    named = out_dtype if out_dtype is not None or not single_product else (torch.float32 if out is None else out.dtype)
+    dt16 = _mh._maps16_route(x, residual, out, named)
     if not (x.is_cuda and weight.is_cuda) or (residual is not None and not residual.is_cuda) or (out is not None and not out.is_cuda):
         raise _lib.CsnError(_NO_CPU)
     if not isinstance(omap, OctantMap):
@@ -156,15 +172,30 @@ def octant_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, n
     CF._need_cuda(omap.parent, norm.weight, norm.bias, norm.running_mean, norm.running_var)
     same = residual is not None and out is not None and residual.data_ptr() == out.data_ptr() and residual.stride() == out.stride()
     w = weight.detach().float().contiguous()
-    x = _rows(x)
+    x = _rows_any(x)
     if out is None:
-        y = torch.empty((n_out, c_out), device=x.device, dtype=torch.float32)
+        y = torch.empty((n_out, c_out), device=x.device, dtype=out_dtype or torch.float32)
     else:
         y = out.detach()
-        if not _pitched(y):
-            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer")
-    r = None if residual is None else (y if same else _rows(residual))
+        if not (_pitched(y) or (dt16 is not None and _pitched16(y))):
+            raise ValueError("out must be fp32 rows with stride(1) == 1, stride(0) % 4 == 0 and a 16-byte aligned data pointer"
+                             + ("" if dt16 is None else f", or {dt16} rows with stride(0) % 8 == 0"))
+    r = None if residual is None else (y if same else _rows_any(residual))
     vec = [CF._ptr(v.detach().float().contiguous()) for v in (norm.weight, norm.bias, norm.running_mean, norm.running_var)]
+    if dt16 is not None:
+        is16 = lambda t: int(t is not None and t.dtype == dt16)
+        tail16 = (float(norm.eps), CF._ptr(r), is16(r), 0 if r is None else r.stride(0), int(bool(relu)), CF._ptr(y), is16(y), y.stride(0),
+                  CF._stream())
+        L = _lib.lib()
+        with CF.rows16(True):
+            if up:
+                _lib.check(L.csn_octant_up_bn_act_fwd_m16(CF._ptr(x), is16(x), x.stride(0), n_coarse, CF._ptr(omap.parent),
+                                                          CF._ptr(omap.order), CF._ptr(omap.seg), n_fine, c_in, c_out, CF._ptr(w), *vec,
+                                                          *tail16), "csn_octant_up_bn_act_fwd_m16")
+            else:
+                _lib.check(L.csn_octant_down_bn_act_fwd_m16(CF._ptr(x), is16(x), x.stride(0), n_fine, CF._ptr(omap.children), n_coarse,
+                                                            c_in, c_out, CF._ptr(w), *vec, *tail16), "csn_octant_down_bn_act_fwd_m16")
+        return y if out is None else out
     tail = (float(norm.eps), CF._ptr(r), 0 if r is None else r.stride(0), int(bool(relu)), CF._ptr(y), y.stride(0), CF._stream())
     L = _lib.lib()
     if up:
@@ -177,10 +208,11 @@ def octant_conv_bn_act(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, n
     return y if out is None else out
 
 
-def _octant_bn_act(conv: SparseConvDown2, norm: nn.BatchNorm1d, x, omap: OctantMap, residual=None, relu=True, out=None) -> torch.Tensor:
+def _octant_bn_act(conv: SparseConvDown2, norm: nn.BatchNorm1d, x, omap: OctantMap, residual=None, relu=True, out=None, out_dtype=None,
+                   single_product=False) -> torch.Tensor:
     if conv.bias is not None:
         raise ValueError("the inference launch of an octant convolution takes no bias (the Res16UNets have none)")
-    return octant_conv_bn_act(x, conv.kernel, omap, norm, conv.up, residual, relu, out)
+    return octant_conv_bn_act(x, conv.kernel, omap, norm, conv.up, residual, relu, out, out_dtype=out_dtype, single_product=single_product)
 
 
 class CatConv3d(nn.Module):
@@ -255,38 +287,54 @@ class UNetBasicBlock(nn.Module):
             cache[id(conv)] = (key, [k.contiguous() for k in conv.kernel.detach().float().split(list(widths), dim=1)])
         return cache[id(conv)][1]
 
-    def _infer_conv(self, conv, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, widths: Sequence[int], relu: bool) -> torch.Tensor:
+    def _infer_conv(self, conv, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: KernelMap, widths: Sequence[int], relu: bool,
+                    dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """One convolution + norm that reads the block's input: one launch up to 256 columns; beyond, a chain over the input's
         column blocks ``widths`` (each a multiple of 32, at most 256): the first launch writes ``z0 s + t`` without a ReLU, each
-        further one adds its ``z_i s`` to that map in place (zero shift) and the last applies the activation."""
+        further one adds its ``z_i s`` to that map in place (zero shift) and the last applies the activation.  ``dtype`` (16-bit
+        maps, ``tuning.unet_maps16``): the type of the result; a chain then keeps its running sum in an fp32 scratch map and its
+        last launch reads that and writes the 16-bit map, so that the sum is rounded once."""
         if isinstance(conv, SparseConv3d):
-            return _conv_bn_act(conv, norm, x, kmap, relu=relu)
+            return _conv_bn_act(conv, norm, x, kmap, relu=relu, out_dtype=dtype)
         if kmap.kernel_size != conv.kernel_size or kmap.stride != 1 or kmap.transposed:
             raise ValueError("the map does not fit this layer")
         if sum(widths) != self.inplanes or any(w % 32 or not 32 <= w <= 256 for w in widths):
             raise ValueError(f"column blocks {list(widths)} do not cut {self.inplanes} columns into multiples of 32 up to 256")
         y, c0 = None, 0
         for i, (w, k) in enumerate(zip(widths, self._column_kernels(conv, widths))):
-            y = sparse_conv_bn_act(x[:, c0:c0 + w], k, kmap, norm, residual=y, relu=relu and i == len(widths) - 1, out=y, shift=i == 0)
+            last = i == len(widths) - 1
+            if dtype is None:
+                y = sparse_conv_bn_act(x[:, c0:c0 + w], k, kmap, norm, residual=y, relu=relu and last, out=y, shift=i == 0)
+            elif last:
+                y = sparse_conv_bn_act(x[:, c0:c0 + w], k, kmap, norm, residual=y, relu=relu, shift=i == 0, out_dtype=dtype)
+            else:
+                y = sparse_conv_bn_act(x[:, c0:c0 + w], k, kmap, norm, residual=y, relu=False, out=y, shift=i == 0,
+                                       out_dtype=torch.float32 if y is None else None)
             c0 += w
         return y
 
     def infer(self, x: torch.Tensor, s1: KernelMap, one: KernelMap, trace: Optional[dict] = None, prefix: str = "",
-              out: Optional[torch.Tensor] = None, widths: Optional[Sequence[int]] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, widths: Optional[Sequence[int]] = None, dtype: Optional[torch.dtype] = None,
+              out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """The block on the inference launches, ``x (n, inplanes)`` a map or the level's ``[up | skip]`` buffer: ``conv1`` + ``norm1``
         + ReLU, the ``downsample`` convolution + its norm without a ReLU, ``conv2`` + ``norm2`` with that result as its residual,
         then the ReLU (written to ``out`` when given, else in place over the residual).  ``widths``: the column blocks of a wider
         input (default: 256 and the rest); the two convolutions that read it are then chains, ``(z0 s + t) + z1 s`` — a summation
-        order of its own, neither ``cat_conv3d``'s ``z0 + z1`` nor the one launch's."""
+        order of its own, neither ``cat_conv3d``'s ``z0 + z1`` nor the one launch's.  ``dtype`` (16-bit maps,
+        ``tuning.unet_maps16``): the type of the two inner maps; ``out_dtype``: that of a result allocated here (a result of another
+        type than the residual map is a map of its own)."""
         if not x.is_cuda:
             raise _lib.CsnError(_NO_CPU)
         if x.dim() != 2 or x.shape[1] != self.inplanes:
             raise ValueError(f"x is {tuple(x.shape)}; this block takes {self.inplanes} columns")
         if widths is None:
             widths = [self.inplanes] if self.inplanes <= 256 else [256, self.inplanes - 256]
-        h = _keep(trace, prefix + "norm1", self._infer_conv(self.conv1, self.norm1, x, s1, widths, True))
-        res = self._infer_conv(self.downsample[0], self.downsample[1], x, one, widths, False)
-        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, s1, residual=res, out=res if out is None else out))
+        h = _keep(trace, prefix + "norm1", self._infer_conv(self.conv1, self.norm1, x, s1, widths, True, dtype))
+        res = self._infer_conv(self.downsample[0], self.downsample[1], x, one, widths, False, dtype)
+        if out is None and (out_dtype is None or out_dtype == res.dtype):
+            out = res
+        return _keep(trace, prefix + "norm2", _conv_bn_act(self.conv2, self.norm2, h, s1, residual=res, out=out,
+                                                           out_dtype=None if out is not None else out_dtype))
 
 
 class Res16UNetBase(nn.Module):
@@ -386,15 +434,19 @@ class Res16UNetBase(nn.Module):
 
     @staticmethod
     def _blocks_infer(seq: nn.Sequential, x: torch.Tensor, widths, s1: KernelMap, one: KernelMap, trace: Optional[dict], name: str,
-                      out: Optional[torch.Tensor]) -> torch.Tensor:
-        """``_blocks`` on the inference launches; the list's last launch writes ``out`` when given."""
+                      out: Optional[torch.Tensor], dtype: Optional[torch.dtype] = None,
+                      out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """``_blocks`` on the inference launches; the list's last launch writes ``out`` when given.  ``dtype`` (16-bit maps): the
+        type of every map but the list's result, which is ``out``'s own or ``out_dtype``."""
         blocks = list(seq)
         for i, blk in enumerate(blocks):
-            to = out if i == len(blocks) - 1 else None
+            last = i == len(blocks) - 1
+            to = out if last else None
+            od = None if to is not None else (out_dtype if last else dtype)
             if isinstance(blk, UNetBasicBlock):
-                x = blk.infer(x, s1, one, trace, f"{name}.{i}.", out=to, widths=widths)
+                x = blk.infer(x, s1, one, trace, f"{name}.{i}.", out=to, widths=widths, dtype=dtype, out_dtype=od)
             else:
-                x = blk.infer(x, s1, trace, f"{name}.{i}.", out=to)
+                x = blk.infer(x, s1, trace, f"{name}.{i}.", out=to, dtype=dtype, out_dtype=od)
         return x
 
     def _forward_infer(self, feats: torch.Tensor, pyr: UNetPyramid, trace: Optional[dict]) -> torch.Tensor:
@@ -406,30 +458,42 @@ class Res16UNetBase(nn.Module):
         its row pitch — no concatenation is ever copied.  Where the buffer would pass the kernels' 2 GiB window the two maps stay
         separate and are joined with ``torch.cat``.  A block that reads more than 256 columns runs ``conv1`` and the
         ``downsample`` convolution as two launches over the buffer's two column blocks, ``(z_up s + t) + z_skip s``: a summation
-        order of its own (``UNetBasicBlock.infer``).  ``final`` stays the ``nn.Linear``."""
+        order of its own (``UNetBasicBlock.infer``).  ``final`` stays the ``nn.Linear``.
+
+        In math mode "bf16" / "fp16" with ``tuning.rows_single_product``: ``tuning.octant_single_product`` hands the eight
+        resolution changes to section 25 (one 16-bit product) on the same fp32 maps; ``tuning.unet_maps16`` does that and makes
+        every stored map — the ``[up | skip]`` buffers included, their window sized in their own bytes — a tensor of the mode's
+        16-bit type (sections 24 and 25).  The stem's input and the last block's output, which ``final`` reads, stay fp32."""
         P, dev = self.PLANES, feats.device
+        t16 = maps16_dtype()
+        d = t16 if tuning.current().unet_maps16 else None              # the type of a stored map; None: fp32 maps, today's calls
+        sp = t16 is not None and (tuning.current().octant_single_product or tuning.current().unet_maps16)
+        esz, last_dtype = (4, None) if d is None else (2, torch.float32)
+        od = lambda to: None if to is not None else d                  # the out_dtype of a launch that writes ``to``
         skip_w = (self.INIT_DIM, P[0], P[1], P[2])                     # the skip map's width at level 0 .. 3
         up_w = (P[7], P[6], P[5], P[4])                                # the transposed convolution's at level 0 .. 3
         cat = []
         for l in range(4):
             n_l, w = pyr.coords[l].shape[0], up_w[l] + skip_w[l]
-            cat.append(torch.empty((n_l, w), device=dev, dtype=torch.float32) if n_l * w * 4 <= _mh._WINDOW else None)
+            cat.append(torch.empty((n_l, w), device=dev, dtype=d or torch.float32) if n_l * w * esz <= _mh._WINDOW else None)
         skip_to = lambda l: None if l > 3 or cat[l] is None else cat[l][:, up_w[l]:]
-        out = _keep(trace, "bn0", _conv_bn_act(self.conv0p1s1, self.bn0, feats, pyr.stem, out=skip_to(0)))
+        out = _keep(trace, "bn0", _conv_bn_act(self.conv0p1s1, self.bn0, feats, pyr.stem, out=skip_to(0), out_dtype=od(skip_to(0))))
         skips = [out]
         for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
-            out = _keep(trace, f"bn{n}", _octant_bn_act(getattr(self, f"conv{n}p{ts}s2"), getattr(self, f"bn{n}"), out, pyr.oct[n - 1]))
-            out = self._blocks_infer(getattr(self, f"block{n}"), out, None, pyr.s1[n], pyr.one[n], trace, f"block{n}", skip_to(n))
+            out = _keep(trace, f"bn{n}", _octant_bn_act(getattr(self, f"conv{n}p{ts}s2"), getattr(self, f"bn{n}"), out, pyr.oct[n - 1],
+                                                        out_dtype=d, single_product=sp))
+            out = self._blocks_infer(getattr(self, f"block{n}"), out, None, pyr.s1[n], pyr.one[n], trace, f"block{n}", skip_to(n), d, d)
             skips.append(out)
         skips.pop()                                                    # block4's output goes up, not across
         for n, ts in ((4, 16), (5, 8), (6, 4), (7, 2)):
             l = 7 - n
+            up_to = None if cat[l] is None else cat[l][:, :up_w[l]]
             up = _keep(trace, f"bntr{n}", _octant_bn_act(getattr(self, f"convtr{n}p{ts}s2"), getattr(self, f"bntr{n}"), out, pyr.oct[l],
-                                                         out=None if cat[l] is None else cat[l][:, :up_w[l]]))
+                                                         out=up_to, out_dtype=od(up_to), single_product=sp))
             skip = skips.pop()
             x = cat[l] if cat[l] is not None else torch.cat([up, skip], dim=1)
             out = self._blocks_infer(getattr(self, f"block{n + 1}"), x, (up_w[l], skip_w[l]), pyr.s1[l], pyr.one[l], trace,
-                                     f"block{n + 1}", None)
+                                     f"block{n + 1}", None, d, last_dtype if n == 7 else d)
         return self.final(out)
 
 

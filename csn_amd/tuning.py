@@ -98,10 +98,23 @@ class Tuning:
     # same; a stored map (and a branch sum, per launch) is rounded once more, so results stay in the class those modes already have
     # (tests/test_gpu_maps16.py holds the graph bit for bit to the fp32-map graph with every stored map rounded once).  In every
     # other combination — modes fp32 / bf16x3, rows_single_product off, eval_epilogue off, training, grad enabled, fused=False — it
-    # changes nothing: the same launches, the same bits.  The Res16UNets ignore it: their octant launches (sections 21 / 23) have no
-    # single-product instances, so their inference graph keeps fp32 maps throughout.  Off: opt-in (bytes and timing: DESIGN.md
+    # changes nothing: the same launches, the same bits.  The Res16UNets ignore it: their inference graph has switches of its own
+    # (octant_single_product and unet_maps16, below).  Off: opt-in (bytes and timing: DESIGN.md
     # "16-bit inference maps", scripts/bench_hrnet_maps16.py)
     infer_maps16: bool = False
+    # The Res16UNets' inference graph (where eval_epilogue already applies to them, and ONLY there) in math mode "bf16" / "fp16" with
+    # rows_single_product.  octant_single_product: the eight resolution changes run as ONE 16-bit product per operand pair
+    # (include/csn_hip.h section 25) instead of bf16x3 (section 23) — arithmetic, like rows_single_product, which by itself never
+    # reaches the octant products; the maps stay fp32 and the kernel-3 / kernel-1 launches stay section 19.  unet_maps16: every
+    # stored map between the launches is a bf16 / fp16 tensor (sections 24 and 25), the four [up | skip] buffers included; it implies
+    # the single-product octant products.  The stem's input, a chain's running sum over more than 256 columns (an fp32 scratch map,
+    # so that the sum is rounded once) and the last block's output, which ``final`` reads, stay fp32
+    # (tests/test_gpu_unet16.py holds the graph bit for bit to the fp32-map graph with every stored map rounded once).  In every
+    # other combination — modes fp32 / bf16x3, rows_single_product off, eval_epilogue off, training, grad enabled, fused=False —
+    # both change nothing: the same launches, the same bits.  infer_maps16 stays ignored by these networks, and the HRNet classes
+    # ignore these two.  Off: opt-in (bytes and timing: DESIGN.md "16-bit inference U-Net", scripts/bench_unet.py --infer)
+    octant_single_product: bool = False
+    unet_maps16: bool = False
     # kNN shape graphs (construct_shape_graph with screen=None, CrossShapeAt.get_knn_graph / get_knn_graph_big): an fp16 pass over all
     # pairs (csn_ragged_retrieval_screen_f16) names the candidates that provably cannot be among a row's top K — more than
     # 2 * screen_eps below its K-th best screen score — and only the rest are scored by the exact fp32 kernels.  The SAME integers

@@ -1111,6 +1111,48 @@ CSN_API int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_
                                    const float* running_mean, const float* running_var, float eps, const void* r, int r16,
                                    long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
 
+/* ---- (25) inference: the launches of (23) as ONE 16-bit product on 16-bit maps (the maps between the launches of a Res16UNet's
+ *           inference graph) ------------------------------------------------------------------------------------------------------
+ * (23) runs the octant products as bf16x3 on fp32 maps whatever csn_set_thread_rows16 says.  Here they are the single product of
+ * (14) / (24): every operand rounded once to the math mode's 16-bit type, ONE matrix instruction per operand pair, and x, r and y
+ * may each be rows of that type (mode 2: bf16, mode 3: fp16).  Additive to ABI version 17.  The arguments are (23)'s with (24)'s type
+ * flag beside each map:
+ *   x16 / r16 / y16   0: fp32 rows, 1: 16-bit rows.  Any other value: CSN_E_ARG.  ld_x / ld_r / ld_y count ELEMENTS of the map's own
+ *                     type.  The index arrays, w and the four vectors are as in (23) (w is fp32 and rounded when it is staged).
+ *   DOWN  acc[j] = sum_k x[children[k][j]] W[k]      y[n_coarse][ld_y], r[n_coarse][ld_r]
+ *   UP    acc[i] = x[parent[i]] W[octant[i]]         y[n_fine][ld_y],   r[n_fine][ld_r]
+ *   s, t              as in (23); y[.][c] = act(acc s + t + r[.][c]) with acc s + t one fused multiply-add, stored as fp32
+ *                     (y16 == 0) or rounded ONCE to the 16-bit type (nearest even, as a CPU cast).  An fp16 store that overflows is
+ *                     a plain conversion (inf), not a clamp.
+ * DOWN is (24)'s kernel over children as a table of 8 offsets (the entry point of (24) itself refuses kv == 8, and that stays): the
+ * same column-block rule, a coarse row without children has acc = 0 and gives act(t + r).  UP are kernels of their own around (21)'s
+ * one-weight walk — tiles of at most 128 entries of order cut at the segment bounds, one W[k] per tile, ceil(n_fine / 128) + 7 row
+ * groups, (21)'s rule for the column blocks a wave owns, CSN_DEV_SCONV_NB included.  (23)'s index rules hold unchanged: a destination
+ * order[r] outside [0, n_fine) is dropped, a parent past n_coarse reads as no voxel (acc = 0), seg is read as a monotone sequence
+ * inside [0, n_fine], x, y and r go through buffer descriptors sized in bytes of the map's own type, every output row is written
+ * exactly once.
+ * EXACTNESS: with all three flags 0 UP gives, element for element, the value DOWN gives over the table t[k][i] = parent[i] where
+ * octant[i] == k and -1 elsewhere (the other seven offsets add exact zeros).  A 16-bit map changes where a value is rounded, not which
+ * product is formed: given the same representable inputs a call is bit-identical to the all-flags-0 call, its output rounded once
+ * when y16 == 1.  No workspace, no atomics; two identical calls give the same bits.  Nothing but y is written; x, r and y may be
+ * column blocks of wider buffers of their own type.
+ * Requires math mode 2 or 3 AND csn_get_thread_rows16() == 1, otherwise CSN_E_ARG.  All three flags 0 is allowed: the single-product
+ * octant product on fp32 maps.
+ * ALIASING as in (24): r may be y itself — the same pointer AND r16 == y16 AND ld_r == ld_y; r == y with another type or pitch returns
+ * CSN_E_ARG.  Any other overlap is the caller's error.
+ * Host-side checks before any launch: (23)'s for NULLs, n_fine, n_coarse and the widths, and for every fp32 map (pitch % 4
+ * CSN_E_ALIGN, >= width CSN_E_ARG, <= 2^20 and rows * pitch * 4 < 2 GiB CSN_E_DIM).  A 16-bit map needs pitch % 8 == 0 (CSN_E_ALIGN),
+ * pitch >= width (CSN_E_ARG), pitch <= 2^20 and rows * pitch * 2 < 2 GiB (CSN_E_DIM).  x, w, y, r 16-byte aligned whatever their
+ * type, the index arrays 4-byte (CSN_E_PTR). */
+CSN_API int csn_octant_down_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_fine, const int* children, int n_coarse,
+                                   int c_in, int c_out, const float* w, const float* gamma, const float* beta,
+                                   const float* running_mean, const float* running_var, float eps, const void* r, int r16,
+                                   long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
+CSN_API int csn_octant_up_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_coarse, const int* parent, const int* order,
+                                 const int* seg, int n_fine, int c_in, int c_out, const float* w, const float* gamma,
+                                 const float* beta, const float* running_mean, const float* running_var, float eps, const void* r,
+                                 int r16, long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

@@ -24,6 +24,12 @@ and bf16x3, the same rounds in one process.  ``counted_bytes`` is the traffic of
 the next gather (``infer_bytes``; the gathers and the weights are the same reads in both graphs), ``library_calls`` the C-ABI calls
 of one forward.
 
+In math modes bf16 and fp16 ``--infer`` times three routes of the one-launch graph, all with ``eval_epilogue + rows_single_product``
+(``eval_fwd_bf16`` / ``eval_fwd_fp16``): ``fp32_maps`` as it stands (sections 19 and 23: the octant products bf16x3),
+``octant16`` with ``octant_single_product`` (section 25 on fp32 maps) and ``maps16`` with ``unet_maps16`` (sections 24 and 25, every
+stored map 16-bit).  ``counted_bytes_16`` counts, on the launches themselves, the bytes each route gathers ((valid table entries,
+or fine rows) x c_in x element size), writes (the output maps) and reads as residuals, as scripts/bench_hrnet_maps16.py does.
+
     python scripts/bench_unet.py --infer --rounds 5 --out profiles/unet_infer_bench.json
 """
 import argparse
@@ -109,6 +115,48 @@ def infer_bytes(net, rows):
     return two, one
 
 
+ROUTES16 = {"fp32_maps": {}, "octant16": {"octant_single_product": True}, "maps16": {"unet_maps16": True}}
+
+
+def count_bytes_16(forward):
+    """One forward with ``sparse_conv_bn_act`` and ``octant_conv_bn_act`` wrapped: the bytes of every launch's maps by their own
+    element size.  A down convolution gathers every fine row once, an up convolution one coarse row per fine row."""
+    from csn_amd import minkowski_hrnet as MH
+    from csn_amd import minkowski_unet as MU
+    conv, octant = MH.sparse_conv_bn_act, MU.octant_conv_bn_act
+    tot = {"gathered": 0, "written": 0, "residual": 0}
+
+    def add(rows, x, y, residual):
+        tot["gathered"] += rows * (-(-x.shape[1] // 32) * 32) * x.element_size()
+        tot["written"] += y.numel() * y.element_size()
+        tot["residual"] += 0 if residual is None else residual.numel() * residual.element_size()
+
+    def counted(x, weight, kmap, norm, residual=None, relu=True, out=None, **kw):
+        y = conv(x, weight, kmap, norm, residual, relu, out, **kw)
+        add(int((kmap.fwd >= 0).sum()), x, y, residual)
+        return y
+
+    def counted_octant(x, weight, omap, norm, up, residual=None, relu=True, out=None, **kw):
+        y = octant(x, weight, omap, norm, up, residual, relu, out, **kw)
+        add(omap.n_fine, x, y, residual)
+        return y
+    MH.sparse_conv_bn_act = MU.sparse_conv_bn_act = counted
+    MU.octant_conv_bn_act = counted_octant
+    try:
+        forward()
+    finally:
+        MH.sparse_conv_bn_act = MU.sparse_conv_bn_act = conv
+        MU.octant_conv_bn_act = octant
+    return tot
+
+
+def faster16(r, new, old="fp32_maps"):
+    gap = r[f"{old}_ms"] - r[f"{new}_ms"]
+    noise = max(r[f"{v}_spread_ms"][1] - r[f"{v}_spread_ms"][0] for v in (new, old))
+    r[f"{new}_speedup"] = r[f"{old}_ms"] / r[f"{new}_ms"]
+    r[f"{new}_is_faster"] = bool(gap > noise and r[f"{new}_spread_ms"][1] < r[f"{old}_spread_ms"][0])
+
+
 def infer(a):
     import csn_amd
     csn_amd.build()
@@ -148,6 +196,19 @@ def infer(a):
             r["speedup"] = r["training_graph_ms"] / r["one_launch_ms"]
             r["one_launch_is_faster"] = bool(gap > noise and r["one_launch_spread_ms"][1] < r["training_graph_spread_ms"][0])
             res[name][f"eval_fwd_{mode}"] = r
+
+        def step16_of(mode, route):
+            def step():
+                with torch.no_grad(), CF.math_mode(CF.mode_id(mode)), tuning.override(eval_epilogue=True, rows_single_product=True,
+                                                                                      **ROUTES16[route]):
+                    net((pyr, feats))
+            return step
+        res[name]["counted_bytes_16"] = {v: count_bytes_16(step16_of("bf16", v)) for v in ROUTES16}
+        for mode in ("bf16", "fp16"):
+            r = compare({v: step16_of(mode, v) for v in ROUTES16}, a.warmup, a.iters, a.rounds)
+            faster16(r, "octant16")
+            faster16(r, "maps16")
+            res[name][f"eval_fwd_{mode}"] = r
     return res
 
 
@@ -161,7 +222,8 @@ def main():
     ap.add_argument("--mode", default="bf16x3", help="math mode: fp32 or bf16x3 (the library's default)")
     ap.add_argument("--skip-network", action="store_true")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--infer", action="store_true", help="time the eval variants (eval_epilogue off against on, fp32 and bf16x3) instead")
+    ap.add_argument("--infer", action="store_true", help="time the eval variants instead: eval_epilogue off against on in fp32 and bf16x3, and the one-launch graph's "
+                                                    "fp32-map, single-product-octant and 16-bit-map routes in bf16 and fp16")
     a = ap.parse_args()
     if a.infer:
         line = json.dumps(infer(a))
