@@ -40,11 +40,13 @@ from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load
 
 # the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks; octant_conv_bn_act is the
 # inference primitive of its resolution changes, on fp32 maps or (single_product / 16-bit tensors, where maps16_dtype() names a
-# type) as one 16-bit product on fp32 or 16-bit maps
+# type) as one 16-bit product on fp32 or 16-bit maps; octant_conv_stats / cat_conv_stats are the training nodes of
+# tuning.unet_fused_tail (the BatchNorm statistics from the product's epilogue; they feed bn_act)
 from .minkowski_unet import (Res16UNet14, Res16UNet14A, Res16UNet14A2, Res16UNet14B, Res16UNet14B2, Res16UNet14B3,  # noqa: E402,F401
                              Res16UNet14C, Res16UNet14D, Res16UNet18, Res16UNet18A, Res16UNet18B, Res16UNet18D, Res16UNet34,
                              Res16UNet34A, Res16UNet34B, Res16UNet34C, Res16UNet50, Res16UNet101, Res16UNetBase, UNetBasicBlock,
-                             UNetPyramid, build_unet_pyramid, load_me_unet_state, octant_conv_bn_act)
+                             UNetPyramid, build_unet_pyramid, cat_conv_stats, load_me_unet_state, octant_conv_bn_act,
+                             octant_conv_stats)
 
 # point fields: the points of a batch quantised to voxel rows, and voxel logits interpolated back onto the points
 # (MinkowskiNet/lib/trainer_csn.py:236-260 TensorField(...).sparse(), :200-205 and :463-471 soutput.interpolate(field))

@@ -16,7 +16,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libcsn_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "octant_conv.hip", "octant_conv_maps16.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "sparse_conv_cat.hip", "octant_conv.hip", "octant_conv_maps16.hip", "octant_conv_stats.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
 HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", "octant_rows_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
 ARCH = "gfx950"
 BUILD_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"]
@@ -33,6 +33,11 @@ class BnTerms(ctypes.Structure):
     _fields_ = [("z", c_void_p * 3), ("ld_z", c_longlong * 3), ("mean", c_void_p * 3), ("scale", c_void_p * 3),
                 ("gamma", c_void_p * 3), ("beta", c_void_p * 3), ("dz", c_void_p * 3), ("ld_dz", c_longlong * 3),
                 ("dgamma", c_void_p * 3), ("dbeta", c_void_p * 3)]
+
+
+class CatParts(ctypes.Structure):
+    """``CsnCatParts`` of include/csn_hip.h section 27: up to four parts of a concatenation as a struct of arrays (``ctypes.byref``)."""
+    _fields_ = [("x", c_void_p * 4), ("ld_x", c_longlong * 4), ("c_in", c_int * 4)]
 
 
 STAMP_PATH = LIB_PATH + ".sha256"
@@ -301,6 +306,16 @@ _SIGNATURES = {
     "csn_octant_up_bn_act_fwd_m16": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_longlong,
                                              c_int, c_void_p, c_int, c_longlong, c_void_p]),
+    "csn_octant_stats_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "csn_octant_down_stats_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_longlong, c_void_p]),
+    "csn_octant_up_stats_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
+                                            c_longlong, c_void_p]),
+    "csn_sparse_conv_cat_stats_workspace_bytes": (c_longlong, [c_int, c_int]),
+    "csn_sparse_conv_cat_stats_fwd_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_longlong,
+                                                  c_void_p]),
     "csn_voxel_mean_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "csn_point_interp_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_longlong,
                                          c_void_p]),

@@ -1664,6 +1664,77 @@ int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_coarse, c
   return csn_launch_octant_up_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
 }
 
+// ---- (26) the octant convolutions with the BatchNorm statistics epilogue (training) ----
+long long csn_octant_stats_workspace_bytes(int n_fine, int n_coarse, int c_out, int up) {
+  if (octant_dims(n_fine, n_coarse, 32, c_out)) return 0;
+  return csn_octant_stats_ws_bytes(n_fine, n_coarse, c_out, up != 0);
+}
+
+// (21)'s checks on the maps, (15a)'s on the batch and the workspace; n_x / n_z: the rows of x / z
+static int octant_stats_args(long long ld_x, int n_x, int n_z, int n_fine, int n_coarse, int c_in, int c_out, long long ld_z,
+                             long long ws_bytes, bool up) {
+  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map(ld_x, c_in, n_x)) return e;
+  if (const int e = sparse_conv_map(ld_z, c_out, n_z)) return e;
+  if (n_z < 2) return CSN_E_ARG;                                  // a one-row batch has no variance
+  if (ws_bytes < csn_octant_stats_ws_bytes(n_fine, n_coarse, c_out, up)) return CSN_E_WORKSPACE;
+  return 0;
+}
+
+int csn_octant_down_stats_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
+                                  const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
+                                  float* running_var, float eps, float momentum, void* ws, long long ws_bytes, void* stream) {
+  if (!x || !children || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
+  if (const int e = octant_stats_args(ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, ld_z, ws_bytes, false)) return e;
+  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || off4(children)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
+  a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  return csn_launch_octant_down_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, octant_mode(), (hipStream_t)stream);
+}
+
+int csn_octant_up_stats_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
+                                int n_fine, int c_in, int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
+                                void* stream) {
+  if (!x || !parent || !order || !seg || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
+  if (const int e = octant_stats_args(ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, ld_z, ws_bytes, true)) return e;
+  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
+  a.order = order; a.seg = seg; a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  return csn_launch_octant_up_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, octant_mode(), (hipStream_t)stream);
+}
+
+// ---- (27) (15a) over a concatenation that is never formed ----
+long long csn_sparse_conv_cat_stats_workspace_bytes(int n_out, int c_out) { return csn_sparse_conv_stats_workspace_bytes(n_out, c_out); }
+
+int csn_sparse_conv_cat_stats_fwd_f32(const CsnCatParts* parts, int n_parts, int n_in, const int* table, int n_out, int kv, int c_out,
+                                      const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
+                                      float* running_var, float eps, float momentum, void* ws, long long ws_bytes, void* stream) {
+  if (!parts || n_parts < 1 || n_parts > 4 || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
+  if (kv != 1 && kv != 27) return CSN_E_DIM;
+  const float* x[4]; int ld_x[4], c_in[4];
+  long long sum = 0;
+  for (int m = 0; m < n_parts; ++m) {
+    if (!parts->x[m]) return CSN_E_ARG;
+    if (const int e = sparse_conv_dims(n_in, n_out, kv, parts->c_in[m], c_out)) return e;
+    if (const int e = sparse_conv_map(parts->ld_x[m], parts->c_in[m], n_in)) return e;
+    if (mis16(parts->x[m])) return CSN_E_PTR;
+    x[m] = parts->x[m]; ld_x[m] = (int)parts->ld_x[m]; c_in[m] = parts->c_in[m];
+    sum += c_in[m];
+  }
+  if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
+  if (mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (n_out < 2) return CSN_E_ARG;                                // a one-row batch has no variance
+  if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
+  CsnSparseConvArgs a{};
+  a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = (int)sum; a.c_out = c_out; a.w = w; a.y = z; a.ld_y = (int)ld_z;
+  a.ws = ws;
+  return csn_launch_sparse_conv_cat_stats_fwd(a, x, ld_x, c_in, n_parts, mean, invstd, running_mean, running_var, eps, momentum,
+                                              rows_mode(), (hipStream_t)stream);
+}
+
 // ---- (24) the launch of (19) on 16-bit maps: x, r and y each fp32 rows or rows of the math mode's 16-bit type ----
 // a 16-bit row-major map of n rows: pitch % 8, >= its width, and the whole map inside one 2 GiB buffer window
 static int sparse_conv_map16(long long ld, int width, int n) {

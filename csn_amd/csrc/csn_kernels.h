@@ -325,6 +325,7 @@ struct CsnSparseConvArgs {
   const float* dy;  int ld_dy;
   float* dx;  int ld_dx;  float* dw;  float* dbias;               // each skipped when NULL
   void* ws;
+  int w_rows;                                                     // forward only: rows of every W[k] (0: c_in); > c_in: w is a row slice
 };
 long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward);
 int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st);
@@ -341,6 +342,11 @@ struct CsnSconvBnArgs {
   const float* r;  int ld_r;  int relu;
 };
 int csn_launch_sparse_conv_bn_act_fwd(const CsnSparseConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
+// (27) the same over a concatenation that is never formed (sparse_conv_cat.hip): x[m] / ld_x[m] / c_in[m] the parts, a.c_in the sum of
+// their widths, a.w the one kernel [kv][a.c_in][c_out]; a chain of one launch per part, the last with the statistics epilogue
+int csn_launch_sparse_conv_cat_stats_fwd(const CsnSparseConvArgs& a, const float* const* x, const int* ld_x, const int* c_in, int n_parts,
+                                         float* mean, float* invstd, float* running_mean, float* running_var, float eps, float momentum,
+                                         int mode, hipStream_t st);
 extern int csn_dev_sconv_nb;                                      // development switch (csn_dev_set): 0 = the launch rule
 // the 32-column blocks a wave owns in a gather-GEMM of J columns over M rows: sparse_conv.hip's launch rule, csn_dev_sconv_nb included
 int csn_sconv_column_blocks(int J, long long M);
@@ -378,6 +384,13 @@ int csn_launch_octant_down_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconv
 int csn_launch_octant_up_bn_act_fwd(const CsnOctantConvArgs& a, const CsnSconvBnArgs& n, int mode, hipStream_t st);
 // the 32-column blocks a wave owns in a one-weight product of J columns over M rows: octant_conv.hip's launch rule
 int csn_octant_column_blocks(int J, long long M);
+// the two forwards with the BatchNorm statistics epilogue (include/csn_hip.h section 26, octant_conv_stats.hip): a.y = z, no bias,
+// a.ws = csn_octant_stats_ws_bytes bytes; down is csn_launch_sparse_conv_stats_fwd over children as a table of 8 offsets
+long long csn_octant_stats_ws_bytes(long long n_fine, long long n_coarse, int c_out, int up);
+int csn_launch_octant_down_stats_fwd(const CsnOctantConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
+                                     float eps, float momentum, int mode, hipStream_t st);
+int csn_launch_octant_up_stats_fwd(const CsnOctantConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
+                                   float eps, float momentum, int mode, hipStream_t st);
 // the same two forwards as ONE 16-bit product (math modes 2 / 3) on maps that are each fp32 or 16-bit rows
 // (octant_conv_maps16.hip): down is csn_launch_sparse_conv_bn_act_fwd_m16 over children as a table of 8 offsets, up kernels of
 // their own; the vectors, eps and relu come from CsnSconvBnArgs (its r / ld_r are not read)

@@ -61,7 +61,7 @@ __device__ __forceinline__ OctRowsBnLateP oct_bn_args_late() {
 // (BN is stated in terms of NB so that the body's choice between the two epilogues is made per instance, as in sparse_conv.hip)
 template <int NB, int MODE, bool B_KN>
 __global__ __launch_bounds__(256) void octant_rows_kernel(const OctRowsP p) {
-  constexpr bool BN = NB < 0;
+  constexpr bool BN = NB < 0, STATS = NB < 0;
 #include "octant_rows_body.inc"
 }
 
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void octant_rows_kernel(const OctRowsP p) {
 // names, arguments and code)
 template <int NB, int MODE>
 __global__ __launch_bounds__(256) void octant_rows_bn_kernel(const OctRowsBnP p) {
-  constexpr bool B_KN = true, BN = NB > 0;
+  constexpr bool B_KN = true, BN = NB > 0, STATS = NB < 0;
 #include "octant_rows_body.inc"
 }
 

@@ -1,15 +1,24 @@
 // The body of the one-weight octant product of octant_conv.hip, included into octant_rows_kernel (p an OctRowsP) and
-// octant_rows_bn_kernel (p an OctRowsBnP: the up convolution's forward with the inference epilogue) with NB, MODE, B_KN, BN and the
-// argument p in scope.  BN stores act(acc * s + t + r) through the same destinations in place of acc + bias.  The loop is the same
-// text either way: the same sums in the same order.  Text and not a __device__ function, as sconv_gemm_body.inc is and for its reason.
+// octant_rows_bn_kernel (p an OctRowsBnP: the up convolution's forward with the inference epilogue) with NB, MODE, B_KN, BN, STATS and
+// the argument p in scope.  BN stores act(acc * s + t + r) through the same destinations in place of acc + bias.  STATS
+// (octant_conv_stats.hip, p an OctRowsStatsP) stores acc + bias and then forms the (mean, M2) of the wave's rows with their count.
+// The loop is the same text in every form: the same sums in the same order.  Text and not a __device__ function, as
+// sconv_gemm_body.inc is and for its reason.
   __shared__ __attribute__((aligned(16))) float Bs[NB * 32 * BS_PITCH];
   __shared__ int s_dst[128];
   const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, li = l & 31, h = l >> 5;
   const int ncg = (p.J + NB * 32 - 1) / (NB * 32);
   const int cg = blockIdx.x % ncg, rg = blockIdx.x / ncg;
   const int j0 = cg * NB * 32;
+  // STATS: the epilogue's own arguments (part, cnt) are reached through a pointer of the instance's argument type, as q below
+  [[maybe_unused]] const auto* sq = [&] { return &p; }();
   int k, lo, hi;
-  if (!octant_span(p.seg, p.M, rg, 128, k, lo, hi)) return;           // uniform over the work-group
+  if (!octant_span(p.seg, p.M, rg, 128, k, lo, hi)) {                 // uniform over the work-group
+    if constexpr (STATS) {
+      if (cg == 0 && tid < 4) sq->cnt[rg * 4 + tid] = 0;                // its four wave tiles hold no rows
+    }
+    return;
+  }
   const int r = lo + wave * 32 + li;                                  // the lane's entry of `order`
   int dst = r < hi ? p.order[r] : -1;
   if (dst >= p.M) dst = -1;
@@ -67,10 +76,36 @@
       }
     } else {
       const float bv = p.bias ? p.bias[col] : 0.f;
+      [[maybe_unused]] unsigned live = 0;                               // STATS: bit e set where accumulator row e has a destination
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int d = s_dst[wave * 32 + csn_acc_row(e, h)];
+        if constexpr (STATS) live |= (d >= 0 ? 1u : 0u) << e;
         csn_bstore(acc[nb][e] + bv, cr, d < 0 ? CSN_OOB : ((unsigned)d * (unsigned)p.ldc + (unsigned)col) * 4u);
+      }
+      if constexpr (STATS) {
+        // (mean, M2) of the column over the wave's rows that have a destination — 0 to 32 of them, counted and not assumed —
+        // in two passes over the registers (store_tile's arithmetic); the count goes beside them once per tile
+        const int cnt = __popcll(__ballot(h == 0 && dst >= 0));
+        float sum = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          if (live >> e & 1u) sum += acc[nb][e] + bv;
+        sum += csn_xhalf(sum);
+        const float mu = cnt > 0 ? sum / (float)cnt : 0.f;
+        float m2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const float dv = (acc[nb][e] + bv) - mu;
+          if (live >> e & 1u) m2 = fmaf(dv, dv, m2);
+        }
+        m2 += csn_xhalf(m2);
+        const int tile = rg * 4 + wave;                                 // < (ceil(M / 128) + 7) * 4, the rows of part and cnt
+        const csn_rsrc_t pr = csn_make_rsrc(sq->part, (((long long)p.M + 127) / 128 + 7) * 4 * 2 * p.J * 4LL);
+        const unsigned po = h == 0 ? ((unsigned)(tile * 2) * (unsigned)p.J + (unsigned)col) * 4u : CSN_OOB;
+        csn_bstore(mu, pr, po);
+        csn_bstore(m2, pr, h == 0 ? po + (unsigned)p.J * 4u : CSN_OOB);
+        if (cg == 0 && nb == 0 && l == 0) sq->cnt[tile] = cnt;
       }
     }
   }

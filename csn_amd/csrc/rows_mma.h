@@ -10,7 +10,7 @@
 //                    mma_step_a16 is the single-product step on A fragments that ARE 16-bit (the 16-bit maps of
 //                    sparse_conv_maps16.hip and octant_conv_maps16.hip: two 16-byte loads per step, no conversion).
 //   octant tiles     octant_span: the (octant, range) of `order` a work-group or a chunk owns (octant_conv.hip,
-//                    octant_conv_maps16.hip).
+//                    octant_conv_maps16.hip, octant_conv_stats.hip).
 //   weight gradient  both operands are k-major (the contraction runs over the rows): a lane holds 8 rows of one column per 16-row
 //                    step (wgrad_row) and splits them in registers (wgrad_step); the four waves of a work-group contract a
 //                    quarter of its row chunk each and are added through LDS in wave order (wgrad_reduce_store).
@@ -18,7 +18,8 @@
 //                    rounded once to 16 bits (to16x4: nearest even) — A in registers, B when it is stored to LDS, so the tile
 //                    holds shorts and a lane's B fragment is one 16-byte read.
 //   statistics       chan_merge / chan_walk / bn_finish: [tile][2][C] (mean, M2) partials of 32-row tiles -> mean, invstd,
-//                    running statistics, in fp64.
+//                    running statistics, in fp64.  chan_walk_counts: the same over tiles that carry their own row counts
+//                    (octant_conv_stats.hip).
 // Every reduction has a fixed order.
 #pragma once
 #include <type_traits>
@@ -333,6 +334,17 @@ __device__ __forceinline__ void chan_walk(double& n, double& mu, double& m2, con
     if (left <= 0) break;
     chan_merge(n, mu, m2, left < 32 ? (double)left : 32.0, (double)part[((long long)t * 2) * C + col],
                (double)part[((long long)t * 2 + 1) * C + col]);
+  }
+}
+
+// the same walk over tiles that hold cnt[t] rows each, 0 .. 32 in any order (the octant tiles of octant_conv_stats.hip, cut at the
+// segment bounds: a short or empty tile may sit anywhere in the list); an empty tile's partial is not read
+__device__ __forceinline__ void chan_walk_counts(double& n, double& mu, double& m2, const float* __restrict__ part,
+                                                 const int* __restrict__ cnt, int t0, int t1, int C, int col) {
+  for (int t = t0; t < t1; ++t) {
+    const int c = cnt[t];
+    if (c <= 0) continue;
+    chan_merge(n, mu, m2, (double)c, (double)part[((long long)t * 2) * C + col], (double)part[((long long)t * 2 + 1) * C + col]);
   }
 }
 

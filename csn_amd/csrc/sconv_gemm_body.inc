@@ -1,5 +1,7 @@
 // The body of the gather-GEMM kernels of sparse_conv.hip, included into sconv_gemm_kernel (MODE 0 fp32 / 1 bf16x3) and
-// sconv_gemm16_kernel (MODE 2 bf16 / 3 fp16: one product, the tile holds shorts) with NB, MODE, B_KN, BN and the argument p in scope.
+// sconv_gemm16_kernel (MODE 2 bf16 / 3 fp16: one product, the tile holds shorts) with NB, MODE, B_KN, BN, ACC and the argument p in
+// scope.  ACC (sconv_gemm_acc_kernel, sparse_conv_cat.hip: a later launch of a chain over the parts of a concatenation) adds the z that
+// is already in c to the accumulators before store_tile, so that the stored sum and its statistics are the chain's.
 // BN (sconv_gemm_bn_kernel / sconv_gemm16_bn_kernel: forward instances, p a SconvBnP) takes the BatchNorm + residual + ReLU epilogue
 // of store_tile_bn in place of store_tile.  The loop is the same text either way: the same sums in the same order.
 // It is text and not a __device__ function on purpose: called through a function (by reference, by value or field by field) the
@@ -82,7 +84,16 @@
       // the lane's column of the block: its two constants, formed here from the four vectors (no preparation launch)
       const float sc = q->gamma[col] / sqrtf(q->rvar[col] + q->eps);
       store_tile_bn(acc[nb], sc, q->beta[col] - q->rmean[col] * sc, q->r, q->ldr, q->relu != 0, p.c, p.ldc, row_w, cnt, col, h);
-    } else
+    } else {
+      if constexpr (ACC) {
+        // the sum of the parts before this one: z is read where store_tile writes it, each element by the lane that stores it
+        const float* cw = p.c + row_w * p.ldc;
+        const int lane = 4 * h * p.ldc + col;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (csn_acc_row(r, h) < cnt) acc[nb][r] += (cw + csn_acc_row(r, 0) * p.ldc)[lane];
+      }
       store_tile(acc[nb], p.bias ? p.bias[col] : 0.f, p.c, p.ldc, row_w, cnt, col, h, p.part != nullptr, p.part, (long long)rg * 4 + wave,
                  p.J);
+    }
   }

@@ -68,7 +68,7 @@ __device__ __forceinline__ SconvBnLateP bn_args_late() {
 // instance does not take is never instantiated for its argument type)
 template <int NB, int MODE, bool B_KN>
 __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
-  constexpr bool BN = NB < 0;
+  constexpr bool BN = NB < 0, ACC = false;
 #include "sconv_gemm_body.inc"
 }
 
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void sconv_gemm_kernel(const SconvGemmP p) {
 template <int NB, bool H16, bool B_KN>
 __global__ __launch_bounds__(256) void sconv_gemm16_kernel(const SconvGemmP p) {
   constexpr int MODE = H16 ? 3 : 2;
-  constexpr bool BN = NB < 0;
+  constexpr bool BN = NB < 0, ACC = false;
 #include "sconv_gemm_body.inc"
 }
 
@@ -84,14 +84,14 @@ __global__ __launch_bounds__(256) void sconv_gemm16_kernel(const SconvGemmP p) {
 // arguments and code)
 template <int NB, int MODE>
 __global__ __launch_bounds__(256) void sconv_gemm_bn_kernel(const SconvBnP p) {
-  constexpr bool B_KN = true, BN = NB > 0;
+  constexpr bool B_KN = true, BN = NB > 0, ACC = false;
 #include "sconv_gemm_body.inc"
 }
 
 template <int NB, bool H16>
 __global__ __launch_bounds__(256) void sconv_gemm16_bn_kernel(const SconvBnP p) {
   constexpr int MODE = H16 ? 3 : 2;
-  constexpr bool B_KN = true, BN = NB > 0;
+  constexpr bool B_KN = true, BN = NB > 0, ACC = false;
 #include "sconv_gemm_body.inc"
 }
 
@@ -266,7 +266,8 @@ long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int 
 // mode: 0 fp32, 1 bf16x3, 2 bf16 / 3 fp16 single product (csn_capi.hip resolves the thread's math mode and rows16 flag)
 int csn_launch_sparse_conv_fwd(const CsnSparseConvArgs& a, int mode, hipStream_t st) {
   SconvGemmP p{};
-  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.c_in; p.c_out = a.c_out;
+  // w_rows: the rows of every W[k] where the contraction takes a slice [c0, c0 + c_in) of them (a.w points at row c0 of W[0])
+  p.a = a.x; p.lda = a.ld_x; p.n_src = a.n_in; p.table = a.fwd_table; p.b = a.w; p.c_in = a.w_rows ? a.w_rows : a.c_in; p.c_out = a.c_out;
   p.c = a.y; p.ldc = a.ld_y; p.M = a.n_out; p.K = a.c_in; p.J = a.c_out; p.KV = a.kv; p.bias = a.bias;
   return launch_gemm<true>(p, mode, st);
 }

@@ -13,6 +13,9 @@ minkowski_hrnet.py (``conv_stats`` + ``bn_act``, section 15): a block whose widt
 ``[up | skip]``: up to 256 columns it is formed with ``torch.cat`` and takes the fused path; beyond, ``conv1`` and the ``downsample``
 convolution go through ``cat_conv3d`` (the concatenation is never formed) with an ATen BatchNorm, and the rest of the block stays
 fused.  ``fused=False`` runs everything on ``sparse_conv3d`` / the octant nodes + ATen: the timing baseline and the tests' yardstick.
+``tuning.override(unet_fused_tail=True)`` (a fused network in training mode, opt-in) puts those two remaining layer kinds on the
+fused nodes as well: a resolution change is ``octant_conv_stats`` + ``bn_act`` (section 26), ``conv1`` / ``downsample.0`` of a block
+wider than 256 columns are ``cat_conv_stats`` (section 27) terms of the block's ``bn_act`` sums — no ATen normalisation is left.
 
 ``UNetPyramid`` holds what one batch needs, built once (``build_unet_pyramid``): five levels at tensor strides 1 .. 16 — the
 coordinate sets ``build_pyramid`` gives —, per level the kernel-3 and the kernel-1 map, at level 0 the stem's map, between
@@ -38,11 +41,13 @@ chain's running sum (an fp32 scratch map: the sum is rounded once, like every ot
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import functional as CF
@@ -215,6 +220,194 @@ def _octant_bn_act(conv: SparseConvDown2, norm: nn.BatchNorm1d, x, omap: OctantM
     return octant_conv_bn_act(x, conv.kernel, omap, norm, conv.up, residual, relu, out, out_dtype=out_dtype, single_product=single_product)
 
 
+# ------------------------------------------------------------------------------------------------------
+# training: the octant products and the convolution over a concatenation with the BatchNorm statistics epilogue (sections 26, 27)
+# ------------------------------------------------------------------------------------------------------
+class _OctantConvStats(torch.autograd.Function):
+    """(z, mean, invstd) = ``csn_octant_{down,up}_stats_fwd_f32``; updates the running statistics in place.  mean / invstd are
+    constants of the graph; the backward is ``csn_octant_{down,up}_bwd_f32`` with dbias = NULL."""
+
+    @staticmethod
+    def forward(ctx, x, w, omap, up, running_mean, running_var, eps, momentum):
+        CF._need_cuda(x, w, omap.parent, running_mean, running_var)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        x = x.contiguous()
+        w_c = w.detach().contiguous()
+        _, c_in, c_out = w_c.shape
+        n_fine, n_coarse = omap.n_fine, omap.n_coarse
+        dev = x.device
+        z = torch.empty((n_fine if up else n_coarse, c_out), device=dev, dtype=torch.float32)
+        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_octant_stats_workspace_bytes(n_fine, n_coarse, c_out, int(up)))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        tail = (CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps),
+                float(momentum), CF._ptr(ws), ws_n, CF._stream())
+        if up:
+            _lib.check(L.csn_octant_up_stats_fwd_f32(CF._ptr(x), c_in, n_coarse, CF._ptr(omap.parent), CF._ptr(omap.order),
+                                                     CF._ptr(omap.seg), n_fine, c_in, c_out, *tail), "csn_octant_up_stats_fwd_f32")
+        else:
+            _lib.check(L.csn_octant_down_stats_fwd_f32(CF._ptr(x), c_in, n_fine, CF._ptr(omap.children), n_coarse, c_in, c_out, *tail),
+                       "csn_octant_down_stats_fwd_f32")
+        ctx.save_for_backward(x, w_c)
+        ctx.omap, ctx.up = omap, up
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dmean, _dinvstd):
+        with CF.math_mode(CF.backward_mode(ctx.mode)):
+            x, w = ctx.saved_tensors
+            omap, up = ctx.omap, ctx.up
+            L = _lib.lib()
+            _, c_in, c_out = w.shape
+            n_fine, n_coarse = omap.n_fine, omap.n_coarse
+            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (need_x or need_w):
+                return (None,) * 8
+            dz = dz.contiguous()
+            dx = torch.empty_like(x) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            ws_n = int(L.csn_octant_conv_workspace_bytes(n_fine, n_coarse, c_in, c_out, int(up), 1))
+            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+            if up:
+                _lib.check(L.csn_octant_up_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
+                                                   CF._ptr(omap.children), CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg),
+                                                   CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None, CF._ptr(ws), ws_n, CF._stream()),
+                           "csn_octant_up_bwd_f32")
+            else:
+                _lib.check(L.csn_octant_down_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
+                                                     CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg), CF._ptr(w),
+                                                     CF._ptr(dx), c_in, CF._ptr(dw), None, CF._ptr(ws), ws_n, CF._stream()),
+                           "csn_octant_down_bwd_f32")
+            return (dx, dw) + (None,) * 6
+
+
+def octant_conv_stats(x: torch.Tensor, weight: torch.Tensor, omap: OctantMap, up: bool, running_mean: Optional[torch.Tensor],
+                      running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``z``, ``mean``, ``invstd`` of the kernel-2 stride-2 convolution (``up`` False: ``x (n_fine, c_in)`` -> ``z (n_coarse,
+    c_out)``) or its transposed form (``up`` True: ``x (n_coarse, c_in)`` -> ``z (n_fine, c_out)``) without a bias, and of ``z``'s
+    BatchNorm batch, formed by the product's own epilogue (include/csn_hip.h section 26); the running statistics (either may be
+    None) are updated in place.  ``z`` holds the bits of ``octant_conv_down`` / ``octant_conv_up``.  ``weight (8, c_in, c_out)``,
+    widths multiples of 32 in [32, 256].  The statistics are constants of the graph: feed ``(z, mean, invstd, gamma, beta)`` to
+    ``bn_act``, whose backward is the complete BatchNorm gradient.  A one-row ``z`` raises ``ValueError`` (no variance)."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise _lib.CsnError(_NO_CPU)
+    if not isinstance(omap, OctantMap):
+        raise ValueError(f"a kernel-2 stride-2 convolution takes an OctantMap, not {type(omap).__name__}")
+    if x.dim() != 2 or weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != 8:
+        raise ValueError("x must be (n_in, c_in) and weight (8, c_in, c_out)")
+    n_in, n_out = (omap.n_coarse, omap.n_fine) if up else (omap.n_fine, omap.n_coarse)
+    if x.shape[0] != n_in:
+        raise ValueError(f"x has {x.shape[0]} rows, the map's input set {n_in}")
+    for name, c in (("c_in", weight.shape[1]), ("c_out", weight.shape[2])):
+        if c % 32 or not 32 <= c <= 256:
+            raise ValueError(f"{name} {c} is not supported: a multiple of 32 in [32, 256]")
+    if n_out < 2:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    return _OctantConvStats.apply(x.float(), weight, omap, bool(up), running_mean, running_var, eps, momentum)
+
+
+class _CatConvStats(torch.autograd.Function):
+    """(z, mean, invstd) = ``csn_sparse_conv_cat_stats_fwd_f32`` on the parts as they lie (row-pitched views are handed over with
+    their pitch); updates the running statistics in place.  The backward is ``csn_sparse_conv_bwd_f32`` per part on a contiguous
+    copy of that part's slice of the kernel; dw is written slice by slice into one (KV, sum c_in, c_out) tensor.
+    Arguments after the fixed ones: the parts."""
+
+    @staticmethod
+    def forward(ctx, w, kmap, running_mean, running_var, eps, momentum, *parts):
+        CF._need_cuda(w, kmap.fwd, running_mean, running_var, *parts)
+        L = _lib.lib()
+        ctx.mode = CF.current_mode()
+        ctx.rows16 = tuning.current().rows_single_product
+        xs = [_mh._rows(p) for p in parts]
+        w_c = w.detach().contiguous()
+        KV, _, c_out = w_c.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        dev = w_c.device
+        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
+        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_sparse_conv_cat_stats_workspace_bytes(n_out, c_out))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        cp = _lib.CatParts()
+        for m, x in enumerate(xs):
+            cp.x[m], cp.ld_x[m], cp.c_in[m] = x.data_ptr(), x.stride(0), x.shape[1]
+        with CF.rows16(ctx.rows16):
+            _lib.check(L.csn_sparse_conv_cat_stats_fwd_f32(ctypes.byref(cp), len(xs), n_in, CF._ptr(kmap.fwd), n_out, KV, c_out,
+                                                           CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd),
+                                                           CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum),
+                                                           CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_cat_stats_fwd_f32")
+        ctx.save_for_backward(w_c, *xs)
+        ctx.kmap = kmap
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dmean, _dinvstd):
+        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
+            w, *xs = ctx.saved_tensors
+            kmap = ctx.kmap
+            L = _lib.lib()
+            KV, _, c_out = w.shape
+            n_in, n_out = kmap.n_in, kmap.n_out
+            need_w = ctx.needs_input_grad[0]
+            need_x = [ctx.needs_input_grad[6 + m] for m in range(len(xs))]
+            if not (need_w or any(need_x)):
+                return (None,) * (6 + len(xs))
+            dz = dz.contiguous()
+            dw = torch.empty_like(w) if need_w else None
+            dxs, c0 = [], 0
+            for x, nx in zip(xs, need_x):
+                c_in = int(x.shape[1])
+                if not (nx or need_w):
+                    dxs.append(None)
+                    c0 += c_in
+                    continue
+                w_m = w[:, c0:c0 + c_in].contiguous() if nx else None
+                dx = torch.empty((n_in, c_in), device=x.device, dtype=torch.float32) if nx else None
+                dw_m = torch.empty((KV, c_in, c_out), device=x.device, dtype=torch.float32) if need_w else None
+                ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+                ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+                bwd = kmap.bwd_table if nx else None
+                _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), x.stride(0), n_in, n_out, KV, c_in, c_out,
+                                                     CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w_m), CF._ptr(dx), c_in, CF._ptr(dw_m), None,
+                                                     CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+                if need_w:
+                    dw[:, c0:c0 + c_in] = dw_m
+                dxs.append(dx)
+                c0 += c_in
+            return (dw, None, None, None, None, None, *dxs)
+
+
+def cat_conv_stats(parts: Sequence[torch.Tensor], weight: torch.Tensor, kmap: KernelMap, running_mean: Optional[torch.Tensor],
+                   running_var: Optional[torch.Tensor], eps: float, momentum: float):
+    """``z (n_out, c_out)``, ``mean``, ``invstd`` of the convolution of ``torch.cat(parts, dim=1)`` and of its BatchNorm batch
+    (include/csn_hip.h section 27): ``parts`` 1 to 4 maps ``(n_in, c_p)``, every ``c_p`` a multiple of 32 in [32, 256], and
+    ``weight (KV, sum c_p, c_out)`` ONE kernel (kernel size 1 or 3), read in place through each part's row offset.  The
+    concatenation is never formed: a chain of one launch per part, the last of which forms the statistics of the completed sum.
+    Parts that are column blocks of one wider buffer are read through their pitch.  The running statistics (either may be None)
+    are updated in place.  With one part it is ``conv_stats``, bit for bit.  A one-row output raises ``ValueError``."""
+    parts = list(parts)
+    if not 1 <= len(parts) <= 4:
+        raise ValueError(f"cat_conv_stats takes 1 to 4 parts, not {len(parts)}")
+    if not (weight.is_cuda and all(p.is_cuda for p in parts)):
+        raise _lib.CsnError(_NO_CPU)
+    if weight.dim() != 3 or any(p.dim() != 2 for p in parts) or sum(int(p.shape[1]) for p in parts) != weight.shape[1]:
+        raise ValueError("the parts must be (n_in, c_p) maps whose widths add up to the weight's c_in")
+    if weight.shape[0] != kmap.KV or kmap.KV not in (1, 27) or any(p.shape[0] != kmap.n_in for p in parts):
+        raise ValueError("weight must be (KV, c_in, c_out) for the map's KV (kernel size 1 or 3) and every part must have its n_in rows")
+    c_out = weight.shape[2]
+    if c_out % 32 or not 32 <= c_out <= 256 or any(p.shape[1] % 32 or not 32 <= p.shape[1] <= 256 for p in parts):
+        raise ValueError("widths: c_out and every part a multiple of 32 in [32, 256]")
+    if kmap.n_out < 2:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    return _CatConvStats.apply(weight, kmap, running_mean, running_var, eps, momentum, *[p.float() for p in parts])
+
+
 class CatConv3d(nn.Module):
     """A stride-1 convolution whose input is a concatenation wider than 256 columns: it holds MinkowskiEngine's ``kernel (KV,
     c_in, c_out)`` and runs ``cat_conv3d`` on the parts."""
@@ -240,6 +433,34 @@ class CatConv3d(nn.Module):
 
     def extra_repr(self) -> str:
         return f"{self.c_in}, {self.c_out}, kernel_size={self.kernel_size}, stride=1, bias=False"
+
+
+def _cat_conv_bn(conv: CatConv3d, norm: nn.BatchNorm1d, parts: Sequence[torch.Tensor], kmap: KernelMap):
+    """``_conv_bn`` for a convolution over a concatenation, training mode on the fused nodes: the term (z, mean, invstd, gamma, beta)
+    of ``bn_act``; the norm's running statistics and ``num_batches_tracked`` advance as ATen's do."""
+    if kmap.kernel_size != conv.kernel_size or kmap.stride != 1 or kmap.transposed:
+        raise ValueError(f"the map (kernel {kmap.kernel_size}, stride {kmap.stride}, transposed {kmap.transposed}) does not fit "
+                         f"this layer (kernel {conv.kernel_size}, stride 1, transposed False)")
+    if kmap.n_out == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    norm.num_batches_tracked += 1
+    z, mean, invstd = cat_conv_stats(parts, conv.kernel, kmap, norm.running_mean, norm.running_var, norm.eps, norm.momentum)
+    return (z, mean, invstd, norm.weight, norm.bias)
+
+
+def _octant_bn_relu(conv: SparseConvDown2, norm: nn.BatchNorm1d, x: torch.Tensor, omap: OctantMap, tail: bool) -> torch.Tensor:
+    """relu(norm(conv(x))) of a resolution change.  ``tail`` (``tuning.unet_fused_tail``, a fused network in training mode):
+    ``octant_conv_stats`` + ``bn_act`` (section 26 + 15b) instead of the octant node + ATen's BatchNorm + ``F.relu``."""
+    if not tail:
+        return F.relu(norm(conv(x, omap)))
+    if conv.bias is not None:
+        raise ValueError("the statistics launch of an octant convolution takes no bias (the Res16UNets have none)")
+    n_out = omap.n_fine if conv.up else omap.n_coarse
+    if n_out == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    norm.num_batches_tracked += 1
+    z, mean, invstd = octant_conv_stats(x, conv.kernel, omap, conv.up, norm.running_mean, norm.running_var, norm.eps, norm.momentum)
+    return _mh.bn_act([(z, mean, invstd, norm.weight, norm.bias)], None, True, True, norm.eps)
 
 
 class UNetBasicBlock(nn.Module):
@@ -272,6 +493,11 @@ class UNetBasicBlock(nn.Module):
             x = parts[0] if len(parts) == 1 else torch.cat(list(parts), dim=1)
             out = _combine([_conv_bn(self.conv1, self.norm1, x, s1, f)], f, tr, self.norm1.eps)
             res = _conv_bn(ds_conv, ds_norm, x, one, f)
+        elif f and tr and tuning.current().unet_fused_tail:
+            # the split path on the fused nodes: each of the two convolutions is a chain over the parts whose last launch forms the
+            # BatchNorm statistics (section 27); the terms join the block's bn_act sums like any other
+            out = _combine([_cat_conv_bn(self.conv1, self.norm1, parts, s1)], f, tr, self.norm1.eps)
+            res = _cat_conv_bn(ds_conv, ds_norm, parts, one)
         else:
             # the split path: the two convolutions that read the concatenation are sums over its parts; their norms are ATen's
             out = F.relu(self.norm1(self.conv1(parts, s1)))
@@ -420,14 +646,16 @@ class Res16UNetBase(nn.Module):
             return self._forward_infer(feats, pyr, trace)
         out_p1 = _keep(trace, "bn0", _combine([_conv_bn(self.conv0p1s1, self.bn0, feats, pyr.stem, f)], f, tr, self.bn0.eps))
         skips, out = [out_p1], out_p1
+        tail = f and tr and tuning.current().unet_fused_tail           # the resolution changes on the fused nodes (section 26)
         for n, ts in ((1, 1), (2, 2), (3, 4), (4, 8)):
-            out = _keep(trace, f"bn{n}", F.relu(getattr(self, f"bn{n}")(getattr(self, f"conv{n}p{ts}s2")(out, pyr.oct[n - 1]))))
+            out = _keep(trace, f"bn{n}", _octant_bn_relu(getattr(self, f"conv{n}p{ts}s2"), getattr(self, f"bn{n}"), out, pyr.oct[n - 1], tail))
             out = self._blocks(getattr(self, f"block{n}"), [out], pyr.s1[n], pyr.one[n], trace, f"block{n}")
             skips.append(out)
         skips.pop()                                                    # block4's output goes up, not across
         for n, ts in ((4, 16), (5, 8), (6, 4), (7, 2)):
             level = 7 - n
-            out = _keep(trace, f"bntr{n}", F.relu(getattr(self, f"bntr{n}")(getattr(self, f"convtr{n}p{ts}s2")(out, pyr.oct[level]))))
+            out = _keep(trace, f"bntr{n}", _octant_bn_relu(getattr(self, f"convtr{n}p{ts}s2"), getattr(self, f"bntr{n}"), out, pyr.oct[level],
+                                                       tail))
             out = self._blocks(getattr(self, f"block{n + 1}"), [out, skips.pop()], pyr.s1[level], pyr.one[level], trace,
                                f"block{n + 1}")
         return self.final(out)

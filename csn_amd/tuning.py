@@ -115,6 +115,15 @@ class Tuning:
     # ignore these two.  Off: opt-in (bytes and timing: DESIGN.md "16-bit inference U-Net", scripts/bench_unet.py --infer)
     octant_single_product: bool = False
     unet_maps16: bool = False
+    # A Res16UNet built with fused=True in TRAINING mode: the two layer kinds that still ran an ATen BatchNorm take the fused nodes
+    # of the rest of the network.  Each of the eight resolution changes is octant_conv_stats (include/csn_hip.h section 26: the
+    # octant product forms the BatchNorm statistics in its epilogue) + bn_act(relu=True); in a decoder block that reads more than
+    # 256 columns conv1 and downsample.0 are cat_conv_stats (section 27: a chain over the parts, the last launch with the
+    # statistics) and join the block's bn_act sums.  No ATen normalisation is left in the step; num_batches_tracked and the running
+    # statistics advance as ATen's do.  Results differ from the ATen path by fp32 rounding (the statistics are merged from 32-row
+    # partials in fp64, the normalisation is one fused multiply-add).  Eval mode, fused=False, the inference graph and the HRNet
+    # classes never see it: the same calls, the same bits.  Off: opt-in (timing: DESIGN.md "Fused U-Net tail", scripts/bench_unet.py)
+    unet_fused_tail: bool = False
     # kNN shape graphs (construct_shape_graph with screen=None, CrossShapeAt.get_knn_graph / get_knn_graph_big): an fp16 pass over all
     # pairs (csn_ragged_retrieval_screen_f16) names the candidates that provably cannot be among a row's top K — more than
     # 2 * screen_eps below its K-th best screen score — and only the rest are scored by the exact fp32 kernels.  The SAME integers

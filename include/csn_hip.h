@@ -1153,6 +1153,64 @@ CSN_API int csn_octant_up_bn_act_fwd_m16(const void* x, int x16, long long ld_x,
                                  const float* beta, const float* running_mean, const float* running_var, float eps, const void* r,
                                  int r16, long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
 
+/* ---- (26) training: the octant products of (21) with the BatchNorm statistics epilogue of (15a) (MinkowskiNet/models/res16unet.py:
+ * conv{1..4}p*s2 + bn{1..4}, convtr{4..7}p*s2 + bntr{4..7}) ---------------------------------------------------------------------
+ * Every resolution change of a Res16UNet is followed by a BatchNorm.  Here the product's epilogue forms the statistics of its
+ * batch, so that (15b) normalises, activates and takes the whole BatchNorm gradient in one launch each way, as for the kernel-3
+ * convolutions.  Additive to ABI version 17.  The map arguments are (21)'s without bias, the tail is (15a)'s:
+ *   z                 exactly what csn_octant_down_fwd_f32 / csn_octant_up_fwd_f32 write with bias = NULL in the same math mode:
+ *                     the same bits, under the same launch rule for the column blocks a wave owns, CSN_DEV_SCONV_NB included.
+ *   mean, invstd      [c_out], of the BatchNorm batch z: n_coarse rows (down), n_fine rows (up); invstd = 1 / sqrt(biased variance
+ *                     + eps).  running_mean / running_var [c_out] (either may be NULL) are updated in place with `momentum`,
+ *                     running_var with the n / (n - 1) variance, as in (15a).
+ * DOWN is (15a)'s kernel over children as a table of 8 offsets.  UP are kernels of their own around (21)'s one-weight loop: a
+ * work-group's tile of <= 128 entries of `order` lies inside ONE octant segment, so a wave's tile holds 0 to 32 rows anywhere in
+ * the grid; the wave stores the (mean, M2) of its rows WITH ITS OWN ROW COUNT, a row group without a span stores zero counts, and
+ * the merge takes every tile's count from there (Chan's formula in fp64, tiles in grid order, 64 segments per column merged pairwise
+ * in a fixed tree).  An empty octant and an empty tile contribute nothing.  (21)'s index rules hold: a destination outside
+ * [0, n_fine) is dropped — and not counted —, a parent past n_coarse reads zeros.  No floating-point atomics: two identical calls
+ * give the same bits.
+ * ws: csn_octant_stats_workspace_bytes(n_fine, n_coarse, c_out, up) bytes (CSN_E_WORKSPACE; 0 for arguments (21) refuses).
+ * Host-side checks before any launch — (21)'s codes for NULLs, n_fine, n_coarse, the widths, pitches, windows and alignment (ws
+ * 16-byte aligned); a BatchNorm batch of fewer than 2 rows (n_coarse for down, n_fine for up): CSN_E_ARG (no variance).
+ * Math modes as in (21): mode 0 the exact fp32 matrix instruction, every other mode bf16x3 whatever csn_set_thread_rows16 says.
+ * The backward is csn_octant_down_bwd_f32 / csn_octant_up_bwd_f32 with dbias = NULL (the statistics are taken up by (15b)'s dz). */
+CSN_API long long csn_octant_stats_workspace_bytes(int n_fine, int n_coarse, int c_out, int up);
+CSN_API int csn_octant_down_stats_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in,
+                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                  float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
+                                  void* stream);
+CSN_API int csn_octant_up_stats_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order,
+                                const int* seg, int n_fine, int c_in, int c_out, const float* w, float* z, long long ld_z,
+                                float* mean, float* invstd, float* running_mean, float* running_var, float eps, float momentum,
+                                void* ws, long long ws_bytes, void* stream);
+
+/* ---- (27) training: (15a) over a concatenation that is never formed (MinkowskiNet/models/res16unet.py: block5 .. block8 read
+ * me.cat(up, skip); a block that reads more than 256 columns) -------------------------------------------------------------------
+ *   z = sum_{m < n_parts} gather-GEMM(x_m, table, W[:, c0_m : c1_m]),  c0_m = sum_{i < m} c_in[i], c1_m = c0_m + c_in[m]
+ * for n_parts in [1, 4] maps x_m[n_in][ld_x[m]] of c_in[m] columns (each a multiple of 32 in [32, 256]; the parts may be column
+ * blocks of one wider buffer) and ONE contiguous kernel w[kv][sum c_in][c_out], the module's parameter: part m's weights are rows
+ * [c0_m, c1_m) of every W[k], reached by a base offset with the unchanged row pitch c_out — no weight is copied or cut.  mean,
+ * invstd and the running statistics of z are (15a)'s, formed by the epilogue of the launch that completes z: no pass of their own
+ * over z.  Additive to ABI version 17.
+ * A chain of one launch per part: the first writes z, each later one adds its product to z in place (every element read and then
+ * written by the same lane), the last also forms the tiles' (mean, M2); then (15a)'s merge.  z therefore must not overlap any x_m.
+ * With one part the call is (15a) and gives its bits.  kv in {1, 27} (CSN_E_DIM), table[kv][n_out] as in (14) at stride 1 or 2.
+ * Host-side checks before any launch: parts NULL or n_parts outside [1, 4] CSN_E_ARG; a width outside the rule or c_out outside
+ * (14)'s CSN_E_DIM; every map's pitch and window as in (14); x_m, w, z, ws 16-byte aligned (CSN_E_PTR); n_out < 2 CSN_E_ARG;
+ * ws: csn_sparse_conv_cat_stats_workspace_bytes(n_out, c_out) bytes (CSN_E_WORKSPACE).
+ * Math modes and csn_set_thread_rows16 as in (15a).  The backward is csn_sparse_conv_bwd_f32 per part on that part's slice of w. */
+typedef struct CsnCatParts {
+  const float* x[4];
+  long long ld_x[4];
+  int c_in[4];
+} CsnCatParts;
+CSN_API long long csn_sparse_conv_cat_stats_workspace_bytes(int n_out, int c_out);
+CSN_API int csn_sparse_conv_cat_stats_fwd_f32(const CsnCatParts* parts, int n_parts, int n_in, const int* table, int n_out, int kv,
+                                      int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                      float* running_mean, float* running_var, float eps, float momentum, void* ws,
+                                      long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product

@@ -31,6 +31,13 @@ stored map 16-bit).  ``counted_bytes_16`` counts, on the launches themselves, th
 or fine rows) x c_in x element size), writes (the output maps) and reads as residuals, as scripts/bench_hrnet_maps16.py does.
 
     python scripts/bench_unet.py --infer --rounds 5 --out profiles/unet_infer_bench.json
+
+``--train`` times the training step and nothing else: forward + backward of ``Res16UNet34C`` and ``Res16UNet14`` in math modes
+bf16x3 and fp32, three columns in the same alternating rounds — ``fused=False``, ``fused`` and ``fused`` under
+``tuning.unet_fused_tail`` (sections 26 and 27: no ATen normalisation left in the step).  The plain run carries the same third
+column for ``Res16UNet34C`` in ``--mode``.
+
+    python scripts/bench_unet.py --train --rounds 5 --iters 20 --out profiles/unet_fused_tail_bench.json
 """
 import argparse
 import json
@@ -212,6 +219,47 @@ def infer(a):
     return res
 
 
+def train(a):
+    """``--train``: the training step (forward + backward) of ``Res16UNet34C`` and ``Res16UNet14`` in math modes bf16x3 and fp32, three
+    columns in the same alternating rounds: ``unfused`` (``fused=False``), ``fused`` and ``fused_tail`` (``fused=True`` under
+    ``tuning.unet_fused_tail``: the resolution changes and the wide blocks' first convolutions on the fused nodes too)."""
+    import csn_amd
+    csn_amd.build()
+    from csn_amd import build_unet_pyramid, tuning
+    from csn_amd import functional as CF
+    torch.manual_seed(0)
+    coords = shell_shapes(a.shapes, a.voxels // a.shapes).cuda()
+    pyr = build_unet_pyramid(coords)
+    n = coords.shape[0]
+    res = {"voxels": int(n), "level_rows": [int(c.shape[0]) for c in pyr.coords], "shapes": a.shapes, "warmup": a.warmup, "iters": a.iters,
+           "rounds": a.rounds, "device": torch.cuda.get_device_name(0),
+           "what": "Res16UNet training forward + backward: fused=False, fused, fused with unet_fused_tail"}
+    feats, dy = torch.randn(n, 3, device="cuda"), torch.randn(n, 16, device="cuda")
+    for name in ("Res16UNet34C", "Res16UNet14"):
+        nets = {"fused": getattr(csn_amd, name)(3, 16, fused=True).cuda().train(), "unfused": getattr(csn_amd, name)(3, 16, fused=False).cuda().train()}
+        nets["unfused"].load_state_dict(nets["fused"].state_dict())
+        res[name] = {"wide_blocks": [getattr(nets["fused"], f"block{i}")[0].inplanes for i in range(5, 9)
+                                     if getattr(nets["fused"], f"block{i}")[0].inplanes > 256]}
+
+        def step_of(mode, net, tail):
+            def step():
+                for p in net.parameters():
+                    p.grad = None
+                with CF.math_mode(CF.mode_id(mode)), tuning.override(unet_fused_tail=tail):
+                    net((pyr, feats)).backward(dy)
+            return step
+        for mode in ("bf16x3", "fp32"):
+            r = compare({"unfused": step_of(mode, nets["unfused"], False), "fused": step_of(mode, nets["fused"], False),
+                         "fused_tail": step_of(mode, nets["fused"], True)}, a.warmup, a.iters, a.rounds)
+            gap = r["fused_ms"] - r["fused_tail_ms"]
+            noise = max(r[f"{v}_spread_ms"][1] - r[f"{v}_spread_ms"][0] for v in ("fused", "fused_tail"))
+            r["fused_tail_gain_ms"] = gap
+            r["fused_tail_speedup"] = r["fused_ms"] / r["fused_tail_ms"]
+            r["fused_tail_is_faster"] = bool(gap > noise and r["fused_tail_spread_ms"][1] < r["fused_spread_ms"][0])
+            res[name][f"train_fwd_bwd_{mode}"] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--voxels", type=int, default=32768)
@@ -224,9 +272,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--infer", action="store_true", help="time the eval variants instead: eval_epilogue off against on in fp32 and bf16x3, and the one-launch graph's "
                                                     "fp32-map, single-product-octant and 16-bit-map routes in bf16 and fp16")
+    ap.add_argument("--train", action="store_true", help="time the training step instead: fused=False, fused and fused with unet_fused_tail, "
+                                                    "Res16UNet34C and Res16UNet14, bf16x3 and fp32")
     a = ap.parse_args()
-    if a.infer:
-        line = json.dumps(infer(a))
+    if a.infer or a.train:
+        line = json.dumps(infer(a) if a.infer else train(a))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:
@@ -280,13 +330,18 @@ def main():
             nets["unfused"].load_state_dict(nets["fused"].state_dict())
             dy = torch.randn(n, 16, device="cuda")
 
-            def step_of(net):
+            from csn_amd import tuning
+
+            def step_of(net, tail=False):
                 def step():
                     for p in net.parameters():
                         p.grad = None
-                    net((pyr, feats)).backward(dy)
+                    with tuning.override(unet_fused_tail=tail):
+                        net((pyr, feats)).backward(dy)
                 return step
-            res["Res16UNet34C_train_fwd_bwd"] = compare({v: step_of(net) for v, net in nets.items()}, a.warmup, a.iters, a.rounds)
+            steps = {v: step_of(net) for v, net in nets.items()}
+            steps["fused_tail"] = step_of(nets["fused"], True)
+            res["Res16UNet34C_train_fwd_bwd"] = compare(steps, a.warmup, a.iters, a.rounds)
             fused_ms = res["Res16UNet34C_train_fwd_bwd"]["fused_ms"]
 
             # the shares: the same modules on maps of the network's sizes, alone
