@@ -37,6 +37,9 @@ from .minkowski_hrnet import GroupedPyramid, bn_act_groups, conv_stats_groups, g
 # or (maps16_dtype: math mode "bf16" / "fp16" with rows_single_product) 16-bit maps
 from .minkowski_hrnet import (HRNetSeg, HRNetSeg2S, HRNetSeg3S, HRNetSeg4S, load_me_seg_state,  # noqa: E402,F401
                               maps16_dtype, sparse_conv_bn_act)
+# bf16 activation maps of the backbone's training graph (tuning.train_maps16): the map type conv_stats / bn_act take and give, and
+# whether the math mode and rows_single_product admit it right now
+from .minkowski_hrnet import Map16, train_maps16_open  # noqa: E402,F401
 
 # the Res16UNet family (MinkowskiNet/models/res16unet.py) on the octant convolutions and the fused blocks; octant_conv_bn_act is the
 # inference primitive of its resolution changes, on fp32 maps or (single_product / 16-bit tensors, where maps16_dtype() names a

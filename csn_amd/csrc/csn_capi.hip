@@ -1767,6 +1767,105 @@ int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n
   return csn_launch_sparse_conv_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
 }
 
+// ---- (28) training on bf16 activation maps: (15a), (15b) and (14)'s backward with a type flag beside the map that may be bf16 ----
+// math mode 2 behind csn_set_thread_rows16, and nothing else: there alone the fp32 form rounds these maps to bf16 itself
+static int train16_mode(int flags) {
+  if (flags & ~1) return CSN_E_ARG;
+  return mode() == 2 && t_rows16 ? 0 : CSN_E_ARG;
+}
+static int map_of(int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); }
+
+int csn_sparse_conv_stats_fwd_t16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
+                                  float* running_var, float eps, float momentum, void* ws, long long ws_bytes, void* stream) {
+  if (const int e = train16_mode(x16)) return e;
+  if (!x16)
+    return sparse_conv_stats_fwd_impl(static_cast<const float*>(x), ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd,
+                                      running_mean, running_var, eps, momentum, false, nullptr, 0, ws, ws_bytes, stream);
+  if (!x || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map16(ld_x, c_in, n_in)) return e;
+  if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
+  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (n_out < 2) return CSN_E_ARG;                                // a one-row batch has no variance
+  if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
+  CsnSparseConvArgs a{};
+  a.x = static_cast<const float*>(x); a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in;
+  a.c_out = c_out; a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  return csn_launch_sparse_conv_stats_fwd_x16(a, mean, invstd, running_mean, running_var, eps, momentum, (hipStream_t)stream);
+}
+
+int csn_rows_bn_act_fwd_t16(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, const void* r, int r16,
+                            long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream) {
+  if (const int e = train16_mode(r16 | y16)) return e;
+  if (!t || !y) return CSN_E_ARG;
+  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
+  CsnRowsBnActArgs a{};
+  for (int m = 0; m < n_terms; ++m) {
+    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m] || !t->beta[m]) return CSN_E_ARG;
+    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
+    if (mis16(t->z[m])) return CSN_E_PTR;
+    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
+    a.beta[m] = t->beta[m];
+  }
+  if (const int e = map_of(y16, ld_y, channels, n_rows)) return e;
+  if (r) if (const int e = map_of(r16, ld_r, channels, n_rows)) return e;
+  if (mis16(y) || (r && mis16(r))) return CSN_E_PTR;
+  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
+  a.r = static_cast<const float*>(r); a.ld_r = (int)ld_r; a.y = static_cast<float*>(y); a.ld_y = (int)ld_y;
+  return csn_launch_rows_bn_act_fwd16(a, r16, y16, (hipStream_t)stream);
+}
+
+int csn_rows_bn_act_bwd_t16(const float* dy, long long ld_dy, const void* y, int y16, long long ld_y, const CsnBnTerms* t, int n_terms,
+                            int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr, void* ws,
+                            long long ws_bytes, void* stream) {
+  if (const int e = train16_mode(y16)) return e;
+  if (!y16 || !relu)                                              // the mask is the only use of y: without it (15b) itself
+    return rows_bn_act_bwd_impl(dy, ld_dy, relu ? static_cast<const float*>(y) : nullptr, ld_y, t, n_terms, n_rows, channels, training, eps,
+                                false, nullptr, 0, relu, dr, ld_dr, ws, ws_bytes, stream);
+  if (!dy || !t || !ws || !y) return CSN_E_ARG;
+  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
+  CsnRowsBnActArgs a{};
+  for (int m = 0; m < n_terms; ++m) {
+    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m]) return CSN_E_ARG;
+    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
+    if (t->dz[m]) if (const int e = sparse_conv_map(t->ld_dz[m], channels, n_rows)) return e;
+    if (mis16(t->z[m]) || (t->dz[m] && mis16(t->dz[m]))) return CSN_E_PTR;
+    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
+    a.dz[m] = t->dz[m]; a.ld_dz[m] = (int)t->ld_dz[m]; a.dgamma[m] = t->dgamma[m]; a.dbeta[m] = t->dbeta[m];
+  }
+  if (const int e = sparse_conv_map(ld_dy, channels, n_rows)) return e;
+  if (const int e = sparse_conv_map16(ld_y, channels, n_rows)) return e;
+  if (dr) if (const int e = sparse_conv_map(ld_dr, channels, n_rows)) return e;
+  if (mis16(dy) || mis16(ws) || mis16(y) || (dr && mis16(dr))) return CSN_E_PTR;
+  if (ws_bytes < csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, 1)) return CSN_E_WORKSPACE;
+  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = 1; a.eps = eps;
+  a.y = static_cast<float*>(const_cast<void*>(y)); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr;
+  a.ws = ws;
+  return csn_launch_rows_bn_act_bwd16(a, (hipStream_t)stream);
+}
+
+int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void* x, int x16, long long ld_x, int n_in, int n_out, int kv,
+                            int c_in, int c_out, const int* fwd_table, const int* bwd_table, const float* w, float* dx, long long ld_dx,
+                            float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
+  if (const int e = train16_mode(x16)) return e;
+  if (!x16 || !dw)                                                // x is the weight gradient's operand alone
+    return csn_sparse_conv_bwd_f32(dy, ld_dy, dw ? static_cast<const float*>(x) : nullptr, ld_x, n_in, n_out, kv, c_in, c_out, fwd_table,
+                                   bwd_table, w, dx, ld_dx, dw, dbias, ws, ws_bytes, stream);
+  if (!dy || !ws || !fwd_table || !x) return CSN_E_ARG;
+  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
+  if (const int e = sparse_conv_map16(ld_x, c_in, n_in)) return e;
+  if (mis16(x) || mis16(dw)) return CSN_E_PTR;
+  // dx and dbias: (14)'s backward as it is (it checks dy, the tables, w, dx, ws and the workspace size for all three outputs)
+  if (const int e = csn_sparse_conv_bwd_f32(dy, ld_dy, nullptr, 0, n_in, n_out, kv, c_in, c_out, fwd_table, bwd_table, w, dx, ld_dx, nullptr,
+                                            dbias, ws, ws_bytes, stream))
+    return e;
+  CsnSparseConvArgs a{};
+  a.x = static_cast<const float*>(x); a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = fwd_table; a.n_out = n_out; a.kv = kv;
+  a.c_in = c_in; a.c_out = c_out; a.dy = dy; a.ld_dy = (int)ld_dy; a.dw = dw; a.ws = ws;
+  return csn_launch_sparse_conv_wgrad_x16(a, (hipStream_t)stream);
+}
+
 // ---- (25) the launches of (23) as one 16-bit product on maps that are each fp32 rows or rows of the mode's 16-bit type ----
 // (24)'s mode and flag checks, (21)'s on the sizes, each map by its own type's rule; n_x: the rows of x, n_y: those of y and r
 static int octant_m16_args(int x16, long long ld_x, int n_x, int n_y, int n_fine, int n_coarse, int c_in, int c_out, const void* r,

@@ -429,7 +429,24 @@ int csn_launch_bn_stats_merge(const float* part, int n_tiles, int n_rows, int C,
                               hipStream_t st);
 long long csn_rows_bn_act_ws_bytes(long long n_rows, int C, int n_terms, int n_groups);      // n_groups 1: the whole map
 int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
-int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st);
+// the backward is pass 1 (dr, the chunks' sums), the sums, pass 2 (dz); `pass` launches row pass 1 or 2 on the workspace's parts and
+// coefficients (NULL: the fp32 kernels of rows_bn_act.hip)
+typedef int (*CsnBnActPass)(int pass, const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, double* part, const float* coef,
+                            int n_parts, hipStream_t st);
+int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st, CsnBnActPass pass = nullptr);
+
+// ---- the HRNet backbone's training step on bf16 activation maps (train_maps16.hip; math mode 2, single product) ----
+// The launches above with ONE map read or written as bf16 rows (pitch in elements, a multiple of 8) where the fp32 form's first use of
+// it is a rounding to bf16: a.x of the statistics forward and of the weight gradient (cast to const float* in the argument struct),
+// y and r of the BatchNorm row kernels.  Every sum is the fp32 form's, in its order.
+int csn_launch_sparse_conv_stats_fwd_x16(const CsnSparseConvArgs& a, float* mean, float* invstd, float* running_mean, float* running_var,
+                                         float eps, float momentum, hipStream_t st);
+int csn_launch_sparse_conv_wgrad_x16(const CsnSparseConvArgs& a, hipStream_t st);           // a.dw alone, from a.x (bf16), a.dy, a.ws
+int csn_launch_rows_bn_act_fwd16(const CsnRowsBnActArgs& a, int r16, int y16, hipStream_t st);
+int csn_launch_rows_bn_act_bwd16(const CsnRowsBnActArgs& a, hipStream_t st);                // a.y: bf16 rows
+// the weight gradient's launch plan (sparse_conv.hip): the 32-row blocks of c_in per work-group, the split-K chunks and where the
+// chunks' slabs lie in the backward's workspace
+void csn_sconv_wgrad_plan(long long n_out, int kv, int c_in, int c_out, int* ta, int* splits, int* chunk, long long* slabs_offset);
 
 // ---- point fields: voxel means, trilinear interpolation onto points and its adjoint (point_field.hip) ----
 struct CsnPointFieldArgs {

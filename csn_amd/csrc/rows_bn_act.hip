@@ -33,37 +33,7 @@
 namespace {
 using namespace rows_mma;
 
-constexpr int MAXT = 3;
-
-struct BnActP {
-  const float* z[MAXT]; int ld_z[MAXT];
-  const float* mean[MAXT]; const float* scale[MAXT]; const float* gamma[MAXT]; const float* beta[MAXT];   // mean / scale: [G][C]
-  float* dz[MAXT]; int ld_dz[MAXT];
-  int M;
-  long long n_rows; int C;
-  int eval, relu; float eps;
-  const float* r; int ld_r;
-  float* y; int ld_y;                          // forward: written; backward: read
-  const float* dy; int ld_dy;
-  float* dr; int ld_dr;
-  const float* coef;                           // pass 2, training: [G][1 + M][C] mean g', mean g' xhat_m
-  double* part;                                // pass 1: [part][1 + M][C]; a part is a chunk, or what a chunk and a group share
-  const int* grp; int G;                       // GROUPED only: [G + 1] row offsets of the groups
-  int n_parts;                                 // GROUPED only: chunks + G - 1, the bound of the part index
-};
-
-__device__ __forceinline__ float inv_std(const BnActP& p, int m, int c, bool eval) {
-  return eval ? 1.f / sqrtf(p.scale[m][c] + p.eps) : p.scale[m][c];
-}
-
-// Thread layout of the three row kernels: 64 rows per work-group; a thread owns 4 consecutive channels (16-byte accesses on every
-// map) of every RL-th row, RL = 256 / (C / 4) row lanes (32 at C = 32, 4 at C = 256; 240 of the 256 threads work at C = 96).  A
-// thread's channels never change, so the terms' per-column constants sit in registers.
-struct Lane { int rl, c, RL; bool on; };
-__device__ __forceinline__ Lane lane_of(int C) {
-  const int c4 = C >> 2, RL = 256 / c4, rl = (int)threadIdx.x / c4;
-  return Lane{rl, ((int)threadIdx.x - rl * c4) * 4, RL, rl < RL};
-}
+#include "rows_bn_act_body.inc"
 
 // the rows [lo, hi) of the work-group's chunk (rows from r0) that belong to group g; false: none
 __device__ __forceinline__ bool group_span(const BnActP& p, int g, long long r0, int rows, int& lo, int& hi) {
@@ -169,92 +139,6 @@ __global__ __launch_bounds__(256) void rows_bn_act_groups_fwd_kernel(const BnAct
   }
 }
 
-// PASS 1: dr = g' and the span's fp64 column sums of g' and g' xhat_m, a thread's rows added in row order and left in LDS per row
-// lane (store_part adds them).  PASS 2: dz_m.  The span: this thread's rows first, first + RL, ... < hi of the chunk at r0, the
-// statistics at column offset so; the whole work-group calls.
-template <int PASS>
-__device__ __forceinline__ void bwd_span(const BnActP& p, const Lane& t, long long r0, int first, int hi, int so, bool eval, double* sh) {
-  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[MAXT][4];
-#pragma unroll
-  for (int m = 0; m < MAXT; ++m)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s1[m][e] = 0.0;
-  if (t.on) {
-    float mu[MAXT][4], is[MAXT][4], gi[MAXT][4], cm[MAXT][4], c0[4];
-    const bool use_coef = PASS == 2 && !eval;
-    const float* coef = p.coef + (long long)so * (1 + p.M);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c0[e] = use_coef ? coef[t.c + e] : 0.f;
-#pragma unroll
-    for (int m = 0; m < MAXT; ++m)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool in = m < p.M;
-        mu[m][e] = in ? p.mean[m][so + t.c + e] : 0.f;
-        is[m][e] = in ? inv_std(p, m, so + t.c + e, eval) : 0.f;
-        gi[m][e] = in ? p.gamma[m][t.c + e] * is[m][e] : 0.f;
-        cm[m][e] = (in && use_coef) ? coef[(1 + m) * p.C + t.c + e] : 0.f;
-      }
-#pragma unroll 2
-    for (int rr = first; rr < hi; rr += t.RL) {
-      const long long row = r0 + rr;
-      f32x4 g = *reinterpret_cast<const f32x4*>(p.dy + row * p.ld_dy + t.c);
-      if (p.relu) {
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(p.y + row * p.ld_y + t.c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = yv[e] > 0.f ? g[e] : 0.f;
-      }
-      if constexpr (PASS == 1) {
-        if (p.dr) *reinterpret_cast<f32x4*>(p.dr + row * p.ld_dr + t.c) = g;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s0[e] += (double)g[e];
-      }
-#pragma unroll
-      for (int m = 0; m < MAXT; ++m) {
-        if (m >= p.M) continue;
-        if (PASS == 2 && !p.dz[m]) continue;
-        if (PASS == 2 && eval) {
-          f32x4 d;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] = g[e] * gi[m][e];
-          *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
-          continue;
-        }
-        const f32x4 zv = *reinterpret_cast<const f32x4*>(p.z[m] + row * p.ld_z[m] + t.c);
-        f32x4 d;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xh = (zv[e] - mu[m][e]) * is[m][e];
-          if constexpr (PASS == 1) s1[m][e] += (double)g[e] * (double)xh;
-          else d[e] = gi[m][e] * (g[e] - c0[e] - xh * cm[m][e]);
-        }
-        if constexpr (PASS == 2) *reinterpret_cast<f32x4*>(p.dz[m] + row * p.ld_dz[m] + t.c) = d;
-      }
-    }
-  }
-  if constexpr (PASS == 1) {
-    if (t.on) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sh[t.rl * p.C + t.c + e] = s0[e];
-#pragma unroll
-        for (int m = 0; m < MAXT; ++m)
-          if (m < p.M) sh[((1 + m) * t.RL + t.rl) * p.C + t.c + e] = s1[m][e];
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// the row lanes' sums of bwd_span<1>, added in lane order, as part `part_i`
-__device__ __forceinline__ void store_part(const BnActP& p, const Lane& t, long long part_i, const double* sh) {
-  for (int i = threadIdx.x; i < (1 + p.M) * p.C; i += 256) {
-    const int q = i / p.C, col = i - q * p.C;
-    double s = 0.0;
-    for (int k = 0; k < t.RL; ++k) s += sh[(q * t.RL + k) * p.C + col];
-    p.part[(part_i * (1 + p.M) + q) * p.C + col] = s;
-  }
-}
 
 template <int PASS, bool GROUPED>
 __global__ __launch_bounds__(256) void rows_bn_act_bwd_kernel(const BnActP p) {
@@ -421,17 +305,6 @@ WsLayout ws_layout(long long n_rows, int C, int M, int G) {
   return L;
 }
 
-BnActP make_p(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups) {
-  BnActP p{};
-  for (int m = 0; m < a.n_terms; ++m) {
-    p.z[m] = a.z[m]; p.ld_z[m] = a.ld_z[m]; p.mean[m] = a.mean[m]; p.scale[m] = a.scale[m]; p.gamma[m] = a.gamma[m];
-    p.beta[m] = a.beta[m]; p.dz[m] = a.dz[m]; p.ld_dz[m] = a.ld_dz[m];
-  }
-  p.M = a.n_terms; p.n_rows = a.n_rows; p.C = a.C; p.eval = !a.training && !group_rows; p.relu = a.relu; p.eps = a.eps;
-  p.r = a.r; p.ld_r = a.ld_r; p.y = a.y; p.ld_y = a.ld_y; p.dy = a.dy; p.ld_dy = a.ld_dy; p.dr = a.dr; p.ld_dr = a.ld_dr;
-  p.grp = group_rows; p.G = group_rows ? n_groups : 1;
-  return p;
-}
 
 }  // namespace
 
@@ -458,38 +331,50 @@ int csn_launch_rows_bn_act_fwd(const CsnRowsBnActArgs& a, const int* group_rows,
   return (int)hipGetLastError();
 }
 
-int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st) {
+// pass 1 or 2 of the backward on fp32 maps (the CsnBnActPass of csn_launch_rows_bn_act_bwd)
+static int bwd_pass_f32(int pass, const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, double* part, const float* coef, int n_parts,
+                        hipStream_t st) {
   BnActP p = make_p(a, group_rows, n_groups);
+  p.part = part; p.coef = coef; p.n_parts = n_parts;
   const bool grouped = group_rows != nullptr;
-  const WsLayout L = ws_layout(a.n_rows, a.C, a.n_terms, p.G);
-  char* ws = static_cast<char*>(a.ws);
-  p.part = reinterpret_cast<double*>(ws + L.part);
-  float* coef = reinterpret_cast<float*>(ws + L.coef);
-  p.coef = coef;
   const int n_chunks = (int)(((long long)a.n_rows + 63) / 64);
-  p.n_parts = n_chunks + p.G - 1;
+  if (pass == 1)
+    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<1, true> : rows_bn_act_bwd_kernel<1, false>), dim3(n_chunks), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<2, true> : rows_bn_act_bwd_kernel<2, false>), dim3(n_chunks), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+// pass 1, the sums, pass 2; `pass` launches the two row passes (NULL: the fp32 kernels of this file; train_maps16.hip hands over
+// the passes that read y as bf16 rows, whole map only)
+int csn_launch_rows_bn_act_bwd(const CsnRowsBnActArgs& a, const int* group_rows, int n_groups, hipStream_t st, CsnBnActPass pass) {
+  if (!pass) pass = bwd_pass_f32;
+  const bool grouped = group_rows != nullptr;
+  const int G = grouped ? n_groups : 1;
+  const WsLayout L = ws_layout(a.n_rows, a.C, a.n_terms, G);
+  char* ws = static_cast<char*>(a.ws);
+  double* part = reinterpret_cast<double*>(ws + L.part);
+  float* coef = reinterpret_cast<float*>(ws + L.coef);
+  const int n_chunks = (int)(((long long)a.n_rows + 63) / 64);
+  const int n_parts = n_chunks + G - 1;
   bool any_dz = false, any_sum = false;
   for (int m = 0; m < a.n_terms; ++m) {
     any_dz |= a.dz[m] != nullptr;
     any_sum |= a.dgamma[m] != nullptr || a.dbeta[m] != nullptr;
   }
   const bool need_coef = any_dz && (a.training || grouped);                  // the grouped passes are training passes
-  if (a.dr || any_sum || need_coef) {
-    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<1, true> : rows_bn_act_bwd_kernel<1, false>), dim3(n_chunks), dim3(256), 0, st, p);
-    if (const int e = (int)hipGetLastError()) return e;
-  }
+  if (a.dr || any_sum || need_coef)
+    if (const int e = pass(1, a, group_rows, n_groups, part, coef, n_parts, st)) return e;
   if (any_sum || need_coef) {
     BnSumsP s{};
-    s.part = p.part; s.n_parts = p.n_parts; s.M = a.n_terms; s.C = a.C; s.n_rows = a.n_rows; s.coef = need_coef ? coef : nullptr;
+    s.part = part; s.n_parts = n_parts; s.M = a.n_terms; s.C = a.C; s.n_rows = a.n_rows; s.coef = need_coef ? coef : nullptr;
     for (int m = 0; m < a.n_terms; ++m) { s.dgamma[m] = a.dgamma[m]; s.dbeta[m] = a.dbeta[m]; }
-    s.grp = group_rows; s.G = p.G;
+    s.grp = group_rows; s.G = G;
     hipLaunchKernelGGL(grouped ? rows_bn_act_sums_kernel<true> : rows_bn_act_sums_kernel<false>, dim3(a.C / SCOLS, 1 + a.n_terms),
                        dim3(SCOLS * SSEG), 0, st, s);
     if (const int e = (int)hipGetLastError()) return e;
   }
-  if (any_dz) {
-    hipLaunchKernelGGL((grouped ? rows_bn_act_bwd_kernel<2, true> : rows_bn_act_bwd_kernel<2, false>), dim3(n_chunks), dim3(256), 0, st, p);
-    if (const int e = (int)hipGetLastError()) return e;
-  }
+  if (any_dz)
+    if (const int e = pass(2, a, group_rows, n_groups, part, coef, n_parts, st)) return e;
   return 0;
 }

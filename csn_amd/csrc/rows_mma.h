@@ -278,6 +278,20 @@ __device__ __forceinline__ void wgrad_step(f32x16 (&acc)[TA][WG_TB], const float
   }
 }
 
+// the single-product step (MODE 2) on A fragments that ARE bf16 (train_maps16.hip: x is a bf16 map): bf converted as there, the
+// same instructions in the same (ta, tb) order
+template <int TA>
+__device__ __forceinline__ void wgrad_step_a16(f32x16 (&acc)[TA][WG_TB], const s16x8 (&a16)[TA], const float (&bf)[WG_TB][8], int nbv) {
+  s16x8 b16[WG_TB];
+#pragma unroll
+  for (int tb = 0; tb < WG_TB; ++tb) b16[tb] = pack8<false>(bf[tb]);
+#pragma unroll
+  for (int ta = 0; ta < TA; ++ta)
+#pragma unroll
+    for (int tb = 0; tb < WG_TB; ++tb)
+      if (tb < nbv) acc[ta][tb] = mfma32<false>(a16[ta], b16[tb], acc[ta][tb]);
+}
+
 // waves 1..3 are added to wave 0 in wave order through red[TA * WG_TB * 16 * 64]; wave 0 stores block (ta, tb) at row
 // row0 + 32 ta, column col0 + 32 tb of o (row pitch `pitch`)
 template <int TA>

@@ -258,6 +258,12 @@ int csn_sconv_column_blocks(int J, long long M) {
   return nb;
 }
 
+void csn_sconv_wgrad_plan(long long n_out, int kv, int c_in, int c_out, int* ta, int* splits, int* chunk, long long* slabs_offset) {
+  *ta = wgrad_ta_for(c_in);
+  wgrad_split(n_out, kv, c_in, c_out, *splits, *chunk);
+  *slabs_offset = ws_layout(n_out, kv, c_in, c_out).slabs;
+}
+
 long long csn_sparse_conv_ws_bytes(long long n_in, long long n_out, int kv, int c_in, int c_out, int backward) {
   (void)n_in;
   return backward ? ws_layout(n_out, kv, c_in, c_out).total : 0;

@@ -24,6 +24,11 @@ allocated once and written in place through the kernels' output pitch: no ``torc
 With ``infer_maps16`` on top, in math mode "bf16" / "fp16" with ``rows_single_product``, the maps between those launches are bf16 /
 fp16 rows (section 24, ``sparse_conv_bn_act`` on 16-bit tensors); the stem's input and the result stay fp32.  Off by default.
 
+Training on bf16 maps (``tuning.override(train_maps16=True)``, a fused backbone in training mode on a plain ``VoxelPyramid``, math mode
+"bf16" with ``rows_single_product``): every ReLU output that only these nodes read is stored as bf16 rows — a ``Map16`` — and gathered
+as it lies by the next convolution and its weight gradient (include/csn_hip.h section 28); z, the statistics, the gradient maps and
+the maps ``torch.cat`` joins stay fp32.  Off by default; ignored everywhere else.
+
 Grouped passes (include/csn_hip.h section 20): the K + 1 batches of a CSN training step merged into ONE coordinate set with
 shifted batch indices (``merge_batches`` -> ``GroupedPyramid``).  The rows of a batch are then a contiguous range at every level, the
 convolutions run once on the merged maps, and ``conv_stats_groups`` / ``bn_act_groups`` take the BatchNorm statistics per row group.
@@ -389,7 +394,13 @@ def conv_stats(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, running_m
                running_var: Optional[torch.Tensor], eps: float, momentum: float):
     """``z (n_out, c_out)``, ``mean``, ``invstd`` of the convolution ``kmap`` describes and of its output's BatchNorm batch; the
     running statistics (either may be None) are updated in place.  An input width that is no multiple of 32 is zero-padded as in
-    ``sparse_conv3d``.  A one-row output raises ``ValueError`` (no variance), as torch does."""
+    ``sparse_conv3d``.  A one-row output raises ``ValueError`` (no variance), as torch does.
+
+    ``x`` may be a ``Map16`` (math mode "bf16" with ``tuning.rows_single_product``, else ``ValueError``): its bf16 rows are gathered as
+    they lie, by the product and by its weight gradient (section 28) — z, mean and invstd are the bits of the call on the same
+    values as fp32 —, and the backward's fp32 dx goes to the map's edge."""
+    if isinstance(x, Map16):
+        return _conv_stats16(x, weight, kmap, running_mean, running_var, eps, momentum)
     return _conv_stats(x, weight, kmap, False, None, running_mean, running_var, eps, momentum)
 
 
@@ -398,7 +409,10 @@ def conv_stats_groups(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, gr
     """``conv_stats`` on a merged map whose output rows are G BatchNorm batches: ``group_rows (G + 1,)`` int32 on the device are the
     row offsets of the groups (``GroupedPyramid.group_rows[level]``: start at 0, ascend, end at ``kmap.n_out``, every group two rows
     or more — the CALLER has checked that, the kernels cannot).  Returns ``z (n_out, c_out)`` — the bits of ``conv_stats`` —,
-    ``mean (G, c_out)`` and ``invstd (G, c_out)``; the running statistics (either may be None) take G updates in group order."""
+    ``mean (G, c_out)`` and ``invstd (G, c_out)``; the running statistics (either may be None) take G updates in group order.
+    Row groups have no bf16-map form: a ``Map16`` raises ``ValueError``."""
+    if isinstance(x, Map16):
+        raise ValueError("row groups have no bf16-map form (include/csn_hip.h section 28 takes the whole map as one batch)")
     return _conv_stats(x, weight, kmap, True, group_rows, running_mean, running_var, eps, momentum)
 
 
@@ -477,6 +491,193 @@ class _BnAct(torch.autograd.Function):
 
 
 Term = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]      # z, mean, scale, gamma, beta
+
+
+# ------------------------------------------------------------------------------------------------------
+# training on bf16 activation maps (section 28, ``tuning.train_maps16``)
+# ------------------------------------------------------------------------------------------------------
+_TRAIN16 = ('bf16 training maps need math mode "bf16" together with tuning.override(rows_single_product=True): only there does the '
+            "fp32 form round these maps to bf16 itself")
+
+
+class Map16:
+    """A ReLU output of the training graph stored as bf16 rows (``bn_act(..., out_dtype=torch.bfloat16)``).
+
+    ``rows`` (N, C) ``bfloat16``: the values, without autograd history.  ``edge`` (N, C) ``float32`` with ONE element of storage
+    (``torch.zeros(1).expand(N, C)``): the map's place in the autograd graph.  Autograd casts a gradient to the dtype of the tensor
+    it belongs to, so a bf16 tensor that required grad would receive its gradients rounded to bf16; the consumers (``conv_stats``,
+    ``bn_act``'s residual) therefore read ``rows`` and return their fp32 ``dx`` / ``dr`` for ``edge``, whose several gradients autograd
+    sums in fp32 as it does for an fp32 map.  No fp32 copy of the map exists."""
+
+    __slots__ = ("rows", "edge")
+
+    def __init__(self, rows: torch.Tensor, edge: torch.Tensor):
+        if rows.dtype != torch.bfloat16:
+            raise ValueError(f"training maps are bfloat16, not {rows.dtype}: math mode \"fp16\" runs its backward in bf16, which would "
+                             "round an fp16 map a second time")
+        if rows.dim() != 2 or edge.dtype != torch.float32 or tuple(edge.shape) != tuple(rows.shape):
+            raise ValueError("rows must be (N, C) bfloat16 and edge an fp32 tensor of the same shape")
+        self.rows, self.edge = rows, edge
+
+    shape = property(lambda self: self.rows.shape)
+    is_cuda = property(lambda self: self.rows.is_cuda)
+
+    def detach(self) -> torch.Tensor:
+        """The stored rows (what ``trace`` receives)."""
+        return self.rows.detach()
+
+
+def train_maps16_open() -> bool:
+    """Whether section 28 takes calls right now: math mode "bf16" with ``tuning.rows_single_product``."""
+    return tuning.current().rows_single_product and CF.current_mode() == 2
+
+
+def _need_train16(*maps: Optional[Map16]) -> None:
+    """The gate of the section-28 calls: the mode first, then the device."""
+    if not train_maps16_open():
+        raise ValueError(_TRAIN16)
+    for m in maps:
+        if m is not None and not m.is_cuda:
+            raise _lib.CsnError(_NO_CPU)
+
+
+class _ConvStats16(torch.autograd.Function):
+    """``_ConvStats`` on a ``Map16`` (``csn_sparse_conv_stats_fwd_t16`` / ``csn_sparse_conv_bwd_t16``): the bf16 rows are gathered as
+    they lie, forward and in the weight gradient; dx is fp32 and belongs to the map's edge."""
+
+    @staticmethod
+    def forward(ctx, x_rows, x_edge, w, kmap, running_mean, running_var, eps, momentum):
+        CF._need_cuda(x_rows, w, kmap.fwd, running_mean, running_var, also=(torch.bfloat16,))
+        L = _lib.lib()
+        x = x_rows if _pitched16(x_rows) else x_rows.contiguous()
+        w_c = w.detach().contiguous()
+        KV, c_in, c_out = w_c.shape
+        n_in, n_out = kmap.n_in, kmap.n_out
+        dev = x.device
+        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
+        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
+        ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        with CF.rows16(True):
+            _lib.check(L.csn_sparse_conv_stats_fwd_t16(CF._ptr(x), 1, x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
+                                                       CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
+                                                       CF._ptr(running_var), float(eps), float(momentum), CF._ptr(ws), ws_n, CF._stream()),
+                       "csn_sparse_conv_stats_fwd_t16")
+        ctx.save_for_backward(x, w_c)
+        ctx.kmap = kmap
+        ctx.mark_non_differentiable(mean, invstd)
+        return z, mean, invstd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dmean, _dinvstd):
+        need_x, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_x or need_w):
+            return (None,) * 8
+        with CF.math_mode(2), CF.rows16(True):
+            x, w = ctx.saved_tensors
+            kmap = ctx.kmap
+            L = _lib.lib()
+            KV, c_in, c_out = w.shape
+            n_in, n_out = kmap.n_in, kmap.n_out
+            dz = dz.contiguous()
+            dx = torch.empty((n_in, c_in), device=x.device, dtype=torch.float32) if need_x else None
+            dw = torch.empty_like(w) if need_w else None
+            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
+            bwd = kmap.bwd_table if need_x else None
+            _lib.check(L.csn_sparse_conv_bwd_t16(CF._ptr(dz), c_out, CF._ptr(x), 1, x.stride(0), n_in, n_out, KV, c_in, c_out,
+                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
+                                                 CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_t16")
+        return (None, dx, dw) + (None,) * 5
+
+
+def _conv_stats16(x: Map16, weight, kmap, running_mean, running_var, eps, momentum):
+    _need_train16(x)
+    if not weight.is_cuda:
+        raise _lib.CsnError(_NO_CPU)
+    if weight.dim() != 3 or x.shape[1] != weight.shape[1] or weight.shape[0] != kmap.KV or x.shape[0] != kmap.n_in:
+        raise ValueError("x must be (n_in, c_in) and weight (KV, c_in, c_out) for the map's KV and n_in")
+    c_in, c_out = weight.shape[1], weight.shape[2]
+    if c_out % 32 or not 32 <= c_out <= 256 or c_in % 32 or not 32 <= c_in <= 256:
+        raise ValueError("widths: c_out and a bf16 map's c_in multiples of 32 in [32, 256]")
+    if kmap.n_out == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a one-row batch has no variance)")
+    return _ConvStats16.apply(x.rows, x.edge, weight, kmap, running_mean, running_var, eps, momentum)
+
+
+class _BnAct16(torch.autograd.Function):
+    """``_BnAct`` with the residual read from and / or the result written as bf16 rows (``csn_rows_bn_act_fwd_t16`` / ``_bwd_t16``; the
+    whole map is one batch).  ``r_rows`` / ``r_edge``: a ``Map16`` residual's two tensors, or (None, an fp32 residual), or (None,
+    None).  ``out16``: returns (rows bf16, edge) — the parts of a ``Map16`` — instead of y fp32.  Arguments after the fixed ones:
+    (z, mean, scale, gamma, beta) per term."""
+
+    @staticmethod
+    def forward(ctx, relu, training, eps, out16, r_rows, r_edge, *flat):
+        M = len(flat) // 5
+        CF._need_cuda(r_rows, *flat, also=(torch.bfloat16,))
+        L = _lib.lib()
+        zs = [flat[5 * m].contiguous() for m in range(M)]
+        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
+        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
+        if not training:                                                    # the running statistics may move before the backward
+            means, scales = [t.clone() for t in means], [t.clone() for t in scales]
+        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
+        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+        N, C = zs[0].shape
+        if r_rows is not None:
+            r_c = r_rows if _pitched16(r_rows) else r_rows.contiguous()
+        else:
+            r_c = None if r_edge is None else _rows(r_edge)
+        y = torch.empty((N, C), device=zs[0].device, dtype=torch.bfloat16 if out16 else torch.float32)
+        t = _lib.BnTerms()
+        for m in range(M):
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
+            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
+        with CF.rows16(True):
+            _lib.check(L.csn_rows_bn_act_fwd_t16(ctypes.addressof(t), M, N, C, int(training), float(eps), CF._ptr(r_c), int(r_rows is not None),
+                                                 0 if r_c is None else r_c.stride(0), int(relu), CF._ptr(y), int(out16), C, CF._stream()),
+                       "csn_rows_bn_act_fwd_t16")
+        ctx.save_for_backward(y if relu else None, *zs, *means, *scales, *gammas)
+        ctx.M, ctx.relu, ctx.training, ctx.eps, ctx.out16 = M, bool(relu), bool(training), float(eps), bool(out16)
+        ctx.has_r = r_c is not None
+        if not out16:
+            return y
+        ctx.mark_non_differentiable(y)
+        return y, _zero_vec(y.device, 1).expand(N, C)                       # (one cached word: no launch, nothing is ever written)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        dy = grads[-1]                                                      # out16: (the rows' None, the edge's gradient)
+        M = ctx.M
+        saved = ctx.saved_tensors
+        y = saved[0]
+        zs, means, scales, gammas = (saved[1 + k * M:1 + (k + 1) * M] for k in range(4))
+        L = _lib.lib()
+        N, C = zs[0].shape
+        dev = dy.device
+        dy = dy.contiguous()
+        need = ctx.needs_input_grad
+        dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[5]) else None
+        t = _lib.BnTerms()
+        outs = []
+        for m in range(M):
+            nz, ng, nb = need[6 + 5 * m], need[6 + 5 * m + 3], need[6 + 5 * m + 4]
+            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
+            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
+            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
+            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
+            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
+            outs += [dz, None, None, dg, db]
+        ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
+        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        with CF.math_mode(2), CF.rows16(True):
+            _lib.check(L.csn_rows_bn_act_bwd_t16(CF._ptr(dy), C, CF._ptr(y), int(ctx.out16), C, ctypes.addressof(t), M, N, C, int(ctx.training),
+                                                 ctx.eps, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),
+                       "csn_rows_bn_act_bwd_t16")
+        return (None, None, None, None, None, dr, *outs)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -635,9 +836,17 @@ def _conv_bn_act(conv: SparseConv3d, norm: nn.BatchNorm1d, x, kmap: KernelMap, r
     return sparse_conv_bn_act(x, conv.kernel, kmap, norm, residual, relu, out, out_dtype=out_dtype)
 
 
-def _bn_act(terms: Sequence[Term], grouped: bool, group_rows, residual, relu, training, eps) -> torch.Tensor:
+def _bn_act(terms: Sequence[Term], grouped: bool, group_rows, residual, relu, training, eps, out_dtype=None):
     if not 1 <= len(terms) <= 3:
         raise ValueError(("bn_act_groups" if grouped else "bn_act") + " takes 1 to 3 terms")
+    m16 = isinstance(residual, Map16) or out_dtype is not None            # a section-28 call
+    if m16:
+        if grouped:
+            raise ValueError("row groups have no bf16-map form (include/csn_hip.h section 28 takes the whole map as one batch)")
+        if out_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16, not {out_dtype}: math mode \"fp16\" runs its backward "
+                             "in bf16, which would round an fp16 map a second time")
+        _need_train16(residual if isinstance(residual, Map16) else None)
     flat = []
     N, C = terms[0][0].shape
     G = None
@@ -661,15 +870,25 @@ def _bn_act(terms: Sequence[Term], grouped: bool, group_rows, residual, relu, tr
             raise _lib.CsnError(_NO_CPU)
         if tuple(residual.shape) != (N, C):
             raise ValueError("the residual must be (N, C)")
-        residual = residual.float()
+        if not isinstance(residual, Map16):
+            residual = residual.float()
+    if m16:
+        r_rows, r_edge = (residual.rows, residual.edge) if isinstance(residual, Map16) else (None, residual)
+        out = _BnAct16.apply(bool(relu), bool(training), float(eps), out_dtype == torch.bfloat16, r_rows, r_edge, *flat)
+        return Map16(*out) if out_dtype == torch.bfloat16 else out
     return _BnAct.apply(bool(relu), bool(training), float(eps), group_rows if grouped else None, residual, *flat)
 
 
-def bn_act(terms: Sequence[Term], residual: Optional[torch.Tensor] = None, relu: bool = True, training: bool = True,
-           eps: float = 1e-5) -> torch.Tensor:
+def bn_act(terms: Sequence[Term], residual=None, relu: bool = True, training: bool = True, eps: float = 1e-5,
+           out_dtype: Optional[torch.dtype] = None):
     """``y (N, C) = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + residual)`` for 1 to 3 terms ``(z, mean, scale, gamma, beta)``:
-    training takes ``scale = invstd`` (of ``conv_stats``), eval the running mean / variance and ``eps``."""
-    return _bn_act(terms, False, None, residual, relu, training, eps)
+    training takes ``scale = invstd`` (of ``conv_stats``), eval the running mean / variance and ``eps``.
+
+    bf16 training maps (section 28; math mode "bf16" with ``tuning.rows_single_product``, else ``ValueError``): ``residual`` may be a
+    ``Map16``, and ``out_dtype=torch.bfloat16`` returns one — the same y rounded once to bf16 (nearest even), whose backward masks
+    on the stored value; ``out_dtype=torch.float32`` names an fp32 result on the same route.  Without either the call is section 15
+    as ever."""
+    return _bn_act(terms, False, None, residual, relu, training, eps, out_dtype)
 
 
 def bn_act_groups(terms: Sequence[Term], group_rows: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = True,
@@ -708,9 +927,10 @@ def _conv_bn(conv: SparseConv3d, norm: nn.BatchNorm1d, x: torch.Tensor, kmap: Ke
     return (sparse_conv3d(x, conv.kernel, None, kmap), norm.running_mean, norm.running_var, norm.weight, norm.bias)
 
 
-def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5, groups=None) -> torch.Tensor:
+def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5, groups=None, out_dtype=None):
     """relu(sum of ``parts``) where a part is a term / normalised map of ``_conv_bn`` or ("r", map) for a plain map.  The ATen path
-    adds in the order given (the reference's, hrnet.py:157-161).  ``groups``: as in ``_conv_bn``, for the level of the sum."""
+    adds in the order given (the reference's, hrnet.py:157-161).  ``groups``: as in ``_conv_bn``, for the level of the sum.
+    ``out_dtype`` (fused, ``tuning.train_maps16``): ``bn_act``'s."""
     if fused:
         terms = [p for p in parts if not (isinstance(p, tuple) and p[0] == "r")]
         res = [p[1] for p in parts if isinstance(p, tuple) and p[0] == "r"]
@@ -720,7 +940,7 @@ def _combine(parts: Sequence, fused: bool, training: bool, eps: float = 1e-5, gr
             return res[0]
         if groups is not None:
             return bn_act_groups(terms, groups[0], res[0] if res else None, True, eps)
-        return bn_act(terms, res[0] if res else None, True, training, eps)
+        return bn_act(terms, res[0] if res else None, True, training, eps, out_dtype)
     maps = [p[1] if isinstance(p, tuple) else p for p in parts]
     buf = maps[0]
     for m in maps[1:]:
@@ -751,18 +971,20 @@ class HRBasicBlock(nn.Module):
         self.norm2 = nn.BatchNorm1d(planes, momentum=bn_momentum)
         self.fused = fused
 
-    def forward(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
-                group_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``group_rows`` (training, fused): the rows are G BatchNorm batches (``conv_stats_groups``)."""
+    def forward(self, x, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "", group_rows: Optional[torch.Tensor] = None,
+                dtype: Optional[torch.dtype] = None, out_dtype: Optional[torch.dtype] = None):
+        """``group_rows`` (training, fused): the rows are G BatchNorm batches (``conv_stats_groups``).  ``dtype`` / ``out_dtype``
+        (training, fused, ``tuning.train_maps16``): ``bn_act``'s ``out_dtype`` for the inner map and for the block's result —
+        ``torch.bfloat16`` stores a ``Map16``; ``x`` may be one."""
         f, tr = self.fused, self.training
         g = None
         if group_rows is not None and tr:
             if not f:
                 raise ValueError("row groups in training need fused=True: ATen has no grouped BatchNorm")
             g = (group_rows, group_rows.numel() - 1)
-        out = _keep(trace, prefix + "norm1", _combine([_conv_bn(self.conv1, self.norm1, x, kmap, f, g)], f, tr, self.norm1.eps, g))
+        out = _keep(trace, prefix + "norm1", _combine([_conv_bn(self.conv1, self.norm1, x, kmap, f, g)], f, tr, self.norm1.eps, g, dtype))
         t2 = _conv_bn(self.conv2, self.norm2, out, kmap, f, g)
-        return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps, g))
+        return _keep(trace, prefix + "norm2", _combine([t2, ("r", x)], f, tr, self.norm2.eps, g, out_dtype))
 
     def infer(self, x: torch.Tensor, kmap: KernelMap, trace: Optional[dict] = None, prefix: str = "",
               out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None,
@@ -793,7 +1015,16 @@ class HRNetBackbone(nn.Module):
     see the groups in order; ``fused=False`` raises ``ValueError``), in eval mode the pass is the one below on the merged pyramid.
 
     Under ``tuning.override(eval_epilogue=True)`` a fused backbone in eval mode, called with autograd disabled, runs the inference
-    graph (``_forward_infer``); in every other case the switch changes nothing."""
+    graph (``_forward_infer``); in every other case the switch changes nothing.
+
+    Under ``tuning.override(train_maps16=True)`` a fused backbone in training mode, on a plain ``VoxelPyramid`` in math mode "bf16"
+    with ``rows_single_product``, stores as bf16 rows (``Map16``) every ReLU output that only its own nodes read: ``bn1s1``, the inner
+    and outer outputs of the blocks, the branch sums, the inner steps of the exchange paths and of the final transitions.  ``bn0s1``,
+    branch 0's last block output and the last step of each final transition — what ``torch.cat`` joins — stay fp32, as do z, the
+    statistics and every gradient; ``trace`` receives the maps as stored.  The step equals the fp32-map step with every stored map
+    rounded once.  Math modes "fp16" (its backward runs in bf16 and would round an fp16 map again), "fp32" and "bf16x3",
+    ``rows_single_product`` off, ``fused=False``, a ``GroupedPyramid`` and eval mode — of the backbone or of any of its submodules (a
+    frozen block or BatchNorm) — ignore the switch: the same calls, the same bits."""
 
     NUM_BLOCKS = 3
 
@@ -869,16 +1100,24 @@ class HRNetBackbone(nn.Module):
         if tuning.current().eval_epilogue and f and not tr and not torch.is_grad_enabled():
             return self._forward_infer(feats, pyramid, trace)
         G = (lambda level: None) if grp is None else grp                    # the groups of a map on `level`
-        act1 = lambda name, t, level: _keep(trace, name, _combine([t], f, tr, groups=G(level)))
+        # tuning.train_maps16: the stored maps' out_dtype (bf16 rows, Map16) and that of the maps torch.cat joins (fp32 on the
+        # same route); None: every map fp32 on section 15, the calls as ever.  A backbone with a submodule in eval mode (a frozen
+        # block or BatchNorm: that layer runs sparse_conv3d on the running statistics) is not in training mode for this purpose
+        on16 = (tuning.current().train_maps16 and f and tr and grp is None and train_maps16_open()
+                and all(m.training for m in self.modules()))
+        m16, f32 = (torch.bfloat16, torch.float32) if on16 else (None, None)
+        act1 = lambda name, t, level, dt=None: _keep(trace, name, _combine([t], f, tr, groups=G(level), out_dtype=dt))
         out_init = act1("bn0s1", _conv_bn(self.conv0s1, self.bn0s1, feats.float(), pyramid.stem, f, G(0)), 0)
-        out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f, G(0)), 0)
+        out = act1("bn1s1", _conv_bn(self.conv1s1, self.bn1s1, out_init, pyramid.s1[0], f, G(0)), 0, m16)
         stage_input = [out]
         for i in range(self.num_stages):
             stage_output = []
             for j in range(i + 1):
                 x = stage_input[j]
                 for b, blk in enumerate(self.stages[i][j]):
-                    x = blk(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", None if grp is None else grp(j)[0])
+                    last = i == self.num_stages - 1 and j == 0 and b == len(self.stages[i][j]) - 1     # torch.cat reads it
+                    x = blk(x, pyramid.s1[j], trace, f"stages.{i}.{j}.{b}.", None if grp is None else grp(j)[0], m16,
+                            f32 if last else m16)
                 stage_output.append(x)
             if i == self.num_stages - 1:
                 break
@@ -897,16 +1136,17 @@ class HRNetBackbone(nn.Module):
                         to = level + 1 if k > j else level - 1             # the level the step ends on
                         t = _conv_bn(path[3 * s], path[3 * s + 1], x, kmap, f, G(to))
                         if s + 1 < steps:
-                            x = act1(f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", t, to)
+                            x = act1(f"exchange_blocks.{i}.{j}.{k}.{3 * s + 1}", t, to, m16)
                         else:
                             parts.append(t)
-                stage_input.append(_keep(trace, f"sum.{i}.{k}", _combine(parts, f, tr, groups=G(k))))
+                stage_input.append(_keep(trace, f"sum.{i}.{k}", _combine(parts, f, tr, groups=G(k), out_dtype=m16)))
         outs = [out_init, stage_output[0]]
         for i in range(1, self.num_stages):
             x, block = stage_output[i], self.final_transitions[i - 1]
             for s in range(i):
                 x = act1(f"final_transitions.{i - 1}.{3 * s + 1}",
-                         _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f, G(i - s - 1)), i - s - 1)
+                         _conv_bn(block[3 * s], block[3 * s + 1], x, pyramid.up(i - s - 1), f, G(i - s - 1)), i - s - 1,
+                         f32 if s == i - 1 else m16)
             outs.append(x)
         return torch.cat(outs, dim=1)
 

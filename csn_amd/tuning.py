@@ -138,6 +138,19 @@ class Tuning:
     # separate passes by rounding.  Batches given as prebuilt VoxelPyramids, an unfused backbone in training and merged maps past
     # the kernels' 2 GiB window keep the separate passes.  Off: opt-in (DESIGN.md "Grouped passes", scripts/bench_hrnet_groups.py)
     grouped_passes: bool = False
+    # HRNetBackbone.forward on a fused=True backbone in TRAINING mode, math mode "bf16" with rows_single_product, on a plain
+    # VoxelPyramid: every ReLU output that only the project's own nodes read — the inner and outer outputs of the blocks, the branch
+    # sums, the inner steps of the exchange paths and final transitions, bn1s1 — is stored as bf16 rows (include/csn_hip.h section
+    # 28) instead of fp32 rows that the next convolution and its weight gradient round to bf16 anyway: the map's write and its
+    # three reads (the gather, the weight gradient's gather, the ReLU mask of the backward) halve, and autograd keeps 2 bytes an
+    # element alive instead of 4.  z, the statistics, every gradient map, the stem's input and the three kinds of map torch.cat joins
+    # (bn0s1, branch 0's last block output, the last step of each final transition) stay fp32.  No product changes; a stored map is
+    # rounded once (tests/test_gpu_train_maps16_net.py holds the step bit for bit to the fp32-map graph with every stored map rounded
+    # once).  Ignored — the same calls, the same bits — everywhere else: math mode "fp16" (its backward runs in bf16: an fp16 map
+    # would be rounded a second time by the weight gradient), fp32 and bf16x3, rows_single_product off, fused=False, a GroupedPyramid
+    # (and with it grouped_passes), eval mode (of the backbone or of any submodule: a frozen block or BatchNorm), and the
+    # Res16UNets.  Off: opt-in (bytes and timing: DESIGN.md "16-bit training maps", scripts/bench_hrnet_train_maps16.py)
+    train_maps16: bool = False
 
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))

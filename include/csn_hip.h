@@ -1211,6 +1211,43 @@ CSN_API int csn_sparse_conv_cat_stats_fwd_f32(const CsnCatParts* parts, int n_pa
                                       float* running_mean, float* running_var, float eps, float momentum, void* ws,
                                       long long ws_bytes, void* stream);
 
+/* ---- (28) training: the fused tail of (15) and the backward of (14) on bf16 activation maps (the ReLU outputs between the layers of
+ * HRNetBackbone's training graph) ------------------------------------------------------------------------------------------------
+ * The training counterpart of (24).  In math mode 2 behind csn_set_thread_rows16 a convolution rounds its gathered input to bf16
+ * before the product and its weight gradient rounds the same map again; a ReLU output y that only such launches read can therefore
+ * be STORED as bf16 rows: the products are the same, y's one write and three reads (the next convolution, its weight gradient, the
+ * ReLU mask of (15b)'s backward) move half the bytes.  z, mean / invstd and every gradient map (dy, dz, dx, dr) stay fp32.
+ * Additive to ABI version 17.  Each entry point is an existing one with a TYPE FLAG beside the map that may be bf16 (0: fp32 rows as
+ * ever — the call IS the existing one —, 1: bf16 rows; anything else CSN_E_ARG); a bf16 map's pitch counts ELEMENTS:
+ *   csn_sparse_conv_stats_fwd_t16   (15a) with x / x16.  z, mean, invstd and the running statistics are the bits of
+ *                                   csn_sparse_conv_stats_fwd_f32 on the same values held as fp32 (the same column-block rule,
+ *                                   offset list, matrix instructions and statistics epilogue).
+ *   csn_rows_bn_act_fwd_t16         (15b) forward with r / r16 and y / y16.  v is formed as there; a bf16 y is to_bf16(v), ONE
+ *                                   rounding to nearest even; a bf16 r is widened exactly.
+ *   csn_rows_bn_act_bwd_t16         (15b) backward with y / y16: g' = dy [y > 0] on the stored value (round(relu(v)) > 0 where the
+ *                                   forward stored bf16); dr, dz, dgamma, dbeta as there, the same fp64 sums in the same order.
+ *   csn_sparse_conv_bwd_t16         (14) backward with x / x16: dw is the bits of csn_sparse_conv_bwd_f32 in mode 2 on the same values
+ *                                   held as fp32 (the same 16-row steps, skipped steps, split-K chunks and slab reduction); dx and
+ *                                   dbias do not read x and are (14)'s launches.
+ * Host-side checks before any launch: the thread's math mode is not 2, or csn_set_thread_rows16 is off, CSN_E_ARG (a bf16 map
+ * under bf16x3 or fp32 would throw away what it pays for; fp16 runs its backward in bf16 and would round an fp16 map twice); a
+ * bf16 map: pitch >= width (CSN_E_ARG), pitch % 8 == 0 (CSN_E_ALIGN), pitch <= 2^20 and rows * pitch * 2 bytes inside the 2 GiB
+ * window (CSN_E_DIM), base 16-byte aligned (CSN_E_PTR); everything else as in (14) / (15): widths multiples of 32 in [32, 256],
+ * n_out >= 2 for the statistics, the workspaces of csn_sparse_conv_stats_workspace_bytes, csn_rows_bn_act_workspace_bytes and
+ * csn_sparse_conv_workspace_bytes(.., 1).  The whole map is one BatchNorm batch: no row-group form. */
+CSN_API int csn_sparse_conv_stats_fwd_t16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                  int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
+                                  float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
+                                  void* stream);
+CSN_API int csn_rows_bn_act_fwd_t16(const CsnBnTerms* terms, int n_terms, int n_rows, int channels, int training, float eps,
+                            const void* r, int r16, long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream);
+CSN_API int csn_rows_bn_act_bwd_t16(const float* dy, long long ld_dy, const void* y, int y16, long long ld_y, const CsnBnTerms* terms,
+                            int n_terms, int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr,
+                            void* ws, long long ws_bytes, void* stream);
+CSN_API int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void* x, int x16, long long ld_x, int n_in, int n_out, int kv,
+                            int c_in, int c_out, const int* fwd_table, const int* bwd_table, const float* w, float* dx,
+                            long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream);
+
 /* ---- DEVELOPMENT SECTION -------------------------------------------------------------------------------------------------
  * Kernel-selection switches for A/B timing and for the equality tests between two kernel forms of one product.  They are
  * PROCESS-wide, not thread-safe, change no result beyond fp32 rounding and are not part of the drop-in surface: a product
