@@ -16,7 +16,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libcsn_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "train_maps16.hip", "sparse_conv_cat.hip", "octant_conv.hip", "octant_conv_maps16.hip", "octant_conv_stats.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "fold.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "train_maps16.hip", "sparse_conv_cat.hip", "octant_conv.hip", "octant_conv_maps16.hip", "octant_conv_stats.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
 HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", "sconv_a16_body.inc", "rows_bn_act_body.inc", "octant_rows_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
 ARCH = "gfx950"
 BUILD_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"]
@@ -168,6 +168,13 @@ _SIGNATURES = {
                                            c_int, c_void_p, c_int, c_void_p]),
     "csn_attn_bwd_grouping": (c_int, [c_int, c_int]),
     "csn_attn_bwd_dv_scores_available": (c_int, [c_int, c_int]),
+    "csn_attn_bwd_dq_no_planes_available": (c_int, [c_int, c_int]),
+    "csn_fold_workspace_floats": (c_longlong, [c_int, c_int]),
+    "csn_fold_weights_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_longlong, c_void_p]),
+    "csn_unfold_wgrads_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "csn_tile_planes_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "csn_block_attn_bwd_dv_scores_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p,
                                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong,
                                                  c_void_p, c_int, c_void_p]),

@@ -82,7 +82,10 @@ constexpr int csn_attn_waves(int npl, int dt, bool bwd, bool rc_f32 = false) {
 // NOP (kept scores, two planes, sc_tiles == 2): the dS planes leave as with sc_tiles == 1, but P is neither split nor stored —
 // the scores stay as the forward wrote them, for the dV kernel that rebuilds P from them (attn_dv_scores.hip).  A compile-time
 // property: the split and the two plane stores are gone from the instance, not branched around in every tile.
-template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, bool NOP = false>
+// NOP = 2 (sc_tiles == 3): no dS planes either — nothing score-sized is written, `dscores` may be null (no descriptor is built
+// from it) and the scores are read-only.  For a caller that needs dQ and delta alone (folded projections: K = V = the input's
+// planes, no dK / dV products follow).  The dS split itself stays: phase 2 consumes (ph, pl).
+template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, int NOP = 0>
 __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
   static_assert(PR::NT == 3 || KVP, "single-product modes take K / V as tile planes");
   static_assert(!RC || BWD, "score recomputation: backward kernel");
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   const long long sc_off = (((long long)e * p.H + hd) * p.n_blocks + blk) * ((long long)Tq * Tp);
   const bool have_scores = p.scores != nullptr;
   const csn_rsrc_t Sr = csn_make_rsrc(have_scores ? p.scores + sc_off : nullptr, have_scores ? (long long)Tq * Tp * 4 : 0);
-  const csn_rsrc_t dSr = csn_make_rsrc(BWD ? p.dscores + sc_off : nullptr, BWD ? (long long)Tq * Tp * 4 : 0);
+  const csn_rsrc_t dSr = csn_make_rsrc((BWD && NOP != 2) ? p.dscores + sc_off : nullptr, (BWD && NOP != 2) ? (long long)Tq * Tp * 4 : 0);
 
   // per-lane byte offsets (scalar offsets handed to the buffer instructions must be wave-uniform, so
   // everything that depends on the lane lives here); lanes of query rows beyond the block are switched off
@@ -609,7 +612,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
       ph[r] = to16<PR::HALF>(t1[r]);
       pl[r] = PR::NT == 3 ? to16<PR::HALF>(t1[r] - from16<PR::HALF>(ph[r])) : ph[r];
     }
-    if (BWD && p.sc_tiles) {
+    if (BWD && NOP != 2 && p.sc_tiles) {
       // P and dS leave as tile planes, per query row 16 tiles of [hi: 32 keys | lo: 32 keys] — the k-major operand
       // the dV / dK products stage without conversion work; keys beyond the block end are written as zeros.
       s16x8 qh, ql;
@@ -760,7 +763,11 @@ int launch_dt(const CsnAttnArgs& a, bool bwd, hipStream_t st) {
           else return -1;
         } else if (a.sc_tiles == 2) {                               // kept scores, dS planes only (the instance that is built)
           if constexpr (csn_attn_dv_scores_fits(PR::NT == 3 ? 1 : 2, 32 * DT))
-            hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, true>), grid, dim3(512), 0, st, a);
+            hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 1>), grid, dim3(512), 0, st, a);
+          else return -1;
+        } else if (a.sc_tiles == 3) {                               // kept scores, no planes at all: dQ and delta alone
+          if constexpr (csn_attn_dv_scores_fits(PR::NT == 3 ? 1 : 2, 32 * DT))
+            hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 2>), grid, dim3(512), 0, st, a);
           else return -1;
         } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true>), grid, dim3(512), 0, st, a);
       } else return -1;                                             // fp16: forward only (gradients underflow fp16)
@@ -788,7 +795,7 @@ int launch_any(const CsnAttnArgs& a, int d, bool bwd, hipStream_t st) {
   if (a.sc_layout && (PR::NPL != 2 || !a.kv_planes || a.Tq > 0 || a.tq_arr || a.t_arr || a.Tp < (a.T + 31) / 32 * 32 || (bwd && !a.sc_tiles)))
     return -1;                                                      // tile-major scores: block mode, two planes, tile-plane K / V
   if (a.q2 && (!bwd || (a.q2_shape_stride & 3))) return -1;
-  if (a.sc_tiles == 2 && (!bwd || !a.kv_planes || a.q2 || a.Tq > 0 || a.tq_arr || a.t_arr)) return -1;   // block mode, kept scores
+  if (a.sc_tiles >= 2 && (a.sc_tiles > 3 || !bwd || !a.kv_planes || a.q2 || a.Tq > 0 || a.tq_arr || a.t_arr)) return -1;   // block mode, kept scores
   if (a.q2 && !a.kv_planes && (a.sc_tiles || a.grp_off)) return -1;     // fp32 K / V maps: nothing score-sized leaves, one evaluation per launch unit
   if ((a.r_fmt || a.ctx_fmt || a.q2_fmt || a.out_fmt) && (PR::NPL != 1 || !a.kv_planes)) return -1;   // 16-bit maps: single-product modes
   if (a.out_fmt && a.accumulate) return -1;

@@ -276,6 +276,91 @@ int csn_project_qkv_f32(const float* x, long long x_shape_stride, int ld_x, cons
                          static_cast<float*>(kv_out), kv_shape_stride, ld_kv, n_shapes, n_points, 0, 1.f, 2, block, stream);
 }
 
+// ---- (1b) folded projections ---------------------------------------------------------------------------------------------
+// Exact fp32 whatever the thread's math mode: these are products of WEIGHTS (256^3, microseconds) whose rounding enters every
+// score and every output of the step, so they go straight to the fp32 matrix-core GEMM, never through launch_gemm's mode switch.
+static int gemm_exact(const float* a, int lda, const float* b, int ldb, int b_is_nk, float* c, int ldc, int M, int N, int K,
+                      float div_val, hipStream_t st) {
+  CsnGemmArgs g;
+  g.A = operand(a, 0, 0, 0, nullptr, lda);
+  g.B = operand(b, 0, 0, 0, nullptr, ldb);
+  g.C = operand(c, 0, 0, 0, nullptr, ldc);
+  g.M = M; g.N = N; g.K = K;
+  g.n0 = 1; g.n1 = 1; g.k_chunk = 0;
+  g.alpha = 1.f; g.div_rows = div_val != 1.f ? M : 0; g.div_val = div_val; g.accumulate = 0; g.eval_ids = nullptr;
+  return csn_launch_gemm_f32(g, b_is_nk, 1, st);
+}
+
+long long csn_fold_workspace_floats(int d_inner, int channels) {
+  return (d_inner <= 0 || channels <= 0) ? 0 : 2ll * d_inner * channels;
+}
+
+int csn_fold_weights_f32(const float* w_q, const float* w_k, const float* w_v, const float* w_fc, int d_inner, int channels,
+                         float temperature, float* m, float* w_fv, float* w_fv_t, float* ws, long long ws_floats, void* stream) {
+  if (!w_q || !w_k || !w_v || !w_fc || !m || !w_fv || !w_fv_t || !ws || d_inner <= 0 || channels <= 0) return CSN_E_ARG;
+  if (!(temperature > 0.f)) return CSN_E_ARG;
+  if ((d_inner & 3) || (channels & 3)) return CSN_E_ALIGN;
+  if (mis16(w_q) || mis16(w_k) || mis16(w_v) || mis16(w_fc) || mis16(m) || mis16(w_fv) || mis16(w_fv_t) || mis16(ws)) return CSN_E_PTR;
+  if (ws_floats < csn_fold_workspace_floats(d_inner, channels)) return CSN_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int D = d_inner, C = channels;
+  float* wk_t = ws;                                  // [C][D]
+  float* wv_t = ws + (long long)D * C;               // [C][D]
+  CsnTransposeArgs t;
+  t.src[0] = w_k; t.dst[0] = wk_t; t.src[1] = w_v; t.dst[1] = wv_t; t.src[2] = nullptr; t.dst[2] = nullptr;
+  t.n = 2; t.rows = D; t.cols = C;
+  int rc = csn_launch_transpose_f32(t, st);
+  if (rc) return rc;
+  rc = gemm_exact(wk_t, D, w_q, C, 0, m, C, C, C, D, temperature, st);          // M = W_k^T W_q / t
+  if (rc) return rc;
+  rc = gemm_exact(w_fc, D, w_v, C, 0, w_fv, C, C, C, D, 1.f, st);               // W_fv = W_fc W_v
+  if (rc) return rc;
+  return gemm_exact(wv_t, D, w_fc, D, 1, w_fv_t, C, C, C, D, 1.f, st);          // W_fv^T = W_v^T W_fc^T
+}
+
+int csn_unfold_wgrads_f32(const float* dm, const float* dw_fv, const float* w_q, const float* w_k, const float* w_v,
+                          const float* w_fc, int d_inner, int channels, float temperature, float* dw_q, float* dw_k, float* dw_v,
+                          float* dw_fc, float* ws, long long ws_floats, void* stream) {
+  if (!dm || !dw_fv || !w_q || !w_k || !w_v || !w_fc || !dw_q || !dw_k || !dw_v || !dw_fc || !ws || d_inner <= 0 || channels <= 0)
+    return CSN_E_ARG;
+  if (!(temperature > 0.f)) return CSN_E_ARG;
+  if ((d_inner & 3) || (channels & 3)) return CSN_E_ALIGN;
+  if (mis16(dm) || mis16(dw_fv) || mis16(w_q) || mis16(w_k) || mis16(w_v) || mis16(w_fc) || mis16(dw_q) || mis16(dw_k) ||
+      mis16(dw_v) || mis16(dw_fc) || mis16(ws))
+    return CSN_E_PTR;
+  if (ws_floats < (long long)d_inner * channels) return CSN_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int D = d_inner, C = channels;
+  CsnTransposeArgs t;
+  t.src[0] = w_fc; t.dst[0] = ws; t.src[1] = t.src[2] = nullptr; t.dst[1] = t.dst[2] = nullptr;      // W_fc^T [D][C]
+  t.n = 1; t.rows = C; t.cols = D;
+  int rc = csn_launch_transpose_f32(t, st);
+  if (rc) return rc;
+  rc = gemm_exact(w_k, C, dm, C, 0, dw_q, C, D, C, C, temperature, st);         // dW_q = W_k dM / t
+  if (rc) return rc;
+  rc = gemm_exact(w_q, C, dm, C, 1, dw_k, C, D, C, C, temperature, st);         // dW_k = W_q dM^T / t
+  if (rc) return rc;
+  rc = gemm_exact(dw_fv, C, w_v, C, 1, dw_fc, D, C, D, C, 1.f, st);             // dW_fc = dW_fv W_v^T
+  if (rc) return rc;
+  return gemm_exact(ws, C, dw_fv, C, 0, dw_v, C, D, C, C, 1.f, st);             // dW_v = W_fc^T dW_fv
+}
+
+int csn_tile_planes_f32(const float* x, long long x_shape_stride, int ld_x, void* out, long long out_shape_stride, int ld_out,
+                        int n_shapes, int rows, int n_points, int block, void* stream) {
+  if (!x || !out || n_shapes <= 0 || rows <= 0 || n_points <= 0) return CSN_E_ARG;
+  if (block <= 0 || block > 512 || (ld_out % 1024)) return CSN_E_ARG;
+  if (((long long)n_points + block - 1) / block * 1024 > ld_out || n_points > ld_x) return CSN_E_ARG;
+  if (rows > 65535 || n_shapes > 65535) return CSN_E_ARG;
+  if ((block & 3) || (ld_x & 3) || (n_points & 3)) return CSN_E_ALIGN;
+  if (mis16(x) || mis16(out)) return CSN_E_PTR;
+  if ((x_shape_stride & 3) || (out_shape_stride & 7)) return CSN_E_STRIDE;
+  CsnTilePlanesArgs a;
+  a.x = x; a.x_item_stride = x_shape_stride; a.ldx = ld_x;
+  a.out = static_cast<short*>(out); a.out_item_stride = out_shape_stride; a.ldo = ld_out;
+  a.n_items = n_shapes; a.rows = rows; a.n_points = n_points; a.tb = block;
+  return csn_launch_tile_planes(a, (hipStream_t)stream);
+}
+
 static int attn_fwd_impl(const float* q, const float* k, const float* v, long long q_shape_stride,
                          long long kv_shape_stride, const int* q_index, const int* kv_index, int ld, float* ctx,
                          long long ctx_eval_stride, float* scores, float* lse, int n_evals, int n_heads,
@@ -395,8 +480,9 @@ static int attn_bwd_dq_impl(const float* dctx, const float* ctx, long long ctx_e
   if ((block & 3) && (block_q == 0 || kv_split)) return CSN_E_ALIGN;
   if (probs_tiles && (mode() == 0 || score_pitch < (block + 31) / 32 * 32)) return CSN_E_ARG;
   // probs_tiles == 2: dS planes only, the scores stay untouched (kept scores, where the dV-from-scores kernel exists)
-  if (probs_tiles < 0 || probs_tiles > 2) return CSN_E_ARG;
-  if (probs_tiles == 2 && (q || !kv_split || block_q != 0 || tq_arr || t_arr || act16() ||
+  // probs_tiles == 3: no planes at all — scores read-only, dscores unused (may be NULL); the same conditions
+  if (probs_tiles < 0 || probs_tiles > 3) return CSN_E_ARG;
+  if (probs_tiles >= 2 && (q || !kv_split || block_q != 0 || tq_arr || t_arr || act16() ||
                            !csn_attn_bwd_dv_scores_available(d_head, block)))
     return CSN_E_ARG;
   if (dropout_p < 0.f || dropout_p >= 1.f) return CSN_E_ARG;
@@ -411,7 +497,7 @@ static int attn_bwd_dq_impl(const float* dctx, const float* ctx, long long ctx_e
     return CSN_E_ARG;
   // (recomputed scores with probs_tiles == 0: nothing is read from or written to scores / dscores — they may be NULL)
   // (recomputed scores in the one-plane mode: P and dS both travel in dscores, `scores` is never touched)
-  const bool need_sc = !q || (probs_tiles && mode() == 1), need_ds = !q || probs_tiles;
+  const bool need_sc = !q || (probs_tiles && mode() == 1), need_ds = (!q || probs_tiles) && probs_tiles != 3;
   if (!dctx || !ctx || !k || !v || !lse || !delta || !dq || (need_sc && !scores) || (need_ds && !dscores)) return CSN_E_ARG;
   if (n_launch_evals <= 0 || n_heads <= 0 || block <= 0 || n_blocks <= 0) return CSN_E_ARG;
   if (!dim_ok(d_head)) return CSN_E_DIM;
@@ -587,6 +673,8 @@ int csn_attn_bwd_grouping(int d_head, int block) {
 int csn_attn_bwd_dv_scores_available(int d_head, int block) {
   return block > 0 && block <= 512 && !(block & 3) && csn_attn_dv_scores_fits(mode(), d_head);
 }
+// probs_tiles = 3 of the dq call: built beside the probs_tiles = 2 instance, for the same geometries
+int csn_attn_bwd_dq_no_planes_available(int d_head, int block) { return csn_attn_bwd_dv_scores_available(d_head, block); }
 
 int csn_block_attn_bwd_dv_scores_f32(const float* dctx, long long ctx_eval_stride, int ld, const float* scores, const float* lse,
                                      float* dv, long long dkv_slot_stride, const int* dv_index, const int* eval_ids,

@@ -61,6 +61,20 @@ int csn_launch_wx(const CsnWxArgs& a, int out_mode /* 0 fp32, 2 tile planes, 3 L
 int csn_wx_ln_sum_slots(int n_items, int n_points);      // out_mode 3: sum_slots the launch will use (sum_ws = n_items * slots * 256 floats)
 int csn_launch_wx_ln_sums(const float* ws, float* out, int n_items, int n_points, hipStream_t st);   // out[item][256] from sum_ws
 
+// ---- folded projections: x as tile planes, small transposes (fold.hip) -------------------------------------
+struct CsnTilePlanesArgs {
+  const float* x;  long long x_item_stride;  int ldx;     // [item][rows][ldx] fp32
+  short* out;  long long out_item_stride;  int ldo;       // bf16 tile planes [item][rows][ldo] (strides in 16-bit elements)
+  int n_items, rows, n_points;
+  int tb;                                                 // points per attention block
+};
+int csn_launch_tile_planes(const CsnTilePlanesArgs& a, hipStream_t st);
+struct CsnTransposeArgs {
+  const float* src[3];  float* dst[3];                    // n contiguous row-major [rows][cols] matrices -> [cols][rows]
+  int n, rows, cols;
+};
+int csn_launch_transpose_f32(const CsnTransposeArgs& a, hipStream_t st);
+
 // ---- fused block attention (attn_f32.hip) -----------------------------------------------------
 struct CsnAttnArgs {
   // channel-major projected features, one slab of [H*d][ld] per shape

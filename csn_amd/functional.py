@@ -428,6 +428,7 @@ class _MHAEvals(torch.autograd.Function):
         dev = x_all.device
         temperature = geo.temperature or float(d) ** 0.5               # csa_models.py:54
         w_qkv = torch.cat((w_qs, w_ks, w_vs), dim=0).contiguous()      # (3D, C)
+        w_fc_in = w_fc.contiguous()
         a16 = ctx.a16
         fwd16 = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}[a16]           # type of the forward's maps Qs, Ctx
         att = torch.empty((E, D, NP), device=dev, dtype=fwd16)
@@ -435,7 +436,42 @@ class _MHAEvals(torch.autograd.Function):
         # values may come from a different slot than the keys (slot kv + v_shift): only the generic
         # MultiHeadAttention.forward(Q, K, V) with three distinct inputs uses that
         tiles = fast_math() and tuning.current().kv_tiles and T <= 512
-        if tiles:
+        # folded projections (csn_hip.h (1b)): one head of the model's width, bias-free layers — W_k goes into W_q,
+        # W_v into W_fc, and the attention runs on the planes of x itself.  Decided from the module, the plan and the tensors alone,
+        # never from the grad mode: a no-grad forward and a training forward give the same logits.  (x_all.requires_grad, not
+        # ctx.needs_input_grad: dx needs dK and dV, and the flag of the tensor is the same in both grad modes)
+        tune = tuning.current()
+        fold = bool(tune.takes_fold() and ctx.mode == 1 and H == 1 and C == d == D == 256 and tiles and not a16
+                    and tuple(w_fc.shape) == (C, D)
+                    and plan.v_shift == 0 and not x_all.requires_grad
+                    and _score_flow(ctx.mode, d, T) == tuning.KEEP_SCORES and L.csn_attn_bwd_dq_no_planes_available(d, T))
+        ctx.fold = fold
+        w_fv = w_fv_t = None
+        if fold:
+            ldp = nb * 1024
+            w_m, w_fv, w_fv_t = (torch.empty((C, C), device=dev, dtype=torch.float32) for _ in range(3))
+            ws_n = int(L.csn_fold_workspace_floats(D, C))
+            ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+            _lib.check(L.csn_fold_weights_f32(_ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]), _ptr(w_fc.contiguous()), D, C,
+                                              temperature, _ptr(w_m), _ptr(w_fv), _ptr(w_fv_t), _ptr(ws), ws_n, _stream()),
+                       "csn_fold_weights_f32")
+            del ws
+            qkv = torch.empty((S, D, NP), device=dev, dtype=torch.float32)                    # Q'' = M x (no temperature left)
+            kv = torch.empty((S, C, ldp), device=dev, dtype=torch.bfloat16)                   # x as tile planes: "K" and "V" at once
+            # (a plan with slot ranges: Q'' of the query slots and planes of the key / value slots only, as the unfolded calls)
+            for first, step, count in (plan.q_ranges or [(0, 1, S)]):
+                _lib.check(L.csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w_m), D, C,
+                                             qkv.data_ptr() + 4 * first * D * NP, step * D * NP, NP, count, NP, 0, 1.0, 0, 0,
+                                             _stream()), "csn_project_f32")
+            for first, step, count in (plan.kv_ranges or [(0, 1, S)]):
+                _lib.check(L.csn_tile_planes_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP,
+                                                 kv.data_ptr() + 2 * first * C * ldp, step * C * ldp, ldp, count, C, NP, T,
+                                                 _stream()), "csn_tile_planes_f32")
+            q_ptr, q_stride = qkv.data_ptr(), D * NP
+            k_ptr, kv_stride = kv.data_ptr(), C * ldp
+            v_ptr = k_ptr
+            kv_flag, kv_pitch = 1, ldp
+        elif tiles:
             # 16-bit modes: K and V leave the projection as "tile planes" (per row and block 16 tiles of [hi 32 | lo 32] bf16 in
             # bf16x3, of [32] bf16 / fp16 in the single-product modes), which the attention kernels stage with plain copies; Q
             # (pre-scaled) stays fp32
@@ -479,7 +515,7 @@ class _MHAEvals(torch.autograd.Function):
             v_ptr = q_ptr + 4 * (2 * D * NP + v_shift * kv_stride)
             kv_flag, kv_pitch = 0, 0
         # attention backward data flow: keep the raw scores for it, or only lse (the backward then rebuilds S from Qs and K)
-        flow = _score_flow(ctx.mode, d, T) if (keep_scores and tiles) else tuning.KEEP_SCORES
+        flow = _score_flow(ctx.mode, d, T) if (keep_scores and tiles) else tuning.KEEP_SCORES      # (folded: KEEP_SCORES)
         scores = torch.empty((E, H, nb, T, Tp), device=dev, dtype=torch.float32) if (keep_scores and flow == tuning.KEEP_SCORES) else None
         # score storage: tile-major where the whole chain (forward, grouped dQ call, grouped dK / dV products on the 256 x 256
         # tiles) takes it — bf16x3 at d = 256 with kept scores; nothing outside this function reads the buffer
@@ -503,7 +539,7 @@ class _MHAEvals(torch.autograd.Function):
                            "csn_block_attn_fwd_f32")
         xhat = torch.empty((E, C, NP), device=dev, dtype=torch.float16 if a16 else torch.float32)
         rstd = torch.empty((E, NP), device=dev, dtype=torch.float32)
-        w_fc = w_fc.contiguous()
+        w_fc = w_fv if fold else w_fc.contiguous()                     # (folded: att = P_drop x, the out-projection takes W_fc W_v)
         # third output (want_sums): sums[e][c] = sum_n xhat[e][c][n], formed in the epilogue of the out-projection (per-tile
         # partials in sum_ws) instead of a separate streaming pass over the 2.6 GB of maps
         sums = torch.empty((E, C), device=dev, dtype=torch.float32) if want_sums else None
@@ -517,9 +553,11 @@ class _MHAEvals(torch.autograd.Function):
         if (keep_scores and link is not None and not a16 and tuning.current().fused_mix_bwd and plan.mixed_not_pooled
                 and n_head_evals > 0):
             # the mix's backward may run the LayerNorm backward of the leading evaluations itself (_lnb_head)
-            link.pre = (xhat, rstd, w_fc, p_fc, seed_fc, n_head_evals, ctx.mode, bool(x_all.requires_grad))
+            link.pre = (xhat, rstd, w_fc, p_fc, seed_fc, n_head_evals, ctx.mode, bool(x_all.requires_grad), w_fv_t)
         if keep_scores:
-            ctx.save_for_backward(x_all, w_qkv, w_fc, qkv, att, lse, scores, xhat, rstd, kv)
+            # (folded: w_fc is W_fv — the unfolding reads W_fc back from the autograd inputs' copy below; Q'' is not needed again)
+            ctx.save_for_backward(x_all, w_qkv, w_fc, None if fold else qkv, att, lse, scores, xhat, rstd, kv, w_fv_t,
+                                  w_fc_in if fold else None)
             ctx.flow = flow
             ctx.geo = geo
             ctx.plan = plan
@@ -557,7 +595,7 @@ class _MHAEvals(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dxhat, dhead, dsums=None, dhandle=None):
-        x_all, w_qkv, w_fc, qkv, att, lse, scores, xhat, rstd, kv = ctx.saved_tensors
+        x_all, w_qkv, w_fc, qkv, att, lse, scores, xhat, rstd, kv, w_fv_t, w_fc_in = ctx.saved_tensors
         geo: MHAGeometry = ctx.geo
         plan: EvalPlan = ctx.plan
         L = _lib.lib()
@@ -624,7 +662,7 @@ class _MHAEvals(torch.autograd.Function):
             dz = torch.empty((E, C, NP), device=dev, dtype=bwd16)
             dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and (p_fc > 0 or a16)) else None
             datt = torch.empty((E, D, NP), device=dev, dtype=bwd16)
-            w_fc_t = w_fc.t().contiguous()
+            w_fc_t = w_fv_t if ctx.fold else w_fc.t().contiguous()       # (folded: dCtx' = dz W_fv, dw_fc below is dW_fv)
             _lib.check(L.csn_outproj_ln_bwd_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(att), D * NP,
                                                 _ptr(w_fc_t), _ptr(dz), _ptr(dz_res), _ptr(datt), _ptr(dw_fc), _ptr(ws), ws_n,
                                                 E, C, D, NP, NP, 0, p_fc, seed_fc, 0, 0, _ptr(rows), n_dense, _ptr(scale), group,
@@ -634,6 +672,47 @@ class _MHAEvals(torch.autograd.Function):
 
         # ---- attention backward, straight into per-slot gradient maps ---------------------------------------
         # evaluations that share a slot (Q of the query shape, K/V of each neighbour) add up: one launch per colour
+        if ctx.fold:
+            # folded projections: one grouped dQ call on the planes of x (K = V = x), nothing score-sized written; G = dS x per
+            # query slot is the gradient of Q'' = M x, so dM is the 256-row weight gradient over (G, x) — no dK / dV products, no
+            # dscores, no 3 D-row gradient map.  (grouped_dq off: the same call colour by colour — the switch selects how dQ is
+            # accumulated, as in the unfolded step, not whether the step folds)
+            delta = torch.empty((E, H, geo.n_padded), device=dev, dtype=torch.float32)
+            g = torch.empty((S, D, NP), device=dev, dtype=torch.float32)
+            if plan.q_ranges is None and plan.q_unwritten.numel():
+                g.index_fill_(0, plan.q_unwritten, 0.0)
+            q_stride, kv_stride, kv_flag, kv_pitch = ctx.ptrs
+            if ctx.tune.grouped_dq and (L.csn_attn_bwd_grouping(d, T) & 1):
+                launches = [(0, plan.q_group_items, E, plan.q_group_off, plan.n_q_groups)]
+            else:
+                launches = [(0 if ci == 0 else 1, ids, ids.numel(), None, 0) for ci, ids in enumerate(plan.dq_colors)]
+            for accumulate, ids, n_ids, off, n_groups in launches:
+                _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, _ptr(kv), _ptr(kv), kv_stride,
+                                                       _ptr(plan.kv_slots), NP, _ptr(scores), None, _ptr(lse), _ptr(delta),
+                                                       _ptr(g), D * NP, _ptr(plan.q_slots), accumulate, _ptr(ids), n_ids, H, d, T,
+                                                       nb, Tp, p_attn, seed_attn, 0, 0, kv_flag, kv_pitch, 3, _ptr(off), n_groups,
+                                                       _stream()), "csn_block_attn_bwd_dq_f32")
+            del delta, datt
+            if plan.q_ranges is None:
+                d_m = project_wgrad(g, x_all)                           # dM = sum_slots G x^T
+            else:                                                       # ... over the query slots of the plan's ranges only
+                d_m = torch.empty((D, C), device=dev, dtype=torch.float32)
+                for i, (first, step, count) in enumerate(plan.q_ranges):
+                    ws_n = L.csn_wgrad_workspace_floats(D, C, count, NP)
+                    ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+                    _lib.check(L.csn_project_wgrad_f32(g.data_ptr() + 4 * first * D * NP, step * D * NP, NP,
+                                                       x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(d_m), D, C,
+                                                       count, NP, 1.0, 0 if i == 0 else 1, _ptr(ws), ws_n, _stream()),
+                               "csn_project_wgrad_f32")
+            del g
+            dw_qkv = torch.empty((3 * D, C), device=dev, dtype=torch.float32)
+            dw_fc_in = torch.empty((C, D), device=dev, dtype=torch.float32)
+            ws = torch.empty((D * C,), device=dev, dtype=torch.float32)
+            _lib.check(L.csn_unfold_wgrads_f32(_ptr(d_m), _ptr(dw_fc), _ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]),
+                                               _ptr(w_fc_in), D, C, temperature, _ptr(dw_qkv), _ptr(dw_qkv[D:]),
+                                               _ptr(dw_qkv[2 * D:]), _ptr(dw_fc_in), _ptr(ws), D * C, _stream()),
+                       "csn_unfold_wgrads_f32")
+            return (None, dw_qkv[:D], dw_qkv[D:2 * D], dw_qkv[2 * D:], dw_fc_in, None, None, None, None, None, None, None, None)
         flow = ctx.flow
         pt = 1 if (fast_math() and Tp >= (T + 31) // 32 * 32) else 0    # P / dS travel to the dV / dK products as tile planes
         # (bf16x3: P overwrites the scores in place, dS fills `dscores`; bf16: both go to `dscores` as compact rows and the
@@ -791,7 +870,7 @@ def _lnb_head(link: MixLink, dfeats: torch.Tensor, scale: torch.Tensor, group: i
     the link; _MHAEvals._backward fills in the others.  None: not taken (nothing was launched)."""
     if link is None or link.pre is None:
         return None
-    xhat, rstd, w_fc, p_fc, seed_fc, n, mode, need_dx = link.pre
+    xhat, rstd, w_fc, p_fc, seed_fc, n, mode, need_dx, w_fc_t = link.pre      # (w_fc_t: W_fv^T of a folded forward, else None)
     E, C, NP = xhat.shape
     D = w_fc.shape[1]
     L = _lib.lib()
@@ -806,7 +885,8 @@ def _lnb_head(link: MixLink, dfeats: torch.Tensor, scale: torch.Tensor, group: i
         dz = torch.empty((E, C, NP), device=dev, dtype=torch.float32)
         dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and p_fc > 0) else None
         datt = torch.empty((E, D, NP), device=dev, dtype=torch.float32)
-        w_fc_t = w_fc.t().contiguous()
+        if w_fc_t is None:
+            w_fc_t = w_fc.t().contiguous()
         _lib.check(L.csn_outproj_lnb_f32(_ptr(dfeats), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
                                          _ptr(datt), 0, n, C, D, NP, NP, p_fc, seed_fc, None, n, _ptr(scale), group, _ptr(rowdot),
                                          _ptr(rowsum), _ptr(red_ws), ws_n, _stream()), "csn_outproj_lnb_f32")

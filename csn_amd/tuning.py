@@ -49,6 +49,20 @@ class Tuning:
     # alone — the dQ launch writes 5.2 GB less per config-3 step (the dV kernel reads S where the product read P).  dQ and dK keep their bits; dV is the same three products summed in another
     # order.  Taken in either score layout where csn_attn_bwd_dv_scores_available says so; the default is what profiles/dv_scores_ab_step.txt measured
     dv_from_scores: bool = True
+    # One head of the model's width (H = 1, C = d = 256, the configuration the metric is quoted on), bf16x3, kept scores,
+    # no input gradients: W_k is folded into W_q and W_v into W_fc (M = W_k^T W_q / t, W_fv = W_fc W_v, exact fp32
+    # products of csn_fold_weights_f32), the attention kernels run on the tile planes of x itself as both "K" and "V"
+    # (csn_tile_planes_f32), and the backward is ONE dQ call that writes nothing score-sized (probs_tiles = 3) plus two 256-row
+    # weight gradients, unfolded to dW_q, dW_k, dW_v, dW_fc by csn_unfold_wgrads_f32.  K, V, dK, dV, dscores and their launches do not
+    # exist.  Unlike its neighbours this re-associates products: results move by fp32 / bf16x3 rounding (both forms measured against
+    # a float64 restatement: DESIGN.md §2 "Folded projections"; tests/test_gpu_folded.py).  The dropout masks are the same bits.  Where
+    # any condition fails the unfolded calls run and give their bits.  The decision never looks at the grad mode.
+    # One more condition lives here: an ``override`` block that NAMES a switch which exists only in the unfolded step
+    # (UNFOLDED_ONLY: dv_from_scores, grouped_dkv, qkv_one_pass — the folded step has no dV / dK product and no K | V projection,
+    # so it would ignore them silently) asks for the unfolded step — whatever value it gives the switch: an A/B of such a switch
+    # (scripts/ab_step.py, tests/test_gpu_dv_scores.py::test_module_step_with_dv_from_scores) keeps measuring the launches it names
+    folded_projections: bool = True
+    named: frozenset = frozenset()   # the switches the enclosing override blocks name (kept by ``override``; not a switch itself)
     # attention backward data flow by (math mode of the backward: 1 bf16x3, 2 bf16 — fp16 forwards run their backward in 2;
     # head width), or by mode alone; taken where the kernels have an instance for it (csn_attn_bwd_grouping bits 2 / 3),
     # KEEP_SCORES otherwise.  Measured per mode and width, DESIGN.md §4 "data flow A/B": at d = 256 the extra matrix products
@@ -155,6 +169,13 @@ class Tuning:
     def flow_for(self, mode: int, d_head: int) -> int:
         return self.score_flow.get((mode, d_head), self.score_flow.get(mode, KEEP_SCORES))
 
+    def takes_fold(self) -> bool:
+        """folded_projections, unless an enclosing override block names a switch of the unfolded step alone"""
+        return self.folded_projections and not (self.named & UNFOLDED_ONLY)
+
+
+UNFOLDED_ONLY = frozenset({"dv_from_scores", "grouped_dkv", "qkv_one_pass"})
+
 
 def cross_takes_score_free(score_bytes: int, budget: int, available: bool) -> bool:
     """The automatic rule of ``cross_score_free=None``: score-free when the flow has kernels for the call's mode and head width
@@ -176,12 +197,12 @@ def override(**changes):
     NOT thread-safe: the object is process-wide and swapped without a lock.  A step is safe against it all the same — every
     forward snapshots the switches into its autograd context and its backward reads only that snapshot."""
     global _current
-    names = {f.name for f in fields(Tuning)}
+    names = {f.name for f in fields(Tuning)} - {"named"}
     unknown = set(changes) - names
     if unknown:
         raise TypeError(f"unknown tuning switch(es): {sorted(unknown)}")
     saved = _current
-    _current = replace(saved, **changes)
+    _current = replace(saved, **changes, named=saved.named | frozenset(changes))
     try:
         yield _current
     finally:

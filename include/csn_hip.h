@@ -155,6 +155,32 @@ CSN_API int csn_project_qkv_f32(const float* x, long long x_shape_stride, int ld
                         float* q_out, long long q_shape_stride, int ld_q, void* kv_out, long long kv_shape_stride, int ld_kv,
                         int n_shapes, int n_points, float temperature, int block, void* stream);
 
+/* ---- (1b) folded projections: W_k folded into W_q, W_v into W_fc (one head, d_head = d_model, no biases) -------------------
+ * With one head, bias-free linear layers and nothing non-linear between a projection and the product that consumes it, the
+ * scores and the out-projection re-associate (row-per-point notation, t = the temperature):
+ *   S = (x_q W_q^T / t)(x_k W_k^T)^T = (x_q M^T) x_k^T,     M    = W_k^T W_q / t     [channels][channels]
+ *   fc(P (x_k W_v^T))                = (P x_k) W_fv^T,      W_fv = W_fc W_v          [channels][channels]
+ * so the attention calls of (2) and (3) run on the INPUT's tile planes as both K and V, and K, V, dK and dV never exist.
+ * csn_fold_weights_f32: m, w_fv and w_fv_t (= W_fv^T, which (5) / (5b) stream) from w_q, w_k, w_v [d_inner][channels] and w_fc
+ *   [channels][d_inner].  csn_unfold_wgrads_f32: from dm = dLoss/dM and dw_fv = dLoss/dW_fv
+ *   dw_q = W_k dM / t,  dw_k = W_q dM^T / t,  dw_fc = dW_fv W_v^T,  dw_v = W_fc^T dW_fv.
+ * Both run exact fp32 products (the fp32 matrix-core GEMM) WHATEVER the thread's math mode, and divide by t as a true division.
+ * ws: csn_fold_workspace_floats(d_inner, channels) floats for the fold, d_inner * channels for the unfold (transposed weights).
+ * csn_tile_planes_f32: x [shape][rows][ld_x] fp32 -> the bf16 tile planes csn_project_f32 writes with out_split = 2 in math mode 1
+ *   (per row and block of `block` points 16 tiles of [hi 32 | lo 32], hi = bf16(x), lo = bf16(x - hi); ld_out = row pitch, a
+ *   multiple of 1024 and >= n_blocks * 1024; out_shape_stride in 16-bit elements) — a copy with a split, no product: the layout
+ *   and (to the last bit of lo) the values of that projection with an identity weight.  The padding keys of every block's last tile are written as zeros, the tiles beyond a
+ *   short last block are not written (nothing reads them).  Mode-independent (the layout is math mode 1's). */
+CSN_API long long csn_fold_workspace_floats(int d_inner, int channels);
+CSN_API int csn_fold_weights_f32(const float* w_q, const float* w_k, const float* w_v, const float* w_fc, int d_inner, int channels,
+                                 float temperature, float* m, float* w_fv, float* w_fv_t, float* ws, long long ws_floats,
+                                 void* stream);
+CSN_API int csn_unfold_wgrads_f32(const float* dm, const float* dw_fv, const float* w_q, const float* w_k, const float* w_v,
+                                  const float* w_fc, int d_inner, int channels, float temperature, float* dw_q, float* dw_k,
+                                  float* dw_v, float* dw_fc, float* ws, long long ws_floats, void* stream);
+CSN_API int csn_tile_planes_f32(const float* x, long long x_shape_stride, int ld_x, void* out, long long out_shape_stride,
+                                int ld_out, int n_shapes, int rows, int n_points, int block, void* stream);
+
 /* ---- (2) block-diagonal scaled-dot-product attention, forward ----------------------------------------
  * For evaluation e, head h, block b:  P = softmax(Qs K^T) over the block's keys, ctx = P V
  * (ScaledDotProductAttention.forward, csa_models.py:138-144, eval mode; Qs is already divided by the
@@ -219,7 +245,11 @@ CSN_API int csn_block_attn_fwd_grouped_f32(const float* q, const float* k, const
  * nor stored; dq, delta and the dS planes are bit for bit those of probs_tiles = 1.  dV then comes from
  * csn_block_attn_bwd_dv_scores_f32 (below), which rebuilds P from the untouched scores, and dK from a
  * csn_block_attn_bwd_dkv_f32 call with probs = NULL and dv = NULL (probs_tiles = 1): that call runs the dK product alone and
- * writes the bits the two-product call writes.  probs_tiles takes the values 0, 1 and 2; anything else is CSN_E_ARG.
+ * writes the bits the two-product call writes.
+ * probs_tiles == 3 (csn_block_attn_bwd_dq_f32 only; the conditions of probs_tiles = 2, where
+ * csn_attn_bwd_dq_no_planes_available says so): NOTHING score-sized is written — `scores` is read-only, `dscores` is not used and
+ * may be NULL; dq and delta are bit for bit those of probs_tiles = 2.  For callers with no dK / dV products behind the call
+ * (folded projections, (1b): k = v = the input's planes).  probs_tiles takes the values 0 .. 3; anything else is CSN_E_ARG.
  * GROUPED calls (group_offsets != NULL): eval_ids lists the n_launch_evals evaluations ordered so that evaluations sharing
  * an output slot are adjacent, group g = entries group_offsets[g] .. group_offsets[g+1] (n_groups + 1 offsets); a group's
  * results are accumulated in registers and its slot is written once — one call for all evaluations instead of one
@@ -298,6 +328,7 @@ CSN_API int csn_block_attn_bwd_dkv_flash_f32(const float* dctx, long long ctx_ev
  * evaluation is its own group).  Geometry as csn_block_attn_bwd_dkv_f32 in block mode: block % 4 == 0, score_pitch >= block,
  * a row may end inside the last block (n_blocks * block > ld). */
 CSN_API int csn_attn_bwd_dv_scores_available(int d_head, int block);
+CSN_API int csn_attn_bwd_dq_no_planes_available(int d_head, int block);
 CSN_API int csn_block_attn_bwd_dv_scores_f32(const float* dctx, long long ctx_eval_stride, int ld, const float* scores,
                                      const float* lse, float* dv, long long dkv_slot_stride, const int* dv_index,
                                      const int* eval_ids, int n_launch_evals, int n_heads, int d_head, int block, int n_blocks,
