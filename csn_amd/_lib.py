@@ -355,7 +355,7 @@ _SIGNATURES = {
 
 EXPORTS = tuple(_SIGNATURES)
 # keys of csn_dev_set / csn_dev_get (include/csn_hip.h, development section)
-DEV_BIG_TILES, DEV_WIDE_GEMM, DEV_WIDE_FORMS, DEV_WX, DEV_LNB_GROUP, DEV_SCONV_NB = 0, 1, 2, 3, 5, 7
+DEV_BIG_TILES, DEV_WIDE_GEMM, DEV_WIDE_FORMS, DEV_WX, DEV_LNB_GROUP, DEV_SCONV_NB, DEV_KV_SAME = 0, 1, 2, 3, 5, 7, 8
 DEV_WX_DEFAULT = 9                     # streaming kernel (1) + LayerNorm backward fused into the dCtx stream (8); the only other
                                        # bit csn_dev_set takes for DEV_WX is 4 (out-projection + LayerNorm on the tiled kernel)
 

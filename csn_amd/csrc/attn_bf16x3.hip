@@ -85,8 +85,13 @@ constexpr int csn_attn_waves(int npl, int dt, bool bwd, bool rc_f32 = false) {
 // NOP = 2 (sc_tiles == 3): no dS planes either — nothing score-sized is written, `dscores` may be null (no descriptor is built
 // from it) and the scores are read-only.  For a caller that needs dQ and delta alone (folded projections: K = V = the input's
 // planes, no dK / dV products follow).  The dS split itself stays: phase 2 consumes (ph, pl).
-template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, int NOP = 0>
+// KV_SAME (the NOP = 2 instance at d = 256): k and v are the SAME planes (folded projections), so a tile is requested ONCE and
+// the same registers are committed into both images — tileA in segment 1, tileB in segment 2, where the two commits of the plain
+// instance sit.  The same LDS contents, hence the same bits; half the tile requests (8 -> 4 per wave and tile).  The forward in
+// the same form (one register set, no early request) was measured +-0 over the step and is not built.
+template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, int NOP = 0, bool KV_SAME = false>
 __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
+  static_assert(!KV_SAME || (DT == 8 && NOP == 2), "one request per tile: the folded d = 256 backward");
   static_assert(PR::NT == 3 || KVP, "single-product modes take K / V as tile planes");
   static_assert(!RC || BWD, "score recomputation: backward kernel");
   static_assert(!NOP || (BWD && KVP && !RC && PR::NPL == 2), "no P planes: the kept-scores backward in two planes");
@@ -416,14 +421,24 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   };
   auto commitA_to = [&](short* img, short* img_lo, f32x4* g, bool cvt = true) {       // img / img_lo: hi / lo plane of a k-major image
     if (cvt) cvt_pieces(g);
+    // KV_SAME: ONE lane constant for the two chunks of a unit (a_dst is a multiple of 8, so the other chunk is ^ 4), formed per
+    // commit — the second address is not kept live beside the first across the operand prologue, where this kernel spills
+    int a_lo = a_dst + 4 * t_sw;
+    if constexpr (KV_SAME) asm volatile("" : "+v"(a_lo));
 #pragma unroll
     for (int i = 0; i < NP_T; ++i)
       if (i < NP_T - 1 || t_last_ok) {
         if (KVP) {
-          short* base = img + a_dst + RPP * KT * i;
           const s16x8 v = __builtin_bit_cast(s16x8, g[i]);
-          *reinterpret_cast<s16x4*>(base + 4 * t_sw) = s16x4{v[0], v[1], v[2], v[3]};
-          *reinterpret_cast<s16x4*>(base + 4 * (t_sw ^ 1)) = s16x4{v[4], v[5], v[6], v[7]};
+          if constexpr (KV_SAME) {
+            short* base = img + RPP * KT * i;
+            *reinterpret_cast<s16x4*>(base + a_lo) = s16x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<s16x4*>(base + (a_lo ^ 4)) = s16x4{v[4], v[5], v[6], v[7]};
+          } else {
+            short* base = img + a_dst + RPP * KT * i;
+            *reinterpret_cast<s16x4*>(base + 4 * t_sw) = s16x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<s16x4*>(base + 4 * (t_sw ^ 1)) = s16x4{v[4], v[5], v[6], v[7]};
+          }
         } else {
           s16x4 hi, lo;
           split4<PR>(g[i], hi, lo);
@@ -686,7 +701,8 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     if (nkt > 1) fetch_to(Ar, 1, g);
   } else {
     fetch(Ar, 0); commitA(0);
-    fetch(Br, 0); commitB(0);
+    if constexpr (!KV_SAME) fetch(Br, 0);
+    commitB(0);
     if (nkt > 1) fetch(Ar, 1);
   }
   __syncthreads();
@@ -699,6 +715,8 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   // starts with its vector work, instead of two waves fighting over the same pipe.  With the commits placed as above the
   // shift is hazard-free: a K stage is rewritten in segments 2kt / 2kt+1 (early / late half), last read in 2kt-1 and
   // next read in 2kt+2; a V stage is rewritten in 2kt+1 / 2kt+2, last read in 2kt and next read in 2kt+3.
+  // (KV_SAME: both commits stay in their segments and only the second request is gone — the table holds unchanged; the one
+  //  request for tile kt+2 sits at the end of segment 2, and g is live across the segment-1 barrier as it is with a V tile in flight.)
   // Static priority for the late half.  The stamps of the d = 256 forward (profiles/r4u_attention_forward_stamps.txt): waves 4..7
   // — dispatched second, the losers of the SIMD's age-ordered issue arbitration — spend 5.65 k cycles of a tile working and
   // 0.5 k at barriers, waves 0..3 4.4 k and 2.1 k: the older half waits for the younger at both barriers of every tile.
@@ -728,7 +746,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
         if (kt + 2 < nkt) fetch_to(Ar, kt + 2, g);            // a whole tile before its commit
       }
     } else {
-      if (more) { commitA(nxt); fetch(Br, kt + 1); }
+      if (more) { commitA(nxt); if constexpr (!KV_SAME) fetch(Br, kt + 1); }     // (KV_SAME: g keeps tile kt + 1 for commitB below)
     }
     __syncthreads();
     pointwise(kt);
@@ -766,9 +784,10 @@ int launch_dt(const CsnAttnArgs& a, bool bwd, hipStream_t st) {
             hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 1>), grid, dim3(512), 0, st, a);
           else return -1;
         } else if (a.sc_tiles == 3) {                               // kept scores, no planes at all: dQ and delta alone
-          if constexpr (csn_attn_dv_scores_fits(PR::NT == 3 ? 1 : 2, 32 * DT))
-            hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 2>), grid, dim3(512), 0, st, a);
-          else return -1;
+          if constexpr (csn_attn_dv_scores_fits(PR::NT == 3 ? 1 : 2, 32 * DT)) {
+            if (a.kv_same) hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 2, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 2>), grid, dim3(512), 0, st, a);
+          } else return -1;
         } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true>), grid, dim3(512), 0, st, a);
       } else return -1;                                             // fp16: forward only (gradients underflow fp16)
     } else hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, false, true>), grid, dim3(512), 0, st, a);
@@ -820,6 +839,9 @@ int launch_mode(const CsnAttnArgs& a, int d, int mode, bool bwd, hipStream_t st)
 }
 
 }  // namespace
+
+// development switch (csn_dev_set): 1 = the no-planes backward may take its KV_SAME instance where k == v
+int csn_dev_kv_same = 1;
 
 int csn_launch_attn_fwd_bf16x3(const CsnAttnArgs& a, int d, int mode, hipStream_t st) {
   return launch_mode(a, d, mode, false, st);

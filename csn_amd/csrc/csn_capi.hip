@@ -128,6 +128,7 @@ int csn_dev_get(int key) {
     case CSN_DEV_WX: return csn_dev_wx;
     case CSN_DEV_LNB_GROUP: return csn_dev_lnb_group;
     case CSN_DEV_SCONV_NB: return csn_dev_sconv_nb;
+    case CSN_DEV_KV_SAME: return csn_dev_kv_same;
     default: return CSN_E_ARG;
   }
 }
@@ -145,6 +146,10 @@ int csn_dev_set(int key, int value) {
     case CSN_DEV_SCONV_NB:
       if (value < 0 || value > 4) return CSN_E_ARG;
       csn_dev_sconv_nb = value;
+      break;
+    case CSN_DEV_KV_SAME:
+      if (value != 0 && value != 1) return CSN_E_ARG;
+      csn_dev_kv_same = value;
       break;
     default: return CSN_E_ARG;
   }
@@ -498,7 +503,8 @@ static int attn_bwd_dq_impl(const float* dctx, const float* ctx, long long ctx_e
   // (recomputed scores with probs_tiles == 0: nothing is read from or written to scores / dscores — they may be NULL)
   // (recomputed scores in the one-plane mode: P and dS both travel in dscores, `scores` is never touched)
   const bool need_sc = !q || (probs_tiles && mode() == 1), need_ds = (!q || probs_tiles) && probs_tiles != 3;
-  if (!dctx || !ctx || !k || !v || !lse || !delta || !dq || (need_sc && !scores) || (need_ds && !dscores)) return CSN_E_ARG;
+  // (delta is an OUTPUT nobody has to want: NULL with probs_tiles == 3, where no dK / dV product follows that would read it)
+  if (!dctx || !ctx || !k || !v || !lse || (!delta && probs_tiles != 3) || !dq || (need_sc && !scores) || (need_ds && !dscores)) return CSN_E_ARG;
   if (n_launch_evals <= 0 || n_heads <= 0 || block <= 0 || n_blocks <= 0) return CSN_E_ARG;
   if (!dim_ok(d_head)) return CSN_E_DIM;
   if ((ld & 3) || (score_pitch & 3) || score_pitch < (block + 3) / 4 * 4) return CSN_E_ALIGN;
@@ -524,6 +530,8 @@ static int attn_bwd_dq_impl(const float* dctx, const float* ctx, long long ctx_e
   a.r_planes = 0; a.kv_planes = kv_split != 0; a.r_plane_stride = 0; a.kv_plane_stride = 0; a.kv_ld = (int)kv_plane_stride;
   a.kv_f16 = kv_split == 2;
   a.sc_tiles = probs_tiles;
+  // keys and values are the same tile planes (folded projections; one stride and one pitch describe both): one request per tile
+  if (kv_split == 1 && k == v && mode() == 1 && d_head == 256 && probs_tiles == 3) a.kv_same = csn_dev_kv_same;
   a.tq_arr = tq_arr; a.t_arr = t_arr;
   a.q2 = q; a.q2_shape_stride = q_shape_stride; a.q2_index = q_index;
   if (t_score_layout) {                                              // tile-major scores in, tile-major P / dS planes out

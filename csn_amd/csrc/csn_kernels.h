@@ -121,7 +121,11 @@ struct CsnAttnArgs {
   // [key tile kt][query][32 keys] (the 128 bytes of a query's tile, fp32 scores or [hi 32 | lo 32] planes): what a wave stores
   // or loads per instruction is then one contiguous run instead of sixteen 64-byte pieces 2 KB apart
   int sc_layout = 0;
+  // backward, sc_tiles == 3: k and v are the same tile planes (folded projections; bf16x3, d = 256) — every tile is fetched
+  // once and committed into both LDS images (attn_bf16x3.hip KV_SAME).  Set by the C-ABI entry point alone
+  int kv_same = 0;
 };
+extern int csn_dev_kv_same;                              // development switch (csn_dev_set): 1 = the entry point may set it
 // score recomputation needs three LDS tile images per stage: one plane at every width, two planes up to d = 128
 // (a two-plane d = 256 instance with its third image laid over the second — a timing build with wrong results — was measured
 //  in round 4: 167 spilled registers, 7.2 -> 24.7 ms; profiles/r4r_recompute_d256_experiment.txt; removed with its switch)

@@ -677,7 +677,7 @@ class _MHAEvals(torch.autograd.Function):
             # query slot is the gradient of Q'' = M x, so dM is the 256-row weight gradient over (G, x) — no dK / dV products, no
             # dscores, no 3 D-row gradient map.  (grouped_dq off: the same call colour by colour — the switch selects how dQ is
             # accumulated, as in the unfolded step, not whether the step folds)
-            delta = torch.empty((E, H, geo.n_padded), device=dev, dtype=torch.float32)
+            # (delta, the row constant of the softmax backward, stays in the kernel's registers: nothing reads the map here)
             g = torch.empty((S, D, NP), device=dev, dtype=torch.float32)
             if plan.q_ranges is None and plan.q_unwritten.numel():
                 g.index_fill_(0, plan.q_unwritten, 0.0)
@@ -686,13 +686,14 @@ class _MHAEvals(torch.autograd.Function):
                 launches = [(0, plan.q_group_items, E, plan.q_group_off, plan.n_q_groups)]
             else:
                 launches = [(0 if ci == 0 else 1, ids, ids.numel(), None, 0) for ci, ids in enumerate(plan.dq_colors)]
+            L.csn_dev_set(_lib.DEV_KV_SAME, int(bool(ctx.tune.kv_same)))     # (process-wide, like the switches themselves)
             for accumulate, ids, n_ids, off, n_groups in launches:
                 _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, _ptr(kv), _ptr(kv), kv_stride,
-                                                       _ptr(plan.kv_slots), NP, _ptr(scores), None, _ptr(lse), _ptr(delta),
+                                                       _ptr(plan.kv_slots), NP, _ptr(scores), None, _ptr(lse), None,
                                                        _ptr(g), D * NP, _ptr(plan.q_slots), accumulate, _ptr(ids), n_ids, H, d, T,
                                                        nb, Tp, p_attn, seed_attn, 0, 0, kv_flag, kv_pitch, 3, _ptr(off), n_groups,
                                                        _stream()), "csn_block_attn_bwd_dq_f32")
-            del delta, datt
+            del datt
             if plan.q_ranges is None:
                 d_m = project_wgrad(g, x_all)                           # dM = sum_slots G x^T
             else:                                                       # ... over the query slots of the plan's ranges only

@@ -62,6 +62,10 @@ class Tuning:
     # so it would ignore them silently) asks for the unfolded step — whatever value it gives the switch: an A/B of such a switch
     # (scripts/ab_step.py, tests/test_gpu_dv_scores.py::test_module_step_with_dv_from_scores) keeps measuring the launches it names
     folded_projections: bool = True
+    # the folded step's dQ kernel (k = v = the planes of x) requests every 32-key tile ONCE and commits the same registers into
+    # both LDS images, instead of once per image (attn_bf16x3.hip KV_SAME; the library's key CSN_DEV_KV_SAME, set before the
+    # launch).  The same LDS contents, the same bits (tests/test_gpu_kv_same.py); timing: profiles/folded_tiles_ab_step.txt
+    kv_same: bool = True
     named: frozenset = frozenset()   # the switches the enclosing override blocks name (kept by ``override``; not a switch itself)
     # attention backward data flow by (math mode of the backward: 1 bf16x3, 2 bf16 — fp16 forwards run their backward in 2;
     # head width), or by mode alone; taken where the kernels have an instance for it (csn_attn_bwd_grouping bits 2 / 3),

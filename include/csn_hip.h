@@ -249,7 +249,10 @@ CSN_API int csn_block_attn_fwd_grouped_f32(const float* q, const float* k, const
  * probs_tiles == 3 (csn_block_attn_bwd_dq_f32 only; the conditions of probs_tiles = 2, where
  * csn_attn_bwd_dq_no_planes_available says so): NOTHING score-sized is written — `scores` is read-only, `dscores` is not used and
  * may be NULL; dq and delta are bit for bit those of probs_tiles = 2.  For callers with no dK / dV products behind the call
- * (folded projections, (1b): k = v = the input's planes).  probs_tiles takes the values 0 .. 3; anything else is CSN_E_ARG.
+ * (folded projections, (1b): k = v = the input's planes) — such a caller has no reader for `delta` either, which may be NULL
+ * with this value alone.  probs_tiles takes the values 0 .. 3; anything else is CSN_E_ARG.
+ * With k == v there (mode 1, d_head = 256) the dq call fetches every key tile once for both of its tile images instead of once
+ * per image — the same bits (CSN_DEV_KV_SAME, development section).
  * GROUPED calls (group_offsets != NULL): eval_ids lists the n_launch_evals evaluations ordered so that evaluations sharing
  * an output slot are adjacent, group g = entries group_offsets[g] .. group_offsets[g+1] (n_groups + 1 offsets); a group's
  * results are accumulated in registers and its slot is written once — one call for all evaluations instead of one
@@ -1301,6 +1304,8 @@ CSN_API int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void
 /* (key 6 was the output-stationary dV / dK stream of round 5: the GEMM route is as fast over the step; profiles/r5_dkv_stream.txt) */
 #define CSN_DEV_SCONV_NB 7  /* default 0: csn_sparse_conv_* choose the 32-column blocks a wave owns by their launch rule; 1..4 pins
                                them (capped at c / 32) so that every kernel instance can be reached at any size — the same sums */
+#define CSN_DEV_KV_SAME 8   /* default 1: csn_block_attn_bwd_dq_f32 with probs_tiles = 3 and k == v (bf16x3, d_head = 256) requests
+                               every key tile once for both LDS images (0: once per image) — the same bits.  Other values: CSN_E_ARG */
 CSN_API int csn_dev_set(int key, int value);
 CSN_API int csn_dev_get(int key);
 
