@@ -55,7 +55,8 @@ class Tuning:
     # (csn_tile_planes_f32), and the backward is ONE dQ call that writes nothing score-sized (probs_tiles = 3) plus two 256-row
     # weight gradients, unfolded to dW_q, dW_k, dW_v, dW_fc by csn_unfold_wgrads_f32.  K, V, dK, dV, dscores and their launches do not
     # exist.  Unlike its neighbours this re-associates products: results move by fp32 / bf16x3 rounding (both forms measured against
-    # a float64 restatement: DESIGN.md §2 "Folded projections"; tests/test_gpu_folded.py).  The dropout masks are the same bits.  Where
+    # a float64 restatement: DESIGN.md §2 "Folded projections"; tests/test_gpu_folded.py for the kernels and the default step,
+    # tests/test_gpu_folded_plans.py for every plan, live switch and block edge).  The dropout masks are the same bits.  Where
     # any condition fails the unfolded calls run and give their bits.  The decision never looks at the grad mode.
     # One more condition lives here: an ``override`` block that NAMES a switch which exists only in the unfolded step
     # (UNFOLDED_ONLY: dv_from_scores, grouped_dkv, qkv_one_pass — the folded step has no dV / dK product and no K | V projection,

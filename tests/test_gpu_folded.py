@@ -274,23 +274,28 @@ def test_fold_and_unfold_are_exact_fp32_in_every_mode(L):
 
 
 # ---- 4. the module step, folded against unfolded, both against float64 ------------------------------------------------------
-def _masked_oracle(p, x, nb, lab, dtype, T, n_blocks, B, K, seeds, p_drop):
+def _masked_oracle(p, x, nb, lab, dtype, T, n_blocks, B, K, seeds, p_drop, masks=None, evals_of=None):
     """orc.forward_csa in `dtype` with an mha that applies the step's own masks (tests/dropout_ref.py) — evaluation numbering of
-    MultiHeadAttention.plan("csa_train") / ("csa"); seeds None: eval mode"""
+    MultiHeadAttention.plan("csa_train") / ("csa"); seeds None: eval mode.
+    masks = (attention mask [e][blk][query][key], fc mask [e][c][n]) together with evals_of(call) -> the B evaluations of the
+    oracle's call-th mha call (pooled self, neighbour self k = 1..K, mixed self, mixed cross k = 1..K): a step that numbers its
+    evaluations otherwise or draws several seed pairs (the two-phase step, tests/test_gpu_folded_plans.py)"""
     K1 = K + 1
     E1, E2 = B * K1, B * K
     N = x.shape[2]
     C = x.shape[1]
     Tp = (T + 31) // 32 * 32
-    train = seeds is not None
+    train = seeds is not None or masks is not None
     E = E1 + E2 + (B if train else 0)
-    if train:
+    if masks is not None:
+        am, fm = masks
+    elif train:
         am = torch.from_numpy(dr.attention_mask(E, 1, n_blocks, T, Tp, seeds[0], p_drop))[:, 0].transpose(-1, -2)   # [e][blk][query][key]
         fm = torch.from_numpy(dr.fc_mask(E, C, N, seeds[1], p_drop))                                                  # [e][c][n]
     q = {k_: v_.to(dtype).clone().requires_grad_(True) for k_, v_ in p.items()}
     calls = []
 
-    def evals_of(call):
+    def plan_evals_of(call):
         # csa_feats: pooled self, neighbour self k = 1..K, mixed self, mixed cross k = 1..K
         if call == 0:
             return [E1 + E2 + b if train else b * K1 for b in range(B)]
@@ -298,6 +303,8 @@ def _masked_oracle(p, x, nb, lab, dtype, T, n_blocks, B, K, seeds, p_drop):
             return [E1 + b * K + call - 1 for b in range(B)]
         k_ = call - K - 1
         return [b * K1 + k_ for b in range(B)]
+
+    evals_of = evals_of or plan_evals_of
 
     def mha(xq, xk, xv, prm, n_head, **kw):
         ev = evals_of(len(calls))

@@ -60,8 +60,16 @@ def test_entry_point_gives_the_ungrouped_calls_bits(L, T, nb, ld, H, d, drop):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("N,nb,train", [(1500, 3, True), (1300, 3, True), (1000, 2, False)])
-def test_training_step_is_bitwise_the_same_grouped_and_ungrouped(L, N, nb, train):
+STEP_CASES = [(1500, 3, True), (1300, 3, True), (1000, 2, False)]
+# with folded projections (the default: the ids these cases always had) and as the unfolded chain
+STEP_CASES = [pytest.param(*c, fold, id="-".join(map(str, c)) + ("" if fold else "-unfolded"))
+              for c in STEP_CASES for fold in (True, False)]
+
+
+@pytest.mark.parametrize("N,nb,train,fold", STEP_CASES)
+def test_training_step_is_bitwise_the_same_grouped_and_ungrouped(L, N, nb, train, fold):
+    """fold: tuning.folded_projections around the step — in bf16x3 the folded step (the forward on the planes of x) and the unfolded
+    chain (K / V planes, dK / dV launches) each; bf16 never folds, whatever the switch says."""
     from csn_amd import tuning
     from csn_amd.csa_models import get_model
     from oracle import csa_oracle as orc
@@ -74,14 +82,24 @@ def test_training_step_is_bitwise_the_same_grouped_and_ungrouped(L, N, nb, train
     x = nbf[:, 0].contiguous()
     lab = torch.from_numpy(rng.integers(0, n_cls, size=(B, N))).cuda()
     outs = []
+    folds = fold and L.lib().csn_get_math_mode() == 1
     for grouped in (False, True):
-        with tuning.override(grouped_fwd=grouped):
-            for prm in model.parameters():
-                prm.grad = None
-            torch.manual_seed(5)
-            logits = model(x, "train", nbf)
-            orc.masked_ce_loss(logits, lab).backward()
-            outs.append((logits.detach().clone(), [p.grad.clone() for p in model.parameters() if p.grad is not None]))
+        calls = []
+        L.set_call_hook(lambda name, phase: calls.append(name) if phase == "begin" else None)
+        try:
+            with tuning.override(folded_projections=fold), tuning.override(grouped_fwd=grouped):
+                for prm in model.parameters():
+                    prm.grad = None
+                torch.manual_seed(5)
+                logits = model(x, "train", nbf)
+                orc.masked_ce_loss(logits, lab).backward()
+                outs.append((logits.detach().clone(), [p.grad.clone() for p in model.parameters() if p.grad is not None]))
+        finally:
+            L.set_call_hook(None)
+        # the intended form ran, with the intended forward
+        assert ("csn_tile_planes_f32" in calls) == ("csn_unfold_wgrads_f32" in calls) == ("csn_fold_weights_f32" in calls) == folds
+        assert ("csn_block_attn_bwd_dkv_f32" in calls) == (not folds)
+        assert ("csn_block_attn_fwd_grouped_f32" in calls) == grouped and ("csn_block_attn_fwd_f32" in calls) == (not grouped)
     assert torch.isfinite(outs[0][0]).all() and len(outs[0][1]) == 11
     assert torch.equal(outs[0][0], outs[1][0])
     for a, b in zip(outs[0][1], outs[1][1]):

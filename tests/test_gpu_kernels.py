@@ -775,7 +775,15 @@ def test_sixteen_wave_gemm_equals_the_eight_wave_one(L, mode, S, C, N, R, div_ro
 
 def test_sixteen_wave_forms_leave_the_step_bit_for_bit(L):
     """The whole module step in bf16x3 with the 16-wave GEMM forms (plain, grouped tile-plane dV / dK, weight gradients) against
-    the 8-wave kernel: logits and all 11 gradients bit for bit (same slabs, same products, same order; train mode, same masks)."""
+    the 8-wave kernel: logits and all 11 gradients bit for bit (same slabs, same products, same order; train mode, same masks).
+    Once with folded projections (tuning.folded_projections: the plain and weight-gradient forms) and once as the unfolded chain,
+    the only step that runs the grouped tile-plane dV / dK products."""
+    for fold in (True, False):
+        _sixteen_wave_step(L, fold)
+
+
+def _sixteen_wave_step(L, fold):
+    from csn_amd import tuning
     from csn_amd.csa_models import get_model
     from oracle import csa_oracle as orc
     lib = L.lib()
@@ -795,10 +803,17 @@ def test_sixteen_wave_forms_leave_the_step_bit_for_bit(L):
             for prm in model.parameters():
                 prm.grad = None
             torch.manual_seed(4)
-            logits = model(x, "train", nbf)
-            orc.masked_ce_loss(logits, lab).backward()
+            calls = []
+            L.set_call_hook(lambda name, phase: calls.append(name) if phase == "begin" else None)
+            with tuning.override(folded_projections=fold):
+                logits = model(x, "train", nbf)
+                orc.masked_ce_loss(logits, lab).backward()
+            L.set_call_hook(None)
+            assert ("csn_tile_planes_f32" in calls) == ("csn_unfold_wgrads_f32" in calls) == fold
+            assert ("csn_block_attn_bwd_dkv_f32" in calls) == (not fold)
             outs.append((logits.detach().clone(), [p.grad.clone() for p in model.parameters() if p.grad is not None]))
     finally:
+        L.set_call_hook(None)
         lib.csn_dev_set(L.DEV_WIDE_FORMS, 7)
         lib.csn_dev_set(L.DEV_WX, L.DEV_WX_DEFAULT)
     assert torch.equal(outs[0][0], outs[1][0]) and len(outs[0][1]) == 11

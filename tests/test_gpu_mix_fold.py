@@ -5,7 +5,11 @@ Shapes: C = d = 256, one head, B = 2, K = 2 (train plan: 6 mixed + 4 + 2 pooled 
   N = 132 in one block   — four 32-point chunks and a 4-point tail chunk per evaluation, one chunk per stream;
   N = 2000 in 4 blocks   — 63 chunks per evaluation, an odd count: with two chunks per stream a run crosses from one
                             evaluation into the next and has to flush its partial sums in the middle.
-Each with fc / attention dropout 0.1 and 0.  bf16x3 only (the fused kernel exists in that mode alone)."""
+Each with fc / attention dropout 0.1 and 0.  bf16x3 only (the fused kernel exists in that mode alone).
+
+Every test that goes through the module runs twice: with folded projections (tuning.folded_projections — W_fv^T travels through
+the link into the mix's LayerNorm backward) and with the unfolded chain (W_fc^T formed in the backward, the dK / dV launches);
+the call hook says which form ran."""
 import numpy as np
 import pytest
 import torch
@@ -19,6 +23,12 @@ SHAPES = {132: (132, 1), 2000: (500, 4)}                # n_points -> (block, n_
 CASES = [(n, p) for n in SHAPES for p in (0.1, 0.0)]
 IDS = [f"N{n}-p{p}" for n, p in CASES]
 TOL = 2e-4                                              # of tests/test_gpu_module.py::test_fused_data_flow_equals_the_unfused_one
+
+
+def _with_fold(cases, ids):
+    """every case with folded projections (the default: the id the case always had) and as the unfolded chain"""
+    return [pytest.param(*(c if isinstance(c, tuple) else (c,)), fold, id=i + ("" if fold else "-unfolded"))
+            for c, i in zip(cases, ids) for fold in (True, False)]
 
 
 @pytest.fixture(autouse=True)
@@ -89,23 +99,30 @@ def _train_step(m, x, nb, lab):
     return logits.detach(), loss.item(), {k: q.grad.clone() for k, q in m.named_parameters() if q.grad is not None}
 
 
-def _run(data, n, drop, fused):
+def _ran_form(names, fold):
+    """the call names of a step say which form ran: folded projections, or the unfolded chain with its dK / dV launches"""
+    assert ("csn_tile_planes_f32" in names) == ("csn_unfold_wgrads_f32" in names) == ("csn_fold_weights_f32" in names) == fold
+    assert ("csn_block_attn_bwd_dkv_f32" in names) == (not fold)
+
+
+def _run(data, n, drop, fused, fold):
     from csn_amd import tuning
     p, x, nb, lab = data[n]
     m = _model(p, n, drop)
     torch.manual_seed(11)                               # the dropout masks' seeds come from torch's CPU generator
-    with tuning.override(fused_mix_bwd=fused), _Calls() as calls:
+    with tuning.override(folded_projections=fold), tuning.override(fused_mix_bwd=fused), _Calls() as calls:
         out = _train_step(m, x.cuda(), nb.cuda().contiguous(), lab.cuda())
+    _ran_form(calls.names, fold)
     return out + (calls.names,)
 
 
-@pytest.mark.parametrize("n,drop", CASES, ids=IDS)
-def test_train_step_with_the_fold_equals_the_step_without(data, n, drop):
+@pytest.mark.parametrize("n,drop,fold", _with_fold(CASES, IDS))
+def test_train_step_with_the_fold_equals_the_step_without(data, n, drop, fold):
     """Switch on against off on the same masks: the separate pass is gone, the forward is untouched, all 11 gradients agree
     within the tolerance the data-flow switches are held to; two runs with the switch on give the same bits."""
-    l_on, s_on, g_on, c_on = _run(data, n, drop, True)
-    l_on2, s_on2, g_on2, _ = _run(data, n, drop, True)
-    l_off, s_off, g_off, c_off = _run(data, n, drop, False)
+    l_on, s_on, g_on, c_on = _run(data, n, drop, True, fold)
+    l_on2, s_on2, g_on2, _ = _run(data, n, drop, True, fold)
+    l_off, s_off, g_off, c_off = _run(data, n, drop, False, fold)
     assert "csn_outproj_lnb_f32" in c_on and "csn_mix_bwd_f32" not in c_on and "csn_outproj_ln_bwd_f32" not in c_on
     assert "csn_mix_bwd_f32" in c_off and "csn_outproj_ln_bwd_f32" in c_off and "csn_outproj_lnb_f32" not in c_off
     assert torch.equal(l_on, l_off) and s_on == s_off
@@ -117,13 +134,13 @@ def test_train_step_with_the_fold_equals_the_step_without(data, n, drop):
         assert err <= TOL * scale + 1e-9, k
 
 
-@pytest.mark.parametrize("n", list(SHAPES), ids=[f"N{n}" for n in SHAPES])
-def test_train_plan_without_dropout_holds_the_1e4_contract_against_float64(data, n):
+@pytest.mark.parametrize("n,fold", _with_fold(list(SHAPES), [f"N{n}" for n in SHAPES]))
+def test_train_plan_without_dropout_holds_the_1e4_contract_against_float64(data, n, fold):
     """At rate 0 the train plan computes what the reference computes: logits, loss and the 11 gradients against the float64
     oracle, with the fold on."""
     p, x, nb, lab = data[n]
     block, n_blocks = SHAPES[n]
-    logits, loss, grads, calls = _run(data, n, 0.0, True)
+    logits, loss, grads, calls = _run(data, n, 0.0, True, fold)
     assert "csn_outproj_lnb_f32" in calls
     p64 = {k: v.double().requires_grad_(True) for k, v in p.items()}
     ref = orc.forward_csa(x.double(), nb.double(), p64, H, block=block, n_blocks=n_blocks)
@@ -203,16 +220,23 @@ def test_pieces_of_the_layernorm_backward_give_the_bits_of_the_one_call(n, drop)
 
 def test_eval_mode_with_gradients_keeps_the_unfolded_backward(data):
     """Eval mode, plan "csa": the k = 0 evaluation is mixed and pooled, so the old path runs whatever the switch says — same
-    calls, same bits."""
+    calls, same bits.  ("unfolded" in the name: the mix backward is not folded into the LayerNorm backward; the projections fold
+    or not as ``fold`` says, once each)"""
+    for fold in (True, False):
+        _eval_mode_with_gradients(data, fold)
+
+
+def _eval_mode_with_gradients(data, fold):
     from csn_amd import tuning
     p, x, nb, lab = data[132]
     outs = []
     for fused in (True, False):
         m = _model(p, 132, 0.1, train=False)
-        with tuning.override(fused_mix_bwd=fused), _Calls() as calls:
+        with tuning.override(folded_projections=fold), tuning.override(fused_mix_bwd=fused), _Calls() as calls:
             logits = m(x.cuda(), "test", nb.cuda().contiguous())
             orc.masked_ce_loss(logits, lab.cuda()).backward()
             torch.cuda.synchronize()
+        _ran_form(calls.names, fold)
         assert "csn_mix_bwd_f32" in calls.names and "csn_outproj_lnb_f32" not in calls.names
         outs.append((logits.detach(), {k: q.grad.clone() for k, q in m.named_parameters() if q.grad is not None}))
     assert torch.equal(outs[0][0], outs[1][0]) and len(outs[0][1]) == 11
@@ -253,6 +277,7 @@ def test_functional_gradients_with_fixed_upstream_gradients(data, dense_too):
             torch.cuda.synchronize()
         assert ("csn_outproj_lnb_f32" in calls.names) == fused
         assert ("csn_outproj_ln_bwd_f32" in calls.names) == (dense_too or not fused)
+        _ran_form(calls.names, False)                   # (input gradients wanted: the projections are never folded here)
         g = {k: q.grad.clone() for k, q in att.named_parameters() if q.grad is not None}
         g["x_all"], g["comp"] = x_all.grad.clone(), comp.grad.clone()
         outs.append(g)

@@ -29,8 +29,16 @@ def test_capability_bit_and_flag_validation(L):
         L.check(lib.csn_set_math_mode(1))
 
 
-@pytest.mark.parametrize("N,nb,train", [(1500, 3, True), (1300, 3, True), (1000, 2, False)])
-def test_training_step_is_bitwise_the_same_in_both_layouts(L, N, nb, train):
+STEP_CASES = [(1500, 3, True), (1300, 3, True), (1000, 2, False)]
+# with folded projections (the default: the ids these cases always had) and as the unfolded chain
+STEP_CASES = [pytest.param(*c, fold, id="-".join(map(str, c)) + ("" if fold else "-unfolded"))
+              for c in STEP_CASES for fold in (True, False)]
+
+
+@pytest.mark.parametrize("N,nb,train,fold", STEP_CASES)
+def test_training_step_is_bitwise_the_same_in_both_layouts(L, N, nb, train, fold):
+    """fold: the step with folded projections (tuning.folded_projections: the forward's scores and the one dQ call take the layout)
+    and the unfolded step (the tile-major P / dS planes, the dK product on them, dV from the scores in tile-major layout)."""
     from csn_amd import tuning
     from csn_amd.csa_models import get_model
     from oracle import csa_oracle as orc
@@ -44,13 +52,29 @@ def test_training_step_is_bitwise_the_same_in_both_layouts(L, N, nb, train):
     lab = torch.from_numpy(rng.integers(0, n_cls, size=(B, N))).cuda()
     outs = []
     for tm in (False, True):
-        with tuning.override(tile_major_scores=tm):
-            for prm in model.parameters():
-                prm.grad = None
-            torch.manual_seed(5)
-            logits = model(x, "train", nbf)
-            orc.masked_ce_loss(logits, lab).backward()
-            outs.append((logits.detach().clone(), [p.grad.clone() for p in model.parameters() if p.grad is not None]))
+        calls, layouts = [], set()
+
+        def hook(name, phase):
+            if phase == "begin":
+                calls.append(name)
+                if name == "csn_block_attn_bwd_dq_f32":
+                    layouts.add(L.lib().csn_get_thread_score_layout())
+
+        L.set_call_hook(hook)
+        try:
+            with tuning.override(folded_projections=fold), tuning.override(tile_major_scores=tm):
+                for prm in model.parameters():
+                    prm.grad = None
+                torch.manual_seed(5)
+                logits = model(x, "train", nbf)
+                orc.masked_ce_loss(logits, lab).backward()
+                outs.append((logits.detach().clone(), [p.grad.clone() for p in model.parameters() if p.grad is not None]))
+        finally:
+            L.set_call_hook(None)
+        # the intended form ran, in the intended layout
+        assert ("csn_tile_planes_f32" in calls) == ("csn_unfold_wgrads_f32" in calls) == fold
+        assert ("csn_block_attn_bwd_dkv_f32" in calls) == (not fold) and not (fold and "csn_block_attn_bwd_dv_scores_f32" in calls)
+        assert layouts == {int(tm)}
     assert torch.isfinite(outs[0][0]).all() and len(outs[0][1]) == 11
     assert torch.equal(outs[0][0], outs[1][0])
     for a, b in zip(outs[0][1], outs[1][1]):
