@@ -1423,6 +1423,12 @@ static int sparse_conv_dims(int n_in, int n_out, int kv, int c_in, int c_out) {
   if (c_in < 32 || c_in > 256 || (c_in & 31) || c_out < 32 || c_out > 256 || (c_out & 31)) return CSN_E_DIM;
   return 0;
 }
+// (21) the sizes of an octant convolution (the two row counts in either order)
+static int octant_dims(int n_fine, int n_coarse, int c_in, int c_out) {
+  if (n_fine <= 0 || n_coarse <= 0) return CSN_E_ARG;
+  if (c_in < 32 || c_in > 256 || (c_in & 31) || c_out < 32 || c_out > 256 || (c_out & 31)) return CSN_E_DIM;
+  return 0;
+}
 // a row-major map of n rows: pitch % 4, >= its width, and the whole map inside one 2 GiB buffer window
 static int sparse_conv_map(long long ld, int width, int n) {
   if (ld < width) return CSN_E_ARG;
@@ -1430,6 +1436,16 @@ static int sparse_conv_map(long long ld, int width, int n) {
   if (ld > (1 << 20) || (long long)n * ld * 4 > 0x7fffffffLL) return CSN_E_DIM;
   return 0;
 }
+// a 16-bit row-major map of n rows (sections 24, 25, 28): pitch % 8, >= its width, and the whole map inside one 2 GiB buffer window
+static int sparse_conv_map16(long long ld, int width, int n) {
+  if (ld < width) return CSN_E_ARG;
+  if (ld & 7) return CSN_E_ALIGN;
+  if (ld > (1 << 20) || (long long)n * ld * 2 > 0x7fffffffLL) return CSN_E_DIM;
+  return 0;
+}
+// a map beside its type flag: fp32 rows (0) or 16-bit rows (1), each by its own rule
+static int map_of(int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); }
+static bool off4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
 long long csn_sparse_conv_workspace_bytes(int n_in, int n_out, int kv, int c_in, int c_out, int backward) {
   if (sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return 0;
@@ -1442,7 +1458,7 @@ int csn_sparse_conv_fwd_f32(const float* x, long long ld_x, int n_in, const int*
   if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
   if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
   if (const int e = sparse_conv_map(ld_y, c_out, n_out)) return e;
-  if (mis16(x) || mis16(w) || mis16(y) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (mis16(x) || mis16(w) || mis16(y) || off4(table)) return CSN_E_PTR;
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
@@ -1462,7 +1478,7 @@ int csn_sparse_conv_bwd_f32(const float* dy, long long ld_dy, const float* x, lo
   if (dw) if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
   if (dx) if (const int e = sparse_conv_map(ld_dx, c_in, n_in)) return e;
   if (mis16(dy) || mis16(ws) || (dx && (mis16(dx) || mis16(w))) || (dw && (mis16(dw) || mis16(x)))) return CSN_E_PTR;
-  if ((reinterpret_cast<uintptr_t>(fwd_table) & 3) || (reinterpret_cast<uintptr_t>(bwd_table) & 3)) return CSN_E_PTR;
+  if (off4(fwd_table) || off4(bwd_table)) return CSN_E_PTR;
   if (ws_bytes < csn_sparse_conv_ws_bytes(n_in, n_out, kv, c_in, c_out, 1)) return CSN_E_WORKSPACE;
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = fwd_table; a.bwd_table = bwd_table; a.n_out = n_out; a.kv = kv;
@@ -1481,25 +1497,27 @@ long long csn_sparse_conv_stats_workspace_bytes(int n_out, int c_out) {
 static int groups_args(const int* group_rows, int n_groups) {
   if (!group_rows || n_groups < 1) return CSN_E_ARG;
   if (n_groups > 8) return CSN_E_DIM;
-  if (reinterpret_cast<uintptr_t>(group_rows) & 3) return CSN_E_PTR;
+  if (off4(group_rows)) return CSN_E_PTR;
   return 0;
 }
 
-static int sparse_conv_stats_fwd_impl(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
-                                      const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
+// x16 (section 28, never with groups): x is bf16 rows, gathered as they lie by a launcher of their own
+static int sparse_conv_stats_fwd_impl(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
+                                      int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
                                       float* running_var, float eps, float momentum, bool grouped, const int* group_rows, int n_groups,
                                       void* ws, long long ws_bytes, void* stream) {
   if (!x || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
   if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
-  if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
+  if (const int e = map_of(x16, ld_x, c_in, n_in)) return e;
   if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
-  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || off4(table)) return CSN_E_PTR;
   if (n_out < 2 * (grouped ? n_groups : 1)) return CSN_E_ARG;    // every batch needs two rows: a one-row batch has no variance
   if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
   CsnSparseConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
-  a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  a.x = static_cast<const float*>(x); a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in;
+  a.c_out = c_out; a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  if (x16) return csn_launch_sparse_conv_stats_fwd_x16(a, mean, invstd, running_mean, running_var, eps, momentum, (hipStream_t)stream);
   return csn_launch_sparse_conv_stats_fwd(a, grouped ? group_rows : nullptr, n_groups, mean, invstd, running_mean, running_var, eps,
                                           momentum, rows_mode(), (hipStream_t)stream);
 }
@@ -1508,7 +1526,7 @@ int csn_sparse_conv_stats_fwd_f32(const float* x, long long ld_x, int n_in, cons
                                   int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
                                   float* running_mean, float* running_var, float eps, float momentum, void* ws, long long ws_bytes,
                                   void* stream) {
-  return sparse_conv_stats_fwd_impl(x, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
+  return sparse_conv_stats_fwd_impl(x, 0, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
                                     eps, momentum, false, nullptr, 0, ws, ws_bytes, stream);
 }
 
@@ -1523,84 +1541,116 @@ long long csn_rows_bn_act_workspace_bytes(int n_rows, int channels, int n_terms)
   return csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, 1);
 }
 
+// the terms of CsnBnTerms, checked term by term and copied into `a`: the forward needs beta, the backward takes dz / dgamma / dbeta
+static int bn_terms(CsnRowsBnActArgs& a, const CsnBnTerms* t, int n_terms, int n_rows, int channels, bool backward) {
+  for (int m = 0; m < n_terms; ++m) {
+    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m] || (!backward && !t->beta[m])) return CSN_E_ARG;
+    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
+    if (backward && t->dz[m]) if (const int e = sparse_conv_map(t->ld_dz[m], channels, n_rows)) return e;
+    if (mis16(t->z[m]) || (backward && t->dz[m] && mis16(t->dz[m]))) return CSN_E_PTR;
+    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
+    if (!backward) { a.beta[m] = t->beta[m]; continue; }
+    a.dz[m] = t->dz[m]; a.ld_dz[m] = (int)t->ld_dz[m]; a.dgamma[m] = t->dgamma[m]; a.dbeta[m] = t->dbeta[m];
+  }
+  return 0;
+}
+
+// r16 / y16: the type flags of r and y (1: bf16 rows); t16: the call of section 28, which has a launcher of its own whatever the flags say
 static int rows_bn_act_fwd_impl(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, bool grouped,
-                                const int* group_rows, int n_groups, const float* r, long long ld_r, int relu, float* y, long long ld_y,
-                                void* stream) {
+                                const int* group_rows, int n_groups, const void* r, int r16, long long ld_r, int relu, void* y, int y16,
+                                long long ld_y, void* stream, bool t16 = false) {
   if (!t || !y) return CSN_E_ARG;
   if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
   CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m] || !t->beta[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (mis16(t->z[m])) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.beta[m] = t->beta[m];
-  }
-  if (const int e = sparse_conv_map(ld_y, channels, n_rows)) return e;
-  if (r) if (const int e = sparse_conv_map(ld_r, channels, n_rows)) return e;
+  if (const int e = bn_terms(a, t, n_terms, n_rows, channels, false)) return e;
+  if (const int e = map_of(y16, ld_y, channels, n_rows)) return e;
+  if (r) if (const int e = map_of(r16, ld_r, channels, n_rows)) return e;
   if (mis16(y) || (r && mis16(r))) return CSN_E_PTR;
   a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
-  a.r = r; a.ld_r = (int)ld_r; a.y = y; a.ld_y = (int)ld_y;
+  a.r = static_cast<const float*>(r); a.ld_r = (int)ld_r; a.y = static_cast<float*>(y); a.ld_y = (int)ld_y;
+  if (t16) return csn_launch_rows_bn_act_fwd16(a, r16, y16, (hipStream_t)stream);
   return csn_launch_rows_bn_act_fwd(a, grouped ? group_rows : nullptr, n_groups, (hipStream_t)stream);
 }
 
 int csn_rows_bn_act_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, const float* r,
                             long long ld_r, int relu, float* y, long long ld_y, void* stream) {
-  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, r, ld_r, relu, y, ld_y, stream);
+  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, r, 0, ld_r, relu, y, 0, ld_y, stream);
 }
 
-static int rows_bn_act_bwd_impl(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
+// y16 (section 28, never with groups): y, the ReLU mask's operand, is bf16 rows, read by a launcher of their own
+static int rows_bn_act_bwd_impl(const float* dy, long long ld_dy, const void* y, int y16, long long ld_y, const CsnBnTerms* t, int n_terms,
                                 int n_rows, int channels, int training, float eps, bool grouped, const int* group_rows, int n_groups,
                                 int relu, float* dr, long long ld_dr, void* ws, long long ws_bytes, void* stream) {
   if (!dy || !t || !ws || (relu && !y)) return CSN_E_ARG;
   if (grouped) if (const int e = groups_args(group_rows, n_groups)) return e;
   if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
   CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (t->dz[m]) if (const int e = sparse_conv_map(t->ld_dz[m], channels, n_rows)) return e;
-    if (mis16(t->z[m]) || (t->dz[m] && mis16(t->dz[m]))) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.dz[m] = t->dz[m]; a.ld_dz[m] = (int)t->ld_dz[m]; a.dgamma[m] = t->dgamma[m]; a.dbeta[m] = t->dbeta[m];
-  }
+  if (const int e = bn_terms(a, t, n_terms, n_rows, channels, true)) return e;
   if (const int e = sparse_conv_map(ld_dy, channels, n_rows)) return e;
-  if (relu) if (const int e = sparse_conv_map(ld_y, channels, n_rows)) return e;
+  if (relu) if (const int e = map_of(y16, ld_y, channels, n_rows)) return e;
   if (dr) if (const int e = sparse_conv_map(ld_dr, channels, n_rows)) return e;
   if (mis16(dy) || mis16(ws) || (relu && mis16(y)) || (dr && mis16(dr))) return CSN_E_PTR;
   if (ws_bytes < csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, grouped ? n_groups : 1)) return CSN_E_WORKSPACE;
   a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
-  a.y = const_cast<float*>(y); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr; a.ws = ws;
+  a.y = static_cast<float*>(const_cast<void*>(y)); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr;
+  a.ws = ws;
+  if (y16) return csn_launch_rows_bn_act_bwd16(a, (hipStream_t)stream);
   return csn_launch_rows_bn_act_bwd(a, grouped ? group_rows : nullptr, n_groups, (hipStream_t)stream);
 }
 
 int csn_rows_bn_act_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
                             int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr, void* ws,
                             long long ws_bytes, void* stream) {
-  return rows_bn_act_bwd_impl(dy, ld_dy, y, ld_y, t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, relu, dr, ld_dr, ws,
+  return rows_bn_act_bwd_impl(dy, ld_dy, y, 0, ld_y, t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, relu, dr, ld_dr, ws,
                               ws_bytes, stream);
 }
 
 // ---- (19) the gather-GEMM with a BatchNorm + residual + ReLU epilogue (inference) ----
+// What the "convolution + BatchNorm epilogue" calls check alike: (19) and (23) on fp32 maps (every flag 0), (24) and (25) on maps
+// beside a type flag, behind the single-product gate (CONV_BN_M16).  CONV_BN_OCTANT: (21)'s sizes, kv is not read.  n_x: the rows of
+// x, n_y: those of y and r, in either order where octant_dims wants (n_fine, n_coarse): it treats the two counts alike.  The caller
+// refuses a NULL table before this and a misaligned one after it
+enum { CONV_BN_M16 = 1, CONV_BN_OCTANT = 2 };
+static int conv_bn_args(int form, const void* x, int x16, long long ld_x, int n_x, int n_y, int kv, int c_in, int c_out, const float* w,
+                        const float* gamma, const float* beta, const float* running_mean, const float* running_var, const void* r, int r16,
+                        long long ld_r, const void* y, int y16, long long ld_y) {
+  if (!x || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
+  if (form & CONV_BN_M16) {
+    if ((x16 | r16 | y16) & ~1) return CSN_E_ARG;
+    // single-product instances only: 16-bit maps under bf16x3 / fp32 would throw away what they pay for
+    if (mode() < 2 || !t_rows16) return CSN_E_ARG;
+  }
+  if (const int e = (form & CONV_BN_OCTANT) ? octant_dims(n_x, n_y, c_in, c_out) : sparse_conv_dims(n_x, n_y, kv, c_in, c_out)) return e;
+  if (const int e = map_of(x16, ld_x, c_in, n_x)) return e;
+  if (const int e = map_of(y16, ld_y, c_out, n_y)) return e;
+  if (r) if (const int e = map_of(r16, ld_r, c_out, n_y)) return e;
+  if (r == y && (r16 != y16 || ld_r != ld_y)) return CSN_E_ARG;   // y as its own residual: element for element, or not at all
+  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r))) return CSN_E_PTR;
+  return 0;
+}
+// the epilogue's vectors; the launches on 16-bit maps carry r in their own struct and pass none here
+static CsnSconvBnArgs sconv_bn(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                               const float* r, long long ld_r, int relu) {
+  CsnSconvBnArgs n{};
+  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
+  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
+  return n;
+}
+
 int csn_sparse_conv_bn_act_fwd_f32(const float* x, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in, int c_out,
                                    const float* w, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
                                    long long ld_y, void* stream) {
-  if (!x || !table || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
-  if (const int e = sparse_conv_map(ld_x, c_in, n_in)) return e;
-  if (const int e = sparse_conv_map(ld_y, c_out, n_out)) return e;
-  if (r) if (const int e = sparse_conv_map(ld_r, c_out, n_out)) return e;
-  if (r == y && ld_r != ld_y) return CSN_E_ARG;                   // y as its own residual: element for element, or not at all
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (!table) return CSN_E_ARG;
+  if (const int e = conv_bn_args(0, x, 0, ld_x, n_in, n_out, kv, c_in, c_out, w, gamma, beta, running_mean, running_var, r, 0, ld_r, y,
+                                 0, ld_y)) return e;
+  if (off4(table)) return CSN_E_PTR;
   CsnSparseConvArgs a{};
   a.x = x; a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.y = y; a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
-  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
-  return csn_launch_sparse_conv_bn_act_fwd(a, n, rows_mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_bn_act_fwd(a, sconv_bn(gamma, beta, running_mean, running_var, eps, r, ld_r, relu), rows_mode(),
+                                           (hipStream_t)stream);
 }
 
 // ---- (20) BatchNorm over row groups: the implementations of (15) with the batch per group, training mode ----
@@ -1613,7 +1663,7 @@ int csn_sparse_conv_stats_groups_fwd_f32(const float* x, long long ld_x, int n_i
                                          int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd,
                                          float* running_mean, float* running_var, float eps, float momentum, const int* group_rows,
                                          int n_groups, void* ws, long long ws_bytes, void* stream) {
-  return sparse_conv_stats_fwd_impl(x, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
+  return sparse_conv_stats_fwd_impl(x, 0, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
                                     eps, momentum, true, group_rows, n_groups, ws, ws_bytes, stream);
 }
 
@@ -1624,28 +1674,34 @@ long long csn_rows_bn_act_groups_workspace_bytes(int n_rows, int channels, int n
 
 int csn_rows_bn_act_groups_fwd_f32(const CsnBnTerms* t, int n_terms, int n_rows, int channels, const int* group_rows, int n_groups,
                                    const float* r, long long ld_r, int relu, float* y, long long ld_y, void* stream) {
-  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, r, ld_r, relu, y, ld_y, stream);
+  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, r, 0, ld_r, relu, y, 0, ld_y, stream);
 }
 
 int csn_rows_bn_act_groups_bwd_f32(const float* dy, long long ld_dy, const float* y, long long ld_y, const CsnBnTerms* t, int n_terms,
                                    int n_rows, int channels, const int* group_rows, int n_groups, int relu, float* dr, long long ld_dr,
                                    void* ws, long long ws_bytes, void* stream) {
-  return rows_bn_act_bwd_impl(dy, ld_dy, y, ld_y, t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, relu, dr, ld_dr, ws,
+  return rows_bn_act_bwd_impl(dy, ld_dy, y, 0, ld_y, t, n_terms, n_rows, channels, 1, 0.f, true, group_rows, n_groups, relu, dr, ld_dr, ws,
                               ws_bytes, stream);
 }
 
 // ---- (21) kernel-2 stride-2 convolution and its transposed form over an octant map ----
-static int octant_dims(int n_fine, int n_coarse, int c_in, int c_out) {
-  if (n_fine <= 0 || n_coarse <= 0) return CSN_E_ARG;
-  if (c_in < 32 || c_in > 256 || (c_in & 31) || c_out < 32 || c_out > 256 || (c_out & 31)) return CSN_E_DIM;
-  return 0;
-}
-static bool off4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 static int octant_mode() { return mode() != 0; }                 // no single-product instances: modes 2 / 3 run as bf16x3
 
 long long csn_octant_conv_workspace_bytes(int n_fine, int n_coarse, int c_in, int c_out, int up, int backward) {
   if (octant_dims(n_fine, n_coarse, c_in, c_out)) return 0;
   return csn_octant_conv_ws_bytes(n_fine, n_coarse, c_in, c_out, up != 0, backward != 0);
+}
+
+// the struct of every octant launch but the 16-bit ones: down names children alone, up parent / order / seg (a backward: what it reads);
+// y / ld_y are z's of the statistics forms; bias, y and ws NULL where the call has none
+static CsnOctantConvArgs octant_args(const float* x, long long ld_x, int n_fine, int n_coarse, int c_in, int c_out, const int* children,
+                                     const int* parent, const int* order, const int* seg, const float* w, const float* bias, float* y,
+                                     long long ld_y, void* ws) {
+  CsnOctantConvArgs a{};
+  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
+  a.children = children; a.parent = parent; a.order = order; a.seg = seg;
+  a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y; a.ws = ws;
+  return a;
 }
 
 int csn_octant_down_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
@@ -1655,10 +1711,8 @@ int csn_octant_down_fwd_f32(const float* x, long long ld_x, int n_fine, const in
   if (const int e = sparse_conv_map(ld_x, c_in, n_fine)) return e;
   if (const int e = sparse_conv_map(ld_y, c_out, n_coarse)) return e;
   if (mis16(x) || mis16(w) || mis16(y) || off4(children)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
-  a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
-  return csn_launch_octant_down_fwd(a, octant_mode(), (hipStream_t)stream);
+  return csn_launch_octant_down_fwd(octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, children, nullptr, nullptr, nullptr, w, bias, y,
+                                                ld_y, nullptr), octant_mode(), (hipStream_t)stream);
 }
 
 int csn_octant_up_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
@@ -1669,16 +1723,16 @@ int csn_octant_up_fwd_f32(const float* x, long long ld_x, int n_coarse, const in
   if (const int e = sparse_conv_map(ld_x, c_in, n_coarse)) return e;
   if (const int e = sparse_conv_map(ld_y, c_out, n_fine)) return e;
   if (mis16(x) || mis16(w) || mis16(y) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
-  a.order = order; a.seg = seg; a.w = w; a.bias = bias; a.y = y; a.ld_y = (int)ld_y;
-  return csn_launch_octant_up_fwd(a, octant_mode(), (hipStream_t)stream);
+  return csn_launch_octant_up_fwd(octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w, bias, y, ld_y,
+                                              nullptr), octant_mode(), (hipStream_t)stream);
 }
 
-// the checks the two backward entry points share: n_x / n_dy are the rows of x / dy, `one` says whether dx is the one-weight form
-static int octant_bwd_args(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_x, int n_dy, int n_fine, int n_coarse,
-                           int c_in, int c_out, const int* children, const int* parent, const int* order, const int* seg,
-                           const float* w, float* dx, long long ld_dx, float* dw, void* ws, long long ws_bytes, bool one, bool up) {
+// the checks the two backward entry points share, and their struct: n_x / n_dy are the rows of x / dy, `one` says whether dx is the
+// one-weight form
+static int octant_bwd_args(CsnOctantConvArgs& a, const float* dy, long long ld_dy, const float* x, long long ld_x, int n_x, int n_dy,
+                           int n_fine, int n_coarse, int c_in, int c_out, const int* children, const int* parent, const int* order,
+                           const int* seg, const float* w, float* dx, long long ld_dx, float* dw, float* dbias, void* ws,
+                           long long ws_bytes, bool one, bool up) {
   if (!dy || !ws) return CSN_E_ARG;
   if (dx && (!w || (one ? (!parent || !order || !seg) : !children))) return CSN_E_ARG;
   if (dw && (!x || !parent || !order || !seg)) return CSN_E_ARG;
@@ -1689,75 +1743,57 @@ static int octant_bwd_args(const float* dy, long long ld_dy, const float* x, lon
   if (mis16(dy) || mis16(ws) || (dx && (mis16(dx) || mis16(w))) || (dw && (mis16(dw) || mis16(x)))) return CSN_E_PTR;
   if (off4(children) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
   if (ws_bytes < csn_octant_conv_ws_bytes(n_fine, n_coarse, c_in, c_out, up, 1)) return CSN_E_WORKSPACE;
+  a = octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, children, parent, order, seg, w, nullptr, nullptr, 0, ws);
+  a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias;
   return 0;
 }
 
 int csn_octant_down_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
                             int c_out, const int* parent, const int* order, const int* seg, const float* w, float* dx,
                             long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
-  if (const int e = octant_bwd_args(dy, ld_dy, x, ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w,
-                                    dx, ld_dx, dw, ws, ws_bytes, true, false)) return e;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
-  a.order = order; a.seg = seg; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx; a.dw = dw; a.dbias = dbias;
-  a.ws = ws;
+  CsnOctantConvArgs a;
+  if (const int e = octant_bwd_args(a, dy, ld_dy, x, ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w,
+                                    dx, ld_dx, dw, dbias, ws, ws_bytes, true, false)) return e;
   return csn_launch_octant_down_bwd(a, octant_mode(), (hipStream_t)stream);
 }
 
 int csn_octant_up_bwd_f32(const float* dy, long long ld_dy, const float* x, long long ld_x, int n_fine, int n_coarse, int c_in,
                           int c_out, const int* children, const int* parent, const int* order, const int* seg, const float* w,
                           float* dx, long long ld_dx, float* dw, float* dbias, void* ws, long long ws_bytes, void* stream) {
-  if (const int e = octant_bwd_args(dy, ld_dy, x, ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, children, parent, order, seg, w,
-                                    dx, ld_dx, dw, ws, ws_bytes, false, true)) return e;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
-  a.parent = parent; a.order = order; a.seg = seg; a.w = w; a.dy = dy; a.ld_dy = (int)ld_dy; a.dx = dx; a.ld_dx = (int)ld_dx;
-  a.dw = dw; a.dbias = dbias; a.ws = ws;
+  CsnOctantConvArgs a;
+  if (const int e = octant_bwd_args(a, dy, ld_dy, x, ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, children, parent, order, seg, w,
+                                    dx, ld_dx, dw, dbias, ws, ws_bytes, false, true)) return e;
   return csn_launch_octant_up_bwd(a, octant_mode(), (hipStream_t)stream);
 }
 
 // ---- (23) the octant convolutions with a BatchNorm + residual + ReLU epilogue (inference) ----
-// (21)'s checks on the maps, (19)'s on the residual; n_y: the rows of y and r
-static int octant_bn_args(long long ld_x, int n_x, int n_y, int n_fine, int n_coarse, int c_in, int c_out, const float* r,
-                          long long ld_r, const float* y, long long ld_y) {
-  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
-  if (const int e = sparse_conv_map(ld_x, c_in, n_x)) return e;
-  if (const int e = sparse_conv_map(ld_y, c_out, n_y)) return e;
-  if (r) if (const int e = sparse_conv_map(ld_r, c_out, n_y)) return e;
-  if (r == y && ld_r != ld_y) return CSN_E_ARG;                   // y as its own residual: element for element, or not at all
-  return 0;
-}
-
+// (21)'s checks on the maps, (19)'s on the residual: conv_bn_args
 int csn_octant_down_bn_act_fwd_f32(const float* x, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in, int c_out,
                                    const float* w, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, const float* r, long long ld_r, int relu, float* y,
                                    long long ld_y, void* stream) {
-  if (!x || !children || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if (const int e = octant_bn_args(ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, r, ld_r, y, ld_y)) return e;
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(children)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
-  a.w = w; a.y = y; a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
-  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
-  return csn_launch_octant_down_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
+  if (!children) return CSN_E_ARG;
+  if (const int e = conv_bn_args(CONV_BN_OCTANT, x, 0, ld_x, n_fine, n_coarse, 0, c_in, c_out, w, gamma, beta, running_mean, running_var,
+                                 r, 0, ld_r, y, 0, ld_y)) return e;
+  if (off4(children)) return CSN_E_PTR;
+  return csn_launch_octant_down_bn_act_fwd(octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, children, nullptr, nullptr, nullptr, w,
+                                                       nullptr, y, ld_y, nullptr),
+                                           sconv_bn(gamma, beta, running_mean, running_var, eps, r, ld_r, relu), octant_mode(),
+                                           (hipStream_t)stream);
 }
 
 int csn_octant_up_bn_act_fwd_f32(const float* x, long long ld_x, int n_coarse, const int* parent, const int* order, const int* seg,
                                  int n_fine, int c_in, int c_out, const float* w, const float* gamma, const float* beta,
                                  const float* running_mean, const float* running_var, float eps, const float* r, long long ld_r,
                                  int relu, float* y, long long ld_y, void* stream) {
-  if (!x || !parent || !order || !seg || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if (const int e = octant_bn_args(ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, r, ld_r, y, ld_y)) return e;
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
-  a.order = order; a.seg = seg; a.w = w; a.y = y; a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps;
-  n.r = r; n.ld_r = (int)ld_r; n.relu = relu != 0;
-  return csn_launch_octant_up_bn_act_fwd(a, n, octant_mode(), (hipStream_t)stream);
+  if (!parent || !order || !seg) return CSN_E_ARG;
+  if (const int e = conv_bn_args(CONV_BN_OCTANT, x, 0, ld_x, n_coarse, n_fine, 0, c_in, c_out, w, gamma, beta, running_mean, running_var,
+                                 r, 0, ld_r, y, 0, ld_y)) return e;
+  if (off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  return csn_launch_octant_up_bn_act_fwd(octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w, nullptr, y,
+                                                     ld_y, nullptr),
+                                         sconv_bn(gamma, beta, running_mean, running_var, eps, r, ld_r, relu), octant_mode(),
+                                         (hipStream_t)stream);
 }
 
 // ---- (26) the octant convolutions with the BatchNorm statistics epilogue (training) ----
@@ -1783,9 +1819,8 @@ int csn_octant_down_stats_fwd_f32(const float* x, long long ld_x, int n_fine, co
   if (!x || !children || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
   if (const int e = octant_stats_args(ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, ld_z, ws_bytes, false)) return e;
   if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || off4(children)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.children = children;
-  a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  const CsnOctantConvArgs a = octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, children, nullptr, nullptr, nullptr, w, nullptr, z,
+                                          ld_z, ws);
   return csn_launch_octant_down_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, octant_mode(), (hipStream_t)stream);
 }
 
@@ -1796,9 +1831,8 @@ int csn_octant_up_stats_fwd_f32(const float* x, long long ld_x, int n_coarse, co
   if (!x || !parent || !order || !seg || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
   if (const int e = octant_stats_args(ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, ld_z, ws_bytes, true)) return e;
   if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
-  CsnOctantConvArgs a{};
-  a.x = x; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out; a.parent = parent;
-  a.order = order; a.seg = seg; a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
+  const CsnOctantConvArgs a = octant_args(x, ld_x, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w, nullptr, z, ld_z,
+                                          ws);
   return csn_launch_octant_up_stats_fwd(a, mean, invstd, running_mean, running_var, eps, momentum, octant_mode(), (hipStream_t)stream);
 }
 
@@ -1821,7 +1855,7 @@ int csn_sparse_conv_cat_stats_fwd_f32(const CsnCatParts* parts, int n_parts, int
     sum += c_in[m];
   }
   if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
-  if (mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (mis16(w) || mis16(z) || mis16(ws) || off4(table)) return CSN_E_PTR;
   if (n_out < 2) return CSN_E_ARG;                                // a one-row batch has no variance
   if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
   CsnSparseConvArgs a{};
@@ -1832,35 +1866,19 @@ int csn_sparse_conv_cat_stats_fwd_f32(const CsnCatParts* parts, int n_parts, int
 }
 
 // ---- (24) the launch of (19) on 16-bit maps: x, r and y each fp32 rows or rows of the math mode's 16-bit type ----
-// a 16-bit row-major map of n rows: pitch % 8, >= its width, and the whole map inside one 2 GiB buffer window
-static int sparse_conv_map16(long long ld, int width, int n) {
-  if (ld < width) return CSN_E_ARG;
-  if (ld & 7) return CSN_E_ALIGN;
-  if (ld > (1 << 20) || (long long)n * ld * 2 > 0x7fffffffLL) return CSN_E_DIM;
-  return 0;
-}
-
 int csn_sparse_conv_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
                                    int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, const void* r, int r16, long long ld_r, int relu, void* y,
                                    int y16, long long ld_y, void* stream) {
-  if (!x || !table || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if ((x16 | r16 | y16) & ~1) return CSN_E_ARG;
-  if (mode() < 2 || !t_rows16) return CSN_E_ARG;                  // single-product instances only: 16-bit maps under bf16x3 / fp32
-                                                                  // would throw away what they pay for
-  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
-  const auto map = [](int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); };
-  if (const int e = map(x16, ld_x, c_in, n_in)) return e;
-  if (const int e = map(y16, ld_y, c_out, n_out)) return e;
-  if (r) if (const int e = map(r16, ld_r, c_out, n_out)) return e;
-  if (r == y && (r16 != y16 || ld_r != ld_y)) return CSN_E_ARG;   // y as its own residual: element for element, or not at all
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
+  if (!table) return CSN_E_ARG;
+  if (const int e = conv_bn_args(CONV_BN_M16, x, x16, ld_x, n_in, n_out, kv, c_in, c_out, w, gamma, beta, running_mean, running_var, r,
+                                 r16, ld_r, y, y16, ld_y)) return e;
+  if (off4(table)) return CSN_E_PTR;
   CsnSparseConvM16Args a{};
   a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_in = n_in; a.table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in; a.c_out = c_out;
   a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16; a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
-  return csn_launch_sparse_conv_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+  return csn_launch_sparse_conv_bn_act_fwd_m16(a, sconv_bn(gamma, beta, running_mean, running_var, eps, nullptr, 0, relu), mode(),
+                                               (hipStream_t)stream);
 }
 
 // ---- (28) training on bf16 activation maps: (15a), (15b) and (14)'s backward with a type flag beside the map that may be bf16 ----
@@ -1869,76 +1887,29 @@ static int train16_mode(int flags) {
   if (flags & ~1) return CSN_E_ARG;
   return mode() == 2 && t_rows16 ? 0 : CSN_E_ARG;
 }
-static int map_of(int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); }
 
 int csn_sparse_conv_stats_fwd_t16(const void* x, int x16, long long ld_x, int n_in, const int* table, int n_out, int kv, int c_in,
                                   int c_out, const float* w, float* z, long long ld_z, float* mean, float* invstd, float* running_mean,
                                   float* running_var, float eps, float momentum, void* ws, long long ws_bytes, void* stream) {
   if (const int e = train16_mode(x16)) return e;
-  if (!x16)
-    return sparse_conv_stats_fwd_impl(static_cast<const float*>(x), ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd,
-                                      running_mean, running_var, eps, momentum, false, nullptr, 0, ws, ws_bytes, stream);
-  if (!x || !table || !w || !z || !mean || !invstd || !ws) return CSN_E_ARG;
-  if (const int e = sparse_conv_dims(n_in, n_out, kv, c_in, c_out)) return e;
-  if (const int e = sparse_conv_map16(ld_x, c_in, n_in)) return e;
-  if (const int e = sparse_conv_map(ld_z, c_out, n_out)) return e;
-  if (mis16(x) || mis16(w) || mis16(z) || mis16(ws) || (reinterpret_cast<uintptr_t>(table) & 3)) return CSN_E_PTR;
-  if (n_out < 2) return CSN_E_ARG;                                // a one-row batch has no variance
-  if (ws_bytes < csn_sparse_conv_stats_ws_bytes(n_out, c_out)) return CSN_E_WORKSPACE;
-  CsnSparseConvArgs a{};
-  a.x = static_cast<const float*>(x); a.ld_x = (int)ld_x; a.n_in = n_in; a.fwd_table = table; a.n_out = n_out; a.kv = kv; a.c_in = c_in;
-  a.c_out = c_out; a.w = w; a.y = z; a.ld_y = (int)ld_z; a.ws = ws;
-  return csn_launch_sparse_conv_stats_fwd_x16(a, mean, invstd, running_mean, running_var, eps, momentum, (hipStream_t)stream);
+  return sparse_conv_stats_fwd_impl(x, x16, ld_x, n_in, table, n_out, kv, c_in, c_out, w, z, ld_z, mean, invstd, running_mean, running_var,
+                                    eps, momentum, false, nullptr, 0, ws, ws_bytes, stream);
 }
 
 int csn_rows_bn_act_fwd_t16(const CsnBnTerms* t, int n_terms, int n_rows, int channels, int training, float eps, const void* r, int r16,
                             long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream) {
   if (const int e = train16_mode(r16 | y16)) return e;
-  if (!t || !y) return CSN_E_ARG;
-  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
-  CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m] || !t->beta[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (mis16(t->z[m])) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.beta[m] = t->beta[m];
-  }
-  if (const int e = map_of(y16, ld_y, channels, n_rows)) return e;
-  if (r) if (const int e = map_of(r16, ld_r, channels, n_rows)) return e;
-  if (mis16(y) || (r && mis16(r))) return CSN_E_PTR;
-  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = relu != 0; a.eps = eps;
-  a.r = static_cast<const float*>(r); a.ld_r = (int)ld_r; a.y = static_cast<float*>(y); a.ld_y = (int)ld_y;
-  return csn_launch_rows_bn_act_fwd16(a, r16, y16, (hipStream_t)stream);
+  return rows_bn_act_fwd_impl(t, n_terms, n_rows, channels, training, eps, false, nullptr, 0, r, r16, ld_r, relu, y, y16, ld_y, stream,
+                              /*t16=*/true);
 }
 
 int csn_rows_bn_act_bwd_t16(const float* dy, long long ld_dy, const void* y, int y16, long long ld_y, const CsnBnTerms* t, int n_terms,
                             int n_rows, int channels, int training, float eps, int relu, float* dr, long long ld_dr, void* ws,
                             long long ws_bytes, void* stream) {
   if (const int e = train16_mode(y16)) return e;
-  if (!y16 || !relu)                                              // the mask is the only use of y: without it (15b) itself
-    return rows_bn_act_bwd_impl(dy, ld_dy, relu ? static_cast<const float*>(y) : nullptr, ld_y, t, n_terms, n_rows, channels, training, eps,
-                                false, nullptr, 0, relu, dr, ld_dr, ws, ws_bytes, stream);
-  if (!dy || !t || !ws || !y) return CSN_E_ARG;
-  if (const int e = bn_act_dims(n_terms, n_rows, channels)) return e;
-  CsnRowsBnActArgs a{};
-  for (int m = 0; m < n_terms; ++m) {
-    if (!t->z[m] || !t->mean[m] || !t->scale[m] || !t->gamma[m]) return CSN_E_ARG;
-    if (const int e = sparse_conv_map(t->ld_z[m], channels, n_rows)) return e;
-    if (t->dz[m]) if (const int e = sparse_conv_map(t->ld_dz[m], channels, n_rows)) return e;
-    if (mis16(t->z[m]) || (t->dz[m] && mis16(t->dz[m]))) return CSN_E_PTR;
-    a.z[m] = t->z[m]; a.ld_z[m] = (int)t->ld_z[m]; a.mean[m] = t->mean[m]; a.scale[m] = t->scale[m]; a.gamma[m] = t->gamma[m];
-    a.dz[m] = t->dz[m]; a.ld_dz[m] = (int)t->ld_dz[m]; a.dgamma[m] = t->dgamma[m]; a.dbeta[m] = t->dbeta[m];
-  }
-  if (const int e = sparse_conv_map(ld_dy, channels, n_rows)) return e;
-  if (const int e = sparse_conv_map16(ld_y, channels, n_rows)) return e;
-  if (dr) if (const int e = sparse_conv_map(ld_dr, channels, n_rows)) return e;
-  if (mis16(dy) || mis16(ws) || mis16(y) || (dr && mis16(dr))) return CSN_E_PTR;
-  if (ws_bytes < csn_rows_bn_act_ws_bytes(n_rows, channels, n_terms, 1)) return CSN_E_WORKSPACE;
-  a.n_terms = n_terms; a.n_rows = n_rows; a.C = channels; a.training = training != 0; a.relu = 1; a.eps = eps;
-  a.y = static_cast<float*>(const_cast<void*>(y)); a.ld_y = (int)ld_y; a.dy = dy; a.ld_dy = (int)ld_dy; a.dr = dr; a.ld_dr = (int)ld_dr;
-  a.ws = ws;
-  return csn_launch_rows_bn_act_bwd16(a, (hipStream_t)stream);
+  // the mask is the only use of y: without it the pointer is dropped and (15b) itself runs
+  return rows_bn_act_bwd_impl(dy, ld_dy, relu ? y : nullptr, relu ? y16 : 0, ld_y, t, n_terms, n_rows, channels, training, eps, false,
+                              nullptr, 0, relu, dr, ld_dr, ws, ws_bytes, stream);
 }
 
 int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void* x, int x16, long long ld_x, int n_in, int n_out, int kv,
@@ -1963,49 +1934,43 @@ int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void* x, int
 }
 
 // ---- (25) the launches of (23) as one 16-bit product on maps that are each fp32 rows or rows of the mode's 16-bit type ----
-// (24)'s mode and flag checks, (21)'s on the sizes, each map by its own type's rule; n_x: the rows of x, n_y: those of y and r
-static int octant_m16_args(int x16, long long ld_x, int n_x, int n_y, int n_fine, int n_coarse, int c_in, int c_out, const void* r,
-                           int r16, long long ld_r, const void* y, int y16, long long ld_y) {
-  if ((x16 | r16 | y16) & ~1) return CSN_E_ARG;
-  if (mode() < 2 || !t_rows16) return CSN_E_ARG;                  // single-product instances only, as in (24)
-  if (const int e = octant_dims(n_fine, n_coarse, c_in, c_out)) return e;
-  const auto map = [](int is16, long long ld, int width, int n) { return is16 ? sparse_conv_map16(ld, width, n) : sparse_conv_map(ld, width, n); };
-  if (const int e = map(x16, ld_x, c_in, n_x)) return e;
-  if (const int e = map(y16, ld_y, c_out, n_y)) return e;
-  if (r) if (const int e = map(r16, ld_r, c_out, n_y)) return e;
-  if (r == y && (r16 != y16 || ld_r != ld_y)) return CSN_E_ARG;   // y as its own residual: element for element, or not at all
-  return 0;
+// (24)'s mode and flag checks, (21)'s on the sizes, each map by its own type's rule: conv_bn_args
+static CsnOctantM16Args octant_m16(const void* x, int x16, long long ld_x, int n_fine, int n_coarse, int c_in, int c_out,
+                                   const int* children, const int* parent, const int* order, const int* seg, const float* w, const void* r,
+                                   int r16, long long ld_r, void* y, int y16, long long ld_y) {
+  CsnOctantM16Args a{};
+  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
+  a.children = children; a.parent = parent; a.order = order; a.seg = seg;
+  a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16; a.ld_y = (int)ld_y;
+  return a;
 }
 
 int csn_octant_down_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_fine, const int* children, int n_coarse, int c_in,
                                    int c_out, const float* w, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, const void* r, int r16, long long ld_r, int relu, void* y,
                                    int y16, long long ld_y, void* stream) {
-  if (!x || !children || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if (const int e = octant_m16_args(x16, ld_x, n_fine, n_coarse, n_fine, n_coarse, c_in, c_out, r, r16, ld_r, y, y16, ld_y)) return e;
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(children)) return CSN_E_PTR;
-  CsnOctantM16Args a{};
-  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
-  a.children = children; a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16; a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
-  return csn_launch_octant_down_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+  if (!children) return CSN_E_ARG;
+  if (const int e = conv_bn_args(CONV_BN_M16 | CONV_BN_OCTANT, x, x16, ld_x, n_fine, n_coarse, 0, c_in, c_out, w, gamma, beta, running_mean,
+                                 running_var, r, r16, ld_r, y, y16, ld_y)) return e;
+  if (off4(children)) return CSN_E_PTR;
+  return csn_launch_octant_down_bn_act_fwd_m16(octant_m16(x, x16, ld_x, n_fine, n_coarse, c_in, c_out, children, nullptr, nullptr, nullptr,
+                                                          w, r, r16, ld_r, y, y16, ld_y),
+                                               sconv_bn(gamma, beta, running_mean, running_var, eps, nullptr, 0, relu), mode(),
+                                               (hipStream_t)stream);
 }
 
 int csn_octant_up_bn_act_fwd_m16(const void* x, int x16, long long ld_x, int n_coarse, const int* parent, const int* order,
                                  const int* seg, int n_fine, int c_in, int c_out, const float* w, const float* gamma,
                                  const float* beta, const float* running_mean, const float* running_var, float eps, const void* r,
                                  int r16, long long ld_r, int relu, void* y, int y16, long long ld_y, void* stream) {
-  if (!x || !parent || !order || !seg || !w || !y || !gamma || !beta || !running_mean || !running_var) return CSN_E_ARG;
-  if (const int e = octant_m16_args(x16, ld_x, n_coarse, n_fine, n_fine, n_coarse, c_in, c_out, r, r16, ld_r, y, y16, ld_y)) return e;
-  if (mis16(x) || mis16(w) || mis16(y) || (r && mis16(r)) || off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
-  CsnOctantM16Args a{};
-  a.x = x; a.x16 = x16; a.ld_x = (int)ld_x; a.n_fine = n_fine; a.n_coarse = n_coarse; a.c_in = c_in; a.c_out = c_out;
-  a.parent = parent; a.order = order; a.seg = seg; a.w = w; a.r = r; a.r16 = r16; a.ld_r = (int)ld_r; a.y = y; a.y16 = y16;
-  a.ld_y = (int)ld_y;
-  CsnSconvBnArgs n{};
-  n.gamma = gamma; n.beta = beta; n.running_mean = running_mean; n.running_var = running_var; n.eps = eps; n.relu = relu != 0;
-  return csn_launch_octant_up_bn_act_fwd_m16(a, n, mode(), (hipStream_t)stream);
+  if (!parent || !order || !seg) return CSN_E_ARG;
+  if (const int e = conv_bn_args(CONV_BN_M16 | CONV_BN_OCTANT, x, x16, ld_x, n_coarse, n_fine, 0, c_in, c_out, w, gamma, beta, running_mean,
+                                 running_var, r, r16, ld_r, y, y16, ld_y)) return e;
+  if (off4(parent) || off4(order) || off4(seg)) return CSN_E_PTR;
+  return csn_launch_octant_up_bn_act_fwd_m16(octant_m16(x, x16, ld_x, n_fine, n_coarse, c_in, c_out, nullptr, parent, order, seg, w, r, r16,
+                                                        ld_r, y, y16, ld_y),
+                                             sconv_bn(gamma, beta, running_mean, running_var, eps, nullptr, 0, relu), mode(),
+                                             (hipStream_t)stream);
 }
 
 // ---- (16) point fields: voxel means, interpolation onto points and its adjoint ----

@@ -345,25 +345,40 @@ class _SparseConv(torch.autograd.Function):
     def backward(ctx, dy):
         with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
             x, w = ctx.saved_tensors
-            kmap = ctx.kmap
-            L = _lib.lib()
-            KV, c_in, c_out = w.shape
-            n_in, n_out = kmap.n_in, kmap.n_out
-            dy = dy.contiguous()
-            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             need_b = ctx.b_shape is not None and ctx.needs_input_grad[2]
-            dx = torch.empty_like(x) if need_x else None
-            dw = torch.empty_like(w) if need_w else None
-            db = torch.empty((c_out,), device=x.device, dtype=torch.float32) if need_b else None
-            if not (need_x or need_w or need_b):
-                return None, None, None, None
-            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
-            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-            bwd = kmap.bwd_table if need_x else None                        # None at stride 1: the kernel reverses ``fwd``
-            _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
-                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw),
-                                                 CF._ptr(db), CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+            dx, dw, db = _sparse_conv_backward(dy, x, x.shape[1], w, ctx.kmap, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_b)
             return dx, dw, None if db is None else db.reshape(ctx.b_shape), None
+
+
+def _workspace(n_bytes: int, device) -> torch.Tensor:
+    """The scratch tensor of one call: the library's byte count, never fewer than 16 (a pointer the checks take)."""
+    return torch.empty((max(n_bytes, 16),), device=device, dtype=torch.uint8)
+
+
+def _sparse_conv_backward(dz, x, ld_x, w, kmap, need_x, need_w, need_b=False):
+    """``(dx, dw, dbias)`` of the convolution ``kmap`` describes, each None unless wanted — the backward of every node on a kernel
+    map.  ``x (n_in, c_in)`` is the saved input with its row pitch ``ld_x`` in elements: fp32 rows go to ``csn_sparse_conv_bwd_f32``,
+    bf16 rows to ``csn_sparse_conv_bwd_t16``, which takes nothing else.  ``w (KV, c_in, c_out)`` may be None without dx.  The caller
+    holds its node's math-mode and rows16 brackets."""
+    if not (need_x or need_w or need_b):
+        return None, None, None
+    L = _lib.lib()
+    KV, n_in, n_out = kmap.KV, kmap.n_in, kmap.n_out
+    c_in, c_out = x.shape[1], dz.shape[1]
+    dz = dz.contiguous()
+    dx = dz.new_empty((n_in, c_in)) if need_x else None                     # fp32 on dz's device, whatever x is
+    dw = dz.new_empty((KV, c_in, c_out)) if need_w else None
+    db = dz.new_empty((c_out,)) if need_b else None
+    ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
+    ws = _workspace(ws_n, dz.device)
+    bwd = kmap.bwd_table if need_x else None                                # None at stride 1: the kernel reverses ``fwd``
+    tail = (ld_x, n_in, n_out, KV, c_in, c_out, CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db),
+            CF._ptr(ws), ws_n, CF._stream())
+    if x.dtype == torch.bfloat16:
+        _lib.check(L.csn_sparse_conv_bwd_t16(CF._ptr(dz), c_out, CF._ptr(x), 1, *tail), "csn_sparse_conv_bwd_t16")
+    else:
+        _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), *tail), "csn_sparse_conv_bwd_f32")
+    return dx, dw, db
 
 
 def sparse_conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], kmap: KernelMap) -> torch.Tensor:
@@ -562,31 +577,33 @@ class _OctantConv(torch.autograd.Function):
     def backward(ctx, dy):
         with CF.math_mode(CF.backward_mode(ctx.mode)):
             x, w = ctx.saved_tensors
-            omap, up = ctx.omap, ctx.up
-            L = _lib.lib()
-            _, c_in, c_out = w.shape
-            n_fine, n_coarse = omap.n_fine, omap.n_coarse
-            dy = dy.contiguous()
-            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             need_b = ctx.b_shape is not None and ctx.needs_input_grad[2]
-            if not (need_x or need_w or need_b):
-                return None, None, None, None, None
-            dx = torch.empty_like(x) if need_x else None
-            dw = torch.empty_like(w) if need_w else None
-            db = torch.empty((c_out,), device=x.device, dtype=torch.float32) if need_b else None
-            ws_n = int(L.csn_octant_conv_workspace_bytes(n_fine, n_coarse, c_in, c_out, int(up), 1))
-            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-            if up:
-                _lib.check(L.csn_octant_up_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
-                                                   CF._ptr(omap.children), CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg),
-                                                   CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db), CF._ptr(ws), ws_n,
-                                                   CF._stream()), "csn_octant_up_bwd_f32")
-            else:
-                _lib.check(L.csn_octant_down_bwd_f32(CF._ptr(dy), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
-                                                     CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg), CF._ptr(w),
-                                                     CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db), CF._ptr(ws), ws_n, CF._stream()),
-                           "csn_octant_down_bwd_f32")
+            dx, dw, db = _octant_conv_backward(dy, x, w, ctx.omap, ctx.up, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_b)
             return dx, dw, None if db is None else db.reshape(ctx.b_shape), None, None
+
+
+def _octant_conv_backward(dz, x, w, omap, up, need_x, need_w, need_b=False):
+    """``(dx, dw, dbias)`` of an octant convolution that saved contiguous ``(x, w)``, each None unless wanted:
+    ``csn_octant_{down,up}_bwd_f32``.  The caller holds its node's math-mode bracket."""
+    if not (need_x or need_w or need_b):
+        return None, None, None
+    L = _lib.lib()
+    _, c_in, c_out = w.shape
+    n_fine, n_coarse = omap.n_fine, omap.n_coarse
+    dz = dz.contiguous()
+    dx = torch.empty_like(x) if need_x else None
+    dw = torch.empty_like(w) if need_w else None
+    db = torch.empty((c_out,), device=x.device, dtype=torch.float32) if need_b else None
+    ws_n = int(L.csn_octant_conv_workspace_bytes(n_fine, n_coarse, c_in, c_out, int(up), 1))
+    ws = _workspace(ws_n, x.device)
+    head = (CF._ptr(dz), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out)
+    tail = (CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), CF._ptr(db),
+            CF._ptr(ws), ws_n, CF._stream())
+    if up:
+        _lib.check(L.csn_octant_up_bwd_f32(*head, CF._ptr(omap.children), *tail), "csn_octant_up_bwd_f32")
+    else:
+        _lib.check(L.csn_octant_down_bwd_f32(*head, *tail), "csn_octant_down_bwd_f32")
+    return dx, dw, db
 
 
 def _octant_conv(x, weight, bias, omap, up):

@@ -318,18 +318,13 @@ class _ConvStats(torch.autograd.Function):
         w_c = w.detach().contiguous()
         KV, c_in, c_out = w_c.shape
         n_in, n_out = kmap.n_in, kmap.n_out
-        dev = x.device
-        stats = (c_out,)
+        G = None
         if group_rows is not None:
             group_rows = group_rows.contiguous()
             G = group_rows.numel() - 1
-            stats = (G, c_out)
-        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty(stats, device=dev, dtype=torch.float32)
-        invstd = torch.empty(stats, device=dev, dtype=torch.float32)
         ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out) if group_rows is None else
                    L.csn_sparse_conv_stats_groups_workspace_bytes(n_out, c_out, G))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        z, mean, invstd, ws = _stats_outputs(n_out, c_out, ws_n, x.device, G)
         head = (CF._ptr(x), c_in, n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean),
                 CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps), float(momentum))
         with CF.rows16(ctx.rows16):
@@ -346,30 +341,20 @@ class _ConvStats(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, _dmean, _dinvstd):
-        return _conv_stats_backward(ctx, dz) + (None,) * 6
+        with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
+            x, w = ctx.saved_tensors
+            dx, dw, _ = _mc._sparse_conv_backward(dz, x, x.shape[1], w, ctx.kmap, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return (dx, dw) + (None,) * 6
 
 
-def _conv_stats_backward(ctx, dz):
-    """(dx, dw) of a convolution node that saved (x, w) and its map: ``csn_sparse_conv_bwd_f32``."""
-    with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
-        x, w = ctx.saved_tensors
-        kmap = ctx.kmap
-        L = _lib.lib()
-        KV, c_in, c_out = w.shape
-        n_in, n_out = kmap.n_in, kmap.n_out
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_x or need_w):
-            return None, None
-        dz = dz.contiguous()
-        dx = torch.empty_like(x) if need_x else None
-        dw = torch.empty_like(w) if need_w else None
-        ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
-        ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-        bwd = kmap.bwd_table if need_x else None
-        _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_in, n_out, KV, c_in, c_out,
-                                             CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
-                                             CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
-        return dx, dw
+def _stats_outputs(n_out: int, c_out: int, ws_n: int, device, n_groups: Optional[int] = None):
+    """``z``, ``mean``, ``invstd`` and the workspace of a convolution with the statistics epilogue (sections 15, 20, 26 - 28): one
+    BatchNorm batch, or with ``n_groups`` one per row group and (G, c_out) statistics.  ``ws_n``: the entry point's byte count."""
+    stats = (c_out,) if n_groups is None else (n_groups, c_out)
+    z = torch.empty((n_out, c_out), device=device, dtype=torch.float32)
+    mean = torch.empty(stats, device=device, dtype=torch.float32)
+    invstd = torch.empty(stats, device=device, dtype=torch.float32)
+    return z, mean, invstd, _mc._workspace(ws_n, device)
 
 
 def _conv_stats(x, weight, kmap, grouped: bool, group_rows, running_mean, running_var, eps, momentum):
@@ -416,6 +401,48 @@ def conv_stats_groups(x: torch.Tensor, weight: torch.Tensor, kmap: KernelMap, gr
     return _conv_stats(x, weight, kmap, True, group_rows, running_mean, running_var, eps, momentum)
 
 
+def _bn_unpack(flat, training):
+    """The flat (z, mean, scale, gamma, beta) per term of a BatchNorm node as lists ``zs, means, scales, gammas, betas``, contiguous;
+    in eval mode mean and scale are cloned: the running statistics may move before the backward."""
+    M = len(flat) // 5
+    zs = [flat[5 * m].contiguous() for m in range(M)]
+    means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
+    scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
+    if not training:
+        means, scales = [t.clone() for t in means], [t.clone() for t in scales]
+    gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
+    betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+    return zs, means, scales, gammas, betas
+
+
+def _bn_terms(zs, means, scales, gammas, betas=None, grads=None) -> "_lib.BnTerms":
+    """``CsnBnTerms`` of contiguous (N, C) terms: with ``betas`` for the forward, with ``grads`` = [(dz, dgamma, dbeta)] for the
+    backward."""
+    C = zs[0].shape[1]
+    t = _lib.BnTerms()
+    for m in range(len(zs)):
+        t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
+        if betas is not None:
+            t.beta[m] = CF._ptr(betas[m])
+        if grads is not None:
+            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(grads[m][0]), C, CF._ptr(grads[m][1]), CF._ptr(grads[m][2])
+    return t
+
+
+def _bn_grads(need, at: int, M: int, N: int, C: int, dev):
+    """[(dz, dgamma, dbeta)] per term, each None unless ``need`` (``needs_input_grad``, the terms from position ``at``) wants it, and
+    the same as the tail of the node's return tuple."""
+    grads, outs = [], []
+    for m in range(M):
+        nz, ng, nb = need[at + 5 * m], need[at + 5 * m + 3], need[at + 5 * m + 4]
+        dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
+        dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
+        db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
+        grads.append((dz, dg, db))
+        outs += [dz, None, None, dg, db]
+    return grads, outs
+
+
 class _BnAct(torch.autograd.Function):
     """y = act(sum_m (gamma_m (z_m - mean_m) s_m + beta_m) + r) through ``csn_rows_bn_act_fwd_f32`` / ``_bwd_f32``, or with
     ``group_rows`` (training mode, (G, C) statistics per term) through ``csn_rows_bn_act_groups_fwd_f32`` / ``_bwd_f32``.
@@ -427,20 +454,11 @@ class _BnAct(torch.autograd.Function):
         CF._need_cuda(r, *flat)
         L = _lib.lib()
         ctx.mode = CF.current_mode()
-        zs = [flat[5 * m].contiguous() for m in range(M)]
-        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
-        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
-        if not training:                                                    # the running statistics may move before the backward
-            means, scales = [t.clone() for t in means], [t.clone() for t in scales]
-        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
-        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+        zs, means, scales, gammas, betas = _bn_unpack(flat, training)
         N, C = zs[0].shape
         r_c = None if r is None else r.contiguous()
         y = torch.empty((N, C), device=zs[0].device, dtype=torch.float32)
-        t = _lib.BnTerms()
-        for m in range(M):
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
-            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
+        t = _bn_terms(zs, means, scales, gammas, betas=betas)
         tail = (CF._ptr(r_c), C, int(relu), CF._ptr(y), C, CF._stream())
         if group_rows is None:
             _lib.check(L.csn_rows_bn_act_fwd_f32(ctypes.addressof(t), M, N, C, int(training), float(eps), *tail), "csn_rows_bn_act_fwd_f32")
@@ -465,26 +483,18 @@ class _BnAct(torch.autograd.Function):
         dy = dy.contiguous()
         need = ctx.needs_input_grad
         dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[4]) else None
-        t = _lib.BnTerms()
-        outs = []
-        for m in range(M):
-            nz, ng, nb = need[5 + 5 * m], need[5 + 5 * m + 3], need[5 + 5 * m + 4]
-            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
-            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
-            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
-            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
-            outs += [dz, None, None, dg, db]
+        grads, outs = _bn_grads(need, 5, M, N, C, dev)
+        t = _bn_terms(zs, means, scales, gammas, grads=grads)
         head = (CF._ptr(dy), C, CF._ptr(y), C, ctypes.addressof(t), M, N, C)
         if group_rows is None:
             ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
-            ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+            ws = _mc._workspace(ws_n, dev)
             _lib.check(L.csn_rows_bn_act_bwd_f32(*head, int(ctx.training), ctx.eps, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n,
                                                  CF._stream()), "csn_rows_bn_act_bwd_f32")
         else:
             G = group_rows.numel() - 1
             ws_n = int(L.csn_rows_bn_act_groups_workspace_bytes(N, C, M, G))
-            ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+            ws = _mc._workspace(ws_n, dev)
             _lib.check(L.csn_rows_bn_act_groups_bwd_f32(*head, group_rows.data_ptr(), G, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n,
                                                         CF._stream()), "csn_rows_bn_act_groups_bwd_f32")
         return (None, None, None, None, dr, *outs)
@@ -553,12 +563,8 @@ class _ConvStats16(torch.autograd.Function):
         w_c = w.detach().contiguous()
         KV, c_in, c_out = w_c.shape
         n_in, n_out = kmap.n_in, kmap.n_out
-        dev = x.device
-        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
-        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
         ws_n = int(L.csn_sparse_conv_stats_workspace_bytes(n_out, c_out))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        z, mean, invstd, ws = _stats_outputs(n_out, c_out, ws_n, x.device)
         with CF.rows16(True):
             _lib.check(L.csn_sparse_conv_stats_fwd_t16(CF._ptr(x), 1, x.stride(0), n_in, CF._ptr(kmap.fwd), n_out, KV, c_in, c_out, CF._ptr(w_c),
                                                        CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean),
@@ -577,19 +583,7 @@ class _ConvStats16(torch.autograd.Function):
             return (None,) * 8
         with CF.math_mode(2), CF.rows16(True):
             x, w = ctx.saved_tensors
-            kmap = ctx.kmap
-            L = _lib.lib()
-            KV, c_in, c_out = w.shape
-            n_in, n_out = kmap.n_in, kmap.n_out
-            dz = dz.contiguous()
-            dx = torch.empty((n_in, c_in), device=x.device, dtype=torch.float32) if need_x else None
-            dw = torch.empty_like(w) if need_w else None
-            ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
-            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-            bwd = kmap.bwd_table if need_x else None
-            _lib.check(L.csn_sparse_conv_bwd_t16(CF._ptr(dz), c_out, CF._ptr(x), 1, x.stride(0), n_in, n_out, KV, c_in, c_out,
-                                                 CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None,
-                                                 CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_t16")
+            dx, dw, _ = _mc._sparse_conv_backward(dz, x, x.stride(0), w, ctx.kmap, need_x, need_w)
         return (None, dx, dw) + (None,) * 5
 
 
@@ -618,23 +612,14 @@ class _BnAct16(torch.autograd.Function):
         M = len(flat) // 5
         CF._need_cuda(r_rows, *flat, also=(torch.bfloat16,))
         L = _lib.lib()
-        zs = [flat[5 * m].contiguous() for m in range(M)]
-        means = [flat[5 * m + 1].detach().contiguous() for m in range(M)]
-        scales = [flat[5 * m + 2].detach().contiguous() for m in range(M)]
-        if not training:                                                    # the running statistics may move before the backward
-            means, scales = [t.clone() for t in means], [t.clone() for t in scales]
-        gammas = [flat[5 * m + 3].detach().contiguous() for m in range(M)]
-        betas = [flat[5 * m + 4].detach().contiguous() for m in range(M)]
+        zs, means, scales, gammas, betas = _bn_unpack(flat, training)
         N, C = zs[0].shape
         if r_rows is not None:
             r_c = r_rows if _pitched16(r_rows) else r_rows.contiguous()
         else:
             r_c = None if r_edge is None else _rows(r_edge)
         y = torch.empty((N, C), device=zs[0].device, dtype=torch.bfloat16 if out16 else torch.float32)
-        t = _lib.BnTerms()
-        for m in range(M):
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m])
-            t.gamma[m], t.beta[m] = CF._ptr(gammas[m]), CF._ptr(betas[m])
+        t = _bn_terms(zs, means, scales, gammas, betas=betas)
         with CF.rows16(True):
             _lib.check(L.csn_rows_bn_act_fwd_t16(ctypes.addressof(t), M, N, C, int(training), float(eps), CF._ptr(r_c), int(r_rows is not None),
                                                  0 if r_c is None else r_c.stride(0), int(relu), CF._ptr(y), int(out16), C, CF._stream()),
@@ -661,18 +646,10 @@ class _BnAct16(torch.autograd.Function):
         dy = dy.contiguous()
         need = ctx.needs_input_grad
         dr = torch.empty((N, C), device=dev, dtype=torch.float32) if (ctx.has_r and need[5]) else None
-        t = _lib.BnTerms()
-        outs = []
-        for m in range(M):
-            nz, ng, nb = need[6 + 5 * m], need[6 + 5 * m + 3], need[6 + 5 * m + 4]
-            dz = torch.empty((N, C), device=dev, dtype=torch.float32) if nz else None
-            dg = torch.empty((C,), device=dev, dtype=torch.float32) if ng else None
-            db = torch.empty((C,), device=dev, dtype=torch.float32) if nb else None
-            t.z[m], t.ld_z[m], t.mean[m], t.scale[m], t.gamma[m] = CF._ptr(zs[m]), C, CF._ptr(means[m]), CF._ptr(scales[m]), CF._ptr(gammas[m])
-            t.dz[m], t.ld_dz[m], t.dgamma[m], t.dbeta[m] = CF._ptr(dz), C, CF._ptr(dg), CF._ptr(db)
-            outs += [dz, None, None, dg, db]
+        grads, outs = _bn_grads(need, 6, M, N, C, dev)
+        t = _bn_terms(zs, means, scales, gammas, grads=grads)
         ws_n = int(L.csn_rows_bn_act_workspace_bytes(N, C, M))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        ws = _mc._workspace(ws_n, dev)
         with CF.math_mode(2), CF.rows16(True):
             _lib.check(L.csn_rows_bn_act_bwd_t16(CF._ptr(dy), C, CF._ptr(y), int(ctx.out16), C, ctypes.addressof(t), M, N, C, int(ctx.training),
                                                  ctx.eps, int(ctx.relu), CF._ptr(dr), C, CF._ptr(ws), ws_n, CF._stream()),

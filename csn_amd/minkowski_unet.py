@@ -236,12 +236,8 @@ class _OctantConvStats(torch.autograd.Function):
         w_c = w.detach().contiguous()
         _, c_in, c_out = w_c.shape
         n_fine, n_coarse = omap.n_fine, omap.n_coarse
-        dev = x.device
-        z = torch.empty((n_fine if up else n_coarse, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
-        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
         ws_n = int(L.csn_octant_stats_workspace_bytes(n_fine, n_coarse, c_out, int(up)))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        z, mean, invstd, ws = _mh._stats_outputs(n_fine if up else n_coarse, c_out, ws_n, x.device)
         tail = (CF._ptr(w_c), CF._ptr(z), c_out, CF._ptr(mean), CF._ptr(invstd), CF._ptr(running_mean), CF._ptr(running_var), float(eps),
                 float(momentum), CF._ptr(ws), ws_n, CF._stream())
         if up:
@@ -260,28 +256,7 @@ class _OctantConvStats(torch.autograd.Function):
     def backward(ctx, dz, _dmean, _dinvstd):
         with CF.math_mode(CF.backward_mode(ctx.mode)):
             x, w = ctx.saved_tensors
-            omap, up = ctx.omap, ctx.up
-            L = _lib.lib()
-            _, c_in, c_out = w.shape
-            n_fine, n_coarse = omap.n_fine, omap.n_coarse
-            need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if not (need_x or need_w):
-                return (None,) * 8
-            dz = dz.contiguous()
-            dx = torch.empty_like(x) if need_x else None
-            dw = torch.empty_like(w) if need_w else None
-            ws_n = int(L.csn_octant_conv_workspace_bytes(n_fine, n_coarse, c_in, c_out, int(up), 1))
-            ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-            if up:
-                _lib.check(L.csn_octant_up_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
-                                                   CF._ptr(omap.children), CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg),
-                                                   CF._ptr(w), CF._ptr(dx), c_in, CF._ptr(dw), None, CF._ptr(ws), ws_n, CF._stream()),
-                           "csn_octant_up_bwd_f32")
-            else:
-                _lib.check(L.csn_octant_down_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), c_in, n_fine, n_coarse, c_in, c_out,
-                                                     CF._ptr(omap.parent), CF._ptr(omap.order), CF._ptr(omap.seg), CF._ptr(w),
-                                                     CF._ptr(dx), c_in, CF._ptr(dw), None, CF._ptr(ws), ws_n, CF._stream()),
-                           "csn_octant_down_bwd_f32")
+            dx, dw, _ = _mc._octant_conv_backward(dz, x, w, ctx.omap, ctx.up, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
             return (dx, dw) + (None,) * 6
 
 
@@ -326,12 +301,8 @@ class _CatConvStats(torch.autograd.Function):
         w_c = w.detach().contiguous()
         KV, _, c_out = w_c.shape
         n_in, n_out = kmap.n_in, kmap.n_out
-        dev = w_c.device
-        z = torch.empty((n_out, c_out), device=dev, dtype=torch.float32)
-        mean = torch.empty((c_out,), device=dev, dtype=torch.float32)
-        invstd = torch.empty((c_out,), device=dev, dtype=torch.float32)
         ws_n = int(L.csn_sparse_conv_cat_stats_workspace_bytes(n_out, c_out))
-        ws = torch.empty((max(ws_n, 16),), device=dev, dtype=torch.uint8)
+        z, mean, invstd, ws = _mh._stats_outputs(n_out, c_out, ws_n, w_c.device)
         cp = _lib.CatParts()
         for m, x in enumerate(xs):
             cp.x[m], cp.ld_x[m], cp.c_in[m] = x.data_ptr(), x.stride(0), x.shape[1]
@@ -350,10 +321,6 @@ class _CatConvStats(torch.autograd.Function):
     def backward(ctx, dz, _dmean, _dinvstd):
         with CF.math_mode(CF.backward_mode(ctx.mode)), CF.rows16(ctx.rows16):
             w, *xs = ctx.saved_tensors
-            kmap = ctx.kmap
-            L = _lib.lib()
-            KV, _, c_out = w.shape
-            n_in, n_out = kmap.n_in, kmap.n_out
             need_w = ctx.needs_input_grad[0]
             need_x = [ctx.needs_input_grad[6 + m] for m in range(len(xs))]
             if not (need_w or any(need_x)):
@@ -363,19 +330,8 @@ class _CatConvStats(torch.autograd.Function):
             dxs, c0 = [], 0
             for x, nx in zip(xs, need_x):
                 c_in = int(x.shape[1])
-                if not (nx or need_w):
-                    dxs.append(None)
-                    c0 += c_in
-                    continue
                 w_m = w[:, c0:c0 + c_in].contiguous() if nx else None
-                dx = torch.empty((n_in, c_in), device=x.device, dtype=torch.float32) if nx else None
-                dw_m = torch.empty((KV, c_in, c_out), device=x.device, dtype=torch.float32) if need_w else None
-                ws_n = int(L.csn_sparse_conv_workspace_bytes(n_in, n_out, KV, c_in, c_out, 1))
-                ws = torch.empty((max(ws_n, 16),), device=x.device, dtype=torch.uint8)
-                bwd = kmap.bwd_table if nx else None
-                _lib.check(L.csn_sparse_conv_bwd_f32(CF._ptr(dz), c_out, CF._ptr(x), x.stride(0), n_in, n_out, KV, c_in, c_out,
-                                                     CF._ptr(kmap.fwd), CF._ptr(bwd), CF._ptr(w_m), CF._ptr(dx), c_in, CF._ptr(dw_m), None,
-                                                     CF._ptr(ws), ws_n, CF._stream()), "csn_sparse_conv_bwd_f32")
+                dx, dw_m, _ = _mc._sparse_conv_backward(dz, x, x.stride(0), w_m, ctx.kmap, nx, need_w)
                 if need_w:
                     dw[:, c0:c0 + c_in] = dw_m
                 dxs.append(dx)
