@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libcsn_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_bf16x3.hip", "wx_stream.hip", "wx_lnb.hip", "loss.hip", "attn_f32.hip", "attn_bf16x3.hip", "attn_dkv.hip", "attn_dv_scores.hip", "fold.hip", "outproj_ln.hip", "retrieval.hip", "retrieval_screen.hip", "combine.hip", "compat.hip", "minkowski_csn.hip", "minkowski_seg.hip", "rows_fc.hip", "sparse_conv.hip", "sparse_conv_maps16.hip", "train_maps16.hip", "sparse_conv_cat.hip", "octant_conv.hip", "octant_conv_maps16.hip", "octant_conv_stats.hip", "rows_bn_act.hip", "point_field.hip", "kernel_map.hip", "octant_map.hip", "points.hip", "csn_capi.hip"]
-HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", "sconv_a16_body.inc", "rows_bn_act_body.inc", "octant_rows_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
+HEADERS = ["csn_common.h", "csn_kernels.h", "csn_window.h", "attn_tile_image.h", "wx_common.h", "rows_mma.h", "sconv_gemm_body.inc", "sconv_a16_body.inc", "rows_bn_act_body.inc", "octant_rows_body.inc", os.path.join("..", "..", "include", "csn_hip.h")]
 ARCH = "gfx950"
 BUILD_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"]
 
@@ -356,6 +356,7 @@ _SIGNATURES = {
 EXPORTS = tuple(_SIGNATURES)
 # keys of csn_dev_set / csn_dev_get (include/csn_hip.h, development section)
 DEV_BIG_TILES, DEV_WIDE_GEMM, DEV_WIDE_FORMS, DEV_WX, DEV_LNB_GROUP, DEV_SCONV_NB, DEV_KV_SAME = 0, 1, 2, 3, 5, 7, 8
+DEV_ATTN_WG64, DEV_ATTN_WG64_LAUNCHES = 9, 10   # the 64-query dQ instance (attn_bf16x3.hip WG64); its launch count
 DEV_WX_DEFAULT = 9                     # streaming kernel (1) + LayerNorm backward fused into the dCtx stream (8); the only other
                                        # bit csn_dev_set takes for DEV_WX is 4 (out-projection + LayerNorm on the tiled kernel)
 

@@ -25,6 +25,7 @@
 // as 16-byte rows through an LDS transpose (a wave-level memory instruction costs ~100 cycles whatever its width).
 #include "csn_common.h"
 #include "csn_kernels.h"
+#include "attn_tile_image.h"
 
 namespace {
 
@@ -89,8 +90,20 @@ constexpr int csn_attn_waves(int npl, int dt, bool bwd, bool rc_f32 = false) {
 // the same registers are committed into both images — tileA in segment 1, tileB in segment 2, where the two commits of the plain
 // instance sit.  The same LDS contents, hence the same bits; half the tile requests (8 -> 4 per wave and tile).  The forward in
 // the same form (one register set, no early request) was measured +-0 over the step and is not built.
-template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, int NOP = 0, bool KV_SAME = false>
-__global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
+// WG64 (the NOP = 2 backward at d = 256 with k and v the SAME planes): four waves and 64 queries per work-group, and ONE tile
+// image per stage that phase 1 reads with the transposing read and phase 2 with the row read (attn_tile_image.h) — 64.3 KB of
+// LDS, so two independent work-groups share a CU: one's operand prologue / epilogue runs beside the other's tile loop, a barrier
+// stops four waves, and a wave's SIMD partner belongs to the other group (no stagger).  A tile is 8 pieces per thread, requested
+// and committed in two halves of 4 through one register set: commit half 0 / request half 1 in segment 1, commit half 1 /
+// request half 0 of the next tile in segment 2.  The same arithmetic per query row in the same order: the same bits; 247
+// registers, nothing spilled.  Takes the place of the KV_SAME instance where the development key allows (step A/B: DESIGN.md §4m
+// "Two work-groups per CU").  The kept-scores FORWARD in this form (two register sets, each half requested a tile ahead; 255
+// registers, no spills; the same bits) gained 0.1-0.2 ms of the step, at the noise bar in two of its three A/B runs: not built.
+template <typename PR, int DT, bool BWD, bool KVP, bool RC = false, int NOP = 0, bool KV_SAME = false, bool WG64 = false>
+__global__ __launch_bounds__(WG64 ? 256 : 512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) void csn_attn_bf16x3_kernel(CsnAttnArgs p) {
+  static_assert(!WG64 || (PR::NT == 3 && DT == 8 && KVP && !RC && !KV_SAME && BWD && NOP == 2), "64-query form: the folded d = 256 backward");
+  constexpr int NTH = WG64 ? 256 : 512;                 // threads, and QW = 16 queries per wave
+  constexpr int QW = NTH / 4;
   static_assert(!KV_SAME || (DT == 8 && NOP == 2), "one request per tile: the folded d = 256 backward");
   static_assert(PR::NT == 3 || KVP, "single-product modes take K / V as tile planes");
   static_assert(!RC || BWD, "score recomputation: backward kernel");
@@ -98,9 +111,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   constexpr int NPL = PR::NPL;                          // planes: hi (+ lo)
   constexpr int D = 32 * DT;
   constexpr int UPR = KVP ? 4 * NPL : 8;                // 16-byte pieces per tile row (tile planes: 4 per plane; fp32: 8)
-  constexpr int RPP = 512 / UPR;                        // tile rows staged per pass of the 512 threads
+  constexpr int RPP = NTH / UPR;                        // tile rows staged per pass of the work-group's threads
   constexpr int PIECES = D * UPR;                       // 16-byte pieces per streamed tile
-  constexpr int NP_T = (PIECES + 511) / 512;            // pieces per thread per tile
+  constexpr int NP_T = (PIECES + NTH - 1) / NTH;        // pieces per thread per tile
+  constexpr int NPG = WG64 ? NP_T / 2 : NP_T;           // pieces per register set (WG64: half a tile)
   // plane pitch: 64 bytes of phase between hi and lo.  LDS STORES bank on 32 dwords (128 bytes): a staging instruction of the
   // tile-plane path writes the hi and the lo unit of a row together (lanes u and u + 4), and with the planes a multiple of
   // 128 bytes apart the two would land on the same banks (measured: SQ_LDS_BANK_CONFLICT = 15 % of the LDS cycles of both
@@ -122,11 +136,11 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   // LDS images: A x 2 stages, B x 2 (RC: x 3 — the key-contiguous K image is then committed in segment 1 too, which needs a
   // third stage), RC: + C x 2 (the K tile in tileA's form)
   constexpr int NB_ST = RC ? 3 : 2;
-  constexpr int TILE_EL = (2 + NB_ST + (RC ? 2 : 0)) * NPL * PLANE, STAGE_EL = D * 128 * 2;
+  constexpr int TILE_EL = (WG64 ? 2 : 2 + NB_ST + (RC ? 2 : 0)) * NPL * PLANE, STAGE_EL = D * QW * 2;
   static_assert(2 * (TILE_EL > STAGE_EL ? TILE_EL : STAGE_EL) <= 160 * 1024, "LDS budget of one CU");
   __shared__ __attribute__((aligned(16))) short tiles[TILE_EL > STAGE_EL ? TILE_EL : STAGE_EL];
   auto tileA = [&](int st, int pl) -> short* { return tiles + (st * NPL + pl) * PLANE; };
-  auto tileB = [&](int st, int pl) -> short* { return tiles + ((2 + st) * NPL + pl) * PLANE; };
+  auto tileB = [&](int st, int pl) -> short* { return tiles + (((WG64 ? 0 : 2) + st) * NPL + pl) * PLANE; };   // (WG64: the one image)
   auto tileC = [&](int st, int pl) -> short* { return tiles + ((2 + NB_ST + st) * NPL + pl) * PLANE; };
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -136,7 +150,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   // unit u get ids 8 * (QT * (u / 8) + qt) + (u % 8): same residue mod 8 (same XCD), adjacent in dispatch order.
   // (Placement only changes speed: every tile is self-contained.)
   const int Tq = p.Tq > 0 ? p.Tq : p.T;                       // queries per block (T: keys per block)
-  const int QT = (Tq + 127) / 128;
+  const int QT = (Tq + QW - 1) / QW;
   const int Y = p.n_blocks * p.H;
   const int L = blockIdx.x, slot = L & 7, jj = L >> 3;
   const int qt = jj % QT, u = (jj / QT) * 8 + slot;
@@ -156,10 +170,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   // ragged batches: this evaluation's own query / key counts (Tq, p.T stay the maxima that lay out the buffers)
   const bool short_blk = p.T_last > 0 && blk == p.n_blocks - 1;     // the row ends inside the last block
   const int Tq_e = p.tq_arr ? p.tq_arr[e0] : (short_blk ? p.T_last : Tq);
-  if (qt * 128 >= Tq_e) return;                                // a query tile beyond a short evaluation (whole work-group)
+  if (qt * QW >= Tq_e) return;                                // a query tile beyond a short evaluation (whole work-group)
   const int T = p.t_arr ? p.t_arr[e0] : (short_blk ? p.T_last : p.T), Tp = p.Tp, ld = p.ld, ldk = p.ld_kv > 0 ? p.ld_kv : p.ld;
   const bool ragged = (T & 3) != 0;                            // keys of the last 4-key group are masked one by one
-  const int qrow = qt * 128 + wave * 16 + lq;                  // query index inside the block
+  const int qrow = qt * QW + wave * 16 + lq;                  // query index inside the block
   const bool q_ok = qrow < Tq_e;
   const long long head_off = (long long)hd * D * ld + (long long)blk * Tq;
   const long long win = ((long long)(D - 1) * ld + Tq) * 4;    // bytes spanned by a [D][Tq] fp32 window of pitch ld
@@ -172,10 +186,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   long long stat_off0 = ((long long)e0 * p.H + hd) * ((long long)p.n_blocks * Tq) + (long long)blk * Tq;
   float* xbuf = reinterpret_cast<float*>(tiles);
   constexpr int CH_T = D / 16;                                     // 16-byte chunks per thread: D rows x 32 chunks / 512
-  const int cc = tid & 31, crow = tid >> 5;                        // chunk column, first row of this thread (rows + 16 t)
-  const unsigned c_off = (qt * 128 + 4 * cc) < Tq_e ? (unsigned)(crow * ld + qt * 128 + 4 * cc) * 4u : CSN_OOB;
-  const int col = 16 * wave + lq;                                  // this lane's query column inside the block of 128
-  const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4;
+  const int cc = tid & (QW / 4 - 1), crow = tid / (QW / 4);        // chunk column, first row of this thread (rows + 16 t)
+  const unsigned c_off = (qt * QW + 4 * cc) < Tq_e ? (unsigned)(crow * ld + qt * QW + 4 * cc) * 4u : CSN_OOB;
+  const int col = 16 * wave + lq;                                  // this lane's query column inside the block of QW
+  const bool late = !WG64 && __builtin_amdgcn_readfirstlane(wave) >= 4;
   f32x4v O[D / 16];
 #pragma unroll
   for (int c = 0; c < D / 16; ++c) O[c] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -201,7 +215,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 16 * c + 4 * kq + r;
-        xbuf[row * 128 + ((((col >> 2) ^ (4 * ((row >> 2) & 1))) << 2) | (col & 3))] = O[c][r] * inv;
+        xbuf[row * QW + ((((col >> 2) ^ (4 * ((row >> 2) & 1))) << 2) | (col & 3))] = O[c][r] * inv;
       }
     __syncthreads();
     {
@@ -209,7 +223,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   #pragma unroll
       for (int t = 0; t < CH_T; ++t) {
         const int row = crow + 16 * t;
-        ch[t] = *reinterpret_cast<const f32x4*>(&xbuf[row * 128 + ((cc ^ (4 * ((row >> 2) & 1))) << 2)]);
+        ch[t] = *reinterpret_cast<const f32x4*>(&xbuf[row * QW + ((cc ^ (4 * ((row >> 2) & 1))) << 2)]);
       }
       const csn_rsrc_t Or = map_rsrc(p.out, os * p.out_eval_stride + head_off, p.out_fmt);
       if (NPL == 1 && p.out_fmt) {                                   // a 16-bit map (written once: the launcher refuses accumulate)
@@ -270,21 +284,21 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   const unsigned t_off = KVP ? (unsigned)(t_row * kld * 2 + t_c * 16) : (unsigned)(t_row * ldk + 4 * t_c) * 4u;
   // only the last piece can fall beyond the tile — and not even that one when the pieces fill the passes (compile-time: the
   // guards around the last piece's stores fold away)
-  const bool t_last_ok = (PIECES % 512 == 0) || (tid + 512 * (NP_T - 1) < PIECES);
+  const bool t_last_ok = (PIECES % NTH == 0) || (tid + NTH * (NP_T - 1) < PIECES);
   // fp32: 8-byte chunk c -> tileA chunk c ^ sw;  tileB unit (c >> 1) ^ swz, half c & 1
   // planes: unit u = c & 3 of plane c >> 2 -> tileA chunks (2 u) ^ sw and (2 u + 1) ^ sw;  tileB unit u ^ swz
   const int t_u = t_c & 3, t_pl = t_c >> 2;
   const int a_dst = KVP ? t_pl * PLANE + t_row * KT + 8 * t_u : t_row * KT + 4 * (t_c ^ t_sw);
   const int b_dst = KVP ? t_pl * PLANE + t_row * KT + 8 * (t_u ^ t_swz) : t_row * KT + 8 * ((t_c >> 1) ^ t_swz) + 4 * (t_c & 1);
-  f32x4 g[NP_T];
-  f32x4 g2[(RC || EARLY) ? NP_T : 1];                   // RC: the K tile's pieces (committed to two images) beside the V tile's; EARLY: tileB's
-  auto fetch_to = [&](const csn_rsrc_t& rs, int kt, f32x4* g) {
+  f32x4 g[NPG];
+  f32x4 g2[(RC || EARLY) ? NPG : 1];                    // RC: the K tile's pieces (committed to two images) beside the V tile's; EARLY: tileB's
+  auto fetch_to = [&](const csn_rsrc_t& rs, int kt, f32x4* g, int i0 = 0) {       // i0: first piece of the set (WG64: 0 or NPG)
     if (KVP) {
       // keys beyond the block end are zero in the planes; units that lie entirely beyond it are not fetched at all
       const unsigned off = (kt * KT + 8 * t_u) < T ? t_off : CSN_OOB;
 #pragma unroll
-      for (int i = 0; i < NP_T; ++i)
-        g[i] = csn_bload4(rs, (i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off, (unsigned)(kt * (64 * NPL) + RPP * i * kld * 2));
+      for (int i = 0; i < NPG; ++i)
+        g[i] = csn_bload4(rs, (i0 + i == NP_T - 1 && !t_last_ok) ? CSN_OOB : off, (unsigned)(kt * (64 * NPL) + RPP * (i0 + i) * kld * 2));
     } else {
       const int k0 = kt * KT;
       // pieces that start past the block end are switched off.  Block mode has T % 4 == 0 (a 16-byte piece is all in or all
@@ -319,10 +333,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
 #pragma unroll
     for (int t = 0; t < CH_T; ++t) {
       const int row = crow + 16 * t;
-      *reinterpret_cast<f32x4*>(&xbuf[row * 128 + ((cc ^ (4 * ((row >> 3) & 1))) << 2)]) = ch[t];
+      *reinterpret_cast<f32x4*>(&xbuf[row * QW + ((cc ^ (4 * ((row >> 3) & 1))) << 2)]) = ch[t];
     }
   };
-  auto pick = [&](int row) { return xbuf[row * 128 + ((((col >> 2) ^ (4 * ((row >> 3) & 1))) << 2) | (col & 3))]; };
+  auto pick = [&](int row) { return xbuf[row * QW + ((((col >> 2) ^ (4 * ((row >> 3) & 1))) << 2) | (col & 3))]; };
   float rv[D / 4];
   if (BWD || it == it0) {                                          // (forward group: the operand of the first item serves them all)
     stage_in(Rr, p.r_fmt);
@@ -462,6 +476,12 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
         }
       }
   };
+  // WG64: pieces i0 .. i0 + NPG - 1 of a tile into the one image of stage st — one 16-byte store per piece (attn_tile_image.h)
+  const int i_dst = WG64 ? csn_tile_image::store_off(D, tid, 0) / 2 : 0;
+  auto commitI = [&](int st, const f32x4* g, int i0) {
+#pragma unroll
+    for (int i = 0; i < NPG; ++i) *reinterpret_cast<f32x4*>(tileA(st, 0) + i_dst + RPP * KT * (i0 + i)) = g[i];
+  };
   auto fetch = [&](const csn_rsrc_t& rs, int kt) { fetch_to(rs, kt, g); };
   auto commitA = [&](int st) { commitA_to(tileA(st, 0), tileA(st, NPL - 1), g); };
   auto commitB = [&](int st) { commitB_from(st, g); };
@@ -473,7 +493,10 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
   const int tr_sw = (kq ^ (lq >> (2 + SWB))) & 1;      // = the store side's swap bit of row tr_row (and of tr_row + 4)
   const int a_pos0 = tr_row * KT + 8 * (lq & 3) + 4 * tr_sw, a_pos1 = tr_row * KT + 8 * (lq & 3) + 4 * (tr_sw ^ 1);
   // tileB: row lq of the 16-channel tile, 16-byte unit kq ^ ((-(lq >> 2)) & 3): keys 8 kq .. 8 kq + 7
-  const int b_pos = lq * KT + 8 * (kq ^ ((-((lq >> 2) & 3)) & 3));
+  const int b_pos = WG64 ? csn_tile_image::rd_off(D, lane, 0, 0) / 2 : lq * KT + 8 * (kq ^ ((-((lq >> 2) & 3)) & 3));
+  // WG64, the one image: read h of the upper / lower four rows (the unit XOR differs between the two, so each has its constant)
+  const int i_pos[2][2] = {{csn_tile_image::tr_off(D, lane, 0, 0, 0, 0) / 2, csn_tile_image::tr_off(D, lane, 0, 0, 1, 0) / 2},
+                           {csn_tile_image::tr_off(D, lane, 0, 1, 0, 0) / 2, csn_tile_image::tr_off(D, lane, 0, 1, 1, 0) / 2}};
 
   const int nkt = (T + KT - 1) / KT;
 
@@ -512,12 +535,13 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     constexpr int NH = 2 * (D / 32);                    // half steps: (s, 16-key tile t)
     s16x8 ah[PD], al[PD];
     auto rd = [&](int h, s16x8& fh, s16x8& fl) {
-      const int o = 32 * (h >> 1) * KT + ((h & 1) ? a_pos1 : a_pos0);
+      const int o = 32 * (h >> 1) * KT + (WG64 ? i_pos[h & 1][0] : (h & 1) ? a_pos1 : a_pos0);
+      const int o4 = WG64 ? 32 * (h >> 1) * KT + i_pos[h & 1][1] : o + 4 * KT;
       fh = join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAh + o)),
-                 __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAh + o + 4 * KT)));
+                 __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAh + o4)));
       if constexpr (NPL == 2)
         fl = join8(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAl + o)),
-                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAl + o + 4 * KT)));
+                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tAl + o4)));
       else fl = fh;
     };
     __builtin_amdgcn_sched_barrier(0);
@@ -548,6 +572,13 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     const bool last_tile = kt == nkt - 1;
     const int nv = T - (kt * KT + 8 * kq);
     float t1[8] = {S0[0], S0[1], S0[2], S0[3], S1[0], S1[1], S1[2], S1[3]};
+    if constexpr (WG64) {                               // odd lane quarters: S0 holds keys 8 kq + 4 .., S1 keys 8 kq .. (attn_tile_image.h)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        t1[r] = (kq & 1) ? S1[r] : S0[r];
+        t1[4 + r] = (kq & 1) ? S0[r] : S1[r];
+      }
+    }
     // keep decisions of this lane's 8 elements: one hash per key pair (csn_common.h)
     bool keep[8];
     if (drop) {
@@ -687,7 +718,11 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  if constexpr (RC) {
+  if constexpr (WG64) {
+    fetch_to(Ar, 0, g, 0); commitI(0, g, 0);
+    fetch_to(Ar, 0, g, NPG); commitI(0, g, NPG);
+    if (nkt > 1) fetch_to(Ar, 1, g, 0);
+  } else if constexpr (RC) {
     // three images: V (k-major, tileA), K (k-major, tileC) and K (key-contiguous, tileB).  Both k-major images are read in
     // segment 1, so both are committed in segment 1 of the tile before (see the hazard note below); the K pieces stay in
     // go into the third stage of the key-contiguous image in segment 1 as well (stage (kt + 1) % 3 was last read two tiles
@@ -733,7 +768,11 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     //  backward: 16 more spilled registers inside the loop, 6.8 -> 9.4 ms; the request stays at the top of its own trip)
     load_sv(kt);
     phase1(cur);
-    if constexpr (RC) {
+    if constexpr (WG64) {
+      // the stage of tile kt + 1 was last read in segment 2 of tile kt - 1 and is next read in segment 1 of tile kt + 1: both of
+      // this tile's segments may write it (every wave of the group is in the same segment — no late half)
+      if (more) { commitI(nxt, g, 0); fetch_to(Ar, kt + 1, g, NPG); }
+    } else if constexpr (RC) {
       if (more) {
         commitA_to(tileA(nxt, 0), tileA(nxt, NPL - 1), g); commitA_to(tileC(nxt, 0), tileC(nxt, NPL - 1), g2);
         commitB_from(b_nxt, g2, false);
@@ -751,7 +790,9 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     __syncthreads();
     pointwise(kt);
     phase2(b_cur);
-    if constexpr (RC) {
+    if constexpr (WG64) {
+      if (more) { commitI(nxt, g, NPG); if (kt + 2 < nkt) fetch_to(Ar, kt + 2, g, 0); }
+    } else if constexpr (RC) {
       // (the key-contiguous K image of tile kt + 1 was committed in segment 1)
     } else if constexpr (EARLY) {
       if (more) commitB_from(nxt, g2);
@@ -761,7 +802,7 @@ __global__ __launch_bounds__(512, csn_attn_waves(PR::NPL, DT, BWD, RC && !KVP)) 
     __syncthreads();
   }
 
-  if (!late) __syncthreads();                           // pairs with the last barrier of the late half: tiles are idle now
+  if (!WG64 && !late) __syncthreads();                  // pairs with the last barrier of the late half: tiles are idle now
   if constexpr (!BWD) write_out();                      // (the barrier that ends the next item's prologue separates its tile commits from this)
   }                                                     // next item of the group (its prologue reuses the tiles as staging)
 
@@ -772,6 +813,16 @@ template <typename PR, int DT>
 int launch_dt(const CsnAttnArgs& a, bool bwd, hipStream_t st) {
   const long long units = (long long)a.n_blocks * a.H * a.E;
   dim3 grid((unsigned)(((units + 7) / 8) * 8 * (((a.Tq > 0 ? a.Tq : a.T) + 127) / 128)));
+  // the 64-query form (WG64): only where its instance exists — bf16x3, d = 256, block mode, the kept-scores backward that writes
+  // nothing score-sized, k and v the same planes (one pointer; stride, pitch and slots are shared by construction)
+  if constexpr (PR::NT == 3 && DT == 8) {
+    if (bwd && csn_dev_attn_wg64 && a.sc_tiles == 3 && a.kv_planes && a.k == a.v && !a.q2 && a.Tq <= 0 && !a.tq_arr && !a.t_arr) {
+      dim3 grid64((unsigned)(((units + 7) / 8) * 8 * ((a.T + 63) / 64)));
+      hipLaunchKernelGGL((csn_attn_bf16x3_kernel<PR, DT, true, true, false, 2, false, true>), grid64, dim3(256), 0, st, a);
+      ++csn_dev_attn_wg64_launches;
+      return (int)hipGetLastError();
+    }
+  }
   if (a.kv_planes) {
     if (bwd) {
       if constexpr (!PR::HALF) {
@@ -842,6 +893,10 @@ int launch_mode(const CsnAttnArgs& a, int d, int mode, bool bwd, hipStream_t st)
 
 // development switch (csn_dev_set): 1 = the no-planes backward may take its KV_SAME instance where k == v
 int csn_dev_kv_same = 1;
+// development switch: 1 = the no-planes backward takes its 64-query instance (WG64) where k == v; and the number of launches that
+// took it (read-only through csn_dev_get)
+int csn_dev_attn_wg64 = 1;
+int csn_dev_attn_wg64_launches = 0;
 
 int csn_launch_attn_fwd_bf16x3(const CsnAttnArgs& a, int d, int mode, hipStream_t st) {
   return launch_mode(a, d, mode, false, st);

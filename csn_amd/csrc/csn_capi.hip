@@ -129,6 +129,8 @@ int csn_dev_get(int key) {
     case CSN_DEV_LNB_GROUP: return csn_dev_lnb_group;
     case CSN_DEV_SCONV_NB: return csn_dev_sconv_nb;
     case CSN_DEV_KV_SAME: return csn_dev_kv_same;
+    case CSN_DEV_ATTN_WG64: return csn_dev_attn_wg64;
+    case CSN_DEV_ATTN_WG64_LAUNCHES: return csn_dev_attn_wg64_launches;
     default: return CSN_E_ARG;
   }
 }
@@ -151,6 +153,11 @@ int csn_dev_set(int key, int value) {
       if (value != 0 && value != 1) return CSN_E_ARG;
       csn_dev_kv_same = value;
       break;
+    case CSN_DEV_ATTN_WG64:
+      if (value != 0 && value != 1) return CSN_E_ARG;
+      csn_dev_attn_wg64 = value;
+      break;
+    case CSN_DEV_ATTN_WG64_LAUNCHES: return CSN_E_ARG;              // a counter: read-only
     default: return CSN_E_ARG;
   }
   return prev;

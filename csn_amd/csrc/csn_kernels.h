@@ -126,6 +126,9 @@ struct CsnAttnArgs {
   int kv_same = 0;
 };
 extern int csn_dev_kv_same;                              // development switch (csn_dev_set): 1 = the entry point may set it
+// development switch: 1 = the d = 256 bf16x3 no-planes backward launches its 64-query instance (attn_bf16x3.hip WG64) where k and v
+// are the same planes; and how many launches took it since the library was loaded
+extern int csn_dev_attn_wg64, csn_dev_attn_wg64_launches;
 // score recomputation needs three LDS tile images per stage: one plane at every width, two planes up to d = 128
 // (a two-plane d = 256 instance with its third image laid over the second — a timing build with wrong results — was measured
 //  in round 4: 167 spilled registers, 7.2 -> 24.7 ms; profiles/r4r_recompute_d256_experiment.txt; removed with its switch)

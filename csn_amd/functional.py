@@ -687,6 +687,7 @@ class _MHAEvals(torch.autograd.Function):
             else:
                 launches = [(0 if ci == 0 else 1, ids, ids.numel(), None, 0) for ci, ids in enumerate(plan.dq_colors)]
             L.csn_dev_set(_lib.DEV_KV_SAME, int(bool(ctx.tune.kv_same)))     # (process-wide, like the switches themselves)
+            L.csn_dev_set(_lib.DEV_ATTN_WG64, int(bool(ctx.tune.wg64)))
             for accumulate, ids, n_ids, off, n_groups in launches:
                 _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, _ptr(kv), _ptr(kv), kv_stride,
                                                        _ptr(plan.kv_slots), NP, _ptr(scores), None, _ptr(lse), None,

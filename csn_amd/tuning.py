@@ -67,6 +67,11 @@ class Tuning:
     # both LDS images, instead of once per image (attn_bf16x3.hip KV_SAME; the library's key CSN_DEV_KV_SAME, set before the
     # launch).  The same LDS contents, the same bits (tests/test_gpu_kv_same.py); timing: profiles/folded_tiles_ab_step.txt
     kv_same: bool = True
+    # the folded step's dQ kernel runs as four waves and 64 queries per work-group on ONE LDS tile image that serves both of a
+    # tile's reads, two independent work-groups per CU, instead of eight waves on two images (attn_bf16x3.hip WG64; the library's
+    # key CSN_DEV_ATTN_WG64, set before the launch; off: the instance ``kv_same`` selects).  The same arithmetic per query row, the
+    # same bits (tests/test_gpu_attn_wg64.py); timing: profiles/wg64_ab_step.txt
+    wg64: bool = True
     named: frozenset = frozenset()   # the switches the enclosing override blocks name (kept by ``override``; not a switch itself)
     # attention backward data flow by (math mode of the backward: 1 bf16x3, 2 bf16 — fp16 forwards run their backward in 2;
     # head width), or by mode alone; taken where the kernels have an instance for it (csn_attn_bwd_grouping bits 2 / 3),

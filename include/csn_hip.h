@@ -1306,6 +1306,10 @@ CSN_API int csn_sparse_conv_bwd_t16(const float* dy, long long ld_dy, const void
                                them (capped at c / 32) so that every kernel instance can be reached at any size — the same sums */
 #define CSN_DEV_KV_SAME 8   /* default 1: csn_block_attn_bwd_dq_f32 with probs_tiles = 3 and k == v (bf16x3, d_head = 256) requests
                                every key tile once for both LDS images (0: once per image) — the same bits.  Other values: CSN_E_ARG */
+#define CSN_DEV_ATTN_WG64 9 /* default 1: csn_block_attn_bwd_dq_f32 with probs_tiles = 3 and k == v (tile planes, bf16x3, d_head = 256)
+                               launches four waves and 64 queries per work-group on ONE LDS tile image, two work-groups per CU
+                               (0: eight waves and 128 queries, as CSN_DEV_KV_SAME says) — the same bits.  Other values: CSN_E_ARG */
+#define CSN_DEV_ATTN_WG64_LAUNCHES 10 /* read-only (csn_dev_set: CSN_E_ARG): launches that took the 64-query instance so far */
 CSN_API int csn_dev_set(int key, int value);
 CSN_API int csn_dev_get(int key);
 
