@@ -11,9 +11,8 @@ evaluations over K+1 slots (csa_models.py:209-242); each slot is projected to Q/
 """
 from __future__ import annotations
 
-import math
-from dataclasses import dataclass
-from typing import Optional, Tuple
+from dataclasses import dataclass, replace
+from typing import Optional
 
 import torch
 
@@ -213,105 +212,141 @@ def backward_mode(mode: int) -> int:
     return 2 if mode == 3 else mode
 
 
-class math_mode:
-    """``with math_mode(m):`` — the calling thread's library calls run in mode ``m`` inside the block (csn_set_thread_math_mode;
-    other threads are untouched; None = leave as is).  The autograd functions of this file record the mode of their forward and
-    open the same block (in ``backward_mode``) in their backward, which runs on autograd's own threads."""
+def forward_mode(mode: int, block: int) -> int:
+    """The mode an attention step runs in for a caller in ``mode``: the single-product kernels take K / V as tile planes (blocks
+    of at most 512 keys), so bf16 / fp16 with a longer block run as bf16x3."""
+    return 1 if (mode >= 2 and block > 512) else mode
 
-    def __init__(self, mode):
-        self.mode = mode_id(mode)
+
+class _ThreadSetting:
+    """``with <setting>(value):`` — one per-thread setting of the library (csn_set_thread_<KEY>) holds ``value`` inside the block;
+    the previous value returns on exit.  The entry points are looked up at call time."""
+    KEY = ""
+
+    def __init__(self, value):
+        self.value = int(value)
 
     def __enter__(self):
-        if self.mode is not None:
-            L = _lib.lib()
-            self.prev = L.csn_get_thread_math_mode()          # the thread's own override as it stands (-1: none) — restored
-            _lib.check(L.csn_set_thread_math_mode(self.mode))   # exactly, also one set directly through the C ABI
+        L = _lib.lib()
+        self.prev = getattr(L, "csn_get_thread_" + self.KEY)()
+        _lib.check(getattr(L, "csn_set_thread_" + self.KEY)(self.value))
         return self
 
     def __exit__(self, *exc):
-        if self.mode is not None:
-            _lib.lib().csn_set_thread_math_mode(self.prev)
+        getattr(_lib.lib(), "csn_set_thread_" + self.KEY)(self.prev)
         return False
 
 
-class act16:
+class math_mode(_ThreadSetting):
+    """``with math_mode(m):`` — the calling thread's library calls run in mode ``m`` inside the block (csn_set_thread_math_mode;
+    other threads are untouched; None = leave as is).  The autograd functions of this file record the mode of their forward and
+    open the same block (in ``backward_mode``) in their backward, which runs on autograd's own threads.  The thread's own override
+    as it stands (-1: none) is restored exactly, also one set directly through the C ABI."""
+    KEY = "math_mode"
+
+    def __init__(self, mode):
+        self.value = self.mode = mode_id(mode)
+
+    def __enter__(self):
+        return super().__enter__() if self.mode is not None else self
+
+    def __exit__(self, *exc):
+        return super().__exit__() if self.mode is not None else False
+
+
+class act16(_ThreadSetting):
     """``with act16(fmt):`` — the calling thread's library calls exchange their intermediate maps as 16-bit planes inside the
     block (csn_set_thread_act16; include/csn_hip.h "16-BIT ACTIVATION MAPS"): fmt 1 = the forward's maps are bf16, 2 = fp16,
     0 = fp32 maps (the default)."""
-
-    def __init__(self, fmt: int):
-        self.fmt = int(fmt)
-
-    def __enter__(self):
-        L = _lib.lib()
-        self.prev = L.csn_get_thread_act16()
-        _lib.check(L.csn_set_thread_act16(self.fmt))
-        return self
-
-    def __exit__(self, *exc):
-        _lib.lib().csn_set_thread_act16(self.prev)
-        return False
+    KEY = "act16"
 
 
-class rows16:
+class rows16(_ThreadSetting):
     """``with rows16(flag):`` — the calling thread's row products of the MinkowskiNet side (fc_layer, sparse convolution and its
     statistics form; include/csn_hip.h sections 13, 14, 15a) run their single-product instances in math modes 2 / 3 inside the block
     (csn_set_thread_rows16); False / 0: those modes run there as bf16x3 (the default).  The previous value returns on exit."""
+    KEY = "rows16"
 
     def __init__(self, flag):
-        self.flag = int(bool(flag))
-
-    def __enter__(self):
-        L = _lib.lib()
-        self.prev = L.csn_get_thread_rows16()
-        _lib.check(L.csn_set_thread_rows16(self.flag))
-        return self
-
-    def __exit__(self, *exc):
-        _lib.lib().csn_set_thread_rows16(self.prev)
-        return False
+        super().__init__(bool(flag))
 
 
-class score_layout:
+class score_layout(_ThreadSetting):
     """Bracket: the block-attention calls inside store their scores / P / dS planes tile-major (csn_set_thread_score_layout)."""
-
-    def __init__(self, layout: int):
-        self.layout = layout
-
-    def __enter__(self):
-        L = _lib.lib()
-        self.prev = L.csn_get_thread_score_layout()
-        _lib.check(L.csn_set_thread_score_layout(self.layout))
-        return self
-
-    def __exit__(self, *exc):
-        _lib.lib().csn_set_thread_score_layout(self.prev)
-        return False
+    KEY = "score_layout"
 
 
-def _score_flow(mode: int, d: int, T: int) -> int:
-    """The attention backward data flow (tuning.KEEP_SCORES / RECOMPUTE_DQ / FLASH) for a forward in `mode` at head width d and
-    block T: the configured flow of the mode the BACKWARD runs in, where the library has kernels for it."""
-    want = tuning.current().flow_for(backward_mode(mode), d)
-    if want == tuning.KEEP_SCORES or mode == 0:
-        return tuning.KEEP_SCORES
-    with math_mode(backward_mode(mode)):
-        bits = _lib.lib().csn_attn_bwd_grouping(d, T)
-    if not (bits & 4) or not (bits & 1):
-        return tuning.KEEP_SCORES
-    if want == tuning.FLASH and not (bits & 8):
-        return tuning.RECOMPUTE_DQ
-    return want
+@dataclass(frozen=True)
+class StepForm:
+    """Everything that selects the launches of one _MHAEvals step, decided ONCE (``step_form``) from the switches, the geometry,
+    the plan and the tensors; both passes read it from the autograd context and decide nothing themselves."""
+    mode: int              # the math mode the forward runs in (``forward_mode``)
+    bwd_mode: int          # ... and the backward (``backward_mode``)
+    a16: int               # 16-bit activation maps Qs, Ctx, xhat, dZ, dCtx: 0 fp32, 1 bf16, 2 fp16 (the ``act16`` format)
+    g16: int               # 4: the gradient maps dQ / dK / dV are bf16 too (added to a16 in the backward's ``act16``)
+    operands: str          # "folded" (the planes of x as K and V) | "tiles" (K | V tile planes) | "maps" (fp32 Q | K | V rows)
+    one_pass: bool         # tiles: Q, K and V from one pass over x (csn_project_qkv_f32)
+    grouped_fwd: bool      # the forward's evaluations grouped by query slot
+    flow: int              # tuning.KEEP_SCORES / RECOMPUTE_DQ / FLASH
+    scores: bool           # the forward writes the raw scores for the backward
+    sc_layout: int         # 1: scores / P / dS planes tile-major (the ``score_layout`` of both passes)
+    pt: int                # backward: P / dS travel to the dV / dK products as tile planes
+    kv_f16: int            # backward: the forward's K / V planes hold fp16 bits (the kernels convert to bf16 while they stage them)
+    dq_grouped: bool       # backward: dQ by one grouped call (False: colour by colour)
+    dkv_grouped: bool      # backward: dK / dV likewise
+    dv_scores: bool        # backward: dV from the untouched scores, the plane product for dK alone
+    ranged: Optional[bool] = None      # backward: weight gradients over the plan's slot ranges only (None until need_dx is known: the backward completes it)
 
 
-def fast_math() -> bool:
-    """True when the contractions run on the 16-bit matrix-core kernels (math modes 1..3)."""
-    return current_mode() != 0
-
-
-def planes() -> int:
-    """Planes of a tile-plane tensor in the current mode: hi + lo in bf16x3, one in the single-product modes."""
-    return 2 if current_mode() == 1 else 1
+def step_form(tune: tuning.Tuning, geo: MHAGeometry, plan: EvalPlan, x_shape, w_fc_shape, mode: int, keep_scores: bool,
+              linked: bool, x_requires_grad: bool, grouping: int, dq_no_planes: int, dv_scores_ok: int,
+              need_dx: Optional[bool] = None) -> StepForm:
+    """The form of a step for a caller in math mode ``mode``.  Pure: no launch, no allocation, no library call — the last three
+    are csn_attn_bwd_grouping and csn_attn_bwd_dv_scores_available in the backward's math mode, csn_attn_bwd_dq_no_planes_available in the forward's."""
+    S, C, NP = x_shape
+    H, d, D, T, Tp = geo.n_head, geo.d_head, geo.d_inner, geo.block, geo.score_pitch
+    mode = forward_mode(mode, T)
+    bwd_mode, fast = backward_mode(mode), mode != 0
+    tiles = fast and tune.kv_tiles and T <= 512            # K / V leave the projection as tile planes
+    # 16-bit activation maps only where nothing outside this file reads the maps: the linked form (the mix and the pooled sums
+    # consume xhat in kernels, gradients arrive through the link), tile-plane K / V
+    a16 = (mode - 1) if (mode >= 2 and tune.act16 and tiles and linked and keep_scores) else 0
+    # the configured flow of the mode the BACKWARD runs in, where the library has kernels for it
+    mode_flow = tune.flow_for(bwd_mode, d)
+    if mode_flow == tuning.KEEP_SCORES or mode == 0 or not (grouping & 4) or not (grouping & 1):
+        mode_flow = tuning.KEEP_SCORES
+    elif mode_flow == tuning.FLASH and not (grouping & 8):
+        mode_flow = tuning.RECOMPUTE_DQ
+    # folded projections (csn_hip.h (1b), DESIGN.md §2): one head of the model's width, bias-free layers — W_k goes into W_q,
+    # W_v into W_fc, and the attention runs on the planes of x itself.  Decided from the module, the plan and the tensors alone,
+    # never from the grad mode: a no-grad forward and a training forward give the same logits.  (x_all.requires_grad, not
+    # ctx.needs_input_grad: dx needs dK and dV, and the flag of the tensor is the same in both grad modes)
+    fold = bool(tune.takes_fold() and mode == 1 and H == 1 and C == d == D == 256 and tiles and not a16
+                and tuple(w_fc_shape) == (C, D) and plan.v_shift == 0 and not x_requires_grad
+                and mode_flow == tuning.KEEP_SCORES and dq_no_planes)
+    # attention backward data flow: keep the raw scores for it, or only lse (the backward then rebuilds S from Qs and K)
+    flow = mode_flow if (keep_scores and tiles) else tuning.KEEP_SCORES                             # (folded: KEEP_SCORES)
+    scores = bool(keep_scores and flow == tuning.KEEP_SCORES)
+    # score storage: tile-major where the whole chain (forward, grouped dQ call, grouped dK / dV products on the 256 x 256
+    # tiles) takes it — bf16x3 at d = 256 with kept scores; nothing outside _MHAEvals reads the buffer
+    sc_layout = 1 if (scores and tiles and mode == 1 and tune.tile_major_scores and tune.grouped_dq and
+                      tune.grouped_dkv and Tp >= (T + 31) // 32 * 32 and (grouping & 19) == 19) else 0
+    # 16-bit maps: the gradient maps dQ / dK / dV too, where every slot is written once (grouped calls, flash)
+    dq_once = flow != tuning.KEEP_SCORES or (tune.grouped_dq and (grouping & 1))
+    dkv_once = flow == tuning.FLASH or (tune.grouped_dkv and (grouping & 2))
+    g16 = 4 if (a16 and dq_once and dkv_once) else 0
+    pt = 1 if (fast and Tp >= (T + 31) // 32 * 32) else 0
+    kv_flag = 1 if tiles else 0
+    # kept scores in two planes, both grouped calls (either score layout; never folded: that step has no dV product)
+    dv_scores = bool(not fold and tune.dv_from_scores and flow == tuning.KEEP_SCORES and mode == 1 and pt == 1 and kv_flag == 1
+                     and not a16 and not g16 and tune.grouped_dq and tune.grouped_dkv and (grouping & 3) == 3 and dv_scores_ok)
+    return StepForm(
+        mode=mode, bwd_mode=bwd_mode, a16=a16, g16=g16, operands="folded" if fold else "tiles" if tiles else "maps",
+        one_pass=bool(tiles and not fold and plan.q_ranges is None and plan.kv_ranges is None and not a16 and tune.qkv_one_pass),
+        grouped_fwd=bool(tune.grouped_fwd and fast and plan.n_q_groups < plan.E), flow=flow, scores=scores, sc_layout=sc_layout,
+        pt=pt, kv_f16=1 if (kv_flag and mode == 3) else 0, dq_grouped=bool(tune.grouped_dq and (grouping & 1)),
+        dkv_grouped=bool(tune.grouped_dkv and (grouping & 2)), dv_scores=dv_scores,
+        ranged=None if need_dx is None else (plan.q_ranges is not None and not need_dx))
 
 
 def project(x: torch.Tensor, w: torch.Tensor, div_rows: int = 0, temperature: float = 1.0,
@@ -327,15 +362,22 @@ def project(x: torch.Tensor, w: torch.Tensor, div_rows: int = 0, temperature: fl
     assert x.stride(2) == 1 and x.stride(1) == N and w.is_contiguous()
     x16 = 16 if x.dtype == torch.bfloat16 else 0                   # a bf16 map as input (math mode 2: the bf16 gradient maps)
     assert not (split and x16)
-    if split:
-        out = torch.empty((S, 2, R, npts), device=x.device, dtype=torch.bfloat16)
-        _lib.check(_lib.lib().csn_project_f32(_ptr(x), x.stride(0), N, _ptr(w), R, C, _ptr(out), 2 * R * npts, npts, S, npts,
-                                              div_rows, float(temperature), 1, R * npts, _stream()), "csn_project_f32")
-        return out
-    out = torch.empty((S, R, npts), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().csn_project_f32(_ptr(x), x.stride(0), N, _ptr(w), R, C, _ptr(out), R * npts, npts, S, npts,
-                                          div_rows, float(temperature), x16, 0, _stream()), "csn_project_f32")
+    out = torch.empty((S, 2, R, npts) if split else (S, R, npts), device=x.device, dtype=torch.bfloat16 if split else torch.float32)
+    _lib.check(_lib.lib().csn_project_f32(_ptr(x), x.stride(0), N, _ptr(w), R, C, _ptr(out), (2 if split else 1) * R * npts, npts,
+                                          S, npts, div_rows, float(temperature), 1 if split else x16, R * npts if split else 0,
+                                          _stream()), "csn_project_f32")
     return out
+
+
+def project_ranges(x_all: torch.Tensor, ranges, w: torch.Tensor, rows: int, out_ptr: int, out_size: int, out_slot: int, ld_out: int,
+                   div_rows: int = 0, temperature: float = 1.0, out_split: int = 0, plane_stride: int = 0) -> None:
+    """The first ``rows`` rows of w applied to the slots of ``ranges`` [(first, step, count), ...] (None: every slot), slot s written at
+    out_ptr + out_size * s * out_slot bytes with rows of ld_out elements; the last four arguments as csn_project_f32 takes them."""
+    S, C, NP = x_all.shape
+    for first, step, count in (ranges or [(0, 1, S)]):
+        _lib.check(_lib.lib().csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w), rows, C,
+                                              out_ptr + out_size * first * out_slot, step * out_slot, ld_out, count, NP, div_rows,
+                                              temperature, out_split, plane_stride, _stream()), "csn_project_f32")
 
 
 def project_wgrad(dout: torch.Tensor, x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
@@ -352,6 +394,91 @@ def project_wgrad(dout: torch.Tensor, x: torch.Tensor, scale: float = 1.0) -> to
     _lib.check(_lib.lib().csn_project_wgrad_f32(_ptr(dout), R * NP, NP, _ptr(x), x.stride(0), N, _ptr(dw), R, C, S, NP,
                                                 float(scale), 0, _ptr(ws), ws_n, _stream()), "csn_project_wgrad_f32")
     return dw
+
+
+def project_wgrad_ranges(dout_ptr: int, dout_size: int, dout_slot: int, x_all: torch.Tensor, ranges, dw_ptr: int, rows: int) -> None:
+    """dw (rows, C) at dw_ptr = sum over the slots of ``ranges`` [(first, step, count), ...] of dout[slot] @ x_all[slot]^T, with
+    dout[slot] (rows, NP) at dout_ptr + dout_size * slot * dout_slot bytes: the first range overwrites, the others accumulate."""
+    (S, C, NP), L = x_all.shape, _lib.lib()
+    for i, (first, step, count) in enumerate(ranges):
+        ws_n = L.csn_wgrad_workspace_floats(rows, C, count, NP)
+        ws = torch.empty((ws_n,), device=x_all.device, dtype=torch.float32)
+        _lib.check(L.csn_project_wgrad_f32(dout_ptr + dout_size * first * dout_slot, step * dout_slot, NP,
+                                           x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, dw_ptr, rows, C, count, NP,
+                                           1.0, 0 if i == 0 else 1, _ptr(ws), ws_n, _stream()), "csn_project_wgrad_f32")
+
+
+def operand_ptrs(form: StepForm, qkv: Optional[torch.Tensor], kv: Optional[torch.Tensor], plan: EvalPlan, D: int, NP: int):
+    """-> q_ptr, q_stride, k_ptr, v_ptr, kv_stride, kv_flag, kv_pitch: where the attention calls of a step read Q, K and V (strides
+    per slot, in elements; the values of slot kv + plan.v_shift).  The one place the three operand forms are laid out."""
+    q_ptr = _ptr(qkv)                                  # (None in the folded backward: Q'' is not kept)
+    if form.operands == "maps":                        # fp32 rows Q | K | V of one (S, 3D, NP) tensor
+        stride = 3 * D * NP
+        return q_ptr, stride, q_ptr + 4 * D * NP, q_ptr + 4 * (2 * D * NP + plan.v_shift * stride), stride, 0, 0
+    k_ptr, ldp = kv.data_ptr(), kv.shape[2]
+    if form.operands == "folded":                      # the tile planes of x, (S, C, ldp), as both K and V
+        return q_ptr, D * NP, k_ptr, k_ptr, kv.shape[1] * ldp, 1, ldp
+    kv_stride = 2 * D * ldp                            # tile planes K | V of one (S, 2D, ldp) 16-bit tensor
+    return q_ptr, D * NP, k_ptr, k_ptr + 2 * (D * ldp + plan.v_shift * kv_stride), kv_stride, 1, ldp
+
+
+def _launches(grouped: bool, items, off, n_groups: int, colors, E: int):
+    """[(accumulate, ids, n_ids, group_off, n_groups), ...] of a backward product over evaluations that share output slots: ONE
+    grouped call (a slot's evaluations accumulate in registers), or one call per colour, the first of which overwrites"""
+    if grouped:
+        return [(0, items, E, off, n_groups)]
+    return [(0 if ci == 0 else 1, ids, ids.numel(), None, 0) for ci, ids in enumerate(colors)]
+
+
+def block_attn_fwd(ops, plan: EvalPlan, geo: MHAGeometry, att, scores, lse, p_attn, seed_attn, groups=None) -> None:
+    """csn_block_attn_fwd_f32 on the operands ``ops`` (``operand_ptrs``) — its grouped form where ``groups`` = (items, offsets,
+    n_groups) is given: evaluations that share their query slot run in one work-group, Qs staged once."""
+    q_ptr, q_stride, k_ptr, v_ptr, kv_stride, kv_flag, kv_pitch = ops
+    NP, L = att.shape[2], _lib.lib()
+    args = (q_ptr, k_ptr, v_ptr, q_stride, kv_stride, _ptr(plan.q_slots), _ptr(plan.kv_slots), NP, _ptr(att), geo.d_inner * NP,
+            _ptr(scores), _ptr(lse), plan.E, geo.n_head, geo.d_head, geo.block, geo.n_blocks, geo.score_pitch, RESCALE_THRESHOLD,
+            p_attn, seed_attn, kv_flag, kv_pitch)
+    if groups is None:
+        return _lib.check(L.csn_block_attn_fwd_f32(*args, _stream()), "csn_block_attn_fwd_f32")
+    items, off, n_groups = groups
+    _lib.check(L.csn_block_attn_fwd_grouped_f32(*args, _ptr(items), _ptr(off), n_groups, _stream()), "csn_block_attn_fwd_grouped_f32")
+
+
+def block_attn_bwd_dq(launches, ops, plan: EvalPlan, geo: MHAGeometry, datt, att, scores, dscores, lse, delta, dq_ptr, dq_stride,
+                      p_attn, seed_attn, kv_flag: int, probs_tiles: int) -> None:
+    """csn_block_attn_bwd_dq_f32 once per launch of ``launches`` (``_launches``); dQ of query slot s at dq_ptr + s * dq_stride
+    elements.  kv_flag: that of ``ops``, + 1 where the planes hold fp16 bits."""
+    _, _, k_ptr, v_ptr, kv_stride, _, kv_pitch = ops
+    NP, L = att.shape[2], _lib.lib()
+    for accumulate, ids, n_ids, off, n_groups in launches:
+        _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), geo.d_inner * NP, k_ptr, v_ptr, kv_stride, _ptr(plan.kv_slots),
+                                               NP, _ptr(scores), _ptr(dscores), _ptr(lse), _ptr(delta), dq_ptr, dq_stride,
+                                               _ptr(plan.q_slots), accumulate, _ptr(ids), n_ids, geo.n_head, geo.d_head, geo.block,
+                                               geo.n_blocks, geo.score_pitch, p_attn, seed_attn, 0, 0, kv_flag, kv_pitch,
+                                               probs_tiles, _ptr(off), n_groups, _stream()), "csn_block_attn_bwd_dq_f32")
+
+
+def block_attn_bwd_dkv(launches, ops, plan: EvalPlan, geo: MHAGeometry, datt, scores, dscores, dk_ptr, dv_ptr, slot_stride,
+                       v_slots, pt: int) -> None:
+    """csn_block_attn_bwd_dkv_f32 once per launch: dK (and dV, where dv_ptr / v_slots / scores are given) from the P / dS of the dQ call."""
+    NP, L = datt.shape[2], _lib.lib()
+    for accumulate, ids, n_ids, off, n_groups in launches:
+        _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), geo.d_inner * NP, ops[0], ops[1], _ptr(plan.q_slots), NP, _ptr(scores),
+                                                _ptr(dscores), dk_ptr, dv_ptr, slot_stride, _ptr(plan.kv_slots), _ptr(v_slots),
+                                                accumulate, _ptr(ids), n_ids, geo.n_head, geo.d_head, geo.block, geo.n_blocks,
+                                                geo.score_pitch, 0, 0, 0, 0, pt, _ptr(off), n_groups, _stream()),
+                   "csn_block_attn_bwd_dkv_f32")
+
+
+def outproj_lnb(dense, xhat, rstd, w_fc_t, dz, dz_res, datt, first: int, count: int, p_fc, seed_fc, rows, n_dense: int, scale,
+                group: int, rowdot=None, rowsum=None, red_ws=None, red_ws_n: int = 0) -> None:
+    """csn_outproj_lnb_f32: LayerNorm backward + dCtx of the evaluations [first, first + count) into dz / dz_res / datt (maps of
+    ALL evaluations); rowdot / rowsum / red_ws: the linked mix's reductions on the way (csn_mix_bwd_f32)."""
+    C, NP, D = xhat.shape[1], xhat.shape[2], datt.shape[1]
+    _lib.check(_lib.lib().csn_outproj_lnb_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
+                                              _ptr(datt), first, count, C, D, NP, NP, p_fc, seed_fc, _ptr(rows), n_dense,
+                                              _ptr(scale), group, _ptr(rowdot), _ptr(rowsum), _ptr(red_ws), red_ws_n, _stream()),
+               "csn_outproj_lnb_f32")
 
 
 def retrieval_measure(f1: torch.Tensor, f2: torch.Tensor, pair_budget: int = 2 ** 28) -> torch.Tensor:
@@ -379,6 +506,59 @@ def retrieval_measure(f1: torch.Tensor, f2: torch.Tensor, pair_budget: int = 2 *
 # ------------------------------------------------------------------------------------------------------
 # the differentiable unit: a batch of MHA evaluations over shared, once-projected slots
 # ------------------------------------------------------------------------------------------------------
+_FWD16 = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}                      # type of the forward's maps Qs, Ctx by a16
+
+
+def _project_folded(x_all, w_qkv, w_fc, plan, geo, temperature):
+    """Operands of the folded step -> Q'' (S, D, NP) fp32, the tile planes of x (S, C, ldp) bf16, W_fv, W_fv^T."""
+    (S, C, NP), D, dev, L, ldp = x_all.shape, geo.d_inner, x_all.device, _lib.lib(), geo.n_blocks * 1024
+    w_m, w_fv, w_fv_t = (torch.empty((C, C), device=dev, dtype=torch.float32) for _ in range(3))
+    ws_n = int(L.csn_fold_workspace_floats(D, C))
+    ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+    _lib.check(L.csn_fold_weights_f32(_ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]), _ptr(w_fc), D, C, temperature,
+                                      _ptr(w_m), _ptr(w_fv), _ptr(w_fv_t), _ptr(ws), ws_n, _stream()), "csn_fold_weights_f32")
+    del ws
+    qkv = torch.empty((S, D, NP), device=dev, dtype=torch.float32)                    # Q'' = M x (no temperature left)
+    kv = torch.empty((S, C, ldp), device=dev, dtype=torch.bfloat16)                   # x as tile planes: "K" and "V" at once
+    # (a plan with slot ranges: Q'' of the query slots and planes of the key / value slots only, as the unfolded calls)
+    project_ranges(x_all, plan.q_ranges, w_m, D, qkv.data_ptr(), 4, D * NP, NP)
+    for first, step, count in (plan.kv_ranges or [(0, 1, S)]):
+        _lib.check(L.csn_tile_planes_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP,
+                                         kv.data_ptr() + 2 * first * C * ldp, step * C * ldp, ldp, count, C, NP, geo.block,
+                                         _stream()), "csn_tile_planes_f32")
+    return qkv, kv, w_fv, w_fv_t
+
+
+def _project_tiles(form, x_all, w_qkv, plan, geo, temperature):
+    """16-bit modes -> Qs (S, D, NP), pre-scaled, fp32 or the 16-bit map of form.a16; K | V (S, 2D, ldp) as "tile planes" (per row
+    and block 16 tiles of [hi 32 | lo 32] bf16 in bf16x3, of [32] bf16 / fp16 in the single-product modes), which the attention
+    kernels stage with plain copies (the projection writes the zero padding of every block's last 32-key tile itself)."""
+    S, C, NP = x_all.shape
+    D, T, ldp = geo.d_inner, geo.block, geo.n_blocks * 512 * (2 if form.mode == 1 else 1)
+    qkv = torch.empty((S, D, NP), device=x_all.device, dtype=_FWD16[form.a16])
+    kv = torch.empty((S, 2 * D, ldp), device=x_all.device, dtype=torch.float16 if form.mode == 3 else torch.bfloat16)
+    if form.one_pass:         # Q, K and V of every slot from ONE pass over x (the same bits as the two calls below)
+        _lib.check(_lib.lib().csn_project_qkv_f32(_ptr(x_all), C * NP, NP, _ptr(w_qkv), D, C, _ptr(qkv), D * NP, NP, _ptr(kv),
+                                                  2 * D * ldp, ldp, S, NP, temperature, T, _stream()), "csn_project_qkv_f32")
+    else:
+        project_ranges(x_all, plan.q_ranges, w_qkv, D, qkv.data_ptr(), qkv.element_size(), D * NP, NP, D, temperature,
+                       3 if form.a16 else 0, 0)
+        project_ranges(x_all, plan.kv_ranges, w_qkv[D:], 2 * D, kv.data_ptr(), 2, 2 * D * ldp, ldp, 0, 1.0, 2, T)
+    return qkv, kv
+
+
+def _project_maps(x_all, w_qkv, plan, geo, temperature):
+    """fp32 maps -> Q | K | V (S, 3D, NP), Q rows pre-scaled; of a plan with slot ranges only the (slot, projection) pairs it reads."""
+    (S, C, NP), D = x_all.shape, geo.d_inner
+    if plan.q_ranges is None:
+        return project(x_all, w_qkv, div_rows=D, temperature=temperature)
+    qkv = torch.empty((S, 3 * D, NP), device=x_all.device, dtype=torch.float32)
+    for rows0, nrows, ranges in ((0, D, plan.q_ranges), (D, 2 * D, plan.kv_ranges)):
+        project_ranges(x_all, ranges, w_qkv[rows0:], nrows, qkv.data_ptr() + 4 * rows0 * NP, 4, 3 * D * NP, NP,
+                       D if rows0 == 0 else 0, temperature)
+    return qkv
+
+
 class _MHAEvals(torch.autograd.Function):
     """xhat[e] = LayerNorm_noaffine( fc( BlockAttn(Wq x[q_e] / sqrt(d), Wk x[kv_e], Wv x[kv_e]) ) + x[q_e] ).
 
@@ -386,6 +566,9 @@ class _MHAEvals(torch.autograd.Function):
              q_slots / kv_slots int32 (E,) on the device.
     Output : xhat (E, C, NP).  The LayerNorm affine is applied by the caller (it is plain elementwise torch,
              and the backward needs the un-affined activations anyway).
+
+    Both passes are a fixed sequence of stages; WHICH launches a stage makes is read from ``ctx.form`` (a StepForm, decided once
+    in ``forward``): a new condition of the step goes into ``step_form``, a new operand form beside ``_project_*``.
     """
 
     @staticmethod
@@ -394,217 +577,148 @@ class _MHAEvals(torch.autograd.Function):
         _need_cuda(x_all, w_qs, w_ks, w_vs, w_fc)
         ctx.link = link
         ctx.set_materialize_grads(False)               # an unused output must not cost a zero-filled (E, C, NP) gradient
-        mode = current_mode()
-        if mode >= 2 and geo.block > 512:
-            mode = 1                                   # the single-product kernels take K / V as tile planes (blocks <= 512 keys)
-        ctx.mode = mode
-        # the switches as they stand NOW: the backward (another thread, possibly after an override() block has ended) reads this
-        # snapshot, never the live object — forward and backward of one step always agree (tuning.override is not thread-safe)
-        ctx.tune = tuning.current()
-        # 16-bit activation maps: Qs, Ctx, xhat (and in the backward dZ, dCtx) travel between the launches as one 16-bit plane.
-        # Only where nothing outside this file reads the maps: the linked form (the mix and the pooled sums consume xhat in
-        # kernels, gradients arrive through the link), tile-plane K / V
-        tiles_ok = tuning.current().kv_tiles and geo.block <= 512
-        ctx.a16 = (mode - 1) if (mode >= 2 and tuning.current().act16 and tiles_ok and link is not None and keep_scores) else 0
-        with math_mode(mode), act16(ctx.a16):
-            return _MHAEvals._forward(ctx, x_all, w_qs, w_ks, w_vs, w_fc, plan, geo, keep_scores, p_attn, p_fc, n_head_evals,
-                                      want_sums, link)
+        # ---- 1. the form, from the switches as they stand NOW: the backward (another thread, possibly after an override() block has
+        # ended) reads this snapshot and the form, never the live object — the two passes of a step always agree
+        tune, L, d, T = tuning.current(), _lib.lib(), geo.d_head, geo.block
+        mode = forward_mode(current_mode(), T)
+        with math_mode(mode):
+            with math_mode(backward_mode(mode)):       # (the library's predicates: each asked in the math mode of the pass it speaks of)
+                grouping, dv_scores_ok = L.csn_attn_bwd_grouping(d, T), L.csn_attn_bwd_dv_scores_available(d, T)
+            form = step_form(tune, geo, plan, x_all.shape, w_fc.shape, mode, keep_scores, link is not None, x_all.requires_grad,
+                             grouping, L.csn_attn_bwd_dq_no_planes_available(d, T), dv_scores_ok)
+            ctx.tune, ctx.form = tune, form
+            with act16(form.a16):
+                return _MHAEvals._forward(ctx, form, tune, x_all, w_qs, w_ks, w_vs, w_fc, plan, geo, keep_scores, p_attn, p_fc,
+                                          n_head_evals, want_sums, link)
 
     @staticmethod
-    def _forward(ctx, x_all, w_qs, w_ks, w_vs, w_fc, plan, geo, keep_scores, p_attn, p_fc, n_head_evals, want_sums, link):
+    def _forward(ctx, form, tune, x_all, w_qs, w_ks, w_vs, w_fc, plan, geo, keep_scores, p_attn, p_fc, n_head_evals, want_sums, link):
         # dropout masks are counter-based: two 62-bit seeds from torch's CPU generator (torch.manual_seed reproduces them)
         seed_attn, seed_fc = draw_seeds(2) if (p_attn > 0 or p_fc > 0) else (0, 0)
-        q_slots, kv_slots, v_shift = plan.q_slots, plan.kv_slots, plan.v_shift
         L = _lib.lib()
         S, C, NP = x_all.shape
-        H, d, D = geo.n_head, geo.d_head, geo.d_inner
-        assert NP == geo.n_points and x_all.is_contiguous()
-        assert S == plan.S
-        E = plan.E
-        T, nb, Tp = geo.block, geo.n_blocks, geo.score_pitch
-        NPP = geo.n_padded                                             # (= NP unless the last block is ragged)
+        H, d, D, E, dev = geo.n_head, geo.d_head, geo.d_inner, plan.E, x_all.device
+        T, nb, Tp, NPP = geo.block, geo.n_blocks, geo.score_pitch, geo.n_padded        # (NPP = NP unless the last block is ragged)
+        assert NP == geo.n_points and x_all.is_contiguous() and S == plan.S
         if not (0 < NP <= NPP and NPP - NP < T and NP % 4 == 0):
             raise _lib.CsnError(f"{NP} points do not fill {nb} blocks of {T} (the last block may be short; counts are multiples of 4)")
-        dev = x_all.device
         temperature = geo.temperature or float(d) ** 0.5               # csa_models.py:54
         w_qkv = torch.cat((w_qs, w_ks, w_vs), dim=0).contiguous()      # (3D, C)
-        w_fc_in = w_fc.contiguous()
-        a16 = ctx.a16
-        fwd16 = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}[a16]           # type of the forward's maps Qs, Ctx
-        att = torch.empty((E, D, NP), device=dev, dtype=fwd16)
+        w_fc_in = w_fc = w_fc.contiguous()
+        a16, fold = form.a16, form.operands == "folded"
+        att = torch.empty((E, D, NP), device=dev, dtype=_FWD16[a16])
         lse = torch.empty((E, H, NPP), device=dev, dtype=torch.float32)
-        # values may come from a different slot than the keys (slot kv + v_shift): only the generic
-        # MultiHeadAttention.forward(Q, K, V) with three distinct inputs uses that
-        tiles = fast_math() and tuning.current().kv_tiles and T <= 512
-        # folded projections (csn_hip.h (1b)): one head of the model's width, bias-free layers — W_k goes into W_q,
-        # W_v into W_fc, and the attention runs on the planes of x itself.  Decided from the module, the plan and the tensors alone,
-        # never from the grad mode: a no-grad forward and a training forward give the same logits.  (x_all.requires_grad, not
-        # ctx.needs_input_grad: dx needs dK and dV, and the flag of the tensor is the same in both grad modes)
-        tune = tuning.current()
-        fold = bool(tune.takes_fold() and ctx.mode == 1 and H == 1 and C == d == D == 256 and tiles and not a16
-                    and tuple(w_fc.shape) == (C, D)
-                    and plan.v_shift == 0 and not x_all.requires_grad
-                    and _score_flow(ctx.mode, d, T) == tuning.KEEP_SCORES and L.csn_attn_bwd_dq_no_planes_available(d, T))
-        ctx.fold = fold
-        w_fv = w_fv_t = None
-        if fold:
-            ldp = nb * 1024
-            w_m, w_fv, w_fv_t = (torch.empty((C, C), device=dev, dtype=torch.float32) for _ in range(3))
-            ws_n = int(L.csn_fold_workspace_floats(D, C))
-            ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
-            _lib.check(L.csn_fold_weights_f32(_ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]), _ptr(w_fc.contiguous()), D, C,
-                                              temperature, _ptr(w_m), _ptr(w_fv), _ptr(w_fv_t), _ptr(ws), ws_n, _stream()),
-                       "csn_fold_weights_f32")
-            del ws
-            qkv = torch.empty((S, D, NP), device=dev, dtype=torch.float32)                    # Q'' = M x (no temperature left)
-            kv = torch.empty((S, C, ldp), device=dev, dtype=torch.bfloat16)                   # x as tile planes: "K" and "V" at once
-            # (a plan with slot ranges: Q'' of the query slots and planes of the key / value slots only, as the unfolded calls)
-            for first, step, count in (plan.q_ranges or [(0, 1, S)]):
-                _lib.check(L.csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w_m), D, C,
-                                             qkv.data_ptr() + 4 * first * D * NP, step * D * NP, NP, count, NP, 0, 1.0, 0, 0,
-                                             _stream()), "csn_project_f32")
-            for first, step, count in (plan.kv_ranges or [(0, 1, S)]):
-                _lib.check(L.csn_tile_planes_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP,
-                                                 kv.data_ptr() + 2 * first * C * ldp, step * C * ldp, ldp, count, C, NP, T,
-                                                 _stream()), "csn_tile_planes_f32")
-            q_ptr, q_stride = qkv.data_ptr(), D * NP
-            k_ptr, kv_stride = kv.data_ptr(), C * ldp
-            v_ptr = k_ptr
-            kv_flag, kv_pitch = 1, ldp
-        elif tiles:
-            # 16-bit modes: K and V leave the projection as "tile planes" (per row and block 16 tiles of [hi 32 | lo 32] bf16 in
-            # bf16x3, of [32] bf16 / fp16 in the single-product modes), which the attention kernels stage with plain copies; Q
-            # (pre-scaled) stays fp32
-            npl = planes()
-            ldp = nb * 512 * npl
-            qkv = torch.empty((S, D, NP), device=dev, dtype=fwd16)                            # Qs
-            kv_dtype = torch.float16 if ctx.mode == 3 else torch.bfloat16
-            # (the projection writes the zero padding of every block's last 32-key tile itself)
-            kv = torch.empty((S, 2 * D, ldp), device=dev, dtype=kv_dtype)
-            one_pass = plan.q_ranges is None and plan.kv_ranges is None and not a16 and tuning.current().qkv_one_pass
-            if one_pass:
-                # Q, K and V of every slot from ONE pass over x (csn_project_qkv_f32; the same bits as the two calls below)
-                _lib.check(L.csn_project_qkv_f32(_ptr(x_all), C * NP, NP, _ptr(w_qkv), D, C, _ptr(qkv), D * NP, NP, _ptr(kv),
-                                                 2 * D * ldp, ldp, S, NP, temperature, T, _stream()), "csn_project_qkv_f32")
-            for first, step, count in ([] if one_pass else (plan.q_ranges or [(0, 1, S)])):
-                _lib.check(L.csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w_qkv), D, C,
-                                             qkv.data_ptr() + qkv.element_size() * first * D * NP, step * D * NP, NP, count, NP, D,
-                                             temperature, 3 if a16 else 0, 0, _stream()), "csn_project_f32")
-            for first, step, count in ([] if one_pass else (plan.kv_ranges or [(0, 1, S)])):
-                _lib.check(L.csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w_qkv[D:]), 2 * D, C,
-                                             kv.data_ptr() + 2 * first * 2 * D * ldp, step * 2 * D * ldp, ldp, count, NP, 0, 1.0, 2,
-                                             T, _stream()), "csn_project_f32")
-            q_ptr, q_stride = qkv.data_ptr(), D * NP
-            k_ptr, kv_stride = kv.data_ptr(), 2 * D * ldp
-            v_ptr = k_ptr + 2 * (D * ldp + v_shift * kv_stride)
-            kv_flag, kv_pitch = 1, ldp
+        # ---- 2. the operands (values may come from another slot than the keys, kv + v_shift: only the generic
+        # MultiHeadAttention.forward(Q, K, V) with three distinct inputs uses that)
+        kv = w_fv_t = None
+        if fold:               # (att = P_drop x: the out-projection takes W_fv = W_fc W_v in place of W_fc)
+            qkv, kv, w_fc, w_fv_t = _project_folded(x_all, w_qkv, w_fc, plan, geo, temperature)
+        elif form.operands == "tiles":
+            qkv, kv = _project_tiles(form, x_all, w_qkv, plan, geo, temperature)
         else:
-            kv = None
-            if plan.q_ranges is None:
-                qkv = project(x_all, w_qkv, div_rows=D, temperature=temperature)              # (S, 3D, NP); Q rows pre-scaled
-            else:
-                qkv = torch.empty((S, 3 * D, NP), device=dev, dtype=torch.float32)
-                for rows0, nrows, ranges in ((0, D, plan.q_ranges), (D, 2 * D, plan.kv_ranges)):
-                    for first, step, count in ranges:
-                        _lib.check(L.csn_project_f32(x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(w_qkv[rows0:]),
-                                                     nrows, C, qkv.data_ptr() + 4 * (first * 3 * D + rows0) * NP, step * 3 * D * NP, NP,
-                                                     count, NP, D if rows0 == 0 else 0, temperature, 0, 0, _stream()),
-                                   "csn_project_f32")
-            q_ptr, q_stride = qkv.data_ptr(), 3 * D * NP
-            k_ptr, kv_stride = q_ptr + 4 * D * NP, 3 * D * NP
-            v_ptr = q_ptr + 4 * (2 * D * NP + v_shift * kv_stride)
-            kv_flag, kv_pitch = 0, 0
-        # attention backward data flow: keep the raw scores for it, or only lse (the backward then rebuilds S from Qs and K)
-        flow = _score_flow(ctx.mode, d, T) if (keep_scores and tiles) else tuning.KEEP_SCORES      # (folded: KEEP_SCORES)
-        scores = torch.empty((E, H, nb, T, Tp), device=dev, dtype=torch.float32) if (keep_scores and flow == tuning.KEEP_SCORES) else None
-        # score storage: tile-major where the whole chain (forward, grouped dQ call, grouped dK / dV products on the 256 x 256
-        # tiles) takes it — bf16x3 at d = 256 with kept scores; nothing outside this function reads the buffer
-        tune = tuning.current()
-        ctx.sc_layout = 1 if (scores is not None and tiles and ctx.mode == 1 and tune.tile_major_scores and tune.grouped_dq and
-                              tune.grouped_dkv and Tp >= (T + 31) // 32 * 32 and (L.csn_attn_bwd_grouping(d, T) & 19) == 19) else 0
-        with score_layout(ctx.sc_layout):
-            if tune.grouped_fwd and fast_math() and plan.n_q_groups < E:
-                # evaluations that share their query slot (the query shape's K+2) run in one work-group, Qs staged once
-                _lib.check(L.csn_block_attn_fwd_grouped_f32(q_ptr, k_ptr, v_ptr, q_stride, kv_stride,
-                                                            _ptr(q_slots), _ptr(kv_slots), NP, _ptr(att), D * NP, _ptr(scores),
-                                                            _ptr(lse), E, H, d, T, nb, Tp, RESCALE_THRESHOLD, p_attn, seed_attn,
-                                                            kv_flag, kv_pitch, _ptr(plan.q_group_items), _ptr(plan.q_group_off),
-                                                            plan.n_q_groups, _stream()),
-                           "csn_block_attn_fwd_grouped_f32")
-            else:
-                _lib.check(L.csn_block_attn_fwd_f32(q_ptr, k_ptr, v_ptr, q_stride, kv_stride,
-                                                    _ptr(q_slots), _ptr(kv_slots), NP, _ptr(att), D * NP, _ptr(scores),
-                                                    _ptr(lse), E, H, d, T, nb, Tp, RESCALE_THRESHOLD, p_attn, seed_attn,
-                                                    kv_flag, kv_pitch, _stream()),
-                           "csn_block_attn_fwd_f32")
+            qkv = _project_maps(x_all, w_qkv, plan, geo, temperature)
+        # ---- 3. attention
+        scores = torch.empty((E, H, nb, T, Tp), device=dev, dtype=torch.float32) if form.scores else None
+        with score_layout(form.sc_layout):
+            block_attn_fwd(operand_ptrs(form, qkv, kv, plan, D, NP), plan, geo, att, scores, lse, p_attn, seed_attn,
+                           (plan.q_group_items, plan.q_group_off, plan.n_q_groups) if form.grouped_fwd else None)
+        # ---- 4. out-projection + LayerNorm
         xhat = torch.empty((E, C, NP), device=dev, dtype=torch.float16 if a16 else torch.float32)
         rstd = torch.empty((E, NP), device=dev, dtype=torch.float32)
-        w_fc = w_fv if fold else w_fc.contiguous()                     # (folded: att = P_drop x, the out-projection takes W_fc W_v)
         # third output (want_sums): sums[e][c] = sum_n xhat[e][c][n], formed in the epilogue of the out-projection (per-tile
         # partials in sum_ws) instead of a separate streaming pass over the 2.6 GB of maps
         sums = torch.empty((E, C), device=dev, dtype=torch.float32) if want_sums else None
-        sum_ws_n = int(L.csn_outproj_ln_workspace_floats(E, C, D, NP)) if (want_sums and tuning.current().fused_point_sums) else 0
+        sum_ws_n = int(L.csn_outproj_ln_workspace_floats(E, C, D, NP)) if (want_sums and tune.fused_point_sums) else 0
         sum_ws = torch.empty((sum_ws_n,), device=dev, dtype=torch.float32) if sum_ws_n else None
-        _lib.check(L.csn_outproj_ln_fwd_f32(_ptr(att), D * NP, _ptr(w_fc), _ptr(x_all), C * NP, _ptr(q_slots),
+        _lib.check(L.csn_outproj_ln_fwd_f32(_ptr(att), D * NP, _ptr(w_fc), _ptr(x_all), C * NP, _ptr(plan.q_slots),
                                             _ptr(xhat), C * NP, _ptr(rstd), E, C, D, NP, NP, LN_EPS, p_fc, seed_fc,
-                                            _ptr(sums), _ptr(sum_ws), sum_ws_n, _stream()),
-                   "csn_outproj_ln_fwd_f32")
+                                            _ptr(sums), _ptr(sum_ws), sum_ws_n, _stream()), "csn_outproj_ln_fwd_f32")
         del sum_ws
-        if (keep_scores and link is not None and not a16 and tuning.current().fused_mix_bwd and plan.mixed_not_pooled
-                and n_head_evals > 0):
+        # ---- 5. what the backward needs
+        if keep_scores and link is not None and not a16 and tune.fused_mix_bwd and plan.mixed_not_pooled and n_head_evals > 0:
             # the mix's backward may run the LayerNorm backward of the leading evaluations itself (_lnb_head)
-            link.pre = (xhat, rstd, w_fc, p_fc, seed_fc, n_head_evals, ctx.mode, bool(x_all.requires_grad), w_fv_t)
+            link.pre = (xhat, rstd, w_fc, p_fc, seed_fc, n_head_evals, form.mode, bool(x_all.requires_grad), w_fv_t)
         if keep_scores:
             # (folded: w_fc is W_fv — the unfolding reads W_fc back from the autograd inputs' copy below; Q'' is not needed again)
             ctx.save_for_backward(x_all, w_qkv, w_fc, None if fold else qkv, att, lse, scores, xhat, rstd, kv, w_fv_t,
                                   w_fc_in if fold else None)
-            ctx.flow = flow
-            ctx.geo = geo
-            ctx.plan = plan
-            ctx.drop = (p_attn, seed_attn, p_fc, seed_fc)
-            ctx.ptrs = (q_stride, kv_stride, kv_flag, kv_pitch)
-        # second output: the first n_head_evals maps again (same storage).  A consumer of all maps whose gradient is
-        # constant along the points (the pooled means) and a consumer of the leading maps only (the mix) then hand the
-        # backward two cheap gradients instead of one dense (E, C, NP) sum.
+            ctx.geo, ctx.plan, ctx.drop = geo, plan, (p_attn, seed_attn, p_fc, seed_fc)
+        # second output: the first n_head_evals maps again (same storage).  A consumer of all maps whose gradient is constant along the
+        # points (the pooled means) and one of the leading maps only (the mix) then hand the backward two cheap gradients, not a dense sum
         ctx.n_head = n_head_evals
         # fourth output: a one-element handle.  A linked mix (csa_mix on LinkedMaps) takes IT as its differentiable input
         # and leaves the gradient of the mixed features in ctx.link instead of returning per-evaluation gradient maps
         handle = x_all.new_zeros(1) if link is not None else None
+        head = xhat[:n_head_evals]
         if a16:
-            # fp16 maps are data for the linked mix and nothing else: gradients reach this function through the link, the sums
-            # and the handle, never through the maps
-            head = xhat[:n_head_evals]
+            # fp16 maps are data for the linked mix alone: gradients arrive through the link, the sums and the handle, never the maps
             ctx.mark_non_differentiable(xhat, head)
-            return xhat, head, sums, handle
-        return xhat, xhat[:n_head_evals], sums, handle
+        return xhat, head, sums, handle
 
     @staticmethod
     def backward(ctx, dxhat, dhead, dsums=None, dhandle=None):
-        with math_mode(backward_mode(ctx.mode)):
-            # 16-bit maps: the gradient maps dQ / dK / dV too, where every slot is written once (grouped calls, flash)
-            g16 = 0
-            if ctx.a16:
-                geo, tune = ctx.geo, ctx.tune
-                grouping = _lib.lib().csn_attn_bwd_grouping(geo.d_head, geo.block)
-                dq_once = ctx.flow != tuning.KEEP_SCORES or (tune.grouped_dq and (grouping & 1))
-                dkv_once = ctx.flow == tuning.FLASH or (tune.grouped_dkv and (grouping & 2))
-                g16 = 4 if (dq_once and dkv_once) else 0
-            ctx.g16 = g16
-            with act16(ctx.a16 + g16), score_layout(getattr(ctx, "sc_layout", 0)):
-                return _MHAEvals._backward(ctx, dxhat, dhead, dsums, dhandle)
+        need_dx = ctx.needs_input_grad[0]
+        form = replace(ctx.form, ranged=ctx.plan.q_ranges is not None and not need_dx)
+        with math_mode(form.bwd_mode), act16(form.a16 + form.g16), score_layout(form.sc_layout):
+            return _MHAEvals._backward(ctx, form, need_dx, dxhat, dhead, dsums, dhandle)
 
     @staticmethod
-    def _backward(ctx, dxhat, dhead, dsums=None, dhandle=None):
+    def _backward(ctx, form, need_dx, dxhat, dhead, dsums, dhandle):
+        # (a scratch tensor that must die before this function ends is deleted HERE by name: a stage cannot end the life of its arguments)
         x_all, w_qkv, w_fc, qkv, att, lse, scores, xhat, rstd, kv, w_fv_t, w_fc_in = ctx.saved_tensors
-        geo: MHAGeometry = ctx.geo
-        plan: EvalPlan = ctx.plan
-        L = _lib.lib()
+        geo, plan = ctx.geo, ctx.plan
         S, C, NP = x_all.shape
-        H, d, D = geo.n_head, geo.d_head, geo.d_inner
-        E = plan.E
-        T, nb, Tp = geo.block, geo.n_blocks, geo.score_pitch
-        dev = x_all.device
-        # incoming gradient = dense maps for the first n_dense evaluations + a per-row constant (gradient of a mean)
+        D, dev, folded = geo.d_inner, x_all.device, form.operands == "folded"
+        temperature = geo.temperature or float(geo.d_head) ** 0.5
+        # ---- 1. the incoming gradient
+        dense, rows, n_dense, scale, group, head_done = _MHAEvals._merge_incoming(ctx, plan.E, dxhat, dhead, dsums, dhandle)
+        # ---- 2. LayerNorm + fc backward (folded: dCtx' = dz W_fv, dw_fc is dW_fv)
+        w_fc_t = head_done[3] if head_done is not None else (w_fv_t if folded else w_fc.t().contiguous())
+        dz, dz_res, datt, dw_fc = _MHAEvals._outproj_backward(ctx, form, need_dx, geo, att, xhat, rstd, w_fc_t, dense, rows, n_dense,
+                                                              scale, group, head_done)
+        # ---- 3. attention backward, 4. weight gradients: folded ...
+        if folded:
+            g = _MHAEvals._dq_folded(ctx, form, geo, plan, att, lse, scores, kv, datt)
+            del datt
+            if plan.q_ranges is None:
+                d_m = project_wgrad(g, x_all)                           # dM = sum_slots G x^T
+            else:                                                       # ... over the query slots of the plan's ranges only
+                d_m = torch.empty((D, C), device=dev, dtype=torch.float32)
+                project_wgrad_ranges(g.data_ptr(), 4, D * NP, x_all, plan.q_ranges, _ptr(d_m), D)
+            del g
+            dw_qkv = torch.empty((3 * D, C), device=dev, dtype=torch.float32)
+            dw_fc_in = torch.empty((C, D), device=dev, dtype=torch.float32)
+            ws = torch.empty((D * C,), device=dev, dtype=torch.float32)
+            _lib.check(_lib.lib().csn_unfold_wgrads_f32(_ptr(d_m), _ptr(dw_fc), _ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]),
+                                                        _ptr(w_fc_in), D, C, temperature, _ptr(dw_qkv), _ptr(dw_qkv[D:]),
+                                                        _ptr(dw_qkv[2 * D:]), _ptr(dw_fc_in), _ptr(ws), D * C, _stream()),
+                       "csn_unfold_wgrads_f32")
+            return (None, dw_qkv[:D], dw_qkv[D:2 * D], dw_qkv[2 * D:], dw_fc_in, None, None, None, None, None, None, None, None)
+        dqkv = _MHAEvals._attn_backward(ctx, form, geo, plan, qkv, kv, att, lse, scores, datt)
+        del datt
+        # the weight gradients contract every slot's gradient maps — or, for a plan with slot ranges (and no input gradients
+        # wanted), only the ranges: the maps of the other (slot, projection) pairs are then neither cleared nor read
+        if form.ranged:
+            dw_qkv, ges = torch.empty((3 * D, C), device=dev, dtype=torch.float32), dqkv.element_size()
+            for rows0, nrows, ranges in ((0, D, plan.q_ranges), (D, 2 * D, plan.kv_ranges)):
+                project_wgrad_ranges(dqkv.data_ptr() + ges * rows0 * NP, ges, 3 * D * NP, x_all, ranges,
+                                     dw_qkv.data_ptr() + 4 * rows0 * C, nrows)
+        else:
+            dw_qkv = project_wgrad(dqkv, x_all)
+        dw_q = dw_qkv[:D] / temperature               # Qs = (x Wq^T) / sqrt(d)  (csa_models.py:139)
+        dw_k, dw_v = dw_qkv[D:2 * D], dw_qkv[2 * D:]
+        dx_all = None
+        if need_dx:
+            # residual path + the three projections (not needed by the reference's training: inputs are constants)
+            dqkv[:, :D] /= temperature
+            dx_all = project(dqkv, w_qkv.t().contiguous())                   # (bf16 gradient maps: read as such)
+            dx_all.index_add_(0, plan.q_slots.long(), dz if dz_res is None else dz_res)
+        return dx_all, dw_q, dw_k, dw_v, dw_fc, None, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _merge_incoming(ctx, E, dxhat, dhead, dsums, dhandle):
+        """The incoming gradient as the LayerNorm backward takes it -> dense, rows, n_dense, scale, group, head_done: dense maps
+        for the first n_dense evaluations + a per-row constant ``rows`` (the gradient of a mean)."""
         rows = None
         if dxhat is not None and dxhat.stride(2) == 0 and dxhat.stride(1) == 1:
             rows, dxhat = dxhat[:, :, 0].contiguous(), None              # expanded (E, C, 1) -> (E, C)
@@ -628,8 +742,8 @@ class _MHAEvals(torch.autograd.Function):
         if dhandle is not None and link is not None and link.dfeats is not None:
             if dense is None:
                 dense, scale, group, n_dense = link.dfeats, link.scale, link.group, ctx.n_head
-            else:
-                head_done = None                                         # (the launch below writes every evaluation again)                                                        # somebody also used the maps densely: materialise
+            else:                                                        # somebody also used the maps densely: materialise
+                head_done = None                                         # (the launch below writes every evaluation again)
                 dense = dense.clone() if dense.shape[0] == E else torch.cat(
                     (dense, dense.new_zeros((E - dense.shape[0],) + tuple(dense.shape[1:]))), dim=0)
                 dense[:ctx.n_head] += link.scale[:, :, None] * link.dfeats.repeat_interleave(link.group, dim=0)[:ctx.n_head]
@@ -637,86 +751,57 @@ class _MHAEvals(torch.autograd.Function):
             link.dfeats = link.scale = None
         else:
             head_done = None
-        temperature = geo.temperature or float(d) ** 0.5
-        p_attn, seed_attn, p_fc, seed_fc = ctx.drop
-        need_dx = ctx.needs_input_grad[0]
+        return dense, rows, n_dense, scale, group, head_done
 
-        # ---- LayerNorm + fc backward -------------------------------------------------------------------
-        a16 = ctx.a16
-        bwd16 = torch.bfloat16 if a16 else torch.float32               # type of the backward's maps dZ, dCtx
-        dw_fc = torch.empty((C, D), device=dev, dtype=torch.float32)
-        ws_n = L.csn_wgrad_workspace_floats(C, D, E, NP)
-        ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+    @staticmethod
+    def _outproj_backward(ctx, form, need_dx, geo, att, xhat, rstd, w_fc_t, dense, rows, n_dense, scale, group, head_done):
+        """LayerNorm + fc backward -> dz, dz_res, dCtx, dW_fc (folded: w_fc_t is W_fv^T and the weight gradient dW_fv)."""
+        (E, C, NP), L = xhat.shape, _lib.lib()
+        D, dev, (p_fc, seed_fc) = geo.d_inner, xhat.device, ctx.drop[2:]
         if head_done is not None:
             # the mix's backward has run the leading evaluations (and taken its reductions from them): the others with the row
             # constants, then the W_fc gradient over all of dz — the pieces of csn_outproj_ln_bwd_f32, the same bits
-            dz, dz_res, datt, w_fc_t = head_done
+            dz, dz_res, datt, _ = head_done
             if E > ctx.n_head:
-                _lib.check(L.csn_outproj_lnb_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
-                                                 _ptr(datt), ctx.n_head, E - ctx.n_head, C, D, NP, NP, p_fc, seed_fc, _ptr(rows),
-                                                 n_dense, _ptr(scale), group, None, None, None, 0, _stream()),
-                           "csn_outproj_lnb_f32")
-            _lib.check(L.csn_project_wgrad_f32(_ptr(dz), C * NP, NP, _ptr(att), D * NP, NP, _ptr(dw_fc), C, D, E, NP, 1.0, 0,
-                                               _ptr(ws), ws_n, _stream()), "csn_project_wgrad_f32")
-        else:
-            dz = torch.empty((E, C, NP), device=dev, dtype=bwd16)
-            dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and (p_fc > 0 or a16)) else None
-            datt = torch.empty((E, D, NP), device=dev, dtype=bwd16)
-            w_fc_t = w_fv_t if ctx.fold else w_fc.t().contiguous()       # (folded: dCtx' = dz W_fv, dw_fc below is dW_fv)
-            _lib.check(L.csn_outproj_ln_bwd_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(att), D * NP,
-                                                _ptr(w_fc_t), _ptr(dz), _ptr(dz_res), _ptr(datt), _ptr(dw_fc), _ptr(ws), ws_n,
-                                                E, C, D, NP, NP, 0, p_fc, seed_fc, 0, 0, _ptr(rows), n_dense, _ptr(scale), group,
-                                                _stream()),
-                       "csn_outproj_ln_bwd_f32")
-        del ws
+                outproj_lnb(dense, xhat, rstd, w_fc_t, dz, dz_res, datt, ctx.n_head, E - ctx.n_head, p_fc, seed_fc, rows, n_dense,
+                            scale, group)
+            return dz, dz_res, datt, project_wgrad(dz, att)
+        dw_fc = torch.empty((C, D), device=dev, dtype=torch.float32)
+        ws_n = L.csn_wgrad_workspace_floats(C, D, E, NP)
+        ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
+        bwd16 = torch.bfloat16 if form.a16 else torch.float32       # type of the backward's maps dZ, dCtx
+        dz = torch.empty((E, C, NP), device=dev, dtype=bwd16)
+        dz_res = torch.empty((E, C, NP), device=dev, dtype=torch.float32) if (need_dx and (p_fc > 0 or form.a16)) else None
+        datt = torch.empty((E, D, NP), device=dev, dtype=bwd16)
+        _lib.check(L.csn_outproj_ln_bwd_f32(_ptr(dense), _ptr(xhat), _ptr(rstd), C * NP, _ptr(att), D * NP, _ptr(w_fc_t), _ptr(dz),
+                                            _ptr(dz_res), _ptr(datt), _ptr(dw_fc), _ptr(ws), ws_n, E, C, D, NP, NP, 0, p_fc, seed_fc,
+                                            0, 0, _ptr(rows), n_dense, _ptr(scale), group, _stream()), "csn_outproj_ln_bwd_f32")
+        return dz, dz_res, datt, dw_fc
 
-        # ---- attention backward, straight into per-slot gradient maps ---------------------------------------
-        # evaluations that share a slot (Q of the query shape, K/V of each neighbour) add up: one launch per colour
-        if ctx.fold:
-            # folded projections: one grouped dQ call on the planes of x (K = V = x), nothing score-sized written; G = dS x per
-            # query slot is the gradient of Q'' = M x, so dM is the 256-row weight gradient over (G, x) — no dK / dV products, no
-            # dscores, no 3 D-row gradient map.  (grouped_dq off: the same call colour by colour — the switch selects how dQ is
-            # accumulated, as in the unfolded step, not whether the step folds)
-            # (delta, the row constant of the softmax backward, stays in the kernel's registers: nothing reads the map here)
-            g = torch.empty((S, D, NP), device=dev, dtype=torch.float32)
-            if plan.q_ranges is None and plan.q_unwritten.numel():
-                g.index_fill_(0, plan.q_unwritten, 0.0)
-            q_stride, kv_stride, kv_flag, kv_pitch = ctx.ptrs
-            if ctx.tune.grouped_dq and (L.csn_attn_bwd_grouping(d, T) & 1):
-                launches = [(0, plan.q_group_items, E, plan.q_group_off, plan.n_q_groups)]
-            else:
-                launches = [(0 if ci == 0 else 1, ids, ids.numel(), None, 0) for ci, ids in enumerate(plan.dq_colors)]
-            L.csn_dev_set(_lib.DEV_KV_SAME, int(bool(ctx.tune.kv_same)))     # (process-wide, like the switches themselves)
-            L.csn_dev_set(_lib.DEV_ATTN_WG64, int(bool(ctx.tune.wg64)))
-            for accumulate, ids, n_ids, off, n_groups in launches:
-                _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, _ptr(kv), _ptr(kv), kv_stride,
-                                                       _ptr(plan.kv_slots), NP, _ptr(scores), None, _ptr(lse), None,
-                                                       _ptr(g), D * NP, _ptr(plan.q_slots), accumulate, _ptr(ids), n_ids, H, d, T,
-                                                       nb, Tp, p_attn, seed_attn, 0, 0, kv_flag, kv_pitch, 3, _ptr(off), n_groups,
-                                                       _stream()), "csn_block_attn_bwd_dq_f32")
-            del datt
-            if plan.q_ranges is None:
-                d_m = project_wgrad(g, x_all)                           # dM = sum_slots G x^T
-            else:                                                       # ... over the query slots of the plan's ranges only
-                d_m = torch.empty((D, C), device=dev, dtype=torch.float32)
-                for i, (first, step, count) in enumerate(plan.q_ranges):
-                    ws_n = L.csn_wgrad_workspace_floats(D, C, count, NP)
-                    ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
-                    _lib.check(L.csn_project_wgrad_f32(g.data_ptr() + 4 * first * D * NP, step * D * NP, NP,
-                                                       x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP, _ptr(d_m), D, C,
-                                                       count, NP, 1.0, 0 if i == 0 else 1, _ptr(ws), ws_n, _stream()),
-                               "csn_project_wgrad_f32")
-            del g
-            dw_qkv = torch.empty((3 * D, C), device=dev, dtype=torch.float32)
-            dw_fc_in = torch.empty((C, D), device=dev, dtype=torch.float32)
-            ws = torch.empty((D * C,), device=dev, dtype=torch.float32)
-            _lib.check(L.csn_unfold_wgrads_f32(_ptr(d_m), _ptr(dw_fc), _ptr(w_qkv), _ptr(w_qkv[D:]), _ptr(w_qkv[2 * D:]),
-                                               _ptr(w_fc_in), D, C, temperature, _ptr(dw_qkv), _ptr(dw_qkv[D:]),
-                                               _ptr(dw_qkv[2 * D:]), _ptr(dw_fc_in), _ptr(ws), D * C, _stream()),
-                       "csn_unfold_wgrads_f32")
-            return (None, dw_qkv[:D], dw_qkv[D:2 * D], dw_qkv[2 * D:], dw_fc_in, None, None, None, None, None, None, None, None)
-        flow = ctx.flow
-        pt = 1 if (fast_math() and Tp >= (T + 31) // 32 * 32) else 0    # P / dS travel to the dV / dK products as tile planes
+    @staticmethod
+    def _dq_folded(ctx, form, geo, plan, att, lse, scores, kv, datt):
+        """The folded attention backward -> G (S, D, NP): dQ calls on the planes of x (K = V = x), nothing score-sized written.  G = dS x
+        per query slot is the gradient of Q'' = M x, so dM is the 256-row weight gradient over (G, x) — no dK / dV products, no dscores,
+        no 3 D-row gradient map.  (grouped_dq off: the same call colour by colour — the switch selects how dQ is accumulated, not whether
+        the step folds.  delta, the row constant of the softmax backward, stays in the kernel's registers: nothing reads the map here)"""
+        (E, D, NP), L = att.shape, _lib.lib()
+        g = torch.empty((plan.S, D, NP), device=att.device, dtype=torch.float32)
+        if plan.q_ranges is None and plan.q_unwritten.numel():
+            g.index_fill_(0, plan.q_unwritten, 0.0)
+        launches = _launches(form.dq_grouped, plan.q_group_items, plan.q_group_off, plan.n_q_groups, plan.dq_colors, E)
+        L.csn_dev_set(_lib.DEV_KV_SAME, int(bool(ctx.tune.kv_same)))     # (process-wide, like the switches themselves)
+        L.csn_dev_set(_lib.DEV_ATTN_WG64, int(bool(ctx.tune.wg64)))
+        ops = operand_ptrs(form, None, kv, plan, D, NP)
+        block_attn_bwd_dq(launches, ops, plan, geo, datt, att, scores, None, lse, None, _ptr(g), D * NP, *ctx.drop[:2], ops[5], 3)
+        return g
+
+    @staticmethod
+    def _attn_backward(ctx, form, geo, plan, qkv, kv, att, lse, scores, datt):
+        """The unfolded attention backward, straight into the per-slot gradient maps dQ | dK | dV (S, 3D, NP), which it returns.
+        Evaluations that share a slot (Q of the query shape, K / V of each neighbour) add up: one grouped call, or a launch per colour."""
+        (E, D, NP), L, dev = att.shape, _lib.lib(), att.device
+        S, H, d, T, nb, Tp = plan.S, geo.n_head, geo.d_head, geo.block, geo.n_blocks, geo.score_pitch
+        (p_attn, seed_attn), flow, pt, kv_f16 = ctx.drop[:2], form.flow, form.pt, form.kv_f16
         # (bf16x3: P overwrites the scores in place, dS fills `dscores`; bf16: both go to `dscores` as compact rows and the
         #  dK / dV call reads them there — csn_hip.h (3))
         if flow == tuning.KEEP_SCORES:
@@ -725,131 +810,50 @@ class _MHAEvals(torch.autograd.Function):
             # recomputed scores: `scores` is only the scratch the P planes travel in (two-plane mode), `dscores` that of dS
             # (+ P in the one-plane mode); the flash flow has neither
             assert pt == 1 and scores is None
-            shape = (E, H, nb, T, Tp)
             travel = flow == tuning.RECOMPUTE_DQ
-            scores = torch.empty(shape, device=dev, dtype=torch.float32) if (travel and planes() == 2) else None
-            dscores = torch.empty(shape, device=dev, dtype=torch.float32) if travel else None
+            scores = torch.empty((E, H, nb, T, Tp), device=dev, dtype=torch.float32) if (travel and form.bwd_mode == 1) else None
+            dscores = torch.empty((E, H, nb, T, Tp), device=dev, dtype=torch.float32) if travel else None
         delta = torch.empty((E, H, geo.n_padded), device=dev, dtype=torch.float32)
-        dqkv = torch.empty((S, 3 * D, NP), device=dev, dtype=torch.bfloat16 if ctx.g16 else torch.float32)
-        ges = dqkv.element_size()
-        # the weight gradients contract every slot's gradient maps — or, for a plan with slot ranges (and no input gradients
-        # wanted), only the ranges: the maps of the other (slot, projection) pairs are then neither cleared nor read
-        ranged = plan.q_ranges is not None and not need_dx
-        if not ranged:
-            if plan.q_unwritten.numel():
-                dqkv[:, :D].index_fill_(0, plan.q_unwritten, 0.0)
-            if plan.k_unwritten.numel():
-                dqkv[:, D:2 * D].index_fill_(0, plan.k_unwritten, 0.0)
-            if plan.v_unwritten.numel():
-                dqkv[:, 2 * D:].index_fill_(0, plan.v_unwritten, 0.0)
-        slot_stride = 3 * D * NP                                   # of the gradient maps, in elements
-        q_stride, kv_stride, kv_flag, kv_pitch = ctx.ptrs
-        gbase, q_ptr = dqkv.data_ptr(), qkv.data_ptr()
-        # fp16 forward / bf16 backward: the forward's K / V planes hold fp16 bits; the attention backward kernels convert every
-        # piece to bf16 in registers while they stage it (no second projection of K and V)
-        kv_f16 = 1 if (kv_flag and ctx.mode == 3) else 0
-        if kv_flag:
-            k_ptr = kv.data_ptr()
-            v_ptr = k_ptr + 2 * (D * kv_pitch + plan.v_shift * kv_stride)
-        else:
-            k_ptr = q_ptr + 4 * D * NP
-            v_ptr = q_ptr + 4 * (2 * D * NP + plan.v_shift * kv_stride)
-        grouping = L.csn_attn_bwd_grouping(d, T)
-        tune = ctx.tune                                              # the forward's snapshot
-        # kept scores in two planes, both grouped calls (either score layout): dV from the scores, dK alone on the plane product
-        dv_scores = bool(tune.dv_from_scores and flow == tuning.KEEP_SCORES and ctx.mode == 1 and pt == 1 and kv_flag == 1
-                         and not a16 and not ctx.g16 and tune.grouped_dq and tune.grouped_dkv and (grouping & 3) == 3
-                         and L.csn_attn_bwd_dv_scores_available(d, T))
+        dqkv = torch.empty((S, 3 * D, NP), device=dev, dtype=torch.bfloat16 if form.g16 else torch.float32)
+        for rows0, unwritten in ((0, plan.q_unwritten), (D, plan.k_unwritten), (2 * D, plan.v_unwritten)):
+            if not form.ranged and unwritten.numel():
+                dqkv[:, rows0:rows0 + D].index_fill_(0, unwritten, 0.0)
+        slot_stride, ges, gbase = 3 * D * NP, dqkv.element_size(), dqkv.data_ptr()     # (the stride in elements)
+        dk_ptr, dv_ptr = gbase + ges * D * NP, gbase + 2 * ges * D * NP
+        ops = q_ptr, q_stride, k_ptr, v_ptr, kv_stride, kv_flag, kv_pitch = operand_ptrs(form, qkv, kv, plan, D, NP)
         if flow != tuning.KEEP_SCORES:
             # one grouped call, scores rebuilt from the pre-scaled queries of the evaluation's query slot
-            _lib.check(L.csn_block_attn_bwd_dq_recompute_f32(_ptr(datt), _ptr(att), D * NP, q_ptr, q_stride, _ptr(plan.q_slots),
-                                                             k_ptr, v_ptr, kv_stride, _ptr(plan.kv_slots), NP, _ptr(scores),
-                                                             _ptr(dscores), _ptr(lse), _ptr(delta), gbase, slot_stride,
-                                                             _ptr(plan.q_slots), 0, _ptr(plan.q_group_items), E, H, d, T, nb, Tp,
-                                                             p_attn, seed_attn, kv_pitch, kv_f16, pt if flow == tuning.RECOMPUTE_DQ else 0,
-                                                             _ptr(plan.q_group_off), plan.n_q_groups, _stream()),
-                       "csn_block_attn_bwd_dq_recompute_f32")
-        elif tune.grouped_dq and (grouping & 1):
-            # one call: the evaluations of a query slot run one after the other into the same dQ accumulators
-            # (dV from the scores: the call leaves the dS planes only and the scores as the forward wrote them)
-            _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, k_ptr, v_ptr, kv_stride,
-                                                   _ptr(plan.kv_slots), NP, _ptr(scores), _ptr(dscores), _ptr(lse),
-                                                   _ptr(delta), gbase, slot_stride, _ptr(plan.q_slots), 0,
-                                                   _ptr(plan.q_group_items), E, H, d, T, nb, Tp, p_attn, seed_attn, 0, 0,
-                                                   kv_flag + kv_f16, kv_pitch, 2 if dv_scores else pt, _ptr(plan.q_group_off),
-                                                   plan.n_q_groups, _stream()),
-                       "csn_block_attn_bwd_dq_f32")
+            _lib.check(L.csn_block_attn_bwd_dq_recompute_f32(
+                _ptr(datt), _ptr(att), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), k_ptr, v_ptr, kv_stride, _ptr(plan.kv_slots), NP,
+                _ptr(scores), _ptr(dscores), _ptr(lse), _ptr(delta), gbase, slot_stride, _ptr(plan.q_slots), 0,
+                _ptr(plan.q_group_items), E, H, d, T, nb, Tp, p_attn, seed_attn, kv_pitch, kv_f16,
+                pt if flow == tuning.RECOMPUTE_DQ else 0, _ptr(plan.q_group_off), plan.n_q_groups, _stream()),
+                "csn_block_attn_bwd_dq_recompute_f32")
         else:
-            for ci, ids in enumerate(plan.dq_colors):
-                _lib.check(L.csn_block_attn_bwd_dq_f32(_ptr(datt), _ptr(att), D * NP, k_ptr, v_ptr, kv_stride,
-                                                       _ptr(plan.kv_slots), NP, _ptr(scores), _ptr(dscores), _ptr(lse),
-                                                       _ptr(delta), gbase, slot_stride, _ptr(plan.q_slots),
-                                                       0 if ci == 0 else 1, _ptr(ids),
-                                                       ids.numel(), H, d, T, nb, Tp, p_attn, seed_attn, 0, 0, kv_flag + kv_f16,
-                                                       kv_pitch, pt, None, 0, _stream()),
-                           "csn_block_attn_bwd_dq_f32")
+            # (dV from the scores: the call leaves the dS planes only and the scores as the forward wrote them)
+            launches = _launches(form.dq_grouped, plan.q_group_items, plan.q_group_off, plan.n_q_groups, plan.dq_colors, E)
+            block_attn_bwd_dq(launches, ops, plan, geo, datt, att, scores, dscores, lse, delta, gbase, slot_stride, p_attn,
+                              seed_attn, kv_flag + kv_f16, 2 if form.dv_scores else pt)
         if flow == tuning.FLASH:
             # key-stationary kernel: P and dS are rebuilt per (key/value slot, head, block, 128 keys) from lse, delta and the
             # masks' seed; the evaluations of a key/value slot accumulate in registers (grouped) — no score-sized tensor exists
-            _lib.check(L.csn_block_attn_bwd_dkv_flash_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), k_ptr, v_ptr,
-                                                          kv_stride, _ptr(plan.kv_slots), kv_pitch, kv_f16, NP, _ptr(lse), _ptr(delta),
-                                                          gbase + ges * D * NP, gbase + 2 * ges * D * NP, slot_stride,
-                                                          _ptr(plan.kv_slots), _ptr(plan.v_slots), 0, _ptr(plan.kv_group_items),
-                                                          E, H, d, T, nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off),
-                                                          plan.n_kv_groups, _stream()), "csn_block_attn_bwd_dkv_flash_f32")
-        elif dv_scores:
+            _lib.check(L.csn_block_attn_bwd_dkv_flash_f32(
+                _ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), k_ptr, v_ptr, kv_stride, _ptr(plan.kv_slots), kv_pitch,
+                kv_f16, NP, _ptr(lse), _ptr(delta), dk_ptr, dv_ptr, slot_stride, _ptr(plan.kv_slots), _ptr(plan.v_slots), 0,
+                _ptr(plan.kv_group_items), E, H, d, T, nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off), plan.n_kv_groups,
+                _stream()), "csn_block_attn_bwd_dkv_flash_f32")
+            return dqkv
+        launches = _launches(form.dkv_grouped, plan.kv_group_items, plan.kv_group_off, plan.n_kv_groups, plan.dkv_colors, E)
+        if form.dv_scores:
             # dV: key-stationary, P rebuilt from the untouched scores; then the grouped plane product for dK alone
-            _lib.check(L.csn_block_attn_bwd_dv_scores_f32(_ptr(datt), D * NP, NP, _ptr(scores), _ptr(lse), gbase + 2 * ges * D * NP,
-                                                          slot_stride, _ptr(plan.v_slots), _ptr(plan.kv_group_items), E, H, d, T,
-                                                          nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off), plan.n_kv_groups,
-                                                          _stream()), "csn_block_attn_bwd_dv_scores_f32")
-            _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), NP,
-                                                    None, _ptr(dscores), gbase + ges * D * NP, None,
-                                                    slot_stride, _ptr(plan.kv_slots), None, 0,
-                                                    _ptr(plan.kv_group_items), E, H, d, T, nb, Tp, 0, 0, 0, 0, pt,
-                                                    _ptr(plan.kv_group_off), plan.n_kv_groups, _stream()),
-                       "csn_block_attn_bwd_dkv_f32")
-        elif tune.grouped_dkv and (grouping & 2):
-            # one call: the evaluations of a key/value slot are contracted one after the other into the same accumulators
-            _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), NP,
-                                                    _ptr(scores), _ptr(dscores), gbase + ges * D * NP, gbase + 2 * ges * D * NP,
-                                                    slot_stride, _ptr(plan.kv_slots), _ptr(plan.v_slots), 0,
-                                                    _ptr(plan.kv_group_items), E, H, d, T, nb, Tp, 0, 0, 0, 0, pt,
-                                                    _ptr(plan.kv_group_off), plan.n_kv_groups, _stream()),
-                       "csn_block_attn_bwd_dkv_f32")
+            _lib.check(L.csn_block_attn_bwd_dv_scores_f32(
+                _ptr(datt), D * NP, NP, _ptr(scores), _ptr(lse), dv_ptr, slot_stride, _ptr(plan.v_slots), _ptr(plan.kv_group_items),
+                E, H, d, T, nb, Tp, p_attn, seed_attn, _ptr(plan.kv_group_off), plan.n_kv_groups, _stream()),
+                "csn_block_attn_bwd_dv_scores_f32")
+            block_attn_bwd_dkv(launches, ops, plan, geo, datt, None, dscores, dk_ptr, None, slot_stride, None, pt)
         else:
-            for ci, ids in enumerate(plan.dkv_colors):
-                _lib.check(L.csn_block_attn_bwd_dkv_f32(_ptr(datt), D * NP, q_ptr, q_stride, _ptr(plan.q_slots), NP,
-                                                        _ptr(scores), _ptr(dscores), gbase + ges * D * NP, gbase + 2 * ges * D * NP,
-                                                        slot_stride, _ptr(plan.kv_slots), _ptr(plan.v_slots),
-                                                        0 if ci == 0 else 1, _ptr(ids),
-                                                        ids.numel(), H, d, T, nb, Tp, 0, 0, 0, 0, pt, None, 0, _stream()),
-                           "csn_block_attn_bwd_dkv_f32")
-        del dscores, delta, datt
-
-        # ---- projection weight gradients ------------------------------------------------------------------
-        if ranged:
-            dw_qkv = torch.empty((3 * D, C), device=dev, dtype=torch.float32)
-            for rows0, nrows, ranges in ((0, D, plan.q_ranges), (D, 2 * D, plan.kv_ranges)):
-                for i, (first, step, count) in enumerate(ranges):
-                    ws_n = L.csn_wgrad_workspace_floats(nrows, C, count, NP)
-                    ws = torch.empty((ws_n,), device=dev, dtype=torch.float32)
-                    _lib.check(L.csn_project_wgrad_f32(dqkv.data_ptr() + ges * (first * 3 * D + rows0) * NP, step * 3 * D * NP, NP,
-                                                       x_all.data_ptr() + 4 * first * C * NP, step * C * NP, NP,
-                                                       dw_qkv.data_ptr() + 4 * rows0 * C, nrows, C, count, NP, 1.0,
-                                                       0 if i == 0 else 1, _ptr(ws), ws_n, _stream()), "csn_project_wgrad_f32")
-        else:
-            dw_qkv = project_wgrad(dqkv, x_all)
-        dw_q = dw_qkv[:D] / temperature               # Qs = (x Wq^T) / sqrt(d)  (csa_models.py:139)
-        dw_k, dw_v = dw_qkv[D:2 * D], dw_qkv[2 * D:]
-
-        dx_all = None
-        if need_dx:
-            # residual path + the three projections (not needed by the reference's training: inputs are constants)
-            dqkv[:, :D] /= temperature
-            dx_all = project(dqkv, w_qkv.t().contiguous())                   # (bf16 gradient maps: read as such)
-            dx_all.index_add_(0, plan.q_slots.long(), dz if dz_res is None else dz_res)
-        return dx_all, dw_q, dw_k, dw_v, dw_fc, None, None, None, None, None, None, None, None
+            block_attn_bwd_dkv(launches, ops, plan, geo, datt, scores, dscores, dk_ptr, dv_ptr, slot_stride, plan.v_slots, pt)
+        return dqkv
 
 
 class MixLink:
@@ -874,9 +878,7 @@ def _lnb_head(link: MixLink, dfeats: torch.Tensor, scale: torch.Tensor, group: i
         return None
     xhat, rstd, w_fc, p_fc, seed_fc, n, mode, need_dx, w_fc_t = link.pre      # (w_fc_t: W_fv^T of a folded forward, else None)
     E, C, NP = xhat.shape
-    D = w_fc.shape[1]
-    L = _lib.lib()
-    dev = xhat.device
+    D, L, dev = w_fc.shape[1], _lib.lib(), xhat.device
     with math_mode(backward_mode(mode)), act16(0):
         if n % group or L.csn_outproj_lnb_workspace_floats(E, C, D, NP, NP) <= 0:
             return None
@@ -889,9 +891,7 @@ def _lnb_head(link: MixLink, dfeats: torch.Tensor, scale: torch.Tensor, group: i
         datt = torch.empty((E, D, NP), device=dev, dtype=torch.float32)
         if w_fc_t is None:
             w_fc_t = w_fc.t().contiguous()
-        _lib.check(L.csn_outproj_lnb_f32(_ptr(dfeats), _ptr(xhat), _ptr(rstd), C * NP, _ptr(w_fc_t), _ptr(dz), _ptr(dz_res),
-                                         _ptr(datt), 0, n, C, D, NP, NP, p_fc, seed_fc, None, n, _ptr(scale), group, _ptr(rowdot),
-                                         _ptr(rowsum), _ptr(red_ws), ws_n, _stream()), "csn_outproj_lnb_f32")
+        outproj_lnb(dfeats, xhat, rstd, w_fc_t, dz, dz_res, datt, 0, n, p_fc, seed_fc, None, n, scale, group, rowdot, rowsum, red_ws, ws_n)
     link.head_done = (dz, dz_res, datt, w_fc_t)
     return rowdot, rowsum
 

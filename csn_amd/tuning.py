@@ -14,7 +14,7 @@ import contextlib
 from dataclasses import dataclass, field, fields, replace
 from typing import Dict, Optional
 
-# attention backward data flows (csn_amd.functional._MHAEvals):
+# attention backward data flows (resolved once per step by csn_amd.functional.step_form, run by _MHAEvals):
 KEEP_SCORES = 0      # the forward writes the raw scores S, the dQ kernel reads them back and leaves P / dS for the dK / dV products
 RECOMPUTE_DQ = 1     # the forward keeps only lse; the dQ kernel rebuilds S = Qs K^T (one more product), P / dS still travel
 FLASH = 2            # ... and a key-stationary kernel rebuilds P / dS for dK / dV: no score-sized tensor exists at all
