@@ -117,27 +117,37 @@ def outproj_id(i):
     return f"C{C}-D{D}-NP{NP}-ld{ld}" + ("-p0.1" if i in OUTPROJ_DROPOUT else "")
 
 
-def outproj_case(i, fmt):
+def outproj_case(i, fmt, shape=None, n_evals=E_OUT, p=None, spike_x=SPIKE_X, spike_g=SPIKE_G, spike_w=None):
     """Inputs of shape i with 16-bit operands of type fmt: ctx (E, D, ld), w (C, D), dxhat (E, C, ld) hold 16-bit values, the
     residual x (S, C, ld), rows (E, C) and scale (E, C) full fp32; keep (E, C, NP) the fc dropout mask (all True without).
     Two points carry weight of their own, so that a sum over ~1500 points still shows ONE missing point at 10x its bound: the last
     point (NP - 1) and the first of the last 8-byte unit of a 16-bit row (NP - 4) have one residual channel of SPIKE_X (|xhat|
-    there ~ sqrt(C) / 2), one ctx row and one gradient channel of SPIKE_G."""
-    C, D, NP, ld = OUTPROJ_SHAPES[i]
+    there ~ sqrt(C) / 2), one ctx row and one gradient channel of SPIKE_G.
+    For tests/outproj_edge_ref.py (the defaults are the cases above, bit for bit): fmt None leaves the operands full fp32 (no
+    rounding, no flush); shape = (C, D, NP, ld) another shape than OUTPROJ_SHAPES[i] (i then only seeds the case); n_evals the
+    case's own number of evaluations (residual slots (e + 1) % S_OUT); p its dropout probability; spike_x / spike_g its spikes;
+    spike_w a third one: the weight that joins the last point's spiked ctx row to its spiked residual channel."""
+    C, D, NP, ld = OUTPROJ_SHAPES[i] if shape is None else shape
+    E = n_evals
     rng = np.random.default_rng(9100 + i)
     f = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32))
-    ctx, w, x = f(E_OUT, D, ld), f(C, D) / D ** 0.5, f(S_OUT, C, ld)
-    dxhat, rows, scale = f(E_OUT, C, ld), 0.25 * f(E_OUT, C), f(E_OUT, C)
+    ctx, w, x = f(E, D, ld), f(C, D) / D ** 0.5, f(S_OUT, C, ld)
+    dxhat, rows, scale = f(E, C, ld), 0.25 * f(E, C), f(E, C)
     for n, c, d in ((NP - 1, 5, D - 1), (NP - 4, 7, D - 2)):
-        x[:, c, n] = SPIKE_X
-        ctx[:, d, n] = SPIKE_G
-        dxhat[:, c + 4, n] = SPIKE_G
-    ctx, w, dxhat = (ar.round16(t, fmt) for t in (ctx, w, dxhat))
-    ctx = flush_f16(ctx)                                  # (a bf16 Ctx is then exact as the fp16 map of an fp16 forward too)
-    p = 0.1 if i in OUTPROJ_DROPOUT else 0.0
+        x[:, c, n] = spike_x
+        ctx[:, d, n] = spike_g
+        dxhat[:, c + 4, n] = spike_g
+    if spike_w is not None:
+        w[5, D - 1] = spike_w
+    if fmt is not None:
+        ctx, w, dxhat = (ar.round16(t, fmt) for t in (ctx, w, dxhat))
+        ctx = flush_f16(ctx)                              # (a bf16 Ctx is then exact as the fp16 map of an fp16 forward too)
+    if p is None:
+        p = 0.1 if i in OUTPROJ_DROPOUT else 0.0
     seed = ar.HIGH_SEED + 31 * i
-    keep = torch.from_numpy(dr.fc_mask(E_OUT, C, NP, seed, p, ld)) if p > 0 else torch.ones((E_OUT, C, NP), dtype=torch.bool)
-    return dict(C=C, D=D, NP=NP, ld=ld, fmt=fmt, ctx=ctx, w=w, x=x, dxhat=dxhat, rows=rows, scale=scale, p=p, seed=seed, keep=keep)
+    keep = torch.from_numpy(dr.fc_mask(E, C, NP, seed, p, ld)) if p > 0 else torch.ones((E, C, NP), dtype=torch.bool)
+    return dict(C=C, D=D, NP=NP, ld=ld, fmt=fmt, ctx=ctx, w=w, x=x, dxhat=dxhat, rows=rows, scale=scale, p=p, seed=seed, keep=keep,
+                E=E, res_index=tuple((e + 1) % S_OUT for e in range(E)))
 
 
 # backward forms: (name, n_dense, rows, scale / group)
@@ -148,19 +158,22 @@ def _ks(p):
     return 1.0 / (1.0 - p)
 
 
-def outproj_fwd(c, n_keep=None, drop_row=False):
+def outproj_fwd(c, n_keep=None, drop_row=False, prod_err=0.0):
     """float64 forward of a case: dict name -> (value, bound) for xhat (E, C, NP), rstd (E, NP), sums (E, C).
     Mutations: n_keep < NP computes the first n_keep points only (the others are zero in every map and enter no sum); drop_row
-    leaves the last ctx row out of the contraction."""
+    leaves the last ctx row out of the contraction.
+    prod_err: an extra error of the contraction, as a multiple of A = sum_D |w ctx| (operands that are not 16-bit values)."""
     C, D, NP = c["C"], c["D"], c["NP"]
     Dk = D - 1 if drop_row else D
     w, ctx = c["w"].double()[:, :Dk], c["ctx"].double()[:, :Dk, :NP]
-    xr = c["x"].double()[list(RES_INDEX)][..., :NP]
+    xr = c["x"].double()[list(c.get("res_index", RES_INDEX))][..., :NP]
     keep, ks = c["keep"].double(), _ks(c["p"])
     fc = torch.einsum("cd,edn->ecn", w, ctx)
     A = torch.einsum("cd,edn->ecn", w.abs(), ctx.abs())
     z = fc * keep * ks + xr
     Ez = U * (ks * (D + 3) * A * keep + z.abs())
+    if prod_err:
+        Ez = Ez + prod_err * ks * A * keep
     mean = z.mean(1, keepdim=True)
     Em = (C + 2) * U * z.abs().mean(1, keepdim=True) + Ez.mean(1, keepdim=True)
     dlt = z - mean
@@ -221,25 +234,33 @@ def outproj_ln_bwd(c, form, xhat, rstd, n_keep=None, drop_row=False):
     return {"dz": (dz, Ez), "dz_res": (dzr, Er)}
 
 
-def outproj_products(c, dz, ctx=None, n_keep=None, drop_row=False):
+def outproj_products(c, dz, ctx=None, n_keep=None, drop_row=False, round_dz=True, prod_err=(0.0, 0.0)):
     """float64 dctx = w^T r16(dz) (E, D, NP) and dwfc = sum_{e,n} r16(dz) ctx (C, D) from a GIVEN dz (E, C, NP), rounded to bf16 as
     the backward (math mode 2) stages it: name -> (value, bound).  ctx: another Ctx than the case's (the 16-bit map's values).
-    Mutations: points from n_keep on enter no sum and are zero in dctx; drop_row leaves the last dz channel out of dctx and dwfc."""
+    Mutations: points from n_keep on enter no sum and are zero in dctx; drop_row leaves the last dz channel out of dctx and dwfc.
+    round_dz False: dz enters the products as it is (math modes 0 and 1); prod_err: an extra error of the two contractions, as
+    multiples of sum |w^T dz| and of sum |dz ctx|."""
     C, D, NP = c["C"], c["D"], c["NP"]
-    dzb = ar.round16(dz.float(), "bf16").double()
+    dzb = ar.round16(dz.float(), "bf16").double() if round_dz else dz.double()
     if drop_row:
         dzb = dzb.clone()
         dzb[:, C - 1] = 0
     w = c["w"].double()
     cx = (c["ctx"] if ctx is None else ctx).double()[..., :NP]
     dctx = torch.einsum("cd,ecn->edn", w, dzb)
-    Ec = C * U * torch.einsum("cd,ecn->edn", w.abs(), dzb.abs())
+    Ac = torch.einsum("cd,ecn->edn", w.abs(), dzb.abs())
+    Ec = C * U * Ac
+    if prod_err[0]:
+        Ec = Ec + prod_err[0] * Ac
     nk = NP if n_keep is None else n_keep
     if n_keep is not None:
         dctx = dctx.clone()
         dctx[..., n_keep:] = 0
     dw = torch.einsum("ecn,edn->cd", dzb[..., :nk], cx[..., :nk])
-    Ew = E_OUT * NP * U * torch.einsum("ecn,edn->cd", dzb.abs(), cx.abs())
+    Aw = torch.einsum("ecn,edn->cd", dzb.abs(), cx.abs())
+    Ew = c.get("E", E_OUT) * NP * U * Aw
+    if prod_err[1]:
+        Ew = Ew + prod_err[1] * Aw
     return {"dctx": (dctx, Ec), "dwfc": (dw, Ew)}
 
 

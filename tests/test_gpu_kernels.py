@@ -339,6 +339,7 @@ def _attn_reference_autograd(q, k, v, H, d, T, nb):
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("S,E,C,D,NP", [(2, 3, 256, 256, 1000), (1, 2, 96, 192, 500), (2, 2, 128, 128, 2048), (1, 1, 32, 64, 36)])
 def test_outproj_ln_fwd_bwd(L, S, E, C, D, NP):
+    # (the edges of every kernel behind these two calls, in math modes 0 and 1: tests/test_gpu_outproj_edges.py)
     rng = np.random.default_rng(6)
     att = _rand(rng, E, D, NP)
     wfc = _rand(rng, C, D) / math.sqrt(D)
