@@ -209,6 +209,9 @@ _SIGNATURES = {
                                       c_void_p, c_longlong, c_void_p, c_void_p]),
     "csn_masked_ce_bwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
+    "csn_masked_ce_metrics_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "csn_masked_ce_metrics_fwd_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),
     "csn_outproj_ln_fwd_f32": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p,
                                        c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                        c_ulonglong, c_void_p, c_void_p, c_longlong, c_void_p]),

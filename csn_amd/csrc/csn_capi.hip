@@ -916,6 +916,25 @@ int csn_masked_ce_fwd_f32(const float* logits, long long shape_stride, int ld, c
   return csn_launch_masked_ce_fwd(a, (hipStream_t)stream);
 }
 
+long long csn_masked_ce_metrics_workspace_bytes(int n_shapes, int n_classes, int n_points) {
+  if (n_classes <= 0) return 0;
+  return csn_masked_ce_workspace_bytes(n_shapes, n_points);
+}
+
+int csn_masked_ce_metrics_fwd_f32(const float* logits, long long shape_stride, int ld, const long long* labels,
+                                  long long label_shape_stride, int n_shapes, int n_classes, int n_points, int mask, float* lse,
+                                  int* pred, int* counts, void* ws, long long ws_bytes, float* stats, void* stream) {
+  if (!logits || !labels || !counts || !ws || !stats || n_shapes <= 0 || n_classes <= 0 || n_points <= 0 || n_points > ld) return CSN_E_ARG;
+  if (n_shapes > 65535 || n_classes > 65535) return CSN_E_DIM;
+  if (reinterpret_cast<unsigned long long>(ws) & 7) return CSN_E_PTR;
+  if (ws_bytes < csn_masked_ce_metrics_workspace_bytes(n_shapes, n_classes, n_points)) return CSN_E_WORKSPACE;
+  CsnMaskedCeArgs a{};
+  a.logits = logits; a.shape_stride = shape_stride; a.ld = ld; a.labels = labels; a.label_shape_stride = label_shape_stride;
+  a.n_shapes = n_shapes; a.n_classes = n_classes; a.n_points = n_points; a.mask = mask;
+  a.lse = lse; a.pred = pred; a.counts = counts; a.partials = static_cast<double*>(ws); a.stats = stats;
+  return csn_launch_masked_ce_fwd(a, (hipStream_t)stream);
+}
+
 int csn_masked_ce_bwd_f32(const float* logits, long long shape_stride, int ld, const long long* labels, long long label_shape_stride,
                           int n_shapes, int n_classes, int n_points, int mask, const float* lse, const float* stats,
                           const float* grad_out, float* dlogits, long long dshape_stride, int dld, void* stream) {

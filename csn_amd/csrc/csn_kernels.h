@@ -204,7 +204,9 @@ struct CsnMaskedCeArgs {
   const float* logits;  long long shape_stride;  int ld;          // [shape][class][ld]
   const long long* labels;  long long label_shape_stride;         // [shape][n_points] int64
   int n_shapes, n_classes, n_points, mask;                        // counted: mask < label < n_classes
-  float* lse;                                                     // [shape][n_points]
+  float* lse;                                                     // [shape][n_points]  (metrics form: may be null)
+  int* pred;  int* counts;                                        // metrics form (counts != null): [shape][n_points] arg-max (may be
+                                                                  // null), [shape][class][3] inter / gt / pr over label > mask
   double* partials;                                               // forward: 3 per block (csn_masked_ce_blocks)
   float* stats;                                                   // [3]: mean loss, accuracy, counted points
   const float* grad_out;  float* dlogits;  long long dshape_stride;  int dld;      // backward

@@ -4,6 +4,9 @@
 //   forward   per point: lse = log sum_c exp(z_c), loss = lse - z_label, hit = (argmax_c z_c == label); per-block partial sums
 //             of (loss, counted points, hits) in fp64, added in a fixed order by a second small kernel
 //   backward  dz[s][c][n] = counted ? (exp(z_c - lse) - [c == label]) * g / count : 0
+//   metrics   the forward pass again, keeping what it already forms: the arg-max of every point (pred) and, over the points
+//             with label > mask (IoU_per_shape's selection, csa_training.py:110-134), the per-shape per-class counts of
+//             intersection / ground truth / prediction — integers through an LDS histogram and integer atomics (exact)
 // Both are byte streams: 4 n_classes bytes per point forward, 8 n_classes backward (39 classes, 320 000 points: 50 / 100 MB).
 #include "csn_common.h"
 #include "csn_kernels.h"
@@ -11,12 +14,23 @@
 namespace {
 
 constexpr int CE_BLOCK = 256;
+constexpr int CE_HIST_CLASSES = 64;      // metrics: the LDS histogram holds up to this many classes (PartNet: <= 51); above, global atomics
 
-// thread = point; the classes of a point are n_points apart, so a wave reads 256 contiguous bytes per class
+// thread = point; the classes of a point are n_points apart, so a wave reads 256 contiguous bytes per class.
+// METRICS: also pred[s][n] = the arg-max (every point) and counts[s][c][3] += (inter, gt, pr) over the points with label > mask;
+// lse is optional there.  The loss arithmetic and the partial sums are the same statements in both instances.
+template <bool METRICS>
 __global__ __launch_bounds__(CE_BLOCK) void csn_masked_ce_fwd_kernel(CsnMaskedCeArgs p) {
   __shared__ double red[3][CE_BLOCK / 64];
+  __shared__ int hist[METRICS ? CE_HIST_CLASSES * 3 : 1];
   const int n = blockIdx.x * CE_BLOCK + threadIdx.x, s = blockIdx.y;
   double loss = 0.0, cnt = 0.0, hit = 0.0;
+  int gt_c = -1, pr_c = -1;                              // (METRICS) the classes this point counts under, -1: none
+  const bool use_hist = METRICS && p.n_classes <= CE_HIST_CLASSES;
+  if constexpr (METRICS) {
+    if (use_hist)
+      for (int i = threadIdx.x; i < p.n_classes * 3; i += CE_BLOCK) hist[i] = 0;     // (visible after the barrier below)
+  }
   if (n < p.n_points) {
     const long long lab = p.labels[(long long)s * p.label_shape_stride + n];
     const float* z = p.logits + (long long)s * p.shape_stride + n;
@@ -34,7 +48,16 @@ __global__ __launch_bounds__(CE_BLOCK) void csn_masked_ce_fwd_kernel(CsnMaskedCe
       if (c == lab) zl = v;
     }
     const float lse = m + __logf(sum);
-    p.lse[(long long)s * p.n_points + n] = lse;
+    if constexpr (METRICS) {
+      if (p.lse) p.lse[(long long)s * p.n_points + n] = lse;
+      if (p.pred) p.pred[(long long)s * p.n_points + n] = arg;
+      if (lab > p.mask) {                                // no upper bound here: a label >= n_classes still counts its prediction
+        pr_c = arg;
+        if (lab < p.n_classes) gt_c = (int)lab;
+      }
+    } else {
+      p.lse[(long long)s * p.n_points + n] = lse;
+    }
     if (lab > p.mask && lab < p.n_classes) {
       loss = (double)(lse - zl);
       cnt = 1.0;
@@ -54,6 +77,23 @@ __global__ __launch_bounds__(CE_BLOCK) void csn_masked_ce_fwd_kernel(CsnMaskedCe
     double t = 0.0;
     for (int w = 0; w < CE_BLOCK / 64; ++w) t += red[threadIdx.x][w];
     p.partials[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = t;
+  }
+  if constexpr (METRICS) {
+    int* __restrict__ out = p.counts + (long long)s * p.n_classes * 3;
+    if (use_hist) {                                      // (work-group uniform)
+      if (pr_c >= 0) atomicAdd(&hist[pr_c * 3 + 2], 1);
+      if (gt_c >= 0) atomicAdd(&hist[gt_c * 3 + 1], 1);
+      if (gt_c >= 0 && gt_c == pr_c) atomicAdd(&hist[gt_c * 3], 1);
+      __syncthreads();
+      for (int i = threadIdx.x; i < p.n_classes * 3; i += CE_BLOCK) {
+        const int h = hist[i];
+        if (h) atomicAdd(out + i, h);
+      }
+    } else {
+      if (pr_c >= 0) atomicAdd(out + pr_c * 3 + 2, 1);
+      if (gt_c >= 0) atomicAdd(out + gt_c * 3 + 1, 1);
+      if (gt_c >= 0 && gt_c == pr_c) atomicAdd(out + gt_c * 3, 1);
+    }
   }
 }
 
@@ -115,7 +155,13 @@ long long csn_masked_ce_blocks(int n_shapes, int n_points) { return (long long)n
 
 int csn_launch_masked_ce_fwd(const CsnMaskedCeArgs& a, hipStream_t st) {
   const int bx = (a.n_points + CE_BLOCK - 1) / CE_BLOCK;
-  hipLaunchKernelGGL(csn_masked_ce_fwd_kernel, dim3(bx, a.n_shapes), dim3(CE_BLOCK), 0, st, a);
+  if (a.counts) {                                        // the metrics form: counts are fully written by the call
+    const hipError_t e = hipMemsetAsync(a.counts, 0, (size_t)a.n_shapes * a.n_classes * 3 * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(csn_masked_ce_fwd_kernel<true>, dim3(bx, a.n_shapes), dim3(CE_BLOCK), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(csn_masked_ce_fwd_kernel<false>, dim3(bx, a.n_shapes), dim3(CE_BLOCK), 0, st, a);
+  }
   hipLaunchKernelGGL(csn_masked_ce_finish_kernel, dim3(1), dim3(256), 0, st, a.partials, (long long)bx * a.n_shapes, a.stats);
   return (int)hipGetLastError();
 }

@@ -1186,3 +1186,49 @@ def masked_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, mask: int =
         logits = logits.squeeze(-1)
     st = _MaskedCE.apply(logits, labels, mask)
     return st[0], st[1], st[2]
+
+
+class _MaskedCEMetrics(torch.autograd.Function):
+    """_MaskedCE's forward through csn_masked_ce_metrics_fwd_f32: the same stats and lse, plus pred (S, N) int32 — every point's
+    first arg-max class — and counts (S, n_classes, 3) int32 — intersection / ground truth / prediction over label > mask."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mask, want_pred):
+        _need_cuda(logits)
+        if labels.dtype != torch.int64 or not labels.is_cuda:
+            raise _lib.CsnError(f"masked_ce_metrics takes int64 labels on the device (got {labels.dtype}, {labels.device})")
+        S, n_cls, N = logits.shape
+        if logits.stride(2) != 1 or tuple(labels.shape) != (S, N) or labels.stride(1) != 1:
+            raise _lib.CsnError("masked_ce_metrics: logits (S, classes, N) with contiguous points, labels (S, N)")
+        L = _lib.lib()
+        dev = logits.device
+        lse = torch.empty((S, N), device=dev, dtype=torch.float32)
+        stats = torch.empty((3,), device=dev, dtype=torch.float32)
+        pred = torch.empty((S, N) if want_pred else (0,), device=dev, dtype=torch.int32)
+        counts = torch.empty((S, n_cls, 3), device=dev, dtype=torch.int32)
+        ws_bytes = int(L.csn_masked_ce_metrics_workspace_bytes(S, n_cls, N))
+        ws = torch.empty((ws_bytes // 8,), device=dev, dtype=torch.float64)
+        _lib.check(L.csn_masked_ce_metrics_fwd_f32(_ptr(logits), logits.stride(0), logits.stride(1), _ptr(labels), labels.stride(0), S,
+                                                   n_cls, N, int(mask), _ptr(lse), _ptr(pred) if want_pred else None, _ptr(counts),
+                                                   _ptr(ws), ws_bytes, _ptr(stats), _stream()), "csn_masked_ce_metrics_fwd_f32")
+        ctx.save_for_backward(logits, labels, lse, stats)
+        ctx.mask = int(mask)
+        ctx.mark_non_differentiable(labels, pred, counts)
+        return stats, pred, counts
+
+    @staticmethod
+    def backward(ctx, g, _gpred, _gcounts):
+        return _MaskedCE.backward(ctx, g) + (None,)
+
+
+def masked_ce_metrics(logits: torch.Tensor, labels: torch.Tensor, mask: int = 0, want_pred: bool = True):
+    """``masked_cross_entropy`` that keeps what its one pass over the logits forms on the way: returns (loss, accuracy, count, pred,
+    counts).  pred (S, N) int32 is every point's arg-max class (the first maximum, like torch.argmax; None with
+    ``want_pred=False``); counts (S, n_classes, 3) int32 holds per shape and class the intersection, ground-truth and
+    prediction counts over the points with label > mask — IoU_per_shape's selection (csa_training.py:110-134), union = gt + pr -
+    inter.  loss, accuracy and count are bit for bit masked_cross_entropy's, and so is the gradient of loss; pred and counts
+    carry none."""
+    if logits.dim() == 4:
+        logits = logits.squeeze(-1)
+    st, pred, counts = _MaskedCEMetrics.apply(logits, labels, mask, bool(want_pred))
+    return st[0], st[1], st[2], (pred if want_pred else None), counts

@@ -42,9 +42,32 @@ def loss_functions_seg(logit: torch.Tensor, label_gt: torch.Tensor, num_class: i
     return loss, accu
 
 
+def _fused_metrics_route(logit: torch.Tensor, label: torch.Tensor, class_num: int) -> bool:
+    """Device fp32 logits whose shape matches the labels (loss_functions_seg's test), with no class asked for beyond the logits'
+    own (a label >= n_classes enters no ground-truth count of the kernel): csn_amd.functional.masked_ce_metrics serves them."""
+    return (logit.is_cuda and logit.dtype == torch.float32 and label.shape[1:] == logit.shape[2:3] and label.shape[0] == logit.shape[0]
+            and class_num <= logit.shape[1])
+
+
+def _iou_from_counts(counts: torch.Tensor, class_num: int):
+    """(shapes, n_classes, 3) int32 intersection / ground truth / prediction -> IoU_per_shape's pair, summed over the shapes
+    (integers well below 2^24: the floats are exact)."""
+    c = counts[:, :class_num].sum(dim=0)
+    return c[:, 0].float(), (c[:, 1] + c[:, 2] - c[:, 0]).float()
+
+
 def IoU_per_shape(pred: torch.Tensor, label: torch.Tensor, class_num: int, mask: int = 0):
     """Per-class intersection / union counts over labelled points (csa_training.py:110-134), as two (class_num,)
-    device tensors (the reference keeps python lists of 0-d tensors)."""
+    device tensors (the reference keeps python lists of 0-d tensors).  Device fp32 logits take the one-pass kernel
+    (csn_amd.functional.masked_ce_metrics: integer counts, no transpose, no ``nonzero``); everything else the torch statements."""
+    if _fused_metrics_route(pred, label, class_num):
+        from .functional import masked_ce_metrics
+        return _iou_from_counts(masked_ce_metrics(pred, label.long(), mask, want_pred=False)[4], class_num)
+    return _iou_per_shape_torch(pred, label, class_num, mask)
+
+
+def _iou_per_shape_torch(pred: torch.Tensor, label: torch.Tensor, class_num: int, mask: int = 0):
+    """IoU_per_shape as torch statements: the host route, and the composition the fused route is measured and tested against."""
     flat, lab = _flatten(pred, label)
     keep = torch.where(lab > mask)[0]
     p, l = flat[keep].argmax(dim=1), lab[keep].long()
@@ -183,16 +206,100 @@ def validate_layers(model, dataloader: Iterable, class_num: int, device, max_bat
         feats, label, nbrs = _unpack(batch)
         feats, label = feats.to(device), label.to(device)
         out = model(feats, "test", nbrs.to(device)) if nbrs is not None else model(feats, "test")
-        loss, _ = loss_functions_seg(out, label, class_num)
+        if _fused_metrics_route(out, label, class_num):          # loss and counts from one pass over the logits
+            from .functional import masked_ce_metrics
+            loss, _, _, _, counts = masked_ce_metrics(out, label.long(), 0, want_pred=False)
+            i_b, u_b = _iou_from_counts(counts, class_num)
+        else:
+            loss, _ = loss_functions_seg(out, label, class_num)
+            i_b, u_b = IoU_per_shape(out, label, class_num)
         ok = (~torch.isnan(loss)).double()                       # a NaN batch is skipped altogether (:239-240), no host sync
         total += torch.where(torch.isnan(loss), torch.zeros_like(loss), loss).double()
-        i_b, u_b = IoU_per_shape(out, label, class_num)
         intsc += i_b.double() * ok
         union += u_b.double() * ok
         n += 1
         if max_batches is not None and n >= max_batches:
             break
     return mean_iou(intsc, union), float(total.item()) / max(n, 1)
+
+
+def _batch_metrics(out: torch.Tensor, label: torch.Tensor, class_num: int, mask: int = 0):
+    """(loss, accuracy, counted points, pred (S, N), counts (S, class_num, 3)) of one batch of logits: the one-pass kernel on
+    the device, torch statements otherwise.  counts = intersection / ground truth / prediction over label > mask, per shape."""
+    if _fused_metrics_route(out, label, class_num):
+        from .functional import masked_ce_metrics
+        loss, accu, cnt, pred, counts = masked_ce_metrics(out, label.long(), mask)
+        return loss, accu, cnt, pred, counts[:, :class_num]
+    loss, accu = loss_functions_seg(out, label, class_num, mask=mask)
+    z = out.squeeze(-1) if out.dim() == 4 else out
+    pred = z.argmax(dim=1)
+    sel = (label > mask)[:, None, :]
+    classes = torch.arange(class_num, device=z.device)[None, :, None]
+    pk, lk = (pred[:, None, :] == classes) & sel, (label[:, None, :] == classes) & sel
+    counts = torch.stack([(pk & lk).sum(dim=2), lk.sum(dim=2), pk.sum(dim=2)], dim=2)
+    return loss, accu, sel.sum().to(loss.dtype), pred, counts
+
+
+@torch.no_grad()
+def test_layers(model, dataloader: Iterable, class_num: int, device, names: Optional[Sequence] = None,
+                save_pred_dir: Optional[str] = None, max_batches: Optional[int] = None) -> dict:
+    """The test mode MID-FC/get_csa_pred.py:117-161 means to be: eval mode, no autograd graph, one pass over the loader.
+    Returns ``part_iou`` (the reference's number: validate_layers' first value), ``loss`` (mean over the batches, a NaN batch
+    adding nothing), ``accuracy`` (over the counted points of all batches), ``shape_iou`` (mean over the shapes of the mean IoU
+    over the classes 1.. present in the shape, a shape with none left out — SegMeter's definition) and ``shapes`` (the shapes
+    that entered it).  A NaN batch enters nothing (:141-142).  The sums stay on the device and are read back once.
+
+    ``save_pred_dir``: every shape's per-point arg-max (:135-137, computed there and never written) goes to ``<dir>/<name>`` as an
+    int64 .npy.  ``names`` lists the shapes in loader order, each a file name or a (file name, own points) pair: only the
+    shape's own points are written — the length of its label file, before data.pad_points' wrap-around — while the metrics
+    run over the padded points, as the reference's do.  Without names the files are ``shape_<index>.npy``, whole."""
+    model.eval()
+    acc = torch.zeros(2 * class_num + 5, device=device, dtype=torch.float64)   # inter, union | loss, hits, counted, shape IoU sum, shapes
+    preds = []
+    n = 0
+    for batch in dataloader:
+        feats, label, nbrs = _unpack(batch)
+        feats, label = feats.to(device), label.to(device)
+        out = model(feats, "test", nbrs.to(device)) if nbrs is not None else model(feats, "test")
+        loss, accu, cnt, pred, counts = _batch_metrics(out, label, class_num)
+        bad = torch.isnan(loss)
+        ok = (~bad).double()
+        c = counts.double()
+        inter, union = c[:, :, 0], c[:, :, 1] + c[:, :, 2] - c[:, :, 0]
+        present = union[:, 1:] > 0
+        kept = present.sum(dim=1)
+        iou = torch.where(present, inter[:, 1:] / union[:, 1:].clamp(min=1.0), torch.zeros_like(inter[:, 1:]))
+        per_shape = torch.where(kept > 0, iou.sum(dim=1) / kept.clamp(min=1).double(), torch.zeros_like(kept, dtype=torch.float64))
+        zero = torch.zeros((), device=loss.device, dtype=torch.float64)
+        # (the batch's hits back from its fp32 accuracy: accuracy x points is within 6e-8 x points of the integer, exact by rounding
+        # up to millions of points a batch)
+        scalars = torch.stack([torch.where(bad, zero, loss.double()), torch.where(bad, zero, torch.round(accu.double() * cnt.double())), cnt.double() * ok,
+                               per_shape.sum() * ok, (kept > 0).sum().double() * ok])
+        acc += torch.cat([inter.sum(dim=0) * ok, union.sum(dim=0) * ok, scalars])
+        if save_pred_dir is not None:
+            preds.append(pred)
+        n += 1
+        if max_batches is not None and n >= max_batches:
+            break
+    # mean_iou's sum where the counts live (validate_layers' number to the bit: the same reduction on the same device), then the one host read
+    part_sum = (acc[:class_num] / (acc[class_num:2 * class_num] + 1.0e-10)).sum()
+    flat = torch.cat([acc[2 * class_num:], part_sum[None]]).cpu().tolist()
+    loss_sum, hits, counted, shape_sum, shapes, part_sum = flat
+    result = {"part_iou": part_sum / (class_num - 1), "loss": loss_sum / max(n, 1), "accuracy": hits / counted if counted > 0 else float("nan"),
+              "shape_iou": shape_sum / shapes if shapes > 0 else float("nan"), "shapes": int(shapes)}
+    if save_pred_dir is not None and preds:
+        import os
+        os.makedirs(save_pred_dir, exist_ok=True)
+        all_pred = torch.cat(preds).cpu().numpy().astype(np.int64)
+        if names is not None and len(names) < len(all_pred):
+            raise ValueError(f"{len(all_pred)} shapes were predicted and names lists {len(names)}")
+        for i, row in enumerate(all_pred):
+            entry = names[i] if names is not None else f"shape_{i:06d}.npy"
+            name, own = (entry, len(row)) if isinstance(entry, str) else (entry[0], min(int(entry[1]), len(row)))
+            with open(os.path.join(save_pred_dir, name), "wb") as fh:          # (np.save(path) would append a second ".npy")
+                np.save(fh, row[:own])
+    return result
+test_layers.__test__ = False                                    # (a library function: pytest collects it nowhere)
 
 
 # ---------------------------------------------------------------------------------------------------------

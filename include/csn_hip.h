@@ -568,6 +568,15 @@ CSN_API int csn_compat_bwd_f32(const float* dcomp, const float* comp, const doub
  *             every shape written; any point count, pitch and alignment (16-byte accesses where n_points, ld, dld and the shape
  *             strides are % 4 == 0 and logits, lse, dlogits 16-byte aligned; one point per thread otherwise).  A logit of -inf
  *             is a probability of zero (also as a point's first class).
+ *   metrics   csn_masked_ce_metrics_fwd_f32: the forward pass, keeping what it forms on the way (the validation and test
+ *             mode's loss, predictions and Part-IoU counts from one read of the logits).  stats and lse (may be NULL here)
+ *             are bit for bit the forward's; pred (int32 [n_shapes][n_points], may be NULL) = every point's first arg-max
+ *             class, masked or not; counts (int32 [n_shapes][n_classes][3], overwritten) = per shape and class the
+ *             intersection / ground-truth / prediction counts over the points with label > mask (IoU_per_shape's selection,
+ *             csa_training.py:110-134, without the loss's upper bound): such a point adds 1 to pr[pred], with label <
+ *             n_classes also 1 to gt[label], and with pred == label also 1 to inter[label]; union = gt + pr - inter.
+ *             Integer atomics only: exact and reproducible.  ws as for the forward
+ *             (csn_masked_ce_metrics_workspace_bytes); csn_masked_ce_bwd_f32 takes its lse and stats.
  * labels are int64 (torch.long), label_shape_stride elements apart per shape. */
 CSN_API long long csn_masked_ce_workspace_bytes(int n_shapes, int n_points);
 CSN_API int csn_masked_ce_fwd_f32(const float* logits, long long shape_stride, int ld, const long long* labels, long long label_shape_stride,
@@ -576,6 +585,11 @@ CSN_API int csn_masked_ce_fwd_f32(const float* logits, long long shape_stride, i
 CSN_API int csn_masked_ce_bwd_f32(const float* logits, long long shape_stride, int ld, const long long* labels, long long label_shape_stride,
                           int n_shapes, int n_classes, int n_points, int mask, const float* lse, const float* stats,
                           const float* grad_out, float* dlogits, long long dshape_stride, int dld, void* stream);
+CSN_API long long csn_masked_ce_metrics_workspace_bytes(int n_shapes, int n_classes, int n_points);
+CSN_API int csn_masked_ce_metrics_fwd_f32(const float* logits, long long shape_stride, int ld, const long long* labels,
+                          long long label_shape_stride, int n_shapes, int n_classes, int n_points, int mask,
+                          float* lse /* may be NULL */, int* pred /* may be NULL */, int* counts,
+                          void* ws, long long ws_bytes, float* stats, void* stream);
 
 /* ---- (11) the MinkowskiNet cross-shape head on ragged shape batches (MinkowskiNet/models/hrnet.py:359-423, 472-490) -------
  * A MinkowskiNet batch packs the points of its shapes row after row; shape b owns the rows offsets[b] .. offsets[b+1] - 1
